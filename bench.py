@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: fused int8 fake-quant fwd+bwd, per-channel, [256,512,56,56] bf16 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already resident in
 HBM: the forward of a stats-scaled per-channel activation quantizer (AbsMax statistic over (N,H,W),
@@ -31,6 +31,11 @@ Other workloads (--workload): the remaining BASELINE.json configs, same JSON sha
   qlinear_8192        config 5: Int4WeightPerChannelFloat on Linear[8192,8192] + Int8ActPerTensorFloat on
                       [8192,8192] bf16 rows per GPU, per-tensor statistic all-reduced over the ranks
   weight_linear_int4  config 5's weight alone (eager and HIP-graph replay)
+
+--dump-outputs DIR: after the timed steps, what the last one returned to its caller -- per quantized tensor the forward's
+y / scale / zero_point / bit_width and the tensor's gradient -- is written as DIR/<name>.npy (act0_y, act0_grad, ...,
+weight0_y, ...), 64 MB at most in all (larger arrays as a fixed seeded sample, see dump_outputs); the inputs are seeded,
+so two builds given the same arguments can be compared output for output.  The line then lists the arrays ("outputs").
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
   roofline     -- the dominant kernel (the backward) priced in algorithmic HBM bytes per launch over its
@@ -154,6 +159,16 @@ class Job:
             y = q(x)[0]
             y.backward(g)
 
+    def kept_step(self):
+        """step() that keeps what the quantizers returned in self.last, for dump_outputs -- detached: a kept autograd
+        graph would keep the leaves' AccumulateGrad nodes, and the stream they were made on, alive into later steps"""
+        self.last = []
+        for x, g, q in self.acts + self.weights:
+            x.grad = None
+            out = q(x)
+            out[0].backward(g)
+            self.last.append(tuple(t.detach() for t in out))
+
 
 class KernelTimer:
     """HIP-event brackets around the named C-ABI calls, on the stream they are launched on"""
@@ -245,8 +260,9 @@ def cpu_baseline(shape, dtype, per_channel, budget_s=12.0):
                                                       iters, el)}
 
 
-def timed_run(job, steps, warmup, settle, world, device, timer=None, stride=8, on_gpu=True):
-    """settle + warm-up steps untimed, then `steps` steps between barriers -> max-over-ranks seconds"""
+def timed_run(job, steps, warmup, settle, world, device, timer=None, stride=8, on_gpu=True, keep_last=False):
+    """settle + warm-up steps untimed, then `steps` steps between barriers -> max-over-ranks seconds
+    keep_last: the last timed step keeps its outputs in job.last (dump_outputs)"""
 
     def barrier():
         if world > 1:
@@ -263,7 +279,7 @@ def timed_run(job, steps, warmup, settle, world, device, timer=None, stride=8, o
     for i in range(steps):
         if timer is not None:
             timer.enabled = i % stride == 0
-        job.step()
+        (job.kept_step if keep_last and i == steps - 1 else job.step)()
     barrier()
     elapsed = time.perf_counter() - t0
     if timer is not None:
@@ -273,6 +289,69 @@ def timed_run(job, steps, warmup, settle, world, device, timer=None, stride=8, o
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs: every file of the dump together
+DUMP_HEADER_BYTES = 256          # room left in the limit for each file's .npy header (128 bytes for these shapes)
+DUMP_SEED = 123456
+
+
+def step_outputs(job):
+    """what a caller of the timed step received from its last step (kept by timed_run(keep_last=True)): for every
+    quantized tensor the forward's (y, scale, zero_point, bit_width) and the tensor's gradient -> [(name, tensor)]"""
+    named = []
+    for i, ((x, _, _), out) in enumerate(zip(job.acts + job.weights, job.last)):
+        tag = 'act%d' % i if i < len(job.acts) else 'weight%d' % (i - len(job.acts))
+        for field, t in zip(('y', 'scale', 'zero_point', 'bit_width'), out):
+            named.append((tag + '_' + field, t))
+        named.append((tag + '_grad', x.grad))
+    return named
+
+
+def dump_outputs(job, directory, limit=DUMP_LIMIT_BYTES):
+    """Write step_outputs(job) as <directory>/<name>.npy: float64 for float64 and 32/64-bit integer tensors, float32 for
+    everything else (exact for bf16 / f16 / f32).  The files together take at most `limit` bytes: the arrays, smallest
+    first, each get an equal share of what is left; one within its share is written whole and leaves the rest to the
+    larger ones, one above it is written as a fixed sample of its flattened elements -- one element at a seeded random
+    offset in each of k equal blocks (generator seeded with DUMP_SEED) -- so a tensor of the same size is sampled at
+    the same positions in every run.
+    -> {name: {'shape', 'dtype', 'sampled' (elements written, or None when whole)}}"""
+    import numpy as np
+    named = step_outputs(job)
+
+    def out_dtype(t):
+        return torch.float64 if t.dtype in (torch.float64, torch.int64, torch.int32) else torch.float32
+
+    def width(t):
+        return 8 if out_dtype(t) == torch.float64 else 4
+
+    budget = limit - DUMP_HEADER_BYTES * len(named)
+    count, left = {}, len(named)
+    for name, t in sorted(named, key=lambda nt: nt[1].numel() * width(nt[1])):
+        share = budget // left
+        count[name] = t.numel() if t.numel() * width(t) <= share else share // width(t)
+        assert count[name] > 0, (name, limit)
+        budget -= count[name] * width(t)
+        left -= 1
+    os.makedirs(directory, exist_ok=True)
+    meta, written = {}, 0
+    for name, t in named:
+        flat = t.detach().reshape(-1)
+        k = count[name]
+        if k < t.numel():
+            stride = t.numel() // k
+            gen = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.arange(k, dtype=torch.int64) * stride + torch.randint(0, stride, (k,), generator=gen)
+            flat = flat.index_select(0, idx.to(flat.device))
+        arr = flat.to(out_dtype(t)).cpu().numpy()
+        if k == t.numel():
+            arr = arr.reshape(tuple(t.shape))
+        path = os.path.join(directory, name + '.npy')
+        np.save(path, arr)
+        written += os.path.getsize(path)
+        meta[name] = {'shape': list(t.shape), 'dtype': str(arr.dtype), 'sampled': k if k < t.numel() else None}
+    assert written <= limit, (written, limit)
+    return meta
 
 
 def graph_replay_us(job, iters=200):
@@ -413,7 +492,16 @@ def parse_args(argv=None):
                     help='N > 1: seconds the HIP-graph measurement may take before the eager line is printed without it')
     ap.add_argument('--launch-timeout', type=float, default=900.0,
                     help='bare --gpus N: seconds the launcher waits for its workers before it kills them')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (forward outputs and gradients) as '
+                         'DIR/<name>.npy, float32 / float64, %d MB at most (larger arrays as a fixed seeded sample); '
+                         'N > 1: rank 0\'s' % (DUMP_LIMIT_BYTES // 10 ** 6))
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
+    return args
 
 
 def free_port():
@@ -697,10 +785,15 @@ def main():
     #  rank's shard of a strong-scaled split is host-bound there -- 0.27 against 0.16 ms, profiles/r03_strong_scaling.md --
     #  so with N > 1 fewer steps are bracketed)
     stride = args.timer_stride if world == 1 else max(args.timer_stride, 16)
-    elapsed = timed_run(job, args.steps, args.warmup, settle, world, device, timer, stride, on_gpu=on_gpu)
+    dump = args.dump_outputs is not None and rank == 0
+    elapsed = timed_run(job, args.steps, args.warmup, settle, world, device, timer, stride, on_gpu=on_gpu, keep_last=dump)
     if timer is not None:
         nat.set_kernel_timer(None)
     main_m = Measurement(job, elapsed, args.steps, world, timer)
+    dumped = None
+    if dump:
+        dumped = dump_outputs(job, args.dump_outputs)
+        job.last = None
     replay_us = None
     graph_error = None
     if world == 1 and on_gpu and (kind in ('weight_conv', 'weight_linear') or args.graph_replay) \
@@ -799,6 +892,8 @@ def main():
         # the streaming calls of the step, same method (each bracket includes its launch-bound helpers); the
         # one-launch forward (statistic + quantizer) moves the statistic's read through the Infinity Cache
         out['calls'] = m.calls
+        if dumped is not None:
+            out['outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         if baseline is not None:
             out['cpu_baseline'] = baseline
 
