@@ -247,8 +247,8 @@ def set_kernel_timer(timer):
 # own the memory): those calls take the two-launch route.
 ARRIVE_WORDS = 1 << 16
 _arrive = {}
-ONEPASS = os.environ.get('BREVITAS_AMD_ONEPASS', '1') != '0'
-ONEPASS_BWD = os.environ.get('BREVITAS_AMD_ONEPASS_BWD', '1') != '0'   # developer A/B switch of the backward alone
+ONEPASS = True       # the one-launch routes (tests and tools/onepass_ab.py switch them off for A/B runs)
+ONEPASS_BWD = True   # the one-launch backward alone
 
 
 def arrival_buffer(dev, stream, words):

@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/bvq.h"
 
 namespace bvq {
@@ -207,7 +209,6 @@ __device__ __forceinline__ void buf_store(buf_t b, uint32_t byte_off, const vec_
 int64_t nt_threshold_bytes();
 // host-side float -> dtype -> float rounding (python scalars that torch converts to the tensor dtype)
 float round_host(float f, int dt);
-int env_flag(const char* name, int dflt);
 
 // read element 0 / element c of a scale-like buffer of runtime dtype as float (wave-uniform use)
 __device__ __forceinline__ float load_scalar_as_f(const void* p, int dt, int64_t idx) {
@@ -337,6 +338,105 @@ constexpr int kColsFwdVec16 = BVQ_COLS_FWD_VEC16;
 
 static inline unsigned grid_for_units(int64_t units) {
   return (unsigned)((units + kWavesPerBlock - 1) / kWavesPerBlock);
+}
+
+// ---- host dispatch: a runtime value -> a template argument -------------------------------------------------
+// Each helper calls the generic lambda f with the value as a compile-time one (a type_tag, or a std::integral_constant)
+// and returns what f returns (BVQ_OK for a void f), or an error code when no instantiation exists for the value.
+template <typename T>
+struct type_tag {
+  using type = T;
+};
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+template <typename F, typename... A>
+int call_rc(F&& f, A... a) {
+  if constexpr (std::is_void_v<decltype(f(a...))>) {
+    f(a...);
+    return BVQ_OK;
+  } else {
+    return f(a...);
+  }
+}
+
+// f(type_tag<T>) for the element type of dtype id dt
+template <typename F>
+int with_dtype(int dt, F&& f) {
+  if (dt == BVQ_F32) return call_rc(f, type_tag<float>{});
+  if (dt == BVQ_BF16) return call_rc(f, type_tag<bf16_t>{});
+  if (dt == BVQ_F16) return call_rc(f, type_tag<f16_t>{});
+  set_error("bad dtype %d", dt);
+  return BVQ_ERR_INVALID;
+}
+
+// f(type_tag<XT>, type_tag<CT>) for the five (tensor, compute) dtype pairs the quantizers are built for
+template <typename F>
+int with_pair(int x_dtype, int ct_dtype, F&& f) {
+  if (x_dtype == BVQ_F32 && ct_dtype == BVQ_F32) return call_rc(f, type_tag<float>{}, type_tag<float>{});
+  if (x_dtype == BVQ_BF16 && ct_dtype == BVQ_BF16) return call_rc(f, type_tag<bf16_t>{}, type_tag<bf16_t>{});
+  if (x_dtype == BVQ_BF16 && ct_dtype == BVQ_F32) return call_rc(f, type_tag<bf16_t>{}, type_tag<float>{});
+  if (x_dtype == BVQ_F16 && ct_dtype == BVQ_F16) return call_rc(f, type_tag<f16_t>{}, type_tag<f16_t>{});
+  if (x_dtype == BVQ_F16 && ct_dtype == BVQ_F32) return call_rc(f, type_tag<f16_t>{}, type_tag<float>{});
+  set_error("unsupported dtype pair x=%d ct=%d", x_dtype, ct_dtype);
+  return BVQ_ERR_UNSUPPORTED;
+}
+
+// f(std::bool_constant<b>)
+template <typename F>
+int with_bool(bool b, F&& f) {
+  return b ? call_rc(f, std::true_type{}) : call_rc(f, std::false_type{});
+}
+
+// f(int_c<v>) for v one of Vs
+template <int... Vs, typename F>
+int with_value(int v, F&& f) {
+  int rc = BVQ_ERR_INVALID;
+  const bool hit = ((v == Vs ? (rc = call_rc(f, int_c<Vs>{}), true) : false) || ...);
+  if (!hit) set_error("no kernel instantiated for value %d", v);
+  return rc;
+}
+
+// the read-only streaming kernels (statistics, select, tie scan): f(int_c<VEC>, std::bool_constant<NT>) -- full
+// vector width with either cache policy, ragged / misaligned rows (vec < V) one element per lane with the default one
+template <int V, typename F>
+int with_read_variant(int vec, bool nt, F&& f) {
+  if (vec != V) return call_rc(f, int_c<1>{}, std::false_type{});
+  return with_bool(nt, [&](auto ntc) { return call_rc(f, int_c<V>{}, ntc); });
+}
+
+// runtime-selected rounding mode (the rarely used variants share one kernel instantiation)
+constexpr int kAnyRM = -1;
+
+// the column-mapped quantizer kernels (no vector width): f(int_c<RM>, std::bool_constant<NT>) -- half-even rounding
+// with either cache policy, every other rounding mode one kernel with the default one
+template <typename F>
+int with_round_variant(int round_mode, bool nt, F&& f) {
+  if (round_mode != BVQ_ROUND) return call_rc(f, int_c<kAnyRM>{}, std::false_type{});
+  return with_bool(nt, [&](auto ntc) { return call_rc(f, int_c<BVQ_ROUND>{}, ntc); });
+}
+
+// The instantiation policy of the row-mapped quantizer kernels, stated once:
+//   full vector width, half-even rounding      -> (V, BVQ_ROUND, nt): both cache policies
+//   full vector width, any other rounding mode -> (V, kAnyRM, false)
+//   ragged / misaligned rows (vec < V)         -> (1, BVQ_ROUND, false) or (1, kAnyRM, false)
+// f(int_c<VEC>, int_c<RM>, std::bool_constant<NT>).  kFullRneOnly: a kernel built for the first row only (the one-launch
+// backward); every other (vec, round_mode) fails with BVQ_ERR_UNSUPPORTED naming `what`.
+static inline bool stream_full_rne(int vec, int full, int round_mode) { return vec == full && round_mode == BVQ_ROUND; }
+
+template <int V, bool kFullRneOnly = false, typename F>
+int with_stream_variant(const char* what, int vec, int round_mode, bool nt, F&& f) {
+  if constexpr (kFullRneOnly) {
+    if (!stream_full_rne(vec, V, round_mode)) {
+      set_error("%s: no kernel for vec %d, round_mode %d", what, vec, round_mode);
+      return BVQ_ERR_UNSUPPORTED;
+    }
+    return with_bool(nt, [&](auto ntc) { return call_rc(f, int_c<V>{}, int_c<BVQ_ROUND>{}, ntc); });
+  } else {
+    if (vec == V) return with_round_variant(round_mode, nt, [&](auto rm, auto ntc) { return call_rc(f, int_c<V>{}, rm, ntc); });
+    if (round_mode == BVQ_ROUND) return call_rc(f, int_c<1>{}, int_c<BVQ_ROUND>{}, std::false_type{});
+    return call_rc(f, int_c<1>{}, int_c<kAnyRM>{}, std::false_type{});
+  }
 }
 
 #ifdef __HIPCC__

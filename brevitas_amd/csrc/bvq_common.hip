@@ -1,7 +1,6 @@
 // bvq_common.hip -- error reporting, tiling and library-level entry points.
 #include <stdarg.h>
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "bvq_common.h"
 
@@ -28,27 +27,67 @@ int check_launch(const char* what) {
   return BVQ_OK;
 }
 
-int default_piece_chunks() {
-  // tunable for experiments only; the shipped default is what bench.py measures
-  static int v = [] {
-    const char* e = getenv("BVQ_PIECE_CHUNKS");
-    int n = e ? atoi(e) : 0;
-    return (n >= 1 && n <= 4096) ? n : 8;
-  }();
-  return v;
-}
+// ---- tuning constants ------------------------------------------------------------------------------
+// The shipped values are what bench.py measures; an experiment build overrides one with a -D define
+// (python -m brevitas_amd.csrc.build -DBVQ_PIECE_CHUNKS=16 --out=...).  0 where noted: the heuristic decides.
+#ifndef BVQ_PIECE_CHUNKS
+#define BVQ_PIECE_CHUNKS 8
+#endif
+#ifndef BVQ_QUANT_PIECE_CHUNKS
+#define BVQ_QUANT_PIECE_CHUNKS 0  // 0: quant_piece_chunks' choice
+#endif
+#ifndef BVQ_QUANT_MAX_UNITS_PER_CHANNEL
+#define BVQ_QUANT_MAX_UNITS_PER_CHANNEL (1 << 20)
+#endif
+#ifndef BVQ_MAX_UNITS_PER_CHANNEL
+#define BVQ_MAX_UNITS_PER_CHANNEL (1 << 17)
+#endif
+#ifndef BVQ_MAX_RPU
+#define BVQ_MAX_RPU 64
+#endif
+#ifndef BVQ_NT_BYTES
+#define BVQ_NT_BYTES (256ll << 20)  // the Infinity Cache size
+#endif
+#ifndef BVQ_COLS
+#define BVQ_COLS 1  // 0: no column-mapped route
+#endif
+#ifndef BVQ_COLS_UNITS
+#define BVQ_COLS_UNITS 0  // 0: cols_plan's choice
+#endif
+#ifndef BVQ_COLS_FWD_ROWS
+#define BVQ_COLS_FWD_ROWS 12
+#endif
+#ifndef BVQ_COLS_TEAM_ROWS
+#define BVQ_COLS_TEAM_ROWS 0  // 0: cols_plan's per-dtype choice
+#endif
+constexpr int kPieceChunks = BVQ_PIECE_CHUNKS;
+constexpr int kQuantPieceChunks = BVQ_QUANT_PIECE_CHUNKS;
+constexpr int kQuantMaxUnitsPerChannel = BVQ_QUANT_MAX_UNITS_PER_CHANNEL;
+constexpr int kMaxUnitsPerChannel = BVQ_MAX_UNITS_PER_CHANNEL;
+constexpr int kMaxRowsPerUnit = BVQ_MAX_RPU;
+constexpr int64_t kNtBytes = BVQ_NT_BYTES;
+constexpr bool kCols = BVQ_COLS != 0;
+constexpr int kColsUnits = BVQ_COLS_UNITS;
+constexpr int kColsFwdRows = BVQ_COLS_FWD_ROWS;
+constexpr int kColsTeamRows = BVQ_COLS_TEAM_ROWS;
+static_assert(kPieceChunks >= 1 && kPieceChunks <= 4096, "BVQ_PIECE_CHUNKS");
+static_assert(kQuantPieceChunks >= 0 && kQuantPieceChunks <= 4096, "BVQ_QUANT_PIECE_CHUNKS");
+static_assert(kQuantMaxUnitsPerChannel >= 1 && kQuantMaxUnitsPerChannel <= (1 << 24), "BVQ_QUANT_MAX_UNITS_PER_CHANNEL");
+static_assert(kMaxUnitsPerChannel >= 1 && kMaxUnitsPerChannel <= (1 << 24), "BVQ_MAX_UNITS_PER_CHANNEL");
+static_assert(kMaxRowsPerUnit >= 1 && kMaxRowsPerUnit <= 64, "BVQ_MAX_RPU");
+static_assert(kNtBytes >= 0, "BVQ_NT_BYTES");
+static_assert(kColsUnits == 0 || (kColsUnits >= 64 && kColsUnits <= (1 << 22)), "BVQ_COLS_UNITS");
+static_assert(kColsFwdRows >= 1, "BVQ_COLS_FWD_ROWS");
+static_assert(kColsTeamRows >= 0, "BVQ_COLS_TEAM_ROWS");
+
+int default_piece_chunks() { return kPieceChunks; }
 
 // the quantizer kernels (a store stream next to the loads) on long rows of 4-byte elements: 4 KiB of each stream
 // per wave -- the no-arithmetic copy of tools/yardstick.py peaks there too.  The 16-bit kernels keep 8 KiB: with the
 // scale-gradient sums they are close to the VALU limit and the per-unit work (scale, reciprocal, two wave reductions)
 // of twice as many units costs more than the shorter units give (profiles/r02_per_tensor_pieces.txt).
 static int quant_piece_chunks(int vec, int64_t row_len) {
-  static int v = [] {
-    const char* e = getenv("BVQ_QUANT_PIECE_CHUNKS");  // experiments only
-    const int n = e ? atoi(e) : 0;
-    return (n >= 1 && n <= 4096) ? n : 0;
-  }();
-  if (v) return v;
+  if (kQuantPieceChunks) return kQuantPieceChunks;
   if (vec == 4) return 4;  // (vec 4 = float32 in 16-byte chunks)
   // 16-bit types: 8 KiB -- except for very long rows (a per-tensor activation), where 7 KiB pieces stream 2-3 %
   // faster than pieces of a power of two (profiles/r02_per_tensor_pieces.txt: 495 -> 510 Gelem/s on the per-tensor
@@ -59,15 +98,6 @@ static int quant_piece_chunks(int vec, int64_t row_len) {
   if (row_len < 16 * (int64_t)default_piece_chunks() * quantum) return 4;
   return row_len >= 64 * (int64_t)default_piece_chunks() * quantum ? 7 : default_piece_chunks();
 }
-static int max_units_per_channel_quant() {
-  static int v = [] {
-    const char* e = getenv("BVQ_QUANT_MAX_UNITS_PER_CHANNEL");  // experiments only
-    const int n = e ? atoi(e) : 0;
-    return (n >= 1 && n <= (1 << 24)) ? n : (1 << 20);
-  }();
-  return v;
-}
-
 int pick_vec(int max_vec, int64_t rows, int64_t row_len, const void* const* ptrs, const int* elsizes,
              int nptr, bool ragged_ok) {
   // ragged_ok: the caller's kernels walk the (< vec) elements after the last full chunk of EVERY row and
@@ -90,14 +120,7 @@ int pick_vec(int max_vec, int64_t rows, int64_t row_len, const void* const* ptrs
   return vec;
 }
 
-int64_t nt_threshold_bytes() {
-  static int64_t v = [] {
-    const char* e = getenv("BVQ_NT_BYTES");  // experiments only
-    const long long n = e ? atoll(e) : -1;
-    return n >= 0 ? (int64_t)n : (int64_t)256 << 20;  // the Infinity Cache size
-  }();
-  return v;
-}
+int64_t nt_threshold_bytes() { return kNtBytes; }
 
 // host-side float -> dtype -> float rounding (python scalars that torch converts to the tensor dtype)
 float round_host(float f, int dt) {
@@ -121,15 +144,7 @@ float round_host(float f, int dt) {
   return copysignf(nearbyintf(a / q) * q, f);
 }
 
-
-// integer environment knob (experiments / kill switches), read by callers once
-int env_flag(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
 ColsPlan cols_plan(int dtype, int64_t outer, int64_t channels, int64_t inner, bool no_partials, bool team, int vec16) {
-  static const int enabled = env_flag("BVQ_COLS", 1);
   ColsPlan p = {};
   const int el = dtype == BVQ_F32 ? 4 : 2;
   // (the backward's workgroup units hold kColsTeamVec16 columns of a 16-bit type per lane: bvq_common.h)
@@ -141,7 +156,7 @@ ColsPlan cols_plan(int dtype, int64_t outer, int64_t channels, int64_t inner, bo
   const int64_t row_bytes = inner * el;
   const bool short_rows = row_bytes < 256;
   const bool ragged_rows = row_bytes % 16 != 0 && row_bytes < 4096 && outer >= 64;
-  if (!enabled || channels < 2 || inner < 1 || outer < 2 || !(short_rows || ragged_rows)) return p;
+  if (!kCols || channels < 2 || inner < 1 || outer < 2 || !(short_rows || ragged_rows)) return p;
   const int64_t L = channels * inner;
   if (L % (16 / el) != 0 || L / vec > (1 << 30)) return p;  // (the same layouts for every kernel: rows of 16-byte chunks)
   p.rows = outer;
@@ -154,29 +169,23 @@ ColsPlan cols_plan(int dtype, int64_t outer, int64_t channels, int64_t inner, bo
   // rows per block: at least 16 chunks per lane, and no more than ~8192 units in all -- every unit leaves a
   // partial row of L entries behind, and those should stay a few percent of the traffic
   int64_t rb = 16 * (int64_t)p.rpp;
-  static const int env_units = [] {
-    const char* e = getenv("BVQ_COLS_UNITS");  // experiments only
-    const int n = e ? atoi(e) : 0;
-    return (n >= 64 && n <= (1 << 22)) ? n : 0;
-  }();
   // (a kernel that leaves no partial rows behind -- the forward -- is faster with 8 x the units: 4.99 -> 5.70 TB/s
   //  on [802816,512] bf16; with partial rows the extra traffic and the longer fold eat the gain)
   // (team units are workgroups of four waves: the same 65536 waves without partials, 32768 waves with them -- a
   //  workgroup leaves ONE partial row behind, so four times the waves cost no more partial traffic)
   // (read-only kernels with partial rows -- abs-max, min/max, moments: 4096 waves, one resident round of four per SIMD,
   //  measured 7-13 % faster than 8192 on every layout; 2048 and fewer starve the memory system)
-  const int want_units = env_units ? env_units : (no_partials ? (team ? 16384 : 65536) : (team ? 8192 : 4096));
+  const int want_units = kColsUnits ? kColsUnits : (no_partials ? (team ? 16384 : 65536) : (team ? 8192 : 4096));
   const int64_t want_blocks = want_units / p.strips > 0 ? want_units / p.strips : 1;
   const int64_t rows_for_that = (outer + want_blocks - 1) / want_blocks;
   if (rows_for_that > rb) rb = ((rows_for_that + p.rpp - 1) / p.rpp) * p.rpp;
-  if (no_partials && !team && !env_units) {
+  if (no_partials && !team && !kColsUnits) {
     // the forward (no partial rows): short blocks by row count -- the resident waves' window of memory again -- and
     // not a power of two (8 / 12 / 16 / 24 rows: [802816,512] float32 0.583 / 0.569 / 0.615 / 0.605 ms, [65536,4096]
     // bf16 0.183 / 0.180 / 0.196 / 0.195; it was 25..98 rows: 0.617 and 0.200 -- profiles/r03_column_mapped.txt)
-    static const int env_frows = env_flag("BVQ_COLS_FWD_ROWS", 0);  // experiments only
-    rb = (env_frows > 0 ? env_frows : 12) * (int64_t)p.rpp;
+    rb = kColsFwdRows * (int64_t)p.rpp;
   }
-  if (team && !no_partials && !env_units) {
+  if (team && !no_partials && !kColsUnits) {
     // a workgroup's rows by count, not by a unit total: short blocks keep the resident workgroups' window of memory
     // small, which is what these kernels' bandwidth follows (profiles/r03_column_mapped.txt) -- down to where a wave's
     // set-up (its columns' scales, reciprocals) stops being hidden: float32 (4 columns per lane, seven waves per SIMD)
@@ -184,8 +193,7 @@ ColsPlan cols_plan(int dtype, int64_t outer, int64_t channels, int64_t inner, bo
     // columns per lane and eight waves per SIMD (with 8 columns per lane in ~104 registers, four waves per SIMD, both
     // wanted 96 and streamed 3-8 % slower).
     // One partial row of 4 L bytes per block: 1/48 (1/16) of a block's 3 x 2 L (3 x 4 L) bytes per row = 1.4 % (2 %).
-    static const int env_rows = env_flag("BVQ_COLS_TEAM_ROWS", 0);  // experiments only
-    const int64_t groups = env_rows > 0 ? env_rows : (dtype == BVQ_BF16 ? 48 : dtype == BVQ_F16 ? 96 : 16);
+    const int64_t groups = kColsTeamRows > 0 ? kColsTeamRows : (dtype == BVQ_BF16 ? 48 : dtype == BVQ_F16 ? 96 : 16);
     rb = groups * (int64_t)p.rpp;
   }
   // a lane's row counter within a unit fits 16 bits (the backward packs it next to a 16-bit key)
@@ -202,24 +210,6 @@ ColsPlan cols_plan(int dtype, int64_t outer, int64_t channels, int64_t inner, bo
   return p;
 }
 
-int max_units_per_channel() {
-  static int v = [] {
-    const char* e = getenv("BVQ_MAX_UNITS_PER_CHANNEL");
-    int n = e ? atoi(e) : 0;
-    return (n >= 1 && n <= (1 << 24)) ? n : (1 << 17);
-  }();
-  return v;
-}
-
-static int max_rows_per_unit() {
-  static int v = [] {
-    const char* e = getenv("BVQ_MAX_RPU");  // experiments only
-    const int n = e ? atoi(e) : 0;
-    return (n >= 1 && n <= 64) ? n : 64;
-  }();
-  return v;
-}
-
 Tiling make_tiling(int64_t outer, int32_t channels, int64_t row_len, int vec, int64_t unit_cap,
                    bool few_rows) {
   Tiling t;
@@ -234,7 +224,7 @@ Tiling make_tiling(int64_t outer, int32_t channels, int64_t row_len, int vec, in
     if (few_rows) piece = (int64_t)quant_piece_chunks(vec, row_len) * quantum;
     // long rows: cut them into default-sized pieces (a per-tensor quantizer is one very long row: ~10^5
     // units, whose partials the finish kernels combine in two stages), bounded by unit_cap per channel.
-    if (unit_cap <= 0) unit_cap = few_rows ? max_units_per_channel_quant() : max_units_per_channel();
+    if (unit_cap <= 0) unit_cap = few_rows ? kQuantMaxUnitsPerChannel : kMaxUnitsPerChannel;
     int64_t max_ppr = unit_cap / (outer > 0 ? outer : 1);
     if (max_ppr < 1) max_ppr = 1;
     if (row_len > piece * max_ppr) {
@@ -263,7 +253,7 @@ Tiling make_tiling(int64_t outer, int32_t channels, int64_t row_len, int vec, in
       // (read-only kernels: never so many rows per unit that the launch has fewer than kMinUnits units -- a
       //  [32,512,56,56] shard walked 8 rows at a time is 2048 waves on 1024 SIMDs and streamed at 2.2 TB/s)
       constexpr int64_t kMinUnits = 16384;
-      for (int64_t r = 1; r <= outer && r <= max_rows_per_unit() && r * cpr <= cap_chunks; ++r) {
+      for (int64_t r = 1; r <= outer && r <= kMaxRowsPerUnit && r * cpr <= cap_chunks; ++r) {
         if (!few_rows && r > 1 && ((outer + r - 1) / r) * channels < kMinUnits) break;
         const int64_t loads = (r * cpr + kWave - 1) / kWave;
         const double eff = (double)(r * cpr) / (double)(loads * kWave);

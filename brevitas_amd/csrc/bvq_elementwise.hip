@@ -83,28 +83,6 @@ struct UnaryF {
   __device__ float operator()(float v, float, float) const { return unary_op<T, OP>(v); }
 };
 
-template <typename T>
-static int dispatch_unary(int op, const void* x, void* y, int64_t n, hipStream_t st) {
-  switch (op) {
-#define BVQ_CASE(OP)                                                  \
-  case OP:                                                            \
-    launch_map<T, 1>(x, nullptr, nullptr, y, n, UnaryF<T, OP>(), st); \
-    return BVQ_OK;
-    BVQ_CASE(BVQ_OP_ROUND)
-    BVQ_CASE(BVQ_OP_FLOOR)
-    BVQ_CASE(BVQ_OP_CEIL)
-    BVQ_CASE(BVQ_OP_ROUND_TO_ZERO)
-    BVQ_CASE(BVQ_OP_DPU_ROUND)
-    BVQ_CASE(BVQ_OP_BINARY_SIGN)
-    BVQ_CASE(BVQ_OP_TERNARY_SIGN)
-    BVQ_CASE(BVQ_OP_ABS)
-#undef BVQ_CASE
-    default:
-      set_error("bvq_unary: bad op %d", op);
-      return BVQ_ERR_INVALID;
-  }
-}
-
 // torch.clamp / clamp_min with scalar bounds already rounded to T; NaN propagates
 struct ScalarClampF {
   float lo, hi;
@@ -194,23 +172,6 @@ static float round_bound(double v) {
 
 using namespace bvq;
 
-#define BVQ_DISPATCH_DTYPE(dt, ...)     \
-  do {                                  \
-    if ((dt) == BVQ_F32) {              \
-      typedef float T;                  \
-      __VA_ARGS__;                      \
-    } else if ((dt) == BVQ_BF16) {      \
-      typedef bf16_t T;                 \
-      __VA_ARGS__;                      \
-    } else if ((dt) == BVQ_F16) {       \
-      typedef f16_t T;                  \
-      __VA_ARGS__;                      \
-    } else {                            \
-      set_error("bad dtype %d", (dt));  \
-      return BVQ_ERR_INVALID;           \
-    }                                   \
-  } while (0)
-
 static int check_n(const char* fn, int64_t n) {
   if (n < 0) {
     set_error("%s: negative size", fn);
@@ -226,7 +187,13 @@ extern "C" int bvq_unary(int op, int dtype, const void* x, void* y, int64_t n, b
     set_error("bvq_unary: null pointer");
     return BVQ_ERR_INVALID;
   }
-  BVQ_DISPATCH_DTYPE(dtype, rc = dispatch_unary<T>(op, x, y, n, (hipStream_t)stream));
+  rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_value<BVQ_OP_ROUND, BVQ_OP_FLOOR, BVQ_OP_CEIL, BVQ_OP_ROUND_TO_ZERO, BVQ_OP_DPU_ROUND, BVQ_OP_BINARY_SIGN,
+                      BVQ_OP_TERNARY_SIGN, BVQ_OP_ABS>(op, [&](auto o) {
+      launch_map<T, 1>(x, nullptr, nullptr, y, n, UnaryF<T, o>(), (hipStream_t)stream);
+    });
+  });
   return rc ? rc : check_launch("bvq_unary");
 }
 
@@ -238,7 +205,8 @@ extern "C" int bvq_scalar_clamp(int dtype, const void* x, void* y, int64_t n, do
     set_error("bvq_scalar_clamp: null pointer");
     return BVQ_ERR_INVALID;
   }
-  BVQ_DISPATCH_DTYPE(dtype, {
+  rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
     ScalarClampF f;
     f.lo = round_bound<T>(lo);
     f.hi = round_bound<T>(hi);
@@ -246,7 +214,7 @@ extern "C" int bvq_scalar_clamp(int dtype, const void* x, void* y, int64_t n, do
     f.use_hi = use_hi;
     launch_map<T, 1>(x, nullptr, nullptr, y, n, f, (hipStream_t)stream);
   });
-  return check_launch("bvq_scalar_clamp");
+  return rc ? rc : check_launch("bvq_scalar_clamp");
 }
 
 extern "C" int bvq_tensor_clamp(int dtype, const void* x, const void* lo, const void* hi,
@@ -257,7 +225,8 @@ extern "C" int bvq_tensor_clamp(int dtype, const void* x, const void* lo, const 
     set_error("bvq_tensor_clamp: null pointer");
     return BVQ_ERR_INVALID;
   }
-  BVQ_DISPATCH_DTYPE(dtype, {
+  rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
     if (bounds_full) {
       launch_map<T, 3>(x, lo, hi, y, n, TensorClampFullF(), (hipStream_t)stream);
     } else {
@@ -267,7 +236,7 @@ extern "C" int bvq_tensor_clamp(int dtype, const void* x, const void* lo, const 
       launch_map<T, 1>(x, nullptr, nullptr, y, n, f, (hipStream_t)stream);
     }
   });
-  return check_launch("bvq_tensor_clamp");
+  return rc ? rc : check_launch("bvq_tensor_clamp");
 }
 
 extern "C" int bvq_tensor_clamp_bwd(int dtype, const void* g, const void* x, const void* lo,
@@ -279,7 +248,8 @@ extern "C" int bvq_tensor_clamp_bwd(int dtype, const void* g, const void* x, con
     set_error("bvq_tensor_clamp_bwd: null pointer");
     return BVQ_ERR_INVALID;
   }
-  BVQ_DISPATCH_DTYPE(dtype, {
+  rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
     if (bounds_full) {
       int64_t nb = (n + kBlock - 1) / kBlock;
       if (nb > 4096) nb = 4096;
@@ -293,7 +263,7 @@ extern "C" int bvq_tensor_clamp_bwd(int dtype, const void* g, const void* x, con
       launch_map<T, 2>(g, x, nullptr, dx, n, f, (hipStream_t)stream);
     }
   });
-  return check_launch("bvq_tensor_clamp_bwd");
+  return rc ? rc : check_launch("bvq_tensor_clamp_bwd");
 }
 
 extern "C" int bvq_abs_binary_sign_grad_bwd(int dtype, const void* g, const void* x, void* dx, int64_t n,
@@ -304,6 +274,8 @@ extern "C" int bvq_abs_binary_sign_grad_bwd(int dtype, const void* g, const void
     set_error("bvq_abs_binary_sign_grad_bwd: null pointer");
     return BVQ_ERR_INVALID;
   }
-  BVQ_DISPATCH_DTYPE(dtype, launch_map<T, 2>(g, x, nullptr, dx, n, SignMulF(), (hipStream_t)stream));
-  return check_launch("bvq_abs_binary_sign_grad_bwd");
+  rc = with_dtype(dtype, [&](auto t) {
+    launch_map<typename decltype(t)::type, 2>(g, x, nullptr, dx, n, SignMulF(), (hipStream_t)stream);
+  });
+  return rc ? rc : check_launch("bvq_abs_binary_sign_grad_bwd");
 }

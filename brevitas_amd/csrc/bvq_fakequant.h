@@ -394,43 +394,16 @@ static void fill_cols_args(ColsQuantArgs& a, const ColsPlan& cp, const bvq_quant
   a.pre_relu = d->pre_op == BVQ_PRE_RELU;
 }
 
-#define BVQ_COLS_LAUNCH(KERNEL, a, nt, st) BVQ_COLS_LAUNCH_G(KERNEL, a, nt, st, grid_for_units((a).p.units))
-// GRID workgroups (a kernel whose unit is the workgroup passes the plan's unit count)
-#define BVQ_COLS_LAUNCH_G(KERNEL, a, nt, st, GRID)                                               \
-  do {                                                                                           \
-    const dim3 grid((unsigned)(GRID)), block(kBlock);                                            \
-    const bool rne = (a).round_mode == BVQ_ROUND;                                                \
-    if (d->x_dtype == BVQ_F32) {                                                                 \
-      if (rne && nt) KERNEL<float, BVQ_ROUND, true><<<grid, block, 0, st>>>(a);                  \
-      else if (rne) KERNEL<float, BVQ_ROUND, false><<<grid, block, 0, st>>>(a);                  \
-      else KERNEL<float, kAnyRM, false><<<grid, block, 0, st>>>(a);                              \
-    } else if (d->x_dtype == BVQ_BF16) {                                                         \
-      if (rne && nt) KERNEL<bf16_t, BVQ_ROUND, true><<<grid, block, 0, st>>>(a);                 \
-      else if (rne) KERNEL<bf16_t, BVQ_ROUND, false><<<grid, block, 0, st>>>(a);                 \
-      else KERNEL<bf16_t, kAnyRM, false><<<grid, block, 0, st>>>(a);                             \
-    } else {                                                                                     \
-      if (rne && nt) KERNEL<f16_t, BVQ_ROUND, true><<<grid, block, 0, st>>>(a);                  \
-      else if (rne) KERNEL<f16_t, BVQ_ROUND, false><<<grid, block, 0, st>>>(a);                  \
-      else KERNEL<f16_t, kAnyRM, false><<<grid, block, 0, st>>>(a);                              \
-    }                                                                                            \
-  } while (0)
+// the column-mapped quantizer kernels (x and the compute dtype agree on this route): f(type_tag<T>, int_c<RM>,
+// std::bool_constant<NT>) for the instantiation the streaming policy gives d's dtype and rounding mode
+template <typename F>
+static int with_cols_variant(const bvq_quant_desc* d, bool nt, F&& f) {
+  return with_dtype(d->x_dtype, [&](auto t) {
+    return with_round_variant(d->round_mode, nt, [&](auto rm, auto ntc) { return call_rc(f, t, rm, ntc); });
+  });
+}
 
 // instantiated vector widths: 16 bytes of x per lane, or one element (ragged / misaligned rows)
 static int snap_vec(int vec, int full) { return vec == full ? full : 1; }
-
-#define BVQ_DISPATCH_PAIR(d, CALL)                                      \
-  do {                                                                  \
-    if ((d)->x_dtype == BVQ_F32) {                                      \
-      CALL(float, float);                                               \
-    } else if ((d)->x_dtype == BVQ_BF16 && (d)->ct_dtype == BVQ_BF16) { \
-      CALL(bf16_t, bf16_t);                                             \
-    } else if ((d)->x_dtype == BVQ_BF16) {                              \
-      CALL(bf16_t, float);                                              \
-    } else if ((d)->x_dtype == BVQ_F16 && (d)->ct_dtype == BVQ_F16) {   \
-      CALL(f16_t, f16_t);                                               \
-    } else {                                                            \
-      CALL(f16_t, float);                                               \
-    }                                                                   \
-  } while (0)
 
 }  // namespace bvq

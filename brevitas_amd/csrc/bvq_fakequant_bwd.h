@@ -877,60 +877,20 @@ __global__ void shard_unpack_deposit_kernel(const double* __restrict__ all, int3
   dp[flat] = from_f<T>(to_f<T>(dp[flat]) + term);
 }
 
-template <typename XT, typename CT, int MODE>
-static void launch_bwd_mode(const QuantArgs& a, int vec, bool nt, hipStream_t st) {
-  constexpr int V = elem<XT>::vec;
-  const dim3 grid(grid_for_units(a.t.units)), block(kBlock);
-  const bool rne = a.round_mode == BVQ_ROUND;
-  // Instantiations: round-half-even at full vector width with either cache policy; every other rounding mode shares
-  // one kernel (default policy), and so do ragged / misaligned rows (one element per lane).  The one-launch form
-  // (kBwdDsArrive) exists for the first pair only: bwd_stats_impl sends everything else to the two-launch route.
-  if (vec == V) {
-    if (rne && nt) {
-      fakequant_bwd_kernel<XT, CT, V, BVQ_ROUND, MODE, true><<<grid, block, 0, st>>>(a);
-      return;
-    }
-    if (rne) {
-      fakequant_bwd_kernel<XT, CT, V, BVQ_ROUND, MODE, false><<<grid, block, 0, st>>>(a);
-      return;
-    }
-  }
-  if constexpr (MODE != kBwdDsArrive) {
-    if (vec == V)
-      fakequant_bwd_kernel<XT, CT, V, kAnyRM, MODE, false><<<grid, block, 0, st>>>(a);
-    else if (rne)
-      fakequant_bwd_kernel<XT, CT, 1, BVQ_ROUND, MODE, false><<<grid, block, 0, st>>>(a);
-    else
-      fakequant_bwd_kernel<XT, CT, 1, kAnyRM, MODE, false><<<grid, block, 0, st>>>(a);
-  }
-}
-// the launches the one-launch backward is instantiated for
-static inline bool bwd_arrive_covers(int vec, int full, int round_mode) { return vec == full && round_mode == BVQ_ROUND; }
-
+// the row-mapped backward of one MODE under the streaming instantiation policy (with_stream_variant); the one-launch
+// form (kBwdDsArrive) exists for full-width half-even rounding only: bwd_stats_impl sends everything else to the
+// two-launch route
 template <typename XT, typename CT>
-void launch_bwd(const QuantArgs& a, int vec, int mode, bool nt, hipStream_t st) {
-  switch (mode) {
-    case kBwdDx:
-      launch_bwd_mode<XT, CT, kBwdDx>(a, vec, nt, st);
-      break;
-    case kBwdDs:
-      launch_bwd_mode<XT, CT, kBwdDs>(a, vec, nt, st);
-      break;
-    case kBwdDsDzp:
-      launch_bwd_mode<XT, CT, kBwdDsDzp>(a, vec, nt, st);
-      break;
-    case kBwdDsBounds:
-      launch_bwd_mode<XT, CT, kBwdDsBounds>(a, vec, nt, st);
-      break;
-    case kBwdDsArrive:
-      launch_bwd_mode<XT, CT, kBwdDsArrive>(a, vec, nt, st);
-      break;
-    default:
-      launch_bwd_mode<XT, CT, kBwdDsTies>(a, vec, nt, st);
-      break;
-  }
+int launch_bwd(const QuantArgs& a, int vec, int mode, bool nt, hipStream_t st) {
+  return with_value<kBwdDx, kBwdDs, kBwdDsDzp, kBwdDsBounds, kBwdDsArrive, kBwdDsTies>(mode, [&](auto m) {
+    constexpr int MODE = decltype(m)::value;
+    return with_stream_variant<elem<XT>::vec, MODE == kBwdDsArrive>(
+        "bvq_fakequant_bwd", vec, a.round_mode, nt, [&](auto v, auto rm, auto ntc) {
+          fakequant_bwd_kernel<XT, CT, v, rm, MODE, ntc><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+        });
+  });
 }
 
-#define BVQ_LAUNCH_BWD(XT, CT) void launch_bwd<XT, CT>(const QuantArgs&, int, int, bool, hipStream_t)
+#define BVQ_LAUNCH_BWD(XT, CT) int launch_bwd<XT, CT>(const QuantArgs&, int, int, bool, hipStream_t)
 
 }  // namespace bvq

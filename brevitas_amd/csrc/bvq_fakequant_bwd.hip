@@ -12,6 +12,12 @@ extern template BVQ_LAUNCH_BWD(f16_t, float);
 
 using namespace bvq;
 
+static int launch_bwd_pair(const bvq_quant_desc* d, const QuantArgs& a, int vec, int mode, bool nt, hipStream_t st) {
+  return with_pair(d->x_dtype, d->ct_dtype, [&](auto xt, auto ct) {
+    return launch_bwd<typename decltype(xt)::type, typename decltype(ct)::type>(a, vec, mode, nt, st);
+  });
+}
+
 // the backward's decomposition: quantizer-style tiling with every unit addressable through 32-bit buffer offsets
 // (4 = the widest element; the same bound for every dtype so that workspace sizing and launch agree)
 static Tiling bwd_tiling(int64_t outer, int32_t channels, int64_t row_len, int vec) {
@@ -104,8 +110,10 @@ static int fakequant_bwd_impl(const bvq_quant_desc* d, const void* g, const void
       ca.tie_stat = tie_stat;
       ca.tie_info = reinterpret_cast<unsigned long long*>(tie_info);
       const bool cnt = n * (int64_t)(3 * dtype_size(d->x_dtype)) >= nt_threshold_bytes();
-      BVQ_COLS_LAUNCH_G(fakequant_bwd_cols_kernel, ca, cnt, st, cp.units);
-      rc = check_launch("bvq_fakequant_bwd/cols");
+      rc = with_cols_variant(d, cnt, [&](auto t, auto rm, auto ntc) {
+        fakequant_bwd_cols_kernel<typename decltype(t)::type, rm, ntc><<<(unsigned)cp.units, kBlock, 0, st>>>(ca);
+      });
+      if (!rc) rc = check_launch("bvq_fakequant_bwd/cols");
       if (rc) return rc;
       if (dscale) {
         float* folded = nullptr;
@@ -149,10 +157,8 @@ static int fakequant_bwd_impl(const bvq_quant_desc* d, const void* g, const void
   const int mode = dbounds ? kBwdDsBounds : (tie_stat ? kBwdDsTies : (dzp ? kBwdDsDzp : (dscale ? kBwdDs : kBwdDx)));
   const bool nt =
       n * (int64_t)(2 * dtype_size(d->x_dtype) + dtype_size(d->ct_dtype)) >= nt_threshold_bytes();
-#define BVQ_CALL(XT, CT) launch_bwd<XT, CT>(a, vec, mode, nt, st)
-  BVQ_DISPATCH_PAIR(d, BVQ_CALL);
-#undef BVQ_CALL
-  rc = check_launch("bvq_fakequant_bwd");
+  rc = launch_bwd_pair(d, a, vec, mode, nt, st);
+  if (!rc) rc = check_launch("bvq_fakequant_bwd");
   if (rc) return rc;
   if (need_sums) {
     // dbounds: [d(qmin) per channel | d(qmax) per channel] (the bounds themselves are scalars: the caller adds the
@@ -258,7 +264,9 @@ extern "C" int bvq_fakequant_bwd_stats_onepass_supported(const bvq_quant_desc* d
   int64_t units, per_channel;
   if (validate(d) || !bwd_stats_supported(d, units, per_channel)) return 0;
   if (cols_quant_plan(d, nullptr, nullptr, nullptr).ok) return 0;  // column-mapped layouts: two launches
-  return 1;
+  // the one-launch kernel's instantiations (x's alignment, which may still narrow the vector width, is checked at launch)
+  const int full = 16 / dtype_size(d->x_dtype);
+  return stream_full_rne(full, full, d->round_mode) ? 1 : 0;
 }
 
 extern "C" int bvq_fakequant_bwd_stats_onepass(const bvq_quant_desc* d, const void* g, const void* x,
@@ -317,16 +325,11 @@ extern "C" int bvq_shard_unpack_deposit(int dtype, const void* x, void* dx, cons
   const dim3 grid((unsigned)((channels + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
   const long long* fp = reinterpret_cast<const long long*>(first_pos);
-  if (dtype == BVQ_F32)
-    shard_unpack_deposit_kernel<float><<<grid, block, 0, st>>>(gathered, world, (int32_t)channels, rank, fp, x, dx, inner,
-                                                              gs, dscale_total);
-  else if (dtype == BVQ_BF16)
-    shard_unpack_deposit_kernel<bf16_t><<<grid, block, 0, st>>>(gathered, world, (int32_t)channels, rank, fp, x, dx, inner,
-                                                               gs, dscale_total);
-  else
-    shard_unpack_deposit_kernel<f16_t><<<grid, block, 0, st>>>(gathered, world, (int32_t)channels, rank, fp, x, dx, inner,
-                                                              gs, dscale_total);
-  return check_launch("bvq_shard_unpack_deposit");
+  const int rc = with_dtype(dtype, [&](auto t) {
+    shard_unpack_deposit_kernel<typename decltype(t)::type><<<grid, block, 0, st>>>(gathered, world, (int32_t)channels,
+                                                                                    rank, fp, x, dx, inner, gs, dscale_total);
+  });
+  return rc ? rc : check_launch("bvq_shard_unpack_deposit");
 }
 
 static int bwd_stats_impl(const bvq_quant_desc* d, const void* g, const void* x, const void* scale, const void* zp,
@@ -389,8 +392,10 @@ static int bwd_stats_impl(const bvq_quant_desc* d, const void* g, const void* x,
       ca.pos_part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + pos_off_c);
       ca.tie_stat = stat;
       launch_tie_init(ca.pos_part, cp.L, st);
-      BVQ_COLS_LAUNCH_G(fakequant_bwd_cols_kernel, ca, nt, st, cp.units);
-      rc = check_launch("bvq_fakequant_bwd_stats/cols");
+      rc = with_cols_variant(d, nt, [&](auto t, auto rm, auto ntc) {
+        fakequant_bwd_cols_kernel<typename decltype(t)::type, rm, ntc><<<(unsigned)cp.units, kBlock, 0, st>>>(ca);
+      });
+      if (!rc) rc = check_launch("bvq_fakequant_bwd_stats/cols");
       if (rc) return rc;
       float* ds_fold = nullptr;
       unsigned long long* pos_fold = ca.pos_part;
@@ -411,17 +416,11 @@ static int bwd_stats_impl(const bvq_quant_desc* d, const void* g, const void* x,
         channel_finish_kernel<float><<<cgrid, dim3(kBlock), 0, st>>>(fa);  // (the message path touches no tensor element)
         return check_launch("bvq_fakequant_bwd_shard/cols_finish");
       }
-      const dim3 fgrid((unsigned)channels), fblock(kBlock);
-      if (d->x_dtype == BVQ_F32)
-        bwd_stats_finish_kernel<float><<<fgrid, fblock, 0, st>>>(ds_fold, pos_fold, dscale, gs, x, dx, 1, channels,
-                                                                 d->inner, d->inner);
-      else if (d->x_dtype == BVQ_BF16)
-        bwd_stats_finish_kernel<bf16_t><<<fgrid, fblock, 0, st>>>(ds_fold, pos_fold, dscale, gs, x, dx, 1, channels,
-                                                                  d->inner, d->inner);
-      else
-        bwd_stats_finish_kernel<f16_t><<<fgrid, fblock, 0, st>>>(ds_fold, pos_fold, dscale, gs, x, dx, 1, channels,
-                                                                 d->inner, d->inner);
-      return check_launch("bvq_fakequant_bwd_stats/cols_finish");
+      rc = with_dtype(d->x_dtype, [&](auto t) {
+        bwd_stats_finish_kernel<typename decltype(t)::type><<<(unsigned)channels, kBlock, 0, st>>>(
+            ds_fold, pos_fold, dscale, gs, x, dx, 1, channels, d->inner, d->inner);
+      });
+      return rc ? rc : check_launch("bvq_fakequant_bwd_stats/cols_finish");
     }
   }
   const void* ptrs[3] = {x, g, dx};
@@ -450,38 +449,28 @@ static int bwd_stats_impl(const bvq_quant_desc* d, const void* g, const void* x,
     a.shard_pos = shard->pos;
     a.shard_rank = shard->rank;
   }
-  if (arrive && !bwd_arrive_covers(vec, full, d->round_mode)) arrive = nullptr;  // two launches for the rare forms
+  if (arrive && !stream_full_rne(vec, full, d->round_mode)) arrive = nullptr;  // two launches for the rare forms
   if (arrive) {  // one launch: the wave that completes a channel finishes it
     a.arrive = arrive;
     a.dscale_out = dscale;
     a.gs_scale_dtype = scale_dtype;
     a.gs_quot_dtype = quot_dtype;
     a.gs_int_threshold = (float)int_threshold;
-#define BVQ_CALL(XT, CT) launch_bwd<XT, CT>(a, vec, kBwdDsArrive, nt, st)
-    BVQ_DISPATCH_PAIR(d, BVQ_CALL);
-#undef BVQ_CALL
-    return check_launch("bvq_fakequant_bwd_stats_onepass");
+    rc = launch_bwd_pair(d, a, vec, kBwdDsArrive, nt, st);
+    return rc ? rc : check_launch("bvq_fakequant_bwd_stats_onepass");
   }
-#define BVQ_CALL(XT, CT) launch_bwd<XT, CT>(a, vec, kBwdDsTies, nt, st)
-  BVQ_DISPATCH_PAIR(d, BVQ_CALL);
-#undef BVQ_CALL
-  rc = check_launch("bvq_fakequant_bwd_stats");
+  rc = launch_bwd_pair(d, a, vec, kBwdDsTies, nt, st);
+  if (!rc) rc = check_launch("bvq_fakequant_bwd_stats");
   if (rc) return rc;
   if (shard) {
     const dim3 cgrid((unsigned)((channels + kWavesPerBlock - 1) / kWavesPerBlock));
     channel_finish_kernel<float><<<cgrid, dim3(kBlock), 0, st>>>(a);  // (the message path touches no tensor element)
     return check_launch("bvq_fakequant_bwd_shard/finish");
   }
-  const dim3 grid((unsigned)channels), block(kBlock);
-  if (d->x_dtype == BVQ_F32)
-    bwd_stats_finish_kernel<float><<<grid, block, 0, st>>>(a.ds_part, a.pos_part, dscale, gs, x, dx, a.t.nob, channels,
-                                                           a.t.ppr, d->inner);
-  else if (d->x_dtype == BVQ_BF16)
-    bwd_stats_finish_kernel<bf16_t><<<grid, block, 0, st>>>(a.ds_part, a.pos_part, dscale, gs, x, dx, a.t.nob, channels,
-                                                            a.t.ppr, d->inner);
-  else
-    bwd_stats_finish_kernel<f16_t><<<grid, block, 0, st>>>(a.ds_part, a.pos_part, dscale, gs, x, dx, a.t.nob, channels,
-                                                           a.t.ppr, d->inner);
-  return check_launch("bvq_fakequant_bwd_stats/finish");
+  rc = with_dtype(d->x_dtype, [&](auto t) {
+    bwd_stats_finish_kernel<typename decltype(t)::type><<<(unsigned)channels, kBlock, 0, st>>>(
+        a.ds_part, a.pos_part, dscale, gs, x, dx, a.t.nob, channels, a.t.ppr, d->inner);
+  });
+  return rc ? rc : check_launch("bvq_fakequant_bwd_stats/finish");
 }
 

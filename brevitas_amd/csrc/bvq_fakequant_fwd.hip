@@ -446,27 +446,6 @@ __global__ __launch_bounds__(kFusedMaxWaves * kWave) void fused_absmax_fakequant
   }
 }
 
-template <typename XT, typename CT>
-static void launch_fwd(const QuantArgs& a, int vec, bool nt, hipStream_t st) {
-  constexpr int V = elem<XT>::vec;
-  const dim3 grid(grid_for_units(a.t.units)), block(kBlock);
-  const bool rne = a.round_mode == BVQ_ROUND;
-  if (vec == V) {
-    if (rne && nt)
-      fakequant_fwd_kernel<XT, CT, V, BVQ_ROUND, true><<<grid, block, 0, st>>>(a);
-    else if (rne)
-      fakequant_fwd_kernel<XT, CT, V, BVQ_ROUND, false><<<grid, block, 0, st>>>(a);
-    else  // (the other rounding modes share one kernel, default cache policy)
-      fakequant_fwd_kernel<XT, CT, V, kAnyRM, false><<<grid, block, 0, st>>>(a);
-  } else {
-    if (rne)
-      fakequant_fwd_kernel<XT, CT, 1, BVQ_ROUND, false><<<grid, block, 0, st>>>(a);
-    else
-      fakequant_fwd_kernel<XT, CT, 1, kAnyRM, false><<<grid, block, 0, st>>>(a);
-  }
-}
-
-
 }  // namespace bvq
 
 using namespace bvq;
@@ -492,8 +471,10 @@ static int fakequant_fwd_impl(const bvq_quant_desc* d, const void* x, const void
       ca.zp = zp;
       hipStream_t cst = (hipStream_t)stream;
       const bool cnt = n * (int64_t)(2 * dtype_size(d->x_dtype)) >= nt_threshold_bytes();
-      BVQ_COLS_LAUNCH(fakequant_fwd_cols_kernel, ca, cnt, cst);
-      return check_launch("bvq_fakequant_fwd/cols");
+      rc = with_cols_variant(d, cnt, [&](auto t, auto rm, auto ntc) {
+        fakequant_fwd_cols_kernel<typename decltype(t)::type, rm, ntc><<<grid_for_units(cp.units), kBlock, 0, cst>>>(ca);
+      });
+      return rc ? rc : check_launch("bvq_fakequant_fwd/cols");
     }
   }
   int64_t outer, row_len;
@@ -514,10 +495,13 @@ static int fakequant_fwd_impl(const bvq_quant_desc* d, const void* x, const void
   fill_args(a, d);
   hipStream_t st = (hipStream_t)stream;
   const bool nt = n * (int64_t)(dtype_size(d->x_dtype) + dtype_size(d->ct_dtype)) >= nt_threshold_bytes();
-#define BVQ_CALL(XT, CT) launch_fwd<XT, CT>(a, vec, nt, st)
-  BVQ_DISPATCH_PAIR(d, BVQ_CALL);
-#undef BVQ_CALL
-  return check_launch("bvq_fakequant_fwd");
+  rc = with_pair(d->x_dtype, d->ct_dtype, [&](auto xt, auto ct) {
+    using XT = typename decltype(xt)::type;
+    return with_stream_variant<elem<XT>::vec>("bvq_fakequant_fwd", vec, a.round_mode, nt, [&](auto v, auto rm, auto ntc) {
+      fakequant_fwd_kernel<XT, typename decltype(ct)::type, v, rm, ntc><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+    });
+  });
+  return rc ? rc : check_launch("bvq_fakequant_fwd");
 }
 
 extern "C" int bvq_fakequant_fwd(const bvq_quant_desc* d, const void* x, const void* scale,
@@ -557,11 +541,16 @@ struct FusedShape {
   int vec;
 };
 
+// 0: no one-launch statistic + quantizer (bvq_stats_fakequant_fwd_workspace_bytes reports it as not covered)
+#ifndef BVQ_FUSED_FWD
+#define BVQ_FUSED_FWD 1
+#endif
+constexpr bool kFusedFwd = BVQ_FUSED_FWD != 0;
+
 // what both one-launch forms need: x and y of one dtype, dequantized output, whole 16-byte chunks
 static FusedShape fused_shape(const bvq_quant_desc* d, const void* x, const void* y) {
   FusedShape f = {};
-  static const int enabled = env_flag("BVQ_FUSED_FWD", 1);
-  if (!enabled) return f;
+  if (!kFusedFwd) return f;
   if (d->x_dtype != d->ct_dtype || d->out_kind != BVQ_OUT_DEQUANT) return f;
   if (d->zp_per_channel) return f;
   const bool pc = d->scale_per_channel && d->channels > 1;
@@ -612,7 +601,6 @@ extern "C" int bvq_stats_fakequant_fwd(const bvq_quant_desc* d, const void* x, d
   hipStream_t st = (hipStream_t)stream;
   const bool pc = d->scale_per_channel && d->channels > 1;
   const int64_t channels = pc ? d->channels : 1;
-  const bool rne = d->round_mode == BVQ_ROUND;
   FusedPlan p;
   if (fused_plan(d, x, y, p)) {
     FusedArgs a = {};
@@ -637,21 +625,11 @@ extern "C" int bvq_stats_fakequant_fwd(const bvq_quant_desc* d, const void* x, d
     a.round_mode = d->round_mode;
     a.pre_relu = d->pre_op == BVQ_PRE_RELU;
     const dim3 grid((unsigned)p.nblocks), block((unsigned)(p.waves * kWave));
-#define BVQ_FUSED(T)                                                        \
-  do {                                                                      \
-    if (rne)                                                                \
-      fused_absmax_fakequant_kernel<T, BVQ_ROUND><<<grid, block, 0, st>>>(a); \
-    else                                                                    \
-      fused_absmax_fakequant_kernel<T, kAnyRM><<<grid, block, 0, st>>>(a);   \
-  } while (0)
-    if (d->x_dtype == BVQ_F32)
-      BVQ_FUSED(float);
-    else if (d->x_dtype == BVQ_BF16)
-      BVQ_FUSED(bf16_t);
-    else
-      BVQ_FUSED(f16_t);
-#undef BVQ_FUSED
-    return check_launch("bvq_stats_fakequant_fwd");
+    // (one cache policy: the kernel streams non-temporally whatever the size)
+    rc = with_cols_variant(d, false, [&](auto t, auto rm, auto) {
+      fused_absmax_fakequant_kernel<typename decltype(t)::type, rm><<<grid, block, 0, st>>>(a);
+    });
+    return rc ? rc : check_launch("bvq_stats_fakequant_fwd");
   }
   set_error("bvq_stats_fakequant_fwd: shape / layout not covered by the one-launch form");
   return BVQ_ERR_UNSUPPORTED;

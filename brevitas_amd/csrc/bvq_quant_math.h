@@ -39,8 +39,6 @@ __device__ __forceinline__ float round_op(float t) {
   }
 }
 
-// runtime-selected rounding mode (the rarely used variants share one kernel instantiation)
-constexpr int kAnyRM = -1;
 template <typename CT>
 __device__ __forceinline__ float round_any(float t, int mode) {
   switch (mode) {

@@ -209,19 +209,6 @@ __global__ void kth_init_kernel(uint32_t* prefix, int64_t* krem, int64_t k, int3
   }
 }
 
-template <typename T, bool ABS>
-static void launch_hist(const SelArgs& a, int vec, bool nt, hipStream_t st) {
-  constexpr int V = elem<T>::vec;
-  const dim3 grid(grid_for_units(a.t.units)), block(kBlock);
-  if (vec == V && nt)
-    kth_hist_kernel<T, V, ABS, true><<<grid, block, 0, st>>>(a);
-  else if (vec == V)
-    kth_hist_kernel<T, V, ABS, false><<<grid, block, 0, st>>>(a);
-  else
-    kth_hist_kernel<T, 1, ABS, false><<<grid, block, 0, st>>>(a);
-}
-
-
 // ---- per-tensor route of bvq_kth_value: 15-bit first digit in LDS, the rest through global counters ----------
 // A workgroup of 1024 threads keeps ALL 32768 bins of the key's top 15 bits in LDS (128 of gfx950's 160 KB).
 //  * |x| of a 16-bit type: that IS the whole key -- one streaming read decides the k-th value, where the digit
@@ -622,21 +609,15 @@ extern "C" int bvq_kth_hist(int abs_key, int dtype, const void* x, int64_t outer
   a.shift = shift;
   a.first_pass = pass == 0;
   const bool nt = outer * channels * inner * (int64_t)dtype_size(dtype) >= nt_threshold_bytes();
-#define BVQ_HIST(T)                             \
-  do {                                          \
-    if (abs_key)                                \
-      launch_hist<T, true>(a, vec, nt, st);     \
-    else                                        \
-      launch_hist<T, false>(a, vec, nt, st);    \
-  } while (0)
-  if (dtype == BVQ_F32)
-    BVQ_HIST(float);
-  else if (dtype == BVQ_BF16)
-    BVQ_HIST(bf16_t);
-  else
-    BVQ_HIST(f16_t);
-#undef BVQ_HIST
-  return check_launch("bvq_kth_hist");
+  rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_bool(abs_key, [&](auto abs) {
+      return with_read_variant<elem<T>::vec>(vec, nt, [&](auto v, auto ntc) {
+        kth_hist_kernel<T, v, abs, ntc><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+      });
+    });
+  });
+  return rc ? rc : check_launch("bvq_kth_hist");
 }
 
 extern "C" int bvq_kth_pick(int dtype, int64_t channels, int pass, int rule, double q, void* workspace,
@@ -667,28 +648,22 @@ extern "C" int bvq_kth_finish(int abs_key, int dtype, int64_t channels, void* ou
   hipStream_t st = (hipStream_t)stream;
   const SelWorkspace w = sel_workspace(dtype, channels, workspace);
   const unsigned nb = (unsigned)((channels + 255) / 256);
-#define BVQ_STORE(T)                                                                       \
-  do {                                                                                     \
-    if (abs_key)                                                                           \
-      kth_store_kernel<T, true><<<dim3(nb), dim3(256), 0, st>>>(w.prefix, out, (int32_t)channels);  \
-    else                                                                                   \
-      kth_store_kernel<T, false><<<dim3(nb), dim3(256), 0, st>>>(w.prefix, out, (int32_t)channels); \
-  } while (0)
-  if (dtype == BVQ_F32)
-    BVQ_STORE(float);
-  else if (dtype == BVQ_BF16)
-    BVQ_STORE(bf16_t);
-  else
-    BVQ_STORE(f16_t);
-#undef BVQ_STORE
-  return check_launch("bvq_kth_finish");
+  rc = with_dtype(dtype, [&](auto t) {
+    return with_bool(abs_key, [&](auto abs) {
+      kth_store_kernel<typename decltype(t)::type, abs><<<nb, 256, 0, st>>>(w.prefix, out, (int32_t)channels);
+    });
+  });
+  return rc ? rc : check_launch("bvq_kth_finish");
 }
 
 // per-tensor route (see kth_hist15_kernel): nk = 1 or 2 ranks from ONE histogram read (+ one read for the low bits
 // of both); out[nk]
+#ifndef BVQ_KTH_WIDE
+#define BVQ_KTH_WIDE 1  // 0: the digit passes for every layout
+#endif
+constexpr bool kKthWide = BVQ_KTH_WIDE != 0;
 static bool wide_select_applies(int64_t channels, int64_t n, const void* x) {
-  static const int wide = env_flag("BVQ_KTH_WIDE", 1);
-  return wide && channels == 1 && n >= ((int64_t)1 << 22) && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  return kKthWide && channels == 1 && n >= ((int64_t)1 << 22) && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
 }
 
 static int wide_select(int abs_key, int dtype, const void* x, int64_t n, const int64_t* ks, int nk, void* out,
@@ -710,44 +685,27 @@ static int wide_select(int abs_key, int dtype, const void* x, int64_t n, const i
   kth_zero_kernel<<<dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st>>>(hist, words);
   const bool nt = n * (int64_t)dtype_size(dtype) >= nt_threshold_bytes();
   // one workgroup per CU is all the LDS allows; 256 of them cover the chip
-#define BVQ_WIDE(T, ABS)                                                                                          \
-  do {                                                                                                            \
-    const T* xp = reinterpret_cast<const T*>(x);                                                                  \
-    if (nt)                                                                                                       \
-      kth_hist15_kernel<T, ABS, true><<<dim3(256), dim3(kBlock15), 0, st>>>(xp, n, shift, hist);                  \
-    else                                                                                                          \
-      kth_hist15_kernel<T, ABS, false><<<dim3(256), dim3(kBlock15), 0, st>>>(xp, n, shift, hist);                 \
-    for (int i = 0; i < nk; ++i)                                                                                  \
-      kth_pick_wide_kernel<<<dim3(1), dim3(kBlock15), 0, st>>>(hist, kBins15, 15, 1, ks[i], sel + i, krem + i);   \
-    if (shift) {                                                                                                  \
-      if (shift <= kDigitBits)                                                                                    \
-        kth_low_kernel<T, ABS, false, true><<<dim3(1024), dim3(kBlock), 0, st>>>(xp, n, shift, sel, low, nk);     \
-      else if (nt)                                                                                                \
-        kth_low_kernel<T, ABS, true, false><<<dim3(2048), dim3(kBlock), 0, st>>>(xp, n, shift, sel, low, nk);     \
-      else                                                                                                        \
-        kth_low_kernel<T, ABS, false, false><<<dim3(2048), dim3(kBlock), 0, st>>>(xp, n, shift, sel, low, nk);    \
-      for (int i = 0; i < nk; ++i)                                                                                \
-        kth_pick_wide_kernel<<<dim3(1), dim3(kBlock15), 0, st>>>(low + i * lstride, 1 << shift, shift, 0, 0,      \
-                                                                 sel + i, krem + i);                              \
-    }                                                                                                             \
-    kth_store_kernel<T, ABS><<<dim3(1), dim3(64), 0, st>>>(sel, out, nk);                                         \
-  } while (0)
-#define BVQ_WIDE_DT(ABS)        \
-  do {                          \
-    if (dtype == BVQ_F32)       \
-      BVQ_WIDE(float, ABS);     \
-    else if (dtype == BVQ_BF16) \
-      BVQ_WIDE(bf16_t, ABS);    \
-    else                        \
-      BVQ_WIDE(f16_t, ABS);     \
-  } while (0)
-  if (abs_key)
-    BVQ_WIDE_DT(true);
-  else
-    BVQ_WIDE_DT(false);
-#undef BVQ_WIDE_DT
-#undef BVQ_WIDE
-  return check_launch("bvq_kth_value/wide");
+  const int rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_bool(abs_key, [&](auto abs) {
+      const T* xp = reinterpret_cast<const T*>(x);
+      with_bool(nt, [&](auto ntc) { kth_hist15_kernel<T, abs, ntc><<<256, kBlock15, 0, st>>>(xp, n, shift, hist); });
+      for (int i = 0; i < nk; ++i)
+        kth_pick_wide_kernel<<<1, kBlock15, 0, st>>>(hist, kBins15, 15, 1, ks[i], sel + i, krem + i);
+      if (shift) {
+        if (shift <= kDigitBits)
+          kth_low_kernel<T, abs, false, true><<<1024, kBlock, 0, st>>>(xp, n, shift, sel, low, nk);
+        else
+          with_bool(nt, [&](auto ntc) {
+            kth_low_kernel<T, abs, ntc, false><<<2048, kBlock, 0, st>>>(xp, n, shift, sel, low, nk);
+          });
+        for (int i = 0; i < nk; ++i)
+          kth_pick_wide_kernel<<<1, kBlock15, 0, st>>>(low + i * lstride, 1 << shift, shift, 0, 0, sel + i, krem + i);
+      }
+      kth_store_kernel<T, abs><<<1, 64, 0, st>>>(sel, out, nk);
+    });
+  });
+  return rc ? rc : check_launch("bvq_kth_value/wide");
 }
 
 // ---- the per-tensor route in steps, for a batch-sharded tensor (include/bvq.h, bvq_kthw_*) --------------------
@@ -834,41 +792,24 @@ extern "C" int bvq_kthw_hist(int abs_key, int dtype, const void* x, int64_t n, i
   g15 = g15 < 1 ? 1 : (g15 > 256 ? 256 : g15);
   unsigned glow = (unsigned)((chunks + kBlock * kSelUnroll - 1) / (kBlock * kSelUnroll));
   glow = glow < 1 ? 1 : (glow > 2048 ? 2048 : glow);
-#define BVQ_KTHW(T, ABS)                                                                                              \
-  do {                                                                                                                \
-    const T* xp = reinterpret_cast<const T*>(xa);                                                                     \
-    if (pass == 0) {                                                                                                  \
-      if (nt)                                                                                                         \
-        kth_hist15_kernel<T, ABS, true><<<dim3(g15), dim3(kBlock15), 0, st>>>(xp, na, shift, w.hist, (int32_t)head);  \
-      else                                                                                                            \
-        kth_hist15_kernel<T, ABS, false><<<dim3(g15), dim3(kBlock15), 0, st>>>(xp, na, shift, w.hist, (int32_t)head); \
-    } else if (shift <= kDigitBits) {                                                                                 \
-      kth_low_kernel<T, ABS, false, true><<<dim3(glow > 1024 ? 1024 : glow), dim3(kBlock), 0, st>>>(                  \
-          xp, na, shift, w.sel, w.low, 1, (int32_t)head);                                                             \
-    } else if (nt) {                                                                                                  \
-      kth_low_kernel<T, ABS, true, false><<<dim3(glow), dim3(kBlock), 0, st>>>(xp, na, shift, w.sel, w.low, 1,        \
-                                                                             (int32_t)head);                         \
-    } else {                                                                                                          \
-      kth_low_kernel<T, ABS, false, false><<<dim3(glow), dim3(kBlock), 0, st>>>(xp, na, shift, w.sel, w.low, 1,       \
-                                                                              (int32_t)head);                        \
-    }                                                                                                                 \
-  } while (0)
-#define BVQ_KTHW_DT(ABS)        \
-  do {                          \
-    if (dtype == BVQ_F32)       \
-      BVQ_KTHW(float, ABS);     \
-    else if (dtype == BVQ_BF16) \
-      BVQ_KTHW(bf16_t, ABS);    \
-    else                        \
-      BVQ_KTHW(f16_t, ABS);     \
-  } while (0)
-  if (abs_key)
-    BVQ_KTHW_DT(true);
-  else
-    BVQ_KTHW_DT(false);
-#undef BVQ_KTHW_DT
-#undef BVQ_KTHW
-  return check_launch("bvq_kthw_hist");
+  rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_bool(abs_key, [&](auto abs) {
+      const T* xp = reinterpret_cast<const T*>(xa);
+      if (pass == 0)
+        with_bool(nt, [&](auto ntc) {
+          kth_hist15_kernel<T, abs, ntc><<<g15, kBlock15, 0, st>>>(xp, na, shift, w.hist, (int32_t)head);
+        });
+      else if (shift <= kDigitBits)
+        kth_low_kernel<T, abs, false, true><<<glow > 1024 ? 1024 : glow, kBlock, 0, st>>>(xp, na, shift, w.sel, w.low, 1,
+                                                                                          (int32_t)head);
+      else
+        with_bool(nt, [&](auto ntc) {
+          kth_low_kernel<T, abs, ntc, false><<<glow, kBlock, 0, st>>>(xp, na, shift, w.sel, w.low, 1, (int32_t)head);
+        });
+    });
+  });
+  return rc ? rc : check_launch("bvq_kthw_hist");
 }
 
 extern "C" int bvq_kthw_pick(int abs_key, int dtype, int pass, int rule, int64_t k, double q, void* workspace,
@@ -901,21 +842,12 @@ extern "C" int bvq_kthw_finish(int abs_key, int dtype, void* out, void* workspac
   }
   hipStream_t st = (hipStream_t)stream;
   const WideWs w = wide_ws(dtype, workspace);
-#define BVQ_KTHW_STORE(T)                                             \
-  do {                                                                \
-    if (abs_key)                                                      \
-      kth_store_kernel<T, true><<<dim3(1), dim3(64), 0, st>>>(w.sel, out, 1);  \
-    else                                                              \
-      kth_store_kernel<T, false><<<dim3(1), dim3(64), 0, st>>>(w.sel, out, 1); \
-  } while (0)
-  if (dtype == BVQ_F32)
-    BVQ_KTHW_STORE(float);
-  else if (dtype == BVQ_BF16)
-    BVQ_KTHW_STORE(bf16_t);
-  else
-    BVQ_KTHW_STORE(f16_t);
-#undef BVQ_KTHW_STORE
-  return check_launch("bvq_kthw_finish");
+  rc = with_dtype(dtype, [&](auto t) {
+    return with_bool(abs_key, [&](auto abs) {
+      kth_store_kernel<typename decltype(t)::type, abs><<<1, 64, 0, st>>>(w.sel, out, 1);
+    });
+  });
+  return rc ? rc : check_launch("bvq_kthw_finish");
 }
 
 extern "C" int bvq_kth_value(int abs_key, int dtype, const void* x, int64_t outer, int64_t channels,

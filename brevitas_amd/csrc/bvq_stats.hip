@@ -1030,54 +1030,12 @@ static int64_t worst_units(int dtype, int64_t outer, int64_t channels, int64_t i
   return a > b ? a : b;
 }
 
-template <typename T, bool RELU>
-static void launch_stat_pre(int kind, const StatArgs& a, int vec, bool nt, hipStream_t st) {
-  constexpr int V = elem<T>::vec;
-  const dim3 grid(grid_for_units(a.t.units)), block(kBlock);
-  if (kind == BVQ_STAT_ABSMAX) {
-    if (vec == V && nt)
-      absmax_kernel<T, V, true, RELU><<<grid, block, 0, st>>>(a);
-    else if (vec == V)
-      absmax_kernel<T, V, false, RELU><<<grid, block, 0, st>>>(a);
-    else
-      absmax_kernel<T, 1, false, RELU><<<grid, block, 0, st>>>(a);
-  } else {
-    if (vec == V && nt)
-      minmax_kernel<T, V, true, RELU><<<grid, block, 0, st>>>(a);
-    else if (vec == V)
-      minmax_kernel<T, V, false, RELU><<<grid, block, 0, st>>>(a);
-    else
-      minmax_kernel<T, 1, false, RELU><<<grid, block, 0, st>>>(a);
-  }
-}
-
-template <typename T>
-static void launch_stat(int kind, int pre_op, const StatArgs& a, int vec, bool nt, hipStream_t st) {
-  if (pre_op == BVQ_PRE_RELU)
-    launch_stat_pre<T, true>(kind, a, vec, nt, st);
-  else
-    launch_stat_pre<T, false>(kind, a, vec, nt, st);
-}
-
-template <typename T, int MATCH, bool WZ>
-static void launch_tie_scan_v(const Tiling& t, int vec, const void* x, const void* stat,
-                              unsigned long long* info, void* dx, int first_only, hipStream_t st) {
-  constexpr int V = elem<T>::vec;
-  const dim3 grid(grid_for_units(t.units)), block(kBlock);
-  if (vec == V)
-    tie_scan_kernel<T, V, MATCH, WZ><<<grid, block, 0, st>>>(t, x, stat, info, dx, first_only);
-  else
-    tie_scan_kernel<T, 1, MATCH, WZ><<<grid, block, 0, st>>>(t, x, stat, info, dx, first_only);
-}
-
-template <typename T, int MATCH>
-static void run_tie_scan(const Tiling& t, int vec, const void* x, const void* stat,
-                         unsigned long long* info, void* dx, int write_zeros, int first_only,
-                         hipStream_t st) {
-  if (write_zeros)
-    launch_tie_scan_v<T, MATCH, true>(t, vec, x, stat, info, dx, first_only, st);
-  else
-    launch_tie_scan_v<T, MATCH, false>(t, vec, x, stat, info, dx, first_only, st);
+// the abs-max kernels stream with the default cache policy under a ReLU pre-op: f(std::bool_constant<NT>,
+// std::bool_constant<RELU>) for (nt, false) and (false, true)
+template <typename F>
+static int with_nt_relu(bool nt, bool relu, F&& f) {
+  if (relu) return call_rc(f, std::false_type{}, std::true_type{});
+  return with_bool(nt, [&](auto ntc) { return call_rc(f, ntc, std::false_type{}); });
 }
 
 template <typename T, int MATCH>
@@ -1161,34 +1119,18 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
     ca.p = cp;
     ca.x = x;
     ca.part = reinterpret_cast<uint32_t*>(workspace);
-    const dim3 grid(grid_for_units(cp.units)), block(kBlock);
-    const bool relu = pre_op == BVQ_PRE_RELU;
-#define BVQ_COLS_STAT(KERNEL, T)                              \
-  do {                                                        \
-    if (relu)                                                 \
-      KERNEL<T, false, true><<<grid, block, 0, st>>>(ca);     \
-    else if (nt)                                              \
-      KERNEL<T, true, false><<<grid, block, 0, st>>>(ca);     \
-    else                                                      \
-      KERNEL<T, false, false><<<grid, block, 0, st>>>(ca);    \
-  } while (0)
-#define BVQ_COLS_STAT_DT(KERNEL)          \
-  do {                                    \
-    if (dtype == BVQ_F32)                 \
-      BVQ_COLS_STAT(KERNEL, float);       \
-    else if (dtype == BVQ_BF16)           \
-      BVQ_COLS_STAT(KERNEL, bf16_t);      \
-    else                                  \
-      BVQ_COLS_STAT(KERNEL, f16_t);       \
-  } while (0)
-    if (kind == BVQ_STAT_MINMAX)
-      BVQ_COLS_STAT_DT(minmax_cols_kernel);
-    else
-      BVQ_COLS_STAT_DT(absmax_cols_kernel);
-#undef BVQ_COLS_STAT_DT
-#undef BVQ_COLS_STAT
-    int rc0 = check_launch("bvq_stats/cols");
-    if (rc0) return rc0;
+    const unsigned grid = grid_for_units(cp.units);
+    int rc = with_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      return with_nt_relu(nt, pre_op == BVQ_PRE_RELU, [&](auto ntc, auto relu) {
+        if (kind == BVQ_STAT_MINMAX)
+          minmax_cols_kernel<T, ntc, relu><<<grid, kBlock, 0, st>>>(ca);
+        else
+          absmax_cols_kernel<T, ntc, relu><<<grid, kBlock, 0, st>>>(ca);
+      });
+    });
+    if (!rc) rc = check_launch("bvq_stats/cols");
+    if (rc) return rc;
     uint32_t* folded = launch_cols_fold_max(ca.part, cp.prows, width, ca.part + cp.prows * width, st);  // [width]
     if (kind == BVQ_STAT_MINMAX) {
       minmax_cols_finish_kernel<<<dim3((unsigned)channels), dim3(kWave), 0, st>>>(folded, out, out_dtype,
@@ -1225,60 +1167,47 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
   a.x = x;
   a.part_a = reinterpret_cast<uint32_t*>(workspace);
   a.part_b = a.part_a + a.t.units;
+  int rc;
   if (long_units && cap_unit_extent(a.t, dtype_size(dtype))) {
     ArriveArgs r = {};
     r.part = a.part_a;
     const ScaleEpilogue no_ep = {};
-    const dim3 grid(grid_for_units(a.t.units)), block(kBlock);
-    const bool relu = pre_op == BVQ_PRE_RELU;
-#define BVQ_LONG(T)                                                                           \
-  do {                                                                                        \
-    constexpr int V = elem<T>::vec;                                                           \
-    if (relu)                                                                                 \
-      absmax_onepass_kernel<T, V, false, true><<<grid, block, 0, st>>>(a, r, no_ep);          \
-    else if (nt)                                                                              \
-      absmax_onepass_kernel<T, V, true, false><<<grid, block, 0, st>>>(a, r, no_ep);          \
-    else                                                                                      \
-      absmax_onepass_kernel<T, V, false, false><<<grid, block, 0, st>>>(a, r, no_ep);         \
-  } while (0)
-    if (dtype == BVQ_F32)
-      BVQ_LONG(float);
-    else if (dtype == BVQ_BF16)
-      BVQ_LONG(bf16_t);
-    else
-      BVQ_LONG(f16_t);
-#undef BVQ_LONG
-  } else if (dtype == BVQ_F32)
-    launch_stat<float>(kind, pre_op, a, vec, nt, st);
-  else if (dtype == BVQ_BF16)
-    launch_stat<bf16_t>(kind, pre_op, a, vec, nt, st);
-  else
-    launch_stat<f16_t>(kind, pre_op, a, vec, nt, st);
-  int rc = check_launch("bvq_stats");
+    rc = with_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      return with_nt_relu(nt, pre_op == BVQ_PRE_RELU, [&](auto ntc, auto relu) {
+        absmax_onepass_kernel<T, elem<T>::vec, ntc, relu><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a, r, no_ep);
+      });
+    });
+  } else {
+    rc = with_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      return with_bool(pre_op == BVQ_PRE_RELU, [&](auto relu) {
+        return with_read_variant<elem<T>::vec>(vec, nt, [&](auto v, auto ntc) {
+          if (kind == BVQ_STAT_ABSMAX)
+            absmax_kernel<T, v, ntc, relu><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+          else
+            minmax_kernel<T, v, ntc, relu><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+        });
+      });
+    });
+  }
+  if (!rc) rc = check_launch("bvq_stats");
   if (rc) return rc;
   uint32_t* mid_a = splits > 1 ? a.part_b + a.t.units : nullptr;
   uint32_t* mid_b = splits > 1 ? mid_a + mid_words : nullptr;
   const ScaleEpilogue none = {};
-#define BVQ_FINISH(KIND)                                                                             \
-  do {                                                                                               \
-    if (splits > 1) {                                                                                \
-      stat_finish_kernel<KIND><<<dim3((unsigned)channels, (unsigned)splits), dim3(kBlock), 0, st>>>( \
-          a.part_a, a.part_b, out, out_dtype, dtype, a.t.nob, (int32_t)channels, a.t.ppr, none, mid_a, \
-          mid_b);                                                                                    \
-      stat_finish_kernel<KIND><<<dim3((unsigned)channels), dim3(kBlock), 0, st>>>(                   \
-          mid_a, mid_b, out, out_dtype, dtype, 1, (int32_t)channels, splits, ep, nullptr, nullptr);  \
-    } else {                                                                                         \
-      stat_finish_kernel<KIND><<<dim3((unsigned)channels), dim3(kBlock), 0, st>>>(                   \
-          a.part_a, a.part_b, out, out_dtype, dtype, a.t.nob, (int32_t)channels, a.t.ppr, ep, nullptr, \
-          nullptr);                                                                                  \
-    }                                                                                                \
-  } while (0)
-  if (kind == BVQ_STAT_ABSMAX)
-    BVQ_FINISH(BVQ_STAT_ABSMAX);
-  else
-    BVQ_FINISH(BVQ_STAT_MINMAX);
-#undef BVQ_FINISH
-  return check_launch("bvq_stats/finish");
+  rc = with_value<BVQ_STAT_ABSMAX, BVQ_STAT_MINMAX>(kind, [&](auto k) {
+    if (splits > 1) {
+      stat_finish_kernel<k><<<dim3((unsigned)channels, (unsigned)splits), kBlock, 0, st>>>(
+          a.part_a, a.part_b, out, out_dtype, dtype, a.t.nob, (int32_t)channels, a.t.ppr, none, mid_a, mid_b);
+      stat_finish_kernel<k><<<(unsigned)channels, kBlock, 0, st>>>(mid_a, mid_b, out, out_dtype, dtype, 1,
+                                                                   (int32_t)channels, splits, ep, nullptr, nullptr);
+    } else {
+      stat_finish_kernel<k><<<(unsigned)channels, kBlock, 0, st>>>(a.part_a, a.part_b, out, out_dtype, dtype, a.t.nob,
+                                                                   (int32_t)channels, a.t.ppr, ep, nullptr, nullptr);
+    }
+  });
+  return rc ? rc : check_launch("bvq_stats/finish");
 }
 
 extern "C" int bvq_stats(int kind, int dtype, const void* x, int64_t outer, int64_t channels,
@@ -1320,15 +1249,18 @@ extern "C" int bvq_absmax_scale(int pre_op, int dtype, const void* x, int64_t ou
 // leave ~kOnepassUnits waves in the launch (a wave's arrival -- two atomic round trips -- then costs a percent of its
 // life, not 7 %), taking the row count near that which wastes the fewest lanes of the 64-wide loads.  Long rows keep
 // their pieces.  A unit's extent stays below 2^31 bytes (32-bit buffer offsets).
-constexpr int64_t kOnepassUnits = 8192;
+#ifndef BVQ_ONEPASS_UNITS
+#define BVQ_ONEPASS_UNITS 8192
+#endif
+constexpr int64_t kOnepassUnits = BVQ_ONEPASS_UNITS;
+static_assert(kOnepassUnits >= 1, "BVQ_ONEPASS_UNITS");
 
 static bool onepass_tiling(int dtype, const void* x, int64_t outer, int64_t channels, int64_t inner, Tiling& t,
                            int& vec) {
   t = stat_tiling(dtype, x, nullptr, outer, channels, inner, vec, true);
   if (t.ppr == 1 && t.outer > 1) {
     const int64_t cpr = t.row_len / vec;
-    static const int64_t target = env_flag("BVQ_ONEPASS_UNITS", (int)kOnepassUnits);  // developer knob (tools/onepass_ab.py)
-    int64_t r0 = t.outer * channels / target;
+    int64_t r0 = t.outer * channels / kOnepassUnits;
     r0 = r0 < 1 ? 1 : (r0 > t.outer ? t.outer : r0);
     int64_t best = r0;
     double best_eff = -1.0;
@@ -1435,30 +1367,17 @@ extern "C" int bvq_absmax_scale_onepass(int pre_op, int dtype, const void* x, in
     ep.one_minus_m = (float)(1.0 - momentum);
     ep.momentum = (float)momentum;
   }
-  const dim3 grid(blocks), block(kBlock);
-  const bool relu = pre_op == BVQ_PRE_RELU;
-#define BVQ_ONEPASS(T)                                                              \
-  do {                                                                              \
-    constexpr int V = elem<T>::vec;                                                 \
-    if (relu && vec == V)                                                           \
-      absmax_onepass_kernel<T, V, false, true><<<grid, block, 0, st>>>(a, r, ep);   \
-    else if (relu)                                                                  \
-      absmax_onepass_kernel<T, 1, false, true><<<grid, block, 0, st>>>(a, r, ep);   \
-    else if (vec == V && nt)                                                        \
-      absmax_onepass_kernel<T, V, true, false><<<grid, block, 0, st>>>(a, r, ep);   \
-    else if (vec == V)                                                              \
-      absmax_onepass_kernel<T, V, false, false><<<grid, block, 0, st>>>(a, r, ep);  \
-    else                                                                            \
-      absmax_onepass_kernel<T, 1, false, false><<<grid, block, 0, st>>>(a, r, ep);  \
-  } while (0)
-  if (dtype == BVQ_F32)
-    BVQ_ONEPASS(float);
-  else if (dtype == BVQ_BF16)
-    BVQ_ONEPASS(bf16_t);
-  else
-    BVQ_ONEPASS(f16_t);
-#undef BVQ_ONEPASS
-  return check_launch("bvq_absmax_scale_onepass");
+  const int rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    constexpr int V = elem<T>::vec;
+    return with_nt_relu(nt && vec == V, pre_op == BVQ_PRE_RELU, [&](auto ntc, auto relu) {
+      with_bool(vec == V, [&](auto full) {
+        if constexpr (full || !ntc)  // (the non-temporal form exists at full width only)
+          absmax_onepass_kernel<T, full ? V : 1, ntc, relu><<<blocks, kBlock, 0, st>>>(a, r, ep);
+      });
+    });
+  });
+  return rc ? rc : check_launch("bvq_absmax_scale_onepass");
 }
 
 // ---- abs-max of a LIST of tensors sharing the channel axis --------------------------------------------------------
@@ -1588,19 +1507,16 @@ extern "C" int bvq_absmax_scale_list(int dtype, int n, const void* const* xs, co
     ep.int_threshold = (float)int_threshold;
   }
   const dim3 grid(grid_for_units(la.start[n])), block(kBlock);
-  if (dtype == BVQ_F32)
-    absmax_list_kernel<float><<<grid, block, 0, st>>>(la, r, ep);
-  else if (dtype == BVQ_BF16)
-    absmax_list_kernel<bf16_t><<<grid, block, 0, st>>>(la, r, ep);
-  else
-    absmax_list_kernel<f16_t><<<grid, block, 0, st>>>(la, r, ep);
+  int rc = with_dtype(dtype, [&](auto t) {
+    absmax_list_kernel<typename decltype(t)::type><<<grid, block, 0, st>>>(la, r, ep);
+  });
   if (channels == 1) {
-    int rc = check_launch("bvq_absmax_scale_list");
+    if (!rc) rc = check_launch("bvq_absmax_scale_list");
     if (rc) return rc;
     stat_finish_kernel<BVQ_STAT_ABSMAX><<<dim3(1), dim3(kBlock), 0, st>>>(r.part, r.part, stat_out, dtype, dtype, 1, 1,
                                                                           la.start[n], ep, nullptr, nullptr);
   }
-  return check_launch("bvq_absmax_scale_list");
+  return rc ? rc : check_launch("bvq_absmax_scale_list");
 }
 
 extern "C" int bvq_absmax_scale_running(int pre_op, int dtype, const void* x, int64_t outer, int64_t channels,
@@ -1680,22 +1596,13 @@ extern "C" int bvq_abs_moments(int dtype, const void* x, int64_t outer, int64_t 
     ca.pivot = sums + 2 * channels;
     ca.inner = inner;
     const dim3 cgrid(grid_for_units(cp.units)), cblock(kBlock);
-#define BVQ_MOMC(T)                                                   \
-  do {                                                                \
-    if (nt)                                                           \
-      absmoments_cols_kernel<T, true><<<cgrid, cblock, 0, st>>>(ca);  \
-    else                                                              \
-      absmoments_cols_kernel<T, false><<<cgrid, cblock, 0, st>>>(ca); \
-  } while (0)
-    if (dtype == BVQ_F32)
-      BVQ_MOMC(float);
-    else if (dtype == BVQ_BF16)
-      BVQ_MOMC(bf16_t);
-    else
-      BVQ_MOMC(f16_t);
-#undef BVQ_MOMC
-    int rc0 = check_launch("bvq_abs_moments/cols");
-    if (rc0) return rc0;
+    int rc = with_dtype(dtype, [&](auto t) {
+      return with_bool(nt, [&](auto ntc) {
+        absmoments_cols_kernel<typename decltype(t)::type, ntc><<<cgrid, cblock, 0, st>>>(ca);
+      });
+    });
+    if (!rc) rc = check_launch("bvq_abs_moments/cols");
+    if (rc) return rc;
     float *f1 = nullptr, *f2 = nullptr;
     launch_cols_fold_sum_min(ca.part1, nullptr, cp.prows, cp.L, ca.part1 + cp.prows * cp.L, nullptr, &f1, nullptr, st);
     launch_cols_fold_sum_min(ca.part2, nullptr, cp.prows, cp.L, ca.part2 + cp.prows * cp.L, nullptr, &f2, nullptr, st);
@@ -1717,25 +1624,13 @@ extern "C" int bvq_abs_moments(int dtype, const void* x, int64_t outer, int64_t 
   a.part_a = reinterpret_cast<uint32_t*>(workspace);
   a.part_b = a.part_a + a.t.units;
   a.pivot = sums + 2 * channels;
-  const dim3 grid(grid_for_units(a.t.units)), block(kBlock);
-#define BVQ_MOM(T)                                                     \
-  do {                                                                 \
-    constexpr int V = elem<T>::vec;                                    \
-    if (vec == V && nt)                                                \
-      absmoments_kernel<T, V, true><<<grid, block, 0, st>>>(a);        \
-    else if (vec == V)                                                 \
-      absmoments_kernel<T, V, false><<<grid, block, 0, st>>>(a);       \
-    else                                                               \
-      absmoments_kernel<T, 1, false><<<grid, block, 0, st>>>(a);       \
-  } while (0)
-  if (dtype == BVQ_F32)
-    BVQ_MOM(float);
-  else if (dtype == BVQ_BF16)
-    BVQ_MOM(bf16_t);
-  else
-    BVQ_MOM(f16_t);
-#undef BVQ_MOM
-  int rc = check_launch("bvq_abs_moments");
+  int rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_read_variant<elem<T>::vec>(vec, nt, [&](auto v, auto ntc) {
+      absmoments_kernel<T, v, ntc><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+    });
+  });
+  if (!rc) rc = check_launch("bvq_abs_moments");
   if (rc) return rc;
   launch_channel_sums(reinterpret_cast<const float*>(a.part_a), reinterpret_cast<const float*>(a.part_b), sums,
                       sums + channels, a.t.nob, (int32_t)channels, a.t.ppr,
@@ -1763,33 +1658,20 @@ extern "C" int bvq_abs_affine_bwd(int dtype, const void* x, const float* a, cons
     gy = gy > outer ? outer : gy;
     gy = gy > 65535 ? 65535 : (gy < 1 ? 1 : gy);
     const dim3 fgrid((unsigned)gx, (unsigned)gy), fblock(kBlock);
-    if (dtype == BVQ_F32)
-      abs_affine_bwd_cols_kernel<float><<<fgrid, fblock, 0, st>>>(x, a, b, dx, outer, L, inner);
-    else if (dtype == BVQ_BF16)
-      abs_affine_bwd_cols_kernel<bf16_t><<<fgrid, fblock, 0, st>>>(x, a, b, dx, outer, L, inner);
-    else
-      abs_affine_bwd_cols_kernel<f16_t><<<fgrid, fblock, 0, st>>>(x, a, b, dx, outer, L, inner);
-    return check_launch("bvq_abs_affine_bwd/cols");
+    const int rc = with_dtype(dtype, [&](auto t) {
+      abs_affine_bwd_cols_kernel<typename decltype(t)::type><<<fgrid, fblock, 0, st>>>(x, a, b, dx, outer, L, inner);
+    });
+    return rc ? rc : check_launch("bvq_abs_affine_bwd/cols");
   }
   int vec;
   const Tiling t = stat_tiling(dtype, x, dx, outer, channels, inner, vec);
-  const dim3 grid(grid_for_units(t.units)), block(kBlock);
-#define BVQ_AFF(T)                                                               \
-  do {                                                                           \
-    constexpr int V = elem<T>::vec;                                              \
-    if (vec == V)                                                                \
-      abs_affine_bwd_kernel<T, V><<<grid, block, 0, st>>>(t, x, a, b, dx);       \
-    else                                                                         \
-      abs_affine_bwd_kernel<T, 1><<<grid, block, 0, st>>>(t, x, a, b, dx);       \
-  } while (0)
-  if (dtype == BVQ_F32)
-    BVQ_AFF(float);
-  else if (dtype == BVQ_BF16)
-    BVQ_AFF(bf16_t);
-  else
-    BVQ_AFF(f16_t);
-#undef BVQ_AFF
-  return check_launch("bvq_abs_affine_bwd");
+  const int rc = with_dtype(dtype, [&](auto tt) {
+    using T = typename decltype(tt)::type;
+    with_bool(vec == elem<T>::vec, [&](auto full) {
+      abs_affine_bwd_kernel<T, full ? elem<T>::vec : 1><<<grid_for_units(t.units), kBlock, 0, st>>>(t, x, a, b, dx);
+    });
+  });
+  return rc ? rc : check_launch("bvq_abs_affine_bwd");
 }
 
 extern "C" int bvq_shard_pack(const float* dscale, const int64_t* tie_info, int64_t channels, int rank,
@@ -1909,12 +1791,11 @@ extern "C" int bvq_histc(int dtype, const void* x, int64_t n, const void* absmax
     int64_t blocks = (n + per_block - 1) / per_block;
     if (blocks > 2048) blocks = 2048;
     const dim3 grid((unsigned)blocks), block(kBlock);
-    if (dtype == BVQ_F32)
-      histc_kernel<float><<<grid, block, 0, st>>>(reinterpret_cast<const float*>(x), n, absmax, bins, counts);
-    else if (dtype == BVQ_BF16)
-      histc_kernel<bf16_t><<<grid, block, 0, st>>>(reinterpret_cast<const bf16_t*>(x), n, absmax, bins, counts);
-    else
-      histc_kernel<f16_t><<<grid, block, 0, st>>>(reinterpret_cast<const f16_t*>(x), n, absmax, bins, counts);
+    const int rc = with_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      histc_kernel<T><<<grid, block, 0, st>>>(reinterpret_cast<const T*>(x), n, absmax, bins, counts);
+    });
+    if (rc) return rc;
   }
   return check_launch("bvq_histc");
 }
@@ -1967,26 +1848,6 @@ extern "C" int bvq_running_stats_update(int run_dtype, void* running, int stat_d
   return check_launch("bvq_running_stats_update");
 }
 
-#define BVQ_DISPATCH_T_MATCH(dtype, match, FN, ...)              \
-  do {                                                             \
-    if ((dtype) == BVQ_F32) {                                      \
-      if ((match) == BVQ_MATCH_ABS)                                \
-        FN<float, BVQ_MATCH_ABS>(__VA_ARGS__);                     \
-      else                                                         \
-        FN<float, BVQ_MATCH_VALUE>(__VA_ARGS__);                   \
-    } else if ((dtype) == BVQ_BF16) {                              \
-      if ((match) == BVQ_MATCH_ABS)                                \
-        FN<bf16_t, BVQ_MATCH_ABS>(__VA_ARGS__);                    \
-      else                                                         \
-        FN<bf16_t, BVQ_MATCH_VALUE>(__VA_ARGS__);                  \
-    } else {                                                       \
-      if ((match) == BVQ_MATCH_ABS)                                \
-        FN<f16_t, BVQ_MATCH_ABS>(__VA_ARGS__);                     \
-      else                                                         \
-        FN<f16_t, BVQ_MATCH_VALUE>(__VA_ARGS__);                   \
-    }                                                              \
-  } while (0)
-
 static int check_stat_args(const char* fn, int match_flags, int dtype, int64_t outer, int64_t channels,
                            int64_t inner) {
   const int match = match_flags & ~BVQ_MATCH_FIRST;
@@ -2027,36 +1888,30 @@ extern "C" int bvq_stat_tie_scan(int match, int dtype, const void* x, const void
                           ? cols_plan(dtype, outer, channels, inner)
                           : ColsPlan{};
   if (cp.ok) {
-    const dim3 grid(grid_for_units(cp.units)), block(kBlock);
-#define BVQ_TSC(T, M)                                                                                        \
-  do {                                                                                                       \
-    if (dx_zero_fill)                                                                                        \
-      tie_scan_cols_kernel<T, M, true><<<grid, block, 0, st>>>(cp, x, stat, info, dx_zero_fill, inner);       \
-    else                                                                                                     \
-      tie_scan_cols_kernel<T, M, false><<<grid, block, 0, st>>>(cp, x, stat, info, nullptr, inner);           \
-  } while (0)
-#define BVQ_TSC_T(T)                      \
-  do {                                    \
-    if (match == BVQ_MATCH_ABS)           \
-      BVQ_TSC(T, BVQ_MATCH_ABS);          \
-    else                                  \
-      BVQ_TSC(T, BVQ_MATCH_VALUE);        \
-  } while (0)
-    if (dtype == BVQ_F32)
-      BVQ_TSC_T(float);
-    else if (dtype == BVQ_BF16)
-      BVQ_TSC_T(bf16_t);
-    else
-      BVQ_TSC_T(f16_t);
-#undef BVQ_TSC_T
-#undef BVQ_TSC
-    return check_launch("bvq_stat_tie_scan/cols");
+    rc = with_dtype(dtype, [&](auto t) {
+      return with_value<BVQ_MATCH_ABS, BVQ_MATCH_VALUE>(match, [&](auto m) {
+        return with_bool(dx_zero_fill != nullptr, [&](auto wz) {
+          tie_scan_cols_kernel<typename decltype(t)::type, m, wz><<<grid_for_units(cp.units), kBlock, 0, st>>>(
+              cp, x, stat, info, dx_zero_fill, inner);
+        });
+      });
+    });
+    return rc ? rc : check_launch("bvq_stat_tie_scan/cols");
   }
   int vec;
   const Tiling t = stat_tiling(dtype, x, dx_zero_fill, outer, channels, inner, vec);
-  BVQ_DISPATCH_T_MATCH(dtype, match, run_tie_scan, t, vec, x, stat, info, dx_zero_fill,
-                       dx_zero_fill != nullptr, first_only, st);
-  return check_launch("bvq_stat_tie_scan");
+  rc = with_dtype(dtype, [&](auto tt) {
+    using T = typename decltype(tt)::type;
+    return with_value<BVQ_MATCH_ABS, BVQ_MATCH_VALUE>(match, [&](auto m) {
+      return with_bool(dx_zero_fill != nullptr, [&](auto wz) {
+        return with_bool(vec == elem<T>::vec, [&](auto full) {
+          tie_scan_kernel<T, full ? elem<T>::vec : 1, m, wz><<<grid_for_units(t.units), kBlock, 0, st>>>(
+              t, x, stat, info, dx_zero_fill, first_only);
+        });
+      });
+    });
+  });
+  return rc ? rc : check_launch("bvq_stat_tie_scan");
 }
 
 extern "C" int bvq_stat_tie_apply(int match, int pre_op, int dtype, const void* x, const void* stat,
@@ -2076,11 +1931,14 @@ extern "C" int bvq_stat_tie_apply(int match, int pre_op, int dtype, const void* 
   src.pre_relu = pre_op == BVQ_PRE_RELU;
   const int first_only = (match & BVQ_MATCH_FIRST) != 0;
   match &= ~BVQ_MATCH_FIRST;
-  BVQ_DISPATCH_T_MATCH(dtype, match, run_tie_apply, x, stat, src,
-                       reinterpret_cast<const unsigned long long*>(tie_info),
-                       reinterpret_cast<const unsigned long long*>(total_ties), dx, outer, channels, inner,
-                       mode_add, first_only, st);
-  return check_launch("bvq_stat_tie_apply");
+  rc = with_dtype(dtype, [&](auto t) {
+    return with_value<BVQ_MATCH_ABS, BVQ_MATCH_VALUE>(match, [&](auto m) {
+      run_tie_apply<typename decltype(t)::type, m>(x, stat, src, reinterpret_cast<const unsigned long long*>(tie_info),
+                                                   reinterpret_cast<const unsigned long long*>(total_ties), dx, outer,
+                                                   channels, inner, mode_add, first_only, st);
+    });
+  });
+  return rc ? rc : check_launch("bvq_stat_tie_apply");
 }
 
 extern "C" int bvq_stat_tie_apply_dscale(int pre_op, int dtype, const void* x, const void* stat,
@@ -2108,11 +1966,12 @@ extern "C" int bvq_stat_tie_apply_dscale(int pre_op, int dtype, const void* x, c
   src.quot_dtype = quot_dtype;
   src.int_threshold = (float)int_threshold;
   src.pre_relu = pre_op == BVQ_PRE_RELU;
-  BVQ_DISPATCH_T_MATCH(dtype, BVQ_MATCH_ABS, run_tie_apply, x, stat, src,
-                       reinterpret_cast<const unsigned long long*>(tie_info),
-                       reinterpret_cast<const unsigned long long*>(total_ties), dx, outer, channels, inner, 1,
-                       0, st);
-  return check_launch("bvq_stat_tie_apply_dscale");
+  rc = with_dtype(dtype, [&](auto t) {
+    run_tie_apply<typename decltype(t)::type, BVQ_MATCH_ABS>(x, stat, src, reinterpret_cast<const unsigned long long*>(tie_info),
+                                                             reinterpret_cast<const unsigned long long*>(total_ties), dx,
+                                                             outer, channels, inner, 1, 0, st);
+  });
+  return rc ? rc : check_launch("bvq_stat_tie_apply_dscale");
 }
 
 extern "C" int bvq_stat_bwd(int match, int dtype, const void* x, const void* stat, const void* gstat,

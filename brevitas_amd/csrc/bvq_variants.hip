@@ -275,27 +275,16 @@ static void var_fill(VarArgs& a, const bvq_variant_desc* d, const void* const* p
   a.round_mode = d->round_mode;
 }
 
+// 16 bytes of x per lane, or one element (ragged / misaligned rows); the rounding mode is a kernel argument here
 template <bool BWD>
-static void var_launch(const VarArgs& a, const bvq_variant_desc* d, int vec, hipStream_t st) {
-  const dim3 grid(grid_for_units(a.t.units)), block(kBlock);
-#define BVQ_VAR(XT, CT)                                                  \
-  do {                                                                   \
-    if (vec == elem<XT>::vec)                                            \
-      variant_kernel<XT, CT, elem<XT>::vec, BWD><<<grid, block, 0, st>>>(a); \
-    else                                                                 \
-      variant_kernel<XT, CT, 1, BWD><<<grid, block, 0, st>>>(a);         \
-  } while (0)
-  if (d->x_dtype == BVQ_F32)
-    BVQ_VAR(float, float);
-  else if (d->x_dtype == BVQ_BF16 && d->ct_dtype == BVQ_BF16)
-    BVQ_VAR(bf16_t, bf16_t);
-  else if (d->x_dtype == BVQ_BF16)
-    BVQ_VAR(bf16_t, float);
-  else if (d->ct_dtype == BVQ_F16)
-    BVQ_VAR(f16_t, f16_t);
-  else
-    BVQ_VAR(f16_t, float);
-#undef BVQ_VAR
+static int var_launch(const VarArgs& a, const bvq_variant_desc* d, int vec, hipStream_t st) {
+  return with_pair(d->x_dtype, d->ct_dtype, [&](auto xt, auto ct) {
+    using XT = typename decltype(xt)::type;
+    with_bool(vec == elem<XT>::vec, [&](auto full) {
+      variant_kernel<XT, typename decltype(ct)::type, full ? elem<XT>::vec : 1, BWD>
+          <<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+    });
+  });
 }
 
 }  // namespace bvq
@@ -322,8 +311,8 @@ extern "C" int bvq_variant_fwd(const bvq_variant_desc* d, const void* x, const v
   a.pre_scale = d->kind == BVQ_VAR_DECOUPLED ? pre_scale : nullptr;
   a.zp = zp;
   a.pre_zp = pre_zp;
-  var_launch<false>(a, d, vec, (hipStream_t)stream);
-  return check_launch("bvq_variant_fwd");
+  rc = var_launch<false>(a, d, vec, (hipStream_t)stream);
+  return rc ? rc : check_launch("bvq_variant_fwd");
 }
 
 static int64_t var_units(const bvq_variant_desc* d) {
@@ -387,8 +376,8 @@ extern "C" int bvq_variant_bwd(const bvq_variant_desc* d, const void* g, const v
   a.pre_scale = d->kind == BVQ_VAR_DECOUPLED ? pre_scale : nullptr;
   a.zp = zp;
   a.pre_zp = pre_zp;
-  var_launch<true>(a, d, vec, st);
-  rc = check_launch("bvq_variant_bwd");
+  rc = var_launch<true>(a, d, vec, st);
+  if (!rc) rc = check_launch("bvq_variant_bwd");
   if (rc) return rc;
   if (dscale || dpre_scale) {
     launch_channel_sums(a.part_a, a.part_b, dscale, dpre_scale, a.t.nob, (int32_t)channels, a.t.ppr,

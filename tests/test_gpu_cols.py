@@ -1,5 +1,5 @@
 """Column-mapped kernels (channel axis last or nearly last: NHWC, [tokens, hidden], 7x7 maps) against the
-row-mapped path they replace on those layouts (BVQ_COLS=0 selects it; it is the path pinned to the
+row-mapped path they replace on those layouts (a build with -DBVQ_COLS=0 selects it; it is the path pinned to the
 reference's golden vectors) and against plain torch reductions: bit-identical statistics, outputs and
 gradients."""
 import pytest

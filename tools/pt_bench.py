@@ -1,7 +1,9 @@
-"""Developer tool: the per-tensor (one very long row) kernels on the headline tensor, per dtype -- used with the
-BVQ_PIECE_CHUNKS / BVQ_MAX_UNITS_PER_CHANNEL knobs to pick the piece size of long rows.
+"""Developer tool: the per-tensor (one very long row) kernels on the headline tensor, per dtype -- used with an
+experiment build of the library to pick the piece size of long rows (the BVQ_PIECE_CHUNKS /
+BVQ_MAX_UNITS_PER_CHANNEL constants of bvq_common.hip, overridden with -D):
 
-    [BVQ_PIECE_CHUNKS=4 BVQ_MAX_UNITS_PER_CHANNEL=1048576] python tools/pt_bench.py [bf16,f32,f16]"""
+    python -m brevitas_amd.csrc.build -DBVQ_PIECE_CHUNKS=4 -DBVQ_MAX_UNITS_PER_CHANNEL=1048576 --out=/tmp/libbvq_pc4.so
+    [BREVITAS_AMD_LIB=/tmp/libbvq_pc4.so] python tools/pt_bench.py [bf16,f32,f16]"""
 import os
 import statistics
 import sys
@@ -33,8 +35,7 @@ def main():
     names = sys.argv[1].split(',') if len(sys.argv) > 1 else ['bf16', 'f32', 'f16']
     dev = 'cuda:0'
     n = 256 * 512 * 56 * 56
-    print('# piece chunks %s, unit cap %s' % (os.environ.get('BVQ_PIECE_CHUNKS', 'default'),
-                                             os.environ.get('BVQ_MAX_UNITS_PER_CHANNEL', 'default')))
+    print('# library %s' % os.environ.get('BREVITAS_AMD_LIB', 'default build'))
     for _ in range(20):  # clock settling
         torch.empty(n, device=dev, dtype=torch.bfloat16).zero_()
     for name in names:
