@@ -14,6 +14,7 @@ if not _BUILDING:
     from . import _native  # noqa: F401
     from . import config  # noqa: F401
     from . import ops  # noqa: F401
+    from .core.quant.weight_group import WeightQuantGroup  # noqa: F401
 
 NATIVE_STE_BACKEND_LOADED = not _BUILDING
 

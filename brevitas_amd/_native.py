@@ -43,7 +43,8 @@ EXPORTS = (
     'bvq_kthw_plan', 'bvq_kthw_begin', 'bvq_kthw_hist', 'bvq_kthw_pick', 'bvq_kthw_finish',
     'bvq_absmax_onepass_supported', 'bvq_absmax_scale_onepass', 'bvq_fakequant_bwd_stats_onepass_supported',
     'bvq_fakequant_bwd_stats_onepass', 'bvq_scale_from_stat_running', 'bvq_fakequant_bwd_shard',
-    'bvq_shard_unpack_deposit', 'bvq_absmax_list_supported', 'bvq_absmax_scale_list')
+    'bvq_shard_unpack_deposit', 'bvq_absmax_list_supported', 'bvq_absmax_scale_list', 'bvq_weight_list_supported',
+    'bvq_weight_quant_list_fwd', 'bvq_weight_quant_list_bwd_workspace_bytes', 'bvq_weight_quant_list_bwd')
 
 
 class QuantDesc(ctypes.Structure):
@@ -68,6 +69,17 @@ class VariantDesc(ctypes.Structure):
 
 
 VAR_BINARY, VAR_CLAMPED_BINARY, VAR_TERNARY, VAR_DECOUPLED, VAR_TRUNC = range(5)
+
+WEIGHT_LIST_MAX = 16  # BVQ_WEIGHT_LIST_MAX: items per bvq_weight_quant_list_* call
+
+
+class WeightItem(ctypes.Structure):
+    """bvq_weight_item of include/bvq.h"""
+    _fields_ = [
+        ('x', ctypes.c_void_p), ('y', ctypes.c_void_p), ('stat', ctypes.c_void_p), ('scale', ctypes.c_void_p),
+        ('g', ctypes.c_void_p), ('dx', ctypes.c_void_p), ('dscale', ctypes.c_void_p), ('channels', ctypes.c_int64),
+        ('inner', ctypes.c_int64), ('min_val', ctypes.c_double), ('int_threshold', ctypes.c_double),
+        ('qmin', ctypes.c_float), ('qmax', ctypes.c_float), ('use_min', ctypes.c_int32), ('clamp_ste', ctypes.c_int32)]
 
 
 class BvqError(RuntimeError):
@@ -145,6 +157,10 @@ def _load(path=None, strict=True):
         'bvq_variant_fwd': (i32, [ctypes.POINTER(VariantDesc), vp, vp, vp, vp, vp, vp, vp]),
         'bvq_variant_bwd_workspace_bytes': (i64, [ctypes.POINTER(VariantDesc)]),
         'bvq_variant_bwd': (i32, [ctypes.POINTER(VariantDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+        'bvq_weight_list_supported': (i32, [i32, i32, i32, vp, i64]),
+        'bvq_weight_quant_list_fwd': (i32, [i32, i32, i32, i32, vp, vp]),
+        'bvq_weight_quant_list_bwd_workspace_bytes': (i64, [i32, i32, vp]),
+        'bvq_weight_quant_list_bwd': (i32, [i32, i32, i32, i32, i32, vp, vp, i64, vp, i64, vp]),
         'bvq_fakequant_bwd_learned': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, i32, dbl, i32, dbl, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
@@ -982,3 +998,97 @@ def fakequant_bwd(desc, g, x, scale, zp, need_dscale, need_dzp, tie_stat=None):
     if tie_stat is not None:
         return dx, ds, dz, info
     return dx, ds, dz
+
+
+# ---- many weights in one launch each way (include/bvq.h, bvq_weight_quant_list_*) -------------------------------------
+# The caller keeps a WeightItem array with the static fields filled (x, channels, inner, min_val, int_threshold, qmin,
+# qmax, use_min, clamp_ste); a call takes the len(xs) items from index `first` on, sets their per-call pointers and
+# launches.
+
+_ITEM = ctypes.sizeof(WeightItem)
+
+
+def weight_list_supported(items, first, n, dtype, round_mode):
+    """the n items from `first` on (static fields and x) are covered by both one-launch forms"""
+    return bool(lib.bvq_weight_list_supported(dtype_code(dtype), round_mode, n,
+                                              ctypes.addressof(items) + first * _ITEM, ARRIVE_WORDS))
+
+
+def weight_quant_list_fwd(items, first, xs, scale_dtype, round_mode):
+    """statistic, scale and quantize-dequantize of every weight of `xs` (items[first + i] describes xs[i]), ONE launch
+    -> (ys, stat, scale): ys fresh tensors like xs, stat [sum of channels] in xs' dtype, scale [sum of channels] in
+    scale_dtype, tensor i's channels after tensor i - 1's"""
+    n = len(xs)
+    dev = xs[0].device
+    dtype = xs[0].dtype
+    channels = 0
+    for i in range(first, first + n):
+        channels += items[i].channels
+    if scale_dtype == dtype:  # one buffer for both per-channel vectors
+        both = torch.empty(2 * channels, dtype=dtype, device=dev)
+        stat, scale = both[:channels], both[channels:]
+    else:
+        stat = torch.empty(channels, dtype=dtype, device=dev)
+        scale = torch.empty(channels, dtype=scale_dtype, device=dev)
+    ys = [torch.empty_like(x) for x in xs]
+    ps, ss = stat.data_ptr(), scale.data_ptr()
+    es, esc = stat.element_size(), scale.element_size()
+    for i in range(n):
+        it = items[first + i]
+        it.y = ys[i].data_ptr()
+        it.stat = ps
+        it.scale = ss
+        ps += it.channels * es
+        ss += it.channels * esc
+    with _DeviceGuard(dev):
+        if _timer is not None:
+            _timer.before('bvq_weight_quant_list_fwd')
+        check(lib.bvq_weight_quant_list_fwd(dtype_code(dtype), dtype_code(scale_dtype), round_mode, n,
+                                            ctypes.addressof(items) + first * _ITEM, stream_ptr(dev)),
+              'bvq_weight_quant_list_fwd')
+        if _timer is not None:
+            _timer.after('bvq_weight_quant_list_fwd')
+    return ys, stat, scale
+
+
+def weight_quant_list_bwd(items, first, gs, xs, stat_ptrs, scale_ptrs, scale_dtype, quot_dtype, round_mode):
+    """backward of weight_quant_list_fwd for the gradients `gs` (contiguous, 16-byte aligned, xs' dtype) with the
+    forward's statistics and scales at stat_ptrs / scale_ptrs, ONE launch -> dxs (the statistics' gradients
+    deposited), or None when no arrival buffer is available -- a stream capturing its first step (arrival buffers are
+    allocated outside captures: capture on the stream the eager warm-up ran on), or the one-launch backward switched off
+    (ONEPASS_BWD) -- and the caller takes the per-tensor route"""
+    n = len(xs)
+    dev = xs[0].device
+    dtype = xs[0].dtype
+    st = stream_ptr(dev)
+    channels = 0
+    for i in range(first, first + n):
+        channels += items[i].channels
+    arrive = arrival_buffer(dev, st, channels) if ONEPASS_BWD else None
+    if arrive is None:
+        return None
+    dxs = [torch.empty_like(x) for x in xs]
+    ds = torch.empty(channels, dtype=torch.float32, device=dev)
+    pd = ds.data_ptr()
+    for i in range(n):
+        it = items[first + i]
+        it.g = gs[i].data_ptr()
+        it.dx = dxs[i].data_ptr()
+        it.stat = stat_ptrs[i]
+        it.scale = scale_ptrs[i]
+        it.dscale = pd
+        pd += it.channels * 4
+    addr = ctypes.addressof(items) + first * _ITEM
+    wsb = int(lib.bvq_weight_quant_list_bwd_workspace_bytes(dtype_code(dtype), n, addr))
+    if wsb < 0:
+        raise BvqError('bvq_weight_quant_list_bwd_workspace_bytes: ' + last_error())
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    with _DeviceGuard(dev):
+        if _timer is not None:
+            _timer.before('bvq_weight_quant_list_bwd')
+        check(lib.bvq_weight_quant_list_bwd(dtype_code(dtype), dtype_code(scale_dtype), dtype_code(quot_dtype),
+                                            round_mode, n, addr, ptr(ws), wsb, ptr(arrive), arrive.numel(), st),
+              'bvq_weight_quant_list_bwd')
+        if _timer is not None:
+            _timer.after('bvq_weight_quant_list_bwd')
+    return dxs

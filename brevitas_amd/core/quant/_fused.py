@@ -826,3 +826,92 @@ def fast_act_stats_fakequant(x, int_threshold, sp, qmin, qmax, round_mode, clamp
     if out is not None and runtime is not None:
         runtime.bvq_running_folded = True
     return out
+
+
+# ---- many weights, one launch each way (brevitas_amd.core.quant.weight_group) -----------------------------------------
+class WeightListFakeQuantFn(Function):
+    """StatsFakeQuantFn for EVERY covered per-channel weight of a model at once: one bvq_weight_quant_list_fwd launch per
+    chunk of the list forward (at most nat.WEIGHT_LIST_MAX weights whose channels fit the arrival buffer), one
+    bvq_weight_quant_list_bwd launch per chunk backward, one autograd node instead of one per weight.  Each weight gets
+    the bits its own StatsFakeQuantFn would give it (same kernels per tensor, same tiling, same sums).
+
+    Inputs: `wl` (the group's _WeightList: the item array of include/bvq.h with each weight's static fields, its chunks,
+    and what the per-tensor route needs) and the weights.  Outputs: every weight's y, then every weight's scale (scaling
+    shape); those of a weight that needs no gradient are not differentiable, as its own StatsFakeQuantFn would make them.
+    Backward: a weight whose scale received a gradient (a bias quantizer fed w_scale), or whose gradient is strided,
+    misaligned or of another dtype, takes stats_backward alone, like the per-layer node; a weight none of whose outputs
+    received a gradient gets none; the rest go through the list kernel, one call per chunk."""
+
+    @staticmethod
+    def forward(ctx, wl, *ws):
+        ctx.set_materialize_grads(False)  # an unused output stays None: no zero-fill, no launch
+        n = len(ws)
+        ys, stats, scales = [], [], []
+        for lo, hi in wl.chunks:
+            y, stat, scale = nat.weight_quant_list_fwd(wl.items, lo, ws[lo:hi], wl.scale_dtype, wl.round_mode)
+            ys += y
+            stats.append(stat)
+            scales.append(scale)
+        out_scales = []
+        for (lo, hi), scale in zip(wl.chunks, scales):
+            for i, s in enumerate(torch.split(scale, wl.channels[lo:hi]), lo):
+                out_scales.append(s.view(wl.shapes[i]))
+        frozen = [i for i in range(n) if not ctx.needs_input_grad[1 + i]]
+        if frozen:
+            ctx.mark_non_differentiable(*[ys[i] for i in frozen], *[out_scales[i] for i in frozen])
+        # the weights are kept without save_for_backward's version check: a weight updated in place inside the block
+        # leaves this node (its layer re-quantizes it on its own) while the others still need it.  Versions are
+        # checked in backward for the weights that receive a gradient.
+        ctx.wl, ctx.ws, ctx.versions = wl, ws, [w._version for w in ws]
+        ctx.stats, ctx.scales = stats, scales
+        return (*ys, *out_scales)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        wl, ws = ctx.wl, ctx.ws
+        n = len(ws)
+        dxs = [None] * n
+        direct = [[] for _ in wl.chunks]  # per forward chunk, the weights its list call takes
+        for i in range(n):
+            gy, gs = grads[i], grads[n + i]
+            if (gy is None and gs is None) or not ctx.needs_input_grad[1 + i]:
+                continue
+            if ws[i]._version != ctx.versions[i]:
+                raise RuntimeError('WeightListFakeQuantFn: weight %d was modified in place after the group quantized it'
+                                   ' and before its gradient was computed' % i)
+            if gs is None and gy.dtype == ws[i].dtype and gy.is_contiguous() and gy.data_ptr() & 15 == 0:
+                direct[wl.chunk_of[i]].append(i)
+            else:
+                dxs[i] = WeightListFakeQuantFn._single(ctx, i, gy, gs)
+        for idx in direct:
+            if not idx:
+                continue
+            if idx[-1] - idx[0] == len(idx) - 1:  # a run of the forward's items
+                items, first = wl.items, idx[0]
+            else:
+                items, first = (nat.WeightItem * len(idx))(), 0
+                for j, i in enumerate(idx):
+                    items[j] = wl.items[i]
+            out = nat.weight_quant_list_bwd(items, first, [grads[i] for i in idx], [ws[i] for i in idx],
+                                            [WeightListFakeQuantFn._ptr(ctx, ctx.stats, i) for i in idx],
+                                            [WeightListFakeQuantFn._ptr(ctx, ctx.scales, i) for i in idx],
+                                            wl.scale_dtype, wl.scale_dtype, wl.round_mode)
+            for j, i in enumerate(idx):
+                dxs[i] = out[j] if out is not None else WeightListFakeQuantFn._single(ctx, i, grads[i], None)
+        return (None, *dxs)
+
+    @staticmethod
+    def _ptr(ctx, bufs, i):
+        """address of weight i's per-channel vector in the forward's statistic / scale buffers"""
+        buf = bufs[ctx.wl.chunk_of[i]]
+        return buf.data_ptr() + ctx.wl.offsets[i] * buf.element_size()
+
+    @staticmethod
+    def _single(ctx, i, gy, gscale):
+        """weight i alone through the per-tensor backward (StatsFakeQuantFn's)"""
+        wl, w = ctx.wl, ctx.ws[i]
+        c, o, ch = wl.chunk_of[i], wl.offsets[i], wl.channels[i]
+        stat = ctx.stats[c][o:o + ch]
+        scale = ctx.scales[c][o:o + ch].view(wl.shapes[i])
+        return stats_backward(w, scale, _zero_zero_point(w.device), stat, wl.int_thresholds[i], wl.descs[i], wl.sps[i],
+                              None, nat.PRE_NONE, None, gy, gscale)

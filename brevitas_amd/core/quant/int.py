@@ -32,6 +32,10 @@ from brevitas_amd.core.zero_point import ZeroZeroPoint
 from brevitas_amd.function.ops import int_range_host
 
 
+# the WeightQuantGroup whose `with` block is running (brevitas_amd/core/quant/weight_group.py), or None
+_ACTIVE_GROUP = None
+
+
 class RescalingIntQuant(torch.nn.Module):
     """
     Examples (B/core/quant/int.py:113-134):
@@ -168,6 +172,10 @@ class RescalingIntQuant(torch.nn.Module):
         return _fused.StatsPlan(outer, x.shape[cd], inner, shape, tmpl['min_val'], tmpl['int_thr']), tmpl
 
     def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        if _ACTIVE_GROUP is not None:  # inside `with WeightQuantGroup(...)`: the group may have quantized this weight
+            out = _ACTIVE_GROUP._member_forward(self, x)
+            if out is not None:
+                return out
         return self.bvq_forward_pre(x, nat.PRE_NONE)
 
     def _learned_scale_args(self, x: Tensor, bit_width: Tensor):

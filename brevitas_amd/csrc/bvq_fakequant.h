@@ -406,4 +406,8 @@ static int with_cols_variant(const bvq_quant_desc* d, bool nt, F&& f) {
 // instantiated vector widths: 16 bytes of x per lane, or one element (ragged / misaligned rows)
 static int snap_vec(int vec, int full) { return vec == full ? full : 1; }
 
+// bvq_fakequant_fwd.hip: the one-launch statistic + quantizer over the items of bvq_weight_quant_list_fwd, descs[i]
+// describing items[i] (the caller has checked the arguments; an item the single-tensor form does not cover fails)
+int fused_list_fwd(int n, const bvq_quant_desc* descs, const bvq_weight_item* items, hipStream_t st);
+
 }  // namespace bvq

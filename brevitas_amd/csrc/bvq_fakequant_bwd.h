@@ -511,13 +511,10 @@ __device__ __forceinline__ void bwd_unit(const QuantArgs& a, const Unit& u, cons
   }
 }
 
-// (96 scalar registers: one more would cost a resident workgroup per CU -- MI355X_MICROARCH.md, Residency)
+// one unit of the row-mapped backward with its channel's scale s and zero-point z: the division form and the
+// template variant chosen from them (fakequant_bwd_kernel, and the list form of bvq_weight_list.hip)
 template <typename XT, typename CT, int VEC, int RM, int MODE, bool NT, bool NTX = NT>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96), amdgpu_waves_per_eu(BVQ_BWD_WAVES, 8))) void fakequant_bwd_kernel(QuantArgs a) {
-  const Unit u = locate_unit(a.t);
-  if (!u.valid) return;
-  float s, z;
-  load_scale_zp<CT>(a, u.channel, s, z);
+__device__ __forceinline__ void bwd_unit_scaled(const QuantArgs& a, const Unit& u, float s, float z) {
   const float qmin = rnd<CT>(a.bounds ? a.bounds[0] : a.qmin), qmax = rnd<CT>(a.bounds ? a.bounds[1] : a.qmax);
   const bool zp0 = sizeof(CT) == 2 && zp_is_pos_zero(z);
 #define BVQ_BWD_UNIT(ZP0, PRE, DIV) bwd_unit<XT, CT, VEC, RM, MODE, NT, ZP0, PRE, NTX>(a, u, DIV, s, z, qmin, qmax)
@@ -562,6 +559,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96), amdgpu_
   BVQ_BWD_PRE(false, div);
 #undef BVQ_BWD_PRE
 #undef BVQ_BWD_UNIT
+}
+
+// (96 scalar registers: one more would cost a resident workgroup per CU -- MI355X_MICROARCH.md, Residency)
+template <typename XT, typename CT, int VEC, int RM, int MODE, bool NT, bool NTX = NT>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96), amdgpu_waves_per_eu(BVQ_BWD_WAVES, 8))) void fakequant_bwd_kernel(QuantArgs a) {
+  const Unit u = locate_unit(a.t);
+  if (!u.valid) return;
+  float s, z;
+  load_scale_zp<CT>(a, u.channel, s, z);
+  bwd_unit_scaled<XT, CT, VEC, RM, MODE, NT, NTX>(a, u, s, z);
 }
 
 
@@ -875,6 +882,14 @@ __global__ void shard_unpack_deposit_kernel(const double* __restrict__ all, int3
   T* dp = reinterpret_cast<T*>(dx);
   const float term = deposit<T, BVQ_MATCH_ABS>(g, xp[flat], gs.pre_relu != 0);
   dp[flat] = from_f<T>(to_f<T>(dp[flat]) + term);
+}
+
+// the backward's decomposition: quantizer-style tiling with every unit addressable through 32-bit buffer offsets
+// (4 = the widest element; the same bound for every dtype so that workspace sizing and launch agree)
+static inline Tiling bwd_tiling(int64_t outer, int32_t channels, int64_t row_len, int vec) {
+  Tiling t = make_tiling(outer, channels, row_len, vec, 0, true);
+  cap_unit_extent(t, 4);
+  return t;
 }
 
 // the row-mapped backward of one MODE under the streaming instantiation policy (with_stream_variant); the one-launch

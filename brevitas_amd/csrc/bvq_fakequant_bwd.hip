@@ -18,14 +18,6 @@ static int launch_bwd_pair(const bvq_quant_desc* d, const QuantArgs& a, int vec,
   });
 }
 
-// the backward's decomposition: quantizer-style tiling with every unit addressable through 32-bit buffer offsets
-// (4 = the widest element; the same bound for every dtype so that workspace sizing and launch agree)
-static Tiling bwd_tiling(int64_t outer, int32_t channels, int64_t row_len, int vec) {
-  Tiling t = make_tiling(outer, channels, row_len, vec, 0, true);
-  cap_unit_extent(t, 4);
-  return t;
-}
-
 static int64_t bwd_units(const bvq_quant_desc* d) {
   int64_t outer, row_len;
   int32_t channels;

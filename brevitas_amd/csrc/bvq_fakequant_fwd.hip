@@ -362,87 +362,132 @@ __global__ void fused_zero_kernel(uint32_t* p, int64_t n) {
   if (i < n) p[i] = 0u;
 }
 
+// the slice of a channel wave `q` of a workgroup holds (q < slices), and which of its 16-byte slots are in the row
+__device__ __forceinline__ void fused_slice(const FusedArgs& a, int q, int lane, int& r, int& sl, bool (&ok)[kFusedSlots]) {
+  const bool active = q < a.slices;
+  r = active ? q / a.spr : 0;
+  sl = active ? q - r * a.spr : 0;
+  const int nch = active ? (a.cpr - sl * kFusedSliceChunks < kFusedSliceChunks ? a.cpr - sl * kFusedSliceChunks
+                                                                              : kFusedSliceChunks)
+                         : 0;
+#pragma unroll
+  for (int j = 0; j < kFusedSlots; ++j) ok[j] = lane + kWave * j < nch;
+}
+
+// one channel c of the tensor `a` by the whole workgroup: every wave loads its slice into registers, the workgroup
+// agrees on the maximum through LDS, every wave quantizes what it holds.  Waves without a slice (ok all false) take
+// part in the barriers only.
+template <typename T, int RM>
+__device__ __forceinline__ void fused_channel(const FusedArgs& a, int32_t c, int r, int sl, const bool (&ok)[kFusedSlots],
+                                              float qmin, float qmax, int wave, int lane, int nwaves,
+                                              uint32_t* sh_max, uint32_t& sh_stat) {
+  constexpr int VEC = elem<T>::vec;
+  const int64_t base = ((int64_t)r * a.channels + c) * a.inner + (int64_t)sl * kFusedSliceChunks * VEC;
+  const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + base;
+  T* __restrict__ yp = reinterpret_cast<T*>(a.y) + base;
+  // phase 1: the slice into registers, its maximum |x| key
+  vec_t<T, VEC> xv[kFusedSlots];
+#pragma unroll
+  for (int j = 0; j < kFusedSlots; ++j)
+    xv[j] = load_vec<T, VEC, true>(ok[j] ? xp + (int64_t)(lane + kWave * j) * VEC : reinterpret_cast<const T*>(a.x));
+  uint32_t m = 0;
+#pragma unroll
+  for (int j = 0; j < kFusedSlots; ++j) {
+    if (ok[j]) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const uint32_t b = a.pre_relu ? pre_abs_bits<T, true>(xv[j].v[k]) : pre_abs_bits<T, false>(xv[j].v[k]);
+        m = b > m ? b : m;
+      }
+    }
+  }
+  m = wave_max_u32(m);
+  if (lane == 0) sh_max[wave] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t bm = 0;
+    for (int w = 0; w < nwaves; ++w) bm = sh_max[w] > bm ? sh_max[w] : bm;
+    sh_stat = bm;
+  }
+  __syncthreads();
+  float stat;
+  float s = scale_from_key<T>(sh_stat, a.use_min, a.min_val, a.int_threshold, a.scale_dtype, stat);
+  if (threadIdx.x == 0) store_stat_scale<T>(a.stat_out, a.scale_out, a.scale_dtype, c, stat, s);
+  // a 0-dim float32 scale next to a 16-bit tensor is rounded again by the device's scalar semantics
+  if (a.scalar_cast && !a.scale_pc) s = rnd<T>(s);
+  // phase 2: quantize what the registers still hold
+  const int mode = a.round_mode;
+  if constexpr (elem<T>::id == BVQ_BF16) {
+    if (bf16_scale_ok(s)) {
+      const DivBf16 div{1.0f / s};
+      if (a.pre_relu)
+        fused_quantize<T, RM, true>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
+      else
+        fused_quantize<T, RM, false>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
+      return;
+    }
+  }
+  if constexpr (elem<T>::id == BVQ_F16) {
+    if (f16_scale_ok(s)) {
+      const DivF16R div{s, 1.0f / s};
+      if (a.pre_relu)
+        fused_quantize<T, RM, true>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
+      else
+        fused_quantize<T, RM, false>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
+      return;
+    }
+  }
+  const DivExact div{s};
+  if (a.pre_relu)
+    fused_quantize<T, RM, true>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
+  else
+    fused_quantize<T, RM, false>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
+}
+
 template <typename T, int RM>
 __global__ __launch_bounds__(kFusedMaxWaves * kWave) void fused_absmax_fakequant_kernel(FusedArgs a) {
-  constexpr int VEC = elem<T>::vec;
   __shared__ uint32_t sh_max[kFusedMaxWaves];
   __shared__ uint32_t sh_stat;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int nwaves = (int)(blockDim.x >> 6);
-  const int q = wave;  // this wave's slice of every channel the workgroup visits
-  const bool active = q < a.slices;
-  const int r = active ? q / a.spr : 0;
-  const int sl = active ? q - r * a.spr : 0;
-  const int nch = active ? (a.cpr - sl * kFusedSliceChunks < kFusedSliceChunks ? a.cpr - sl * kFusedSliceChunks
-                                                                              : kFusedSliceChunks)
-                         : 0;
+  int r, sl;  // this wave's slice of every channel the workgroup visits
   bool ok[kFusedSlots];
-#pragma unroll
-  for (int j = 0; j < kFusedSlots; ++j) ok[j] = lane + kWave * j < nch;
+  fused_slice(a, wave, lane, r, sl, ok);
   const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
+  for (int32_t c = blockIdx.x; c < a.channels; c += gridDim.x)
+    fused_channel<T, RM>(a, c, r, sl, ok, qmin, qmax, wave, lane, nwaves, sh_max, sh_stat);
+}
 
-  for (int32_t c = blockIdx.x; c < a.channels; c += gridDim.x) {
-    const int64_t base = ((int64_t)r * a.channels + c) * a.inner + (int64_t)sl * kFusedSliceChunks * VEC;
-    const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + base;
-    T* __restrict__ yp = reinterpret_cast<T*>(a.y) + base;
-    // phase 1: the slice into registers, its maximum |x| key
-    vec_t<T, VEC> xv[kFusedSlots];
-#pragma unroll
-    for (int j = 0; j < kFusedSlots; ++j)
-      xv[j] = load_vec<T, VEC, true>(ok[j] ? xp + (int64_t)(lane + kWave * j) * VEC : reinterpret_cast<const T*>(a.x));
-    uint32_t m = 0;
-#pragma unroll
-    for (int j = 0; j < kFusedSlots; ++j) {
-      if (ok[j]) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-          const uint32_t b = a.pre_relu ? pre_abs_bits<T, true>(xv[j].v[k]) : pre_abs_bits<T, false>(xv[j].v[k]);
-          m = b > m ? b : m;
-        }
-      }
+// The same over a LIST of tensors (bvq_weight_quant_list_fwd): the workgroups are dealt over the (tensor, channel) pairs
+// of the whole list; the workgroup has the list's largest number of slices per channel in waves, and a tensor with
+// fewer leaves the rest idle.  Every channel is done exactly as fused_absmax_fakequant_kernel does it.
+struct FusedListArgs {
+  FusedArgs a[BVQ_WEIGHT_LIST_MAX];
+  int32_t start[BVQ_WEIGHT_LIST_MAX + 1];  // first pair of tensor i; start[n] = all pairs
+  int32_t n;
+};
+static_assert(sizeof(FusedListArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+template <typename T, int RM>
+__global__ __launch_bounds__(kFusedMaxWaves * kWave) void fused_list_fakequant_kernel(FusedListArgs la) {
+  __shared__ uint32_t sh_max[kFusedMaxWaves];
+  __shared__ uint32_t sh_stat;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nwaves = (int)(blockDim.x >> 6);
+  int p = -1, r = 0, sl = 0;
+  bool ok[kFusedSlots];
+  float qmin = 0.f, qmax = 0.f;
+  for (int32_t pair = blockIdx.x; pair < la.start[la.n]; pair += gridDim.x) {
+    if (p < 0 || pair >= la.start[p + 1]) {  // (workgroup-uniform) the pairs only grow: the tensor index follows them
+      if (p < 0) p = 0;
+      while (p + 1 < la.n && pair >= la.start[p + 1]) ++p;
+      fused_slice(la.a[p], wave, lane, r, sl, ok);
+      qmin = rnd<T>(la.a[p].qmin);
+      qmax = rnd<T>(la.a[p].qmax);
     }
-    m = wave_max_u32(m);
-    if (lane == 0) sh_max[wave] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t bm = 0;
-      for (int w = 0; w < nwaves; ++w) bm = sh_max[w] > bm ? sh_max[w] : bm;
-      sh_stat = bm;
-    }
-    __syncthreads();
-    float stat;
-    float s = scale_from_key<T>(sh_stat, a.use_min, a.min_val, a.int_threshold, a.scale_dtype, stat);
-    if (threadIdx.x == 0) store_stat_scale<T>(a.stat_out, a.scale_out, a.scale_dtype, c, stat, s);
-    // a 0-dim float32 scale next to a 16-bit tensor is rounded again by the device's scalar semantics
-    if (a.scalar_cast && !a.scale_pc) s = rnd<T>(s);
-    // phase 2: quantize what the registers still hold
-    const int mode = a.round_mode;
-    if constexpr (elem<T>::id == BVQ_BF16) {
-      if (bf16_scale_ok(s)) {
-        const DivBf16 div{1.0f / s};
-        if (a.pre_relu)
-          fused_quantize<T, RM, true>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
-        else
-          fused_quantize<T, RM, false>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
-        continue;
-      }
-    }
-    if constexpr (elem<T>::id == BVQ_F16) {
-      if (f16_scale_ok(s)) {
-        const DivF16R div{s, 1.0f / s};
-        if (a.pre_relu)
-          fused_quantize<T, RM, true>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
-        else
-          fused_quantize<T, RM, false>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
-        continue;
-      }
-    }
-    const DivExact div{s};
-    if (a.pre_relu)
-      fused_quantize<T, RM, true>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
-    else
-      fused_quantize<T, RM, false>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
+    fused_channel<T, RM>(la.a[p], pair - la.start[p], r, sl, ok, qmin, qmax, wave, lane, nwaves, sh_max, sh_stat);
   }
 }
 
@@ -589,6 +634,34 @@ extern "C" int64_t bvq_stats_fakequant_fwd_workspace_bytes(const bvq_quant_desc*
   return 0;  // not applicable: use bvq_absmax_scale + bvq_fakequant_fwd
 }
 
+// the kernel arguments of one tensor of the one-launch statistic + quantizer
+static FusedArgs fused_args(const bvq_quant_desc* d, const FusedPlan& p, const void* x, void* y, void* stat_out,
+                            void* scale_out, double min_val, int use_min, double int_threshold) {
+  const bool pc = d->scale_per_channel && d->channels > 1;
+  FusedArgs a = {};
+  a.x = x;
+  a.y = y;
+  a.stat_out = stat_out;
+  a.scale_out = scale_out;
+  a.outer = pc ? d->outer : 1;
+  a.inner = pc ? d->inner : d->outer * d->channels * d->inner;
+  a.channels = (int32_t)(pc ? d->channels : 1);
+  a.cpr = p.cpr;
+  a.spr = p.spr;
+  a.slices = p.slices;
+  a.qmin = d->qmin;
+  a.qmax = d->qmax;
+  a.min_val = round_host((float)min_val, d->x_dtype);  // python scalar -> the statistic's dtype
+  a.use_min = use_min;
+  a.int_threshold = (float)int_threshold;
+  a.scale_dtype = d->scale_dtype;
+  a.scale_pc = pc ? 1 : 0;
+  a.scalar_cast = d->scalar_mode == BVQ_SCALAR_CAST;
+  a.round_mode = d->round_mode;
+  a.pre_relu = d->pre_op == BVQ_PRE_RELU;
+  return a;
+}
+
 extern "C" int bvq_stats_fakequant_fwd(const bvq_quant_desc* d, const void* x, double min_val, int use_min,
                                        double int_threshold, void* stat_out, void* scale_out, void* y,
                                        void* workspace, int64_t workspace_bytes, bvq_stream_t stream) {
@@ -599,31 +672,9 @@ extern "C" int bvq_stats_fakequant_fwd(const bvq_quant_desc* d, const void* x, d
     return BVQ_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
-  const bool pc = d->scale_per_channel && d->channels > 1;
-  const int64_t channels = pc ? d->channels : 1;
   FusedPlan p;
   if (fused_plan(d, x, y, p)) {
-    FusedArgs a = {};
-    a.x = x;
-    a.y = y;
-    a.stat_out = stat_out;
-    a.scale_out = scale_out;
-    a.outer = pc ? d->outer : 1;
-    a.inner = pc ? d->inner : d->outer * d->channels * d->inner;
-    a.channels = (int32_t)channels;
-    a.cpr = p.cpr;
-    a.spr = p.spr;
-    a.slices = p.slices;
-    a.qmin = d->qmin;
-    a.qmax = d->qmax;
-    a.min_val = round_host((float)min_val, d->x_dtype);  // python scalar -> the statistic's dtype
-    a.use_min = use_min;
-    a.int_threshold = (float)int_threshold;
-    a.scale_dtype = d->scale_dtype;
-    a.scale_pc = pc ? 1 : 0;
-    a.scalar_cast = d->scalar_mode == BVQ_SCALAR_CAST;
-    a.round_mode = d->round_mode;
-    a.pre_relu = d->pre_op == BVQ_PRE_RELU;
+    const FusedArgs a = fused_args(d, p, x, y, stat_out, scale_out, min_val, use_min, int_threshold);
     const dim3 grid((unsigned)p.nblocks), block((unsigned)(p.waves * kWave));
     // (one cache policy: the kernel streams non-temporally whatever the size)
     rc = with_cols_variant(d, false, [&](auto t, auto rm, auto) {
@@ -634,6 +685,39 @@ extern "C" int bvq_stats_fakequant_fwd(const bvq_quant_desc* d, const void* x, d
   set_error("bvq_stats_fakequant_fwd: shape / layout not covered by the one-launch form");
   return BVQ_ERR_UNSUPPORTED;
 }
+
+namespace bvq {
+int fused_list_fwd(int n, const bvq_quant_desc* descs, const bvq_weight_item* items, hipStream_t st) {
+  FusedListArgs la = {};
+  la.n = n;
+  int64_t pairs = 0;
+  int waves = 1;
+  for (int i = 0; i < n; ++i) {
+    const bvq_weight_item& it = items[i];
+    FusedPlan p;
+    if (!fused_plan(&descs[i], it.x, it.y, p)) {
+      set_error("bvq_weight_quant_list_fwd: item %d not covered by the one-launch form", i);
+      return BVQ_ERR_UNSUPPORTED;
+    }
+    la.a[i] = fused_args(&descs[i], p, it.x, it.y, it.stat, it.scale, it.min_val, it.use_min, it.int_threshold);
+    la.start[i] = (int32_t)pairs;
+    pairs += la.a[i].channels;
+    waves = p.waves > waves ? p.waves : waves;
+  }
+  if (pairs >= ((int64_t)1 << 31)) {
+    set_error("bvq_weight_quant_list_fwd: too many channels");
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  la.start[n] = (int32_t)pairs;
+  // residency budget of the single-tensor launch: 2 workgroups of 512 threads per CU (or as many waves in smaller ones)
+  const int64_t budget = (int64_t)num_cus() * 2 * kFusedMaxWaves / waves;
+  const dim3 grid((unsigned)(budget < pairs ? budget : pairs)), block((unsigned)(waves * kWave));
+  const int rc = with_cols_variant(&descs[0], false, [&](auto t, auto rm, auto) {
+    fused_list_fakequant_kernel<typename decltype(t)::type, rm><<<grid, block, 0, st>>>(la);
+  });
+  return rc ? rc : check_launch("bvq_weight_quant_list_fwd");
+}
+}  // namespace bvq
 
 // self-test of the float16 division (DivF16R): out[j * n_a + i] = the quotient the kernels compute for numerator
 // a[i] and scale s[j], so that a test can compare EVERY pair with a / s on the device itself

@@ -10,8 +10,9 @@ import torch
 import torch.nn.functional as F
 
 from brevitas_amd.core.quant import RescalingIntQuant
+from brevitas_amd.core.quant.weight_group import WeightQuantGroup
 
-__all__ = ['QuantConv2d', 'QuantLinear', 'QuantIdentity']
+__all__ = ['QuantConv2d', 'QuantLinear', 'QuantIdentity', 'WeightQuantGroup']
 
 WeightQuantFactory = Callable[[torch.nn.Parameter], RescalingIntQuant]
 
