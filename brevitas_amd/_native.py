@@ -26,6 +26,7 @@ MATCH_ABS, MATCH_VALUE = 0, 1
 MATCH_FIRST = 16  # OR-ed: only the first attaining element, even for a whole-tensor reduction
 PRE_NONE, PRE_RELU = 0, 1
 CODES_I32, CODES_I8, CODES_U8 = 0, 1, 2
+CLUSTER_FORCE_FALLBACK = 1  # BVQ_CLUSTER_FORCE_FALLBACK: tests only
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
 ABI_VERSION = 2
 
@@ -44,7 +45,8 @@ EXPORTS = (
     'bvq_absmax_onepass_supported', 'bvq_absmax_scale_onepass', 'bvq_fakequant_bwd_stats_onepass_supported',
     'bvq_fakequant_bwd_stats_onepass', 'bvq_scale_from_stat_running', 'bvq_fakequant_bwd_shard',
     'bvq_shard_unpack_deposit', 'bvq_absmax_list_supported', 'bvq_absmax_scale_list', 'bvq_weight_list_supported',
-    'bvq_weight_quant_list_fwd', 'bvq_weight_quant_list_bwd_workspace_bytes', 'bvq_weight_quant_list_bwd')
+    'bvq_weight_quant_list_fwd', 'bvq_weight_quant_list_bwd_workspace_bytes', 'bvq_weight_quant_list_bwd',
+    'bvq_absmax_fakequant_cluster_supported', 'bvq_absmax_fakequant_cluster')
 
 
 class QuantDesc(ctypes.Structure):
@@ -161,6 +163,9 @@ def _load(path=None, strict=True):
         'bvq_weight_quant_list_fwd': (i32, [i32, i32, i32, i32, vp, vp]),
         'bvq_weight_quant_list_bwd_workspace_bytes': (i64, [i32, i32, vp]),
         'bvq_weight_quant_list_bwd': (i32, [i32, i32, i32, i32, i32, vp, vp, i64, vp, i64, vp]),
+        'bvq_absmax_fakequant_cluster_supported': (i64, [ctypes.POINTER(QuantDesc), vp, vp]),
+        'bvq_absmax_fakequant_cluster': (i32, [ctypes.POINTER(QuantDesc), vp, dbl, i32, dbl, vp, vp, i32, vp, dbl, i32, vp,
+                                               vp, i64, i32, vp, vp]),
         'bvq_fakequant_bwd_learned': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, i32, dbl, i32, dbl, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
@@ -436,6 +441,37 @@ def stats_fakequant_fwd(desc, x, min_val, int_threshold, scale_dtype):
         check(lib.bvq_stats_fakequant_fwd(ctypes.byref(desc), ptr(x), float(min_val or 0.0), int(bool(min_val)),
                                           float(int_threshold), ptr(stat), ptr(scale), ptr(y), ptr(ws), wsb,
                                           stream_ptr(dev)), 'bvq_stats_fakequant_fwd')
+        if _timer is not None:
+            _timer.after('bvq_stats_fakequant_fwd')
+    return stat, scale, y
+
+
+def absmax_fakequant_cluster(desc, x, min_val, int_threshold, scale_dtype, running=None, momentum=0.0,
+                             first_batch=False, flags=0, fallbacks=None):
+    """abs-max statistic, scale, running statistic and quantize-dequantize in ONE launch for channels held by a cluster
+    of workgroups (x read once) -> (stat, scale, y), the bits of absmax_scale + fakequant_fwd; or None when the shape is
+    not covered or there is no arrival buffer (capturing, ONEPASS off): the caller takes the two-call route.
+    fallbacks: optional int32 device counter of the workgroups that read their channel themselves."""
+    dev = require_device(x)
+    assert x.is_contiguous()
+    y = torch.empty_like(x)
+    words = int(lib.bvq_absmax_fakequant_cluster_supported(ctypes.byref(desc), ptr(x), ptr(y)))
+    if words <= 0:
+        return None
+    with _DeviceGuard(dev):
+        st = stream_ptr(dev)
+        arrive = arrival_buffer(dev, st, words)
+        if arrive is None:
+            return None
+        stat = torch.empty(desc.channels, dtype=x.dtype, device=dev)
+        scale = torch.empty(desc.channels, dtype=scale_dtype, device=dev)
+        if _timer is not None:
+            _timer.before('bvq_stats_fakequant_fwd')
+        check(lib.bvq_absmax_fakequant_cluster(
+            ctypes.byref(desc), ptr(x), float(min_val or 0.0), int(bool(min_val)), float(int_threshold), ptr(stat),
+            ptr(scale), dtype_code(running.dtype) if running is not None else 0, ptr(running), float(momentum),
+            int(first_batch), ptr(y), ptr(arrive), arrive.numel(), int(flags), ptr(fallbacks), st),
+            'bvq_absmax_fakequant_cluster')
         if _timer is not None:
             _timer.after('bvq_stats_fakequant_fwd')
     return stat, scale, y

@@ -427,6 +427,21 @@ class StatsFakeQuantFn(Function):
                                  nat.dtype_code(zp.dtype), int(sp.channels > 1), 0, qmin, qmax, round_mode,
                                  scalar_mode(), int(clamp_ste), nat.OUT_DEQUANT, pre_op)
             fused = nat.stats_fakequant_fwd(desc, xc, sp.min_val, thr_div, scale_dtype)
+            if fused is None and len(sp.scaling_shape) > 0 and sp.channels > 1:
+                # a channel larger than one workgroup: held by a cluster of workgroups, x still read once; the running
+                # statistic rides on the same launch
+                running = None
+                if runtime is not None:
+                    buf = runtime.running_stats
+                    if buf.is_cuda and buf.is_contiguous() and buf.numel() == sp.channels and buf.dtype in _FLOATS:
+                        running = buf
+                if runtime is None or running is not None:
+                    fused = nat.absmax_fakequant_cluster(
+                        desc, xc, sp.min_val, thr_div, scale_dtype, running,
+                        runtime.momentum if running is not None else 0.0,
+                        runtime.first_batch if running is not None else False)
+                    if fused is not None and running is not None:
+                        runtime.bvq_running_folded = True
         if fused is not None:
             stat, scale, y = fused
             scale = scale.view(sp.scaling_shape)

@@ -9,7 +9,8 @@
 //   StatsFakeQuant (weights)       forward   bvq_stats_fakequant_fwd      statistic + scale + quantize, one launch
 //                                  backward  bvq_fakequant_bwd_stats      dx with the statistic's gradient deposited
 //   ActStatsFakeQuant (activations whose channels do not fit one workgroup; RuntimeStatsScaling in training mode)
-//                                  forward   bvq_absmax_scale_onepass | bvq_absmax_scale[_running]   statistic (+ scale,
+//                                  forward   bvq_absmax_fakequant_cluster (unsharded, covered: one launch) |
+//                                            bvq_absmax_scale_onepass | bvq_absmax_scale[_running]   statistic (+ scale,
 //                                            running average), bvq_fakequant_fwd
 //                                  backward  bvq_fakequant_bwd_stats[_onepass] (per-channel) |
 //                                            bvq_fakequant_bwd + bvq_stat_tie_apply_dscale (per-tensor)
@@ -58,6 +59,8 @@ namespace {
   X(bvq_fakequant_bwd_stats_onepass)         \
   X(bvq_absmax_onepass_supported)            \
   X(bvq_absmax_scale_onepass)                \
+  X(bvq_absmax_fakequant_cluster_supported)  \
+  X(bvq_absmax_fakequant_cluster)            \
   X(bvq_stats_workspace_bytes)               \
   X(bvq_stats_pre)                           \
   X(bvq_absmax_scale)                        \
@@ -291,9 +294,18 @@ class ActStatsFakeQuant : public torch::autograd::Function<ActStatsFakeQuant> {
     const bool has_running = running.numel() > 0, has_arrive = arrive.numel() > 0;
     void* run_ptr = has_running ? running.data_ptr() : nullptr;
     const int run_dt = has_running ? code_of(running.scalar_type()) : BVQ_F32;
-    const bool onepass = has_arrive &&
+    at::Tensor y = at::empty(x.sizes(), x.options().dtype(dtype_of(d.ct_dtype)));
+    // unsharded, covered: statistic + scale + running + quantizer in one launch, channels held by clusters of workgroups
+    const int64_t words = (!sharded && has_arrive) ? p_bvq_absmax_fakequant_cluster_supported(&d, x.data_ptr(), y.data_ptr()) : 0;
+    const bool cluster = words > 0 && words <= arrive.numel();
+    const bool onepass = !cluster && has_arrive &&
                          p_bvq_absmax_onepass_supported(d.x_dtype, x.data_ptr(), d.outer, ch, d.inner);
-    if (onepass) {
+    if (cluster) {
+      check(p_bvq_absmax_fakequant_cluster(&d, x.data_ptr(), p.min_val, p.has_min, p.thr_fwd, stat.data_ptr(),
+                                           scale.data_ptr(), run_dt, run_ptr, p.momentum, p.first_batch, y.data_ptr(),
+                                           reinterpret_cast<uint32_t*>(arrive.data_ptr()), arrive.numel(), 0, nullptr, st),
+            "bvq_absmax_fakequant_cluster");
+    } else if (onepass) {
       check(p_bvq_absmax_scale_onepass(d.pre_op, d.x_dtype, x.data_ptr(), d.outer, ch, d.inner,
                                        sharded ? BVQ_F32 : d.x_dtype, sharded ? stat32.data_ptr() : stat.data_ptr(),
                                        p.min_val, p.has_min, p.thr_fwd, p.scale_dtype,
@@ -337,9 +349,9 @@ class ActStatsFakeQuant : public torch::autograd::Function<ActStatsFakeQuant> {
                                           p.first_batch, st),
             "bvq_scale_from_stat_running");
     }
-    at::Tensor y = at::empty(x.sizes(), x.options().dtype(dtype_of(d.ct_dtype)));
-    check(p_bvq_fakequant_fwd(&d, x.data_ptr(), scale.data_ptr(), zp.data_ptr(), y.data_ptr(), nullptr, st),
-          "bvq_fakequant_fwd");
+    if (!cluster)
+      check(p_bvq_fakequant_fwd(&d, x.data_ptr(), scale.data_ptr(), zp.data_ptr(), y.data_ptr(), nullptr, st),
+            "bvq_fakequant_fwd");
     ctx->save_for_backward({x, scale, zp, stat, int_threshold, arrive});
     ctx->saved_data["desc"] = desc_ints(p);
     ctx->saved_data["qrange"] = std::vector<double>{d.qmin, d.qmax, p.thr_bwd, p.thr_raw};

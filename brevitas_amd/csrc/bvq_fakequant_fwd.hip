@@ -8,6 +8,7 @@
 //   forward  sizeof(x) + sizeof(y)          backward  sizeof(g) + sizeof(x) + sizeof(dx).
 
 #include "bvq_fakequant.h"
+#include "bvq_stat_epilogue.h"
 
 namespace bvq {
 
@@ -279,10 +280,9 @@ __global__ __launch_bounds__(kBlock) void fakequant_fwd_cols_kernel(ColsQuantArg
 // channel at a time: every wave loads one slice of the channel (<= 8 chunks of 16 bytes per lane: 8 KiB
 // per wave) into registers, the workgroup agrees on the channel's maximum through LDS, and every wave
 // quantizes what it still holds.  x is read ONCE, one launch instead of three.  Channels that do not fit
-// one workgroup's registers take the two-kernel route: holding them across several workgroups (round 1) or
-// pipelining slabs of channels through the Infinity Cache in one launch (round 2,
-// profiles/r02_slab_pipeline_experiment.txt) both lost to it -- the hand-off between workgroups costs more
-// than the saved read.
+// one workgroup's registers: the cluster form below (several workgroups hold one channel and exchange one key word
+// each).  Pipelining slabs of channels through the Infinity Cache instead (round 2,
+// profiles/r02_slab_pipeline_experiment.txt) lost to the two-kernel route.
 constexpr int kFusedSlots = 8;          // 16-byte chunks per lane held in registers
 constexpr int kFusedSliceChunks = 512;  // kWave * kFusedSlots
 constexpr int kFusedMaxWaves = 8;       // waves per workgroup
@@ -374,48 +374,45 @@ __device__ __forceinline__ void fused_slice(const FusedArgs& a, int q, int lane,
   for (int j = 0; j < kFusedSlots; ++j) ok[j] = lane + kWave * j < nch;
 }
 
-// one channel c of the tensor `a` by the whole workgroup: every wave loads its slice into registers, the workgroup
-// agrees on the maximum through LDS, every wave quantizes what it holds.  Waves without a slice (ok all false) take
-// part in the barriers only.
-template <typename T, int RM>
-__device__ __forceinline__ void fused_channel(const FusedArgs& a, int32_t c, int r, int sl, const bool (&ok)[kFusedSlots],
-                                              float qmin, float qmax, int wave, int lane, int nwaves,
-                                              uint32_t* sh_max, uint32_t& sh_stat) {
+// phase 1 of a channel: the slice (r, sl) of channel c into registers (slots that are not in the row read the tensor's
+// first chunk and are never used)
+template <typename T>
+__device__ __forceinline__ void fused_load(const FusedArgs& a, int32_t c, int r, int sl, const bool (&ok)[kFusedSlots],
+                                           int lane, vec_t<T, elem<T>::vec> (&xv)[kFusedSlots]) {
   constexpr int VEC = elem<T>::vec;
   const int64_t base = ((int64_t)r * a.channels + c) * a.inner + (int64_t)sl * kFusedSliceChunks * VEC;
   const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + base;
-  T* __restrict__ yp = reinterpret_cast<T*>(a.y) + base;
-  // phase 1: the slice into registers, its maximum |x| key
-  vec_t<T, VEC> xv[kFusedSlots];
 #pragma unroll
   for (int j = 0; j < kFusedSlots; ++j)
     xv[j] = load_vec<T, VEC, true>(ok[j] ? xp + (int64_t)(lane + kWave * j) * VEC : reinterpret_cast<const T*>(a.x));
+}
+
+// ... and its maximum |x| key (this lane's)
+template <typename T>
+__device__ __forceinline__ uint32_t fused_key(const FusedArgs& a, const vec_t<T, elem<T>::vec> (&xv)[kFusedSlots],
+                                              const bool (&ok)[kFusedSlots]) {
   uint32_t m = 0;
 #pragma unroll
   for (int j = 0; j < kFusedSlots; ++j) {
     if (ok[j]) {
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) {
+      for (int k = 0; k < elem<T>::vec; ++k) {
         const uint32_t b = a.pre_relu ? pre_abs_bits<T, true>(xv[j].v[k]) : pre_abs_bits<T, false>(xv[j].v[k]);
         m = b > m ? b : m;
       }
     }
   }
-  m = wave_max_u32(m);
-  if (lane == 0) sh_max[wave] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t bm = 0;
-    for (int w = 0; w < nwaves; ++w) bm = sh_max[w] > bm ? sh_max[w] : bm;
-    sh_stat = bm;
-  }
-  __syncthreads();
-  float stat;
-  float s = scale_from_key<T>(sh_stat, a.use_min, a.min_val, a.int_threshold, a.scale_dtype, stat);
-  if (threadIdx.x == 0) store_stat_scale<T>(a.stat_out, a.scale_out, a.scale_dtype, c, stat, s);
-  // a 0-dim float32 scale next to a 16-bit tensor is rounded again by the device's scalar semantics
-  if (a.scalar_cast && !a.scale_pc) s = rnd<T>(s);
-  // phase 2: quantize what the registers still hold
+  return m;
+}
+
+// phase 2 of a channel: quantize what the registers still hold with the scale s
+template <typename T, int RM>
+__device__ __forceinline__ void fused_apply(const FusedArgs& a, int32_t c, int r, int sl,
+                                            const vec_t<T, elem<T>::vec> (&xv)[kFusedSlots], const bool (&ok)[kFusedSlots],
+                                            float s, float qmin, float qmax, int lane) {
+  constexpr int VEC = elem<T>::vec;
+  const int64_t base = ((int64_t)r * a.channels + c) * a.inner + (int64_t)sl * kFusedSliceChunks * VEC;
+  T* __restrict__ yp = reinterpret_cast<T*>(a.y) + base;
   const int mode = a.round_mode;
   if constexpr (elem<T>::id == BVQ_BF16) {
     if (bf16_scale_ok(s)) {
@@ -442,6 +439,32 @@ __device__ __forceinline__ void fused_channel(const FusedArgs& a, int32_t c, int
     fused_quantize<T, RM, true>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
   else
     fused_quantize<T, RM, false>(xv, ok, yp, lane, div, s, qmin, qmax, mode);
+}
+
+// one channel c of the tensor `a` by the whole workgroup: every wave loads its slice into registers, the workgroup
+// agrees on the maximum through LDS, every wave quantizes what it holds.  Waves without a slice (ok all false) take
+// part in the barriers only.
+template <typename T, int RM>
+__device__ __forceinline__ void fused_channel(const FusedArgs& a, int32_t c, int r, int sl, const bool (&ok)[kFusedSlots],
+                                              float qmin, float qmax, int wave, int lane, int nwaves,
+                                              uint32_t* sh_max, uint32_t& sh_stat) {
+  vec_t<T, elem<T>::vec> xv[kFusedSlots];
+  fused_load<T>(a, c, r, sl, ok, lane, xv);
+  const uint32_t m = wave_max_u32(fused_key<T>(a, xv, ok));
+  if (lane == 0) sh_max[wave] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t bm = 0;
+    for (int w = 0; w < nwaves; ++w) bm = sh_max[w] > bm ? sh_max[w] : bm;
+    sh_stat = bm;
+  }
+  __syncthreads();
+  float stat;
+  float s = scale_from_key<T>(sh_stat, a.use_min, a.min_val, a.int_threshold, a.scale_dtype, stat);
+  if (threadIdx.x == 0) store_stat_scale<T>(a.stat_out, a.scale_out, a.scale_dtype, c, stat, s);
+  // a 0-dim float32 scale next to a 16-bit tensor is rounded again by the device's scalar semantics
+  if (a.scalar_cast && !a.scale_pc) s = rnd<T>(s);
+  fused_apply<T, RM>(a, c, r, sl, xv, ok, s, qmin, qmax, lane);
 }
 
 template <typename T, int RM>
@@ -488,6 +511,172 @@ __global__ __launch_bounds__(kFusedMaxWaves * kWave) void fused_list_fakequant_k
       qmax = rnd<T>(la.a[p].qmax);
     }
     fused_channel<T, RM>(la.a[p], pair - la.start[p], r, sl, ok, qmin, qmax, wave, lane, nwaves, sh_max, sh_stat);
+  }
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// statistic + quantizer in ONE kernel, channels held by a CLUSTER of workgroups
+// ------------------------------------------------------------------------------------------------
+// A channel that does not fit one workgroup's registers ([256,512,56,56] bf16: 1.53 MiB) is held by `members`
+// workgroups at once, one slice (fused_slice) per wave, so x is still read once.  The members agree on the channel's
+// maximum through one 32-bit word each: every member folds its key in LDS, its wave 0 publishes the key (tagged, one
+// agent-scope store: the word is the data and its own flag, so no release fence; cdna_hip_programming §6 Guideline 16
+// R2) and then sweeps the cluster's words with one relaxed agent-scope load per lane (one member per lane, s_sleep
+// between passes) while the other waves wait at the barrier -- and every wave already has the NEXT channel's loads in
+// flight.  A persistent grid of clusters walks the channels: cluster k takes k, k + nclusters, ...
+//
+// Never an unbounded wait: the sweep has a budget on the constant-rate clock (s_memrealtime, 100 MHz); when it runs
+// out (partners not resident, or the test bit BVQ_CLUSTER_FORCE_FALLBACK) the workgroup reads every row of the channel
+// itself.  A max is exact and order-independent, so that gives the same bits; the workgroup has already published, so
+// its partners still finish.
+//
+// Arrival words (zero on entry, handed back as zeros): key[c * members + i] for member i of channel c, then dep[c]:
+// every member adds one to dep[c] once it has its maximum (after its sweep's loads returned, or, on the fallback, after
+// its own key store has been written through: s_waitcnt vmcnt(0)); the member whose add completes the count knows no
+// partner still reads channel c's words and zeroes them.  Member 0 writes the statistic, scale and running statistic
+// (absmax_epilogue: the bits of bvq_absmax_scale_onepass).
+// (profiles/cluster_fwd.md, [256,512,56,56] bf16: 16 waves 0.352 ms, 8 waves 0.363; without the prefetch 0.409 at
+//  16 waves per CU, 0.365 at 24 -- 110 VGPRs with it, 73 without)
+#ifndef BVQ_CLUSTER_WAVES
+#define BVQ_CLUSTER_WAVES 16  // waves per workgroup: 16 workgroups per headline channel
+#endif
+#ifndef BVQ_CLUSTER_WAVES_PER_CU
+#define BVQ_CLUSTER_WAVES_PER_CU 16  // resident waves per CU the grid is sized for (4 per SIMD: <= 128 VGPRs)
+#endif
+#ifndef BVQ_CLUSTER_PREFETCH
+#define BVQ_CLUSTER_PREFETCH 1  // the next channel's loads are issued before the sweep for this one
+#endif
+constexpr int kClusterWaves = BVQ_CLUSTER_WAVES;
+constexpr int kClusterWavesPerCu = BVQ_CLUSTER_WAVES_PER_CU;
+constexpr bool kClusterPrefetch = BVQ_CLUSTER_PREFETCH != 0;
+constexpr int kClusterMaxMembers = kWave;           // one sweeping lane per member
+constexpr uint32_t kClusterTag = 0x80000000u;       // abs keys never have the top bit set
+constexpr uint64_t kClusterBudgetTicks = 200000;    // 2 ms of s_memrealtime (100 MHz) before the fallback
+static_assert(kClusterWaves >= 1 && kClusterWaves * kWave <= 1024, "BVQ_CLUSTER_WAVES");
+
+struct ClusterArgs {
+  FusedArgs f;        // the tensor (f.stat_out / f.scale_out unused: the epilogue writes the outputs)
+  ScaleEpilogue ep;
+  void* stat_out;     // [channels], dtype of x
+  int32_t in_dtype;
+  uint32_t* key;      // [channels][members]
+  uint32_t* dep;      // [channels]
+  uint32_t* fallbacks;  // nullable: fallbacks taken
+  int32_t members, nclusters, force_fallback;
+};
+
+template <typename T, int RM>
+__global__ __launch_bounds__(kClusterWaves * kWave, kClusterWavesPerCu / 4) void cluster_absmax_fakequant_kernel(ClusterArgs ca) {
+  constexpr int VEC = elem<T>::vec;
+  __shared__ uint32_t sh_max[kClusterWaves];
+  __shared__ uint32_t sh_stat, sh_ok;
+  const FusedArgs& a = ca.f;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int32_t members = ca.members;
+  const int32_t member = (int32_t)blockIdx.x % members, cluster = (int32_t)blockIdx.x / members;
+  int r, sl;
+  bool ok[kFusedSlots];
+  fused_slice(a, member * kClusterWaves + wave, lane, r, sl, ok);
+  const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
+  int32_t c = cluster;
+  if (c >= a.channels) return;  // (workgroup-uniform)
+  vec_t<T, VEC> xv[kFusedSlots];
+  fused_load<T>(a, c, r, sl, ok, lane, xv);
+  for (; c < a.channels; c += ca.nclusters) {
+    const uint32_t m = wave_max_u32(fused_key<T>(a, xv, ok));
+    if (lane == 0) sh_max[wave] = m;
+    __syncthreads();
+    uint32_t* const keys = ca.key + (int64_t)c * members;
+    if (wave == 0) {
+      uint32_t bm = 0;
+      for (int w = 0; w < kClusterWaves; ++w) bm = sh_max[w] > bm ? sh_max[w] : bm;
+      if (lane == 0) __hip_atomic_store(keys + member, bm | kClusterTag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const int32_t cn = c + ca.nclusters;
+    vec_t<T, VEC> xn[kFusedSlots];
+    if (kClusterPrefetch && cn < a.channels) fused_load<T>(a, cn, r, sl, ok, lane, xn);
+    if (wave == 0) {
+      bool done = false;
+      uint32_t v = 0;
+      if (!ca.force_fallback) {
+        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+        for (;;) {
+          v = lane < members ? __hip_atomic_load(keys + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kClusterTag;
+          if (__all((v & kClusterTag) != 0)) {
+            done = true;
+            break;
+          }
+          if (__builtin_amdgcn_s_memrealtime() - t0 > kClusterBudgetTicks) break;
+          __builtin_amdgcn_s_sleep(2);
+        }
+      }
+      v = wave_max_u32(v) & ~kClusterTag;
+      if (lane == 0) {
+        sh_stat = v;
+        sh_ok = done ? 1u : 0u;
+      }
+    }
+    __syncthreads();
+    if (!sh_ok) {  // (workgroup-uniform) the fallback: every row of the channel, one chunk at a time
+      uint32_t fm = 0;
+      for (int q = wave; q < a.slices; q += kClusterWaves) {
+        int fr, fsl;
+        bool fok[kFusedSlots];
+        fused_slice(a, q, lane, fr, fsl, fok);
+        const T* xp = reinterpret_cast<const T*>(a.x) + ((int64_t)fr * a.channels + c) * a.inner +
+                      (int64_t)fsl * kFusedSliceChunks * VEC;
+        for (int j = 0; j < kFusedSlots; ++j) {
+          if (!fok[j]) break;
+          const vec_t<T, VEC> u = load_vec<T, VEC, false>(xp + (int64_t)(lane + kWave * j) * VEC);
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            const uint32_t b = a.pre_relu ? pre_abs_bits<T, true>(u.v[k]) : pre_abs_bits<T, false>(u.v[k]);
+            fm = b > fm ? b : fm;
+          }
+        }
+      }
+      fm = wave_max_u32(fm);
+      if (lane == 0) sh_max[wave] = fm;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        uint32_t bm = 0;
+        for (int w = 0; w < kClusterWaves; ++w) bm = sh_max[w] > bm ? sh_max[w] : bm;
+        sh_stat = bm;
+        if (ca.fallbacks) __hip_atomic_fetch_add(ca.fallbacks, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      __syncthreads();
+    }
+    const uint32_t key = sh_stat;
+    // departure: this member no longer reads channel c's words (on the fallback its key store is drained first, so
+    // that the zeroing below cannot overtake it)
+    uint32_t before = 0;
+    if (wave == 0) {
+      if (lane == 0) {
+        if (!sh_ok) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        before = __hip_atomic_fetch_add(ca.dep + c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    float stat;
+    const float s = scale_from_key<T>(key, a.use_min, a.min_val, a.int_threshold, a.scale_dtype, stat);
+    if (member == 0 && threadIdx.x == 0) absmax_epilogue(ca.stat_out, ca.in_dtype, ca.in_dtype, ca.ep, c, key);
+    fused_apply<T, RM>(a, c, r, sl, xv, ok, s, qmin, qmax, lane);
+    if (wave == 0) {
+      before = __builtin_amdgcn_readfirstlane(before);
+      if (before + 1 == (uint32_t)members) {  // the last departure hands the channel's words back as zeros
+        if (lane < members) __hip_atomic_store(keys + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 0) __hip_atomic_store(ca.dep + c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    if (cn < a.channels) {
+      if constexpr (kClusterPrefetch) {
+#pragma unroll
+        for (int j = 0; j < kFusedSlots; ++j) xv[j] = xn[j];
+      } else {
+        fused_load<T>(a, cn, r, sl, ok, lane, xv);
+      }
+    }
   }
 }
 
@@ -684,6 +873,104 @@ extern "C" int bvq_stats_fakequant_fwd(const bvq_quant_desc* d, const void* x, d
   }
   set_error("bvq_stats_fakequant_fwd: shape / layout not covered by the one-launch form");
   return BVQ_ERR_UNSUPPORTED;
+}
+
+// ---- statistic + quantizer in one launch, channels held by a cluster of workgroups ---------------------------------
+struct ClusterPlan {
+  FusedPlan p;
+  int32_t members, nclusters;
+  int64_t words;  // arrival words
+};
+
+static bool cluster_plan(const bvq_quant_desc* d, const void* x, const void* y, ClusterPlan& cp) {
+  if (!(d->scale_per_channel && d->channels > 1) || d->channels >= ((int64_t)1 << 31)) return false;
+  const FusedShape f = fused_shape(d, x, y);
+  if (!f.ok) return false;
+  // y must not overlap x: a fallback re-reads x while partners write y
+  const uintptr_t bytes = (uintptr_t)(f.outer * f.channels * f.inner * dtype_size(d->x_dtype));
+  const uintptr_t xa = reinterpret_cast<uintptr_t>(x), ya = reinterpret_cast<uintptr_t>(y);
+  if (xa < ya + bytes && ya < xa + bytes) return false;
+  const int64_t cpr = f.inner / f.vec;
+  const int64_t spr = (cpr + kFusedSliceChunks - 1) / kFusedSliceChunks;
+  const int64_t slices = f.outer * spr;
+  const int64_t members = (slices + kClusterWaves - 1) / kClusterWaves;
+  if (cpr > (1 << 30) || members > kClusterMaxMembers) return false;
+  cp.p.cpr = (int32_t)cpr;
+  cp.p.spr = (int32_t)spr;
+  cp.p.slices = (int32_t)slices;
+  cp.p.waves = kClusterWaves;
+  cp.members = (int32_t)members;
+  // persistent grid: whole clusters within the resident workgroups (kClusterWavesPerCu waves per CU)
+  const int64_t resident = (int64_t)num_cus() * kClusterWavesPerCu / kClusterWaves;
+  int64_t nc = resident / members;
+  nc = nc < 1 ? 1 : (nc > f.channels ? f.channels : nc);
+  cp.nclusters = (int32_t)nc;
+  cp.p.nblocks = (int32_t)(nc * members);
+  cp.words = f.channels * (members + 1);
+  return true;
+}
+
+extern "C" int64_t bvq_absmax_fakequant_cluster_supported(const bvq_quant_desc* d, const void* x, const void* y) {
+  if (validate(d)) return 0;
+  ClusterPlan cp;
+  return cluster_plan(d, x, y, cp) ? cp.words : 0;
+}
+
+extern "C" int bvq_absmax_fakequant_cluster(const bvq_quant_desc* d, const void* x, double min_val, int use_min,
+                                            double int_threshold, void* stat_out, void* scale_out, int run_dtype,
+                                            void* running, double momentum, int first_batch, void* y, uint32_t* arrive,
+                                            int64_t arrive_words, int flags, uint32_t* fallbacks,
+                                            bvq_stream_t stream) {
+  int rc = validate(d);
+  if (rc) return rc;
+  if (!x || !y || !stat_out || !scale_out || !arrive) {
+    set_error("bvq_absmax_fakequant_cluster: null pointer");
+    return BVQ_ERR_INVALID;
+  }
+  auto bad_dtype = [](int dt) { return dt < BVQ_F32 || dt > BVQ_F16; };
+  if ((running && bad_dtype(run_dtype)) || bad_dtype(d->scale_dtype) || !(int_threshold == int_threshold) ||
+      (flags & ~BVQ_CLUSTER_FORCE_FALLBACK)) {
+    set_error("bvq_absmax_fakequant_cluster: bad argument");
+    return BVQ_ERR_INVALID;
+  }
+  ClusterPlan cp;
+  if (!cluster_plan(d, x, y, cp)) {
+    set_error("bvq_absmax_fakequant_cluster: shape / layout not covered (bvq_absmax_fakequant_cluster_supported)");
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (arrive_words < cp.words) {
+    set_error("bvq_absmax_fakequant_cluster: arrival buffer of %lld words, %lld needed", (long long)arrive_words,
+              (long long)cp.words);
+    return BVQ_ERR_WORKSPACE;
+  }
+  ClusterArgs ca = {};
+  ca.f = fused_args(d, cp.p, x, y, stat_out, scale_out, min_val, use_min, int_threshold);
+  ca.ep.scale_out = scale_out;
+  ca.ep.scale_dtype = d->scale_dtype;
+  ca.ep.use_min = use_min;
+  ca.ep.min_val = ca.f.min_val;
+  ca.ep.int_threshold = ca.f.int_threshold;
+  if (running) {
+    ca.ep.running = running;
+    ca.ep.run_dtype = run_dtype;
+    ca.ep.first_batch = first_batch;
+    // as bvq_absmax_scale_onepass: torch's float32 (1 - momentum) and momentum
+    ca.ep.one_minus_m = (float)(1.0 - momentum);
+    ca.ep.momentum = (float)momentum;
+  }
+  ca.stat_out = stat_out;
+  ca.in_dtype = d->x_dtype;
+  ca.key = arrive;
+  ca.dep = arrive + (int64_t)ca.f.channels * cp.members;
+  ca.fallbacks = fallbacks;
+  ca.members = cp.members;
+  ca.nclusters = cp.nclusters;
+  ca.force_fallback = (flags & BVQ_CLUSTER_FORCE_FALLBACK) ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  rc = with_cols_variant(d, false, [&](auto t, auto rm, auto) {
+    cluster_absmax_fakequant_kernel<typename decltype(t)::type, rm><<<dim3((unsigned)cp.p.nblocks), dim3(kClusterWaves * kWave), 0, st>>>(ca);
+  });
+  return rc ? rc : check_launch("bvq_absmax_fakequant_cluster");
 }
 
 namespace bvq {

@@ -14,6 +14,7 @@
 #include "bvq_common.h"
 #include "bvq_ties.h"
 #include "bvq_sums.h"
+#include "bvq_stat_epilogue.h"
 
 namespace bvq {
 
@@ -368,15 +369,6 @@ __global__ __launch_bounds__(kBlock) void absmoments_cols_kernel(ColsMomentArgs 
   }
 }
 
-__device__ __forceinline__ void store_stat(void* out, int out_dtype, int64_t idx, float v) {
-  if (out_dtype == BVQ_F32)
-    reinterpret_cast<float*>(out)[idx] = v;
-  else if (out_dtype == BVQ_BF16)
-    reinterpret_cast<bf16_t*>(out)[idx] = (bf16_t)v;  // exact: v is a bf16 value
-  else
-    reinterpret_cast<f16_t*>(out)[idx] = (f16_t)v;
-}
-
 // min/max over the same mapping.  Partials are order-preserving unsigned keys so that the abs-max fold
 // (an unsigned max) serves both: columns [0, L) hold key(max), columns [L, 2L) hold key(-min); a NaN
 // anywhere in a column turns both of its keys into 0xffffffff (torch.max / torch.min propagate NaN).
@@ -464,36 +456,6 @@ __global__ __launch_bounds__(kWave) void minmax_cols_finish_kernel(const uint32_
     store_stat(out, out_dtype, c, bad ? qn : order_key_value(kx));
     store_stat(out, out_dtype, (int64_t)channels + c, bad ? qn : -order_key_value(kn));
   }
-}
-
-// optional epilogue of the abs-max finisher: statistic -> scale in the same launch
-//   thr   = scalar_clamp_min_ste(stat, min_val)      (B/core/restrict_val.py:22-42)
-//   scale = thr / int_threshold                       (B/core/quant/int.py:160)
-// min_val is already rounded to the statistic's dtype and int_threshold to the dtype the division
-// runs in, so the kernel only has to round the quotient to scale_dtype.
-struct ScaleEpilogue {
-  void* scale_out;  // null: no epilogue
-  int32_t scale_dtype;
-  int32_t use_min;
-  float min_val;
-  float int_threshold;
-  // optionally, in the same launch: _RuntimeStats' running average of the statistic (B/core/stats/stats_wrapper.py:61-66)
-  void* running;    // null: none
-  int32_t run_dtype, first_batch;
-  float momentum, one_minus_m;
-};
-
-// running *= out (first batch)  |  running *= (1 - momentum); running += momentum * out -- every torch op rounds to
-// its result dtype: running's for the in-place ops, out's for momentum * out
-__device__ __forceinline__ float running_update(float r, float o, int run_dtype, int stat_dtype, float one_minus_m,
-                                                float m, int first) {
-  auto round_to = [](float v, int dt) {
-    return dt == BVQ_F32 ? v : (dt == BVQ_BF16 ? rnd<bf16_t>(v) : rnd<f16_t>(v));
-  };
-  if (first) return round_to(r * o, run_dtype);
-  r = round_to(r * one_minus_m, run_dtype);
-  const float u = round_to(o * m, stat_dtype);
-  return round_to(r + u, run_dtype);
 }
 
 // Combines the per-unit partials of one channel.  grid = (channels, splits): with splits == 1 the
@@ -633,18 +595,7 @@ __device__ __forceinline__ bool arrive_max(uint32_t* key, uint32_t* cnt, uint32_
 
 // statistic, scale epilogue, running statistic of channel c from the key `bits` (what stat_finish_kernel does)
 __device__ __forceinline__ void absmax_finish(const ArriveArgs& r, const ScaleEpilogue& ep, int32_t c, uint32_t bits) {
-  const float v = r.in_dtype == BVQ_F16 ? (float)__builtin_bit_cast(f16_t, (uint16_t)bits)
-                                         : __builtin_bit_cast(float, bits);
-  store_stat(r.stat_out, r.stat_dtype, c, v);
-  if (ep.scale_out) {
-    const float thr = (ep.use_min && v < ep.min_val) ? ep.min_val : v;  // NaN passes, like torch.clamp_min
-    store_stat(ep.scale_out, ep.scale_dtype, c, thr / ep.int_threshold);
-  }
-  if (ep.running) {
-    const float run = load_scalar_as_f(ep.running, ep.run_dtype, c);
-    store_stat(ep.running, ep.run_dtype, c,
-               running_update(run, v, ep.run_dtype, r.stat_dtype, ep.one_minus_m, ep.momentum, ep.first_batch));
-  }
+  absmax_epilogue(r.stat_out, r.stat_dtype, r.in_dtype, ep, c, bits);
 }
 
 // per-channel layouts: every wave arrives for itself (m: the lanes' maxima of the wave's unit)

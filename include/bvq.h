@@ -473,6 +473,25 @@ int bvq_stats_fakequant_fwd(const bvq_quant_desc* desc, const void* x, double mi
                             double int_threshold, void* stat_out, void* scale_out, void* y, void* workspace,
                             int64_t workspace_bytes, bvq_stream_t stream);
 
+/* The same AbsMax -> scale -> IntQuant in ONE launch (x read once) for channels that do NOT fit one workgroup: each
+ * channel is held in registers by a CLUSTER of workgroups, which agree on its maximum through one arrival word each;
+ * a persistent grid of clusters walks the channels.  stat_out [channels] in x's dtype, scale_out [channels] in
+ * desc->scale_dtype, running (nullable, [channels] of run_dtype: the running average of bvq_absmax_scale_onepass) and
+ * y are the bits of bvq_absmax_scale_onepass + bvq_fakequant_fwd on the same descriptor.  A workgroup never waits
+ * without a bound: past a time budget it reads the whole channel itself (same bits; `fallbacks`, nullable, counts
+ * those).  flags: BVQ_CLUSTER_FORCE_FALLBACK (tests) takes that path every time.
+ * bvq_absmax_fakequant_cluster_supported -> the arrival words the call needs, or 0 when not covered.  Covered: a
+ * per-channel scale with channels > 1, x and y of one dtype, not overlapping, dequantized output, zero zero-point,
+ * 16-byte aligned, rows of whole 16-byte chunks, a channel of at most 64 workgroups' registers.  Host-side only.
+ * arrive: `arrive_words` uint32 words, all zero on entry, handed back as zeros (the contract of
+ * bvq_absmax_scale_onepass). */
+#define BVQ_CLUSTER_FORCE_FALLBACK 1
+int64_t bvq_absmax_fakequant_cluster_supported(const bvq_quant_desc* desc, const void* x, const void* y);
+int bvq_absmax_fakequant_cluster(const bvq_quant_desc* desc, const void* x, double min_val, int use_min,
+                                 double int_threshold, void* stat_out, void* scale_out, int run_dtype, void* running,
+                                 double momentum, int first_batch, void* y, uint32_t* arrive, int64_t arrive_words,
+                                 int flags, uint32_t* fallbacks, bvq_stream_t stream);
+
 /* bytes of scratch bvq_fakequant_bwd needs */
 int64_t bvq_fakequant_bwd_workspace_bytes(const bvq_quant_desc* desc);
 

@@ -35,8 +35,11 @@ def main():
         '_source_digest': digest,
         'act_per_channel_bf16': {'bvq_fakequant_bwd': bytes_of('fakequant_bwd_kernel'),
                                  'bvq_fakequant_fwd': bytes_of('fakequant_fwd_kernel'),
-                                 'bvq_stats': bytes_of('absmax_onepass_kernel') or bytes_of('absmax_kernel')},
+                                 'bvq_stats': bytes_of('absmax_onepass_kernel') or bytes_of('absmax_kernel'),
+                                 'bvq_stats_fakequant_fwd': bytes_of('cluster_absmax_fakequant_kernel')},
     }
+    # kernels the step no longer launches (the cluster forward replaces statistic + quantizer)
+    out['act_per_channel_bf16'] = {k: v for k, v in out['act_per_channel_bf16'].items() if v is not None}
     with open(os.path.join('profiles', 'traffic.json'), 'w') as fh:
         json.dump(out, fh, indent=1)
     print(json.dumps(out, indent=1))
