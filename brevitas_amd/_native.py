@@ -24,7 +24,7 @@ SCALAR_OPMATH, SCALAR_CAST = 0, 1
 OUT_DEQUANT, OUT_INT = 0, 1
 MATCH_ABS, MATCH_VALUE = 0, 1
 MATCH_FIRST = 16  # OR-ed: only the first attaining element, even for a whole-tensor reduction
-PRE_NONE, PRE_RELU = 0, 1
+PRE_NONE, PRE_RELU, PRE_SIGMOID, PRE_TANH = 0, 1, 2, 3
 CODES_I32, CODES_I8, CODES_U8 = 0, 1, 2
 CLUSTER_FORCE_FALLBACK = 1  # BVQ_CLUSTER_FORCE_FALLBACK: tests only
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
@@ -46,7 +46,7 @@ EXPORTS = (
     'bvq_fakequant_bwd_stats_onepass', 'bvq_scale_from_stat_running', 'bvq_fakequant_bwd_shard',
     'bvq_shard_unpack_deposit', 'bvq_absmax_list_supported', 'bvq_absmax_scale_list', 'bvq_weight_list_supported',
     'bvq_weight_quant_list_fwd', 'bvq_weight_quant_list_bwd_workspace_bytes', 'bvq_weight_quant_list_bwd',
-    'bvq_absmax_fakequant_cluster_supported', 'bvq_absmax_fakequant_cluster')
+    'bvq_absmax_fakequant_cluster_supported', 'bvq_absmax_fakequant_cluster', 'bvq_selftest_pre_op')
 
 
 class QuantDesc(ctypes.Structure):
@@ -154,6 +154,7 @@ def _load(path=None, strict=True):
         'bvq_learned_scale': (i32, [i32, vp, i64, dbl, i32, dbl, i32, vp, vp]),
         'bvq_histc': (i32, [i32, vp, i64, vp, i32, vp, vp]),
         'bvq_selftest_div_f16r': (i32, [vp, i32, vp, i32, vp, vp]),
+        'bvq_selftest_pre_op': (i32, [i32, i32, vp, vp, vp, vp, i64, vp]),
         'bvq_fakequant_fwd_bounds': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp]),
         'bvq_fakequant_bwd_bounds': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
         'bvq_variant_fwd': (i32, [ctypes.POINTER(VariantDesc), vp, vp, vp, vp, vp, vp, vp]),
@@ -358,7 +359,8 @@ def stats(kind, x, outer, channels, inner, out_f32=False, pre_op=PRE_NONE):
     dt = dtype_code(x.dtype)
     nout = channels * (2 if kind == STAT_MINMAX else 1)
     out = torch.empty(nout, dtype=torch.float32 if out_f32 else x.dtype, device=dev)
-    if kind == STAT_ABSMAX and lib.bvq_absmax_onepass_supported(dt, ptr(x), outer, channels, inner):
+    if kind == STAT_ABSMAX and pre_op in (PRE_NONE, PRE_RELU) and \
+            lib.bvq_absmax_onepass_supported(dt, ptr(x), outer, channels, inner):
         with _DeviceGuard(dev):
             st = stream_ptr(dev)
             arrive = arrival_buffer(dev, st, max(2 * channels, 18))
@@ -518,7 +520,7 @@ def absmax_scale(x, outer, channels, inner, min_val, int_threshold, scale_dtype,
     dt = dtype_code(x.dtype)
     stat = torch.empty(channels, dtype=x.dtype, device=dev)
     scale = torch.empty(channels, dtype=scale_dtype, device=dev)
-    if lib.bvq_absmax_onepass_supported(dt, ptr(x), outer, channels, inner):
+    if pre_op in (PRE_NONE, PRE_RELU) and lib.bvq_absmax_onepass_supported(dt, ptr(x), outer, channels, inner):
         # one launch: the statistic kernel's last-arriving wave per channel finishes it
         with _DeviceGuard(dev):
             st = stream_ptr(dev)
@@ -964,6 +966,19 @@ def selftest_div_f16r(a, scales):
         check(lib.bvq_selftest_div_f16r(ptr(a), a.numel(), ptr(scales), scales.numel(), ptr(out), stream_ptr(dev)),
               'bvq_selftest_div_f16r')
     return out
+
+
+def selftest_pre_op(pre_op, x, g):
+    """diagnostic: (act(x), act_backward(g, act(x))) as the quantizer kernels compute the fused activation pre_op
+    (PRE_SIGMOID / PRE_TANH), element by element, in x's dtype"""
+    dev = require_device(x, g)
+    assert x.dtype == g.dtype and x.shape == g.shape and x.is_contiguous() and g.is_contiguous()
+    a = torch.empty_like(x)
+    da = torch.empty_like(x)
+    with _DeviceGuard(dev):
+        check(lib.bvq_selftest_pre_op(pre_op, dtype_code(x.dtype), ptr(x), ptr(g), ptr(a), ptr(da), x.numel(),
+                                      stream_ptr(dev)), 'bvq_selftest_pre_op')
+    return a, da
 
 
 def learned_scale(value, min_val, int_threshold, scale_dtype):

@@ -83,6 +83,31 @@ def plan(x: Tensor, scale: Tensor, zp: Tensor) -> Optional[Plan]:
     return Plan(outer, x.shape[cd], inner, sd is not None, zd is not None, ct)
 
 
+_ACT_OPS = {nat.PRE_RELU: torch.relu, nat.PRE_SIGMOID: torch.sigmoid, nat.PRE_TANH: torch.tanh}
+ACT_PRE_OPS = (nat.PRE_SIGMOID, nat.PRE_TANH)  # the activations of csrc/bvq_act.h
+
+
+def apply_pre_op(x: Tensor, pre_op: int) -> Tensor:
+    """the activation `pre_op` (include/bvq.h, bvq_pre_op) as its own torch op: the route where it is not fused"""
+    if pre_op == nat.PRE_NONE:
+        return x
+    return _ACT_OPS[pre_op](x)
+
+
+def act_fusable(x: Tensor, p: Optional['Plan'], pre_op: int) -> bool:
+    """sigmoid / tanh fold into the row-mapped quantizer kernels: dequantized output in x's dtype, no column-mapped
+    (channels_last per-channel) layout, a dtype whose activation the kernels reproduce (act_dtype_ok)"""
+    # x off a 16-byte boundary: the kernels would tile it (and add up the scale gradient) unlike the fresh, aligned
+    # activation tensor of the materialised route
+    return act_dtype_ok(x, pre_op) and p is not None and not p.nhwc and p.ct == x.dtype and x.data_ptr() % 16 == 0
+
+
+def act_dtype_ok(x: Tensor, pre_op: int) -> bool:
+    """the kernels' activation and its backward equal torch's for x's dtype: sigmoid in every dtype, tanh in float32
+    (torch's 16-bit tanh / tanh_backward are not reproduced on every input)"""
+    return pre_op != nat.PRE_TANH or x.dtype == torch.float32
+
+
 def scalar_mode():
     return nat.SCALAR_CAST if config.SCALAR_OPERAND_MODE == 'device' else nat.SCALAR_OPMATH
 

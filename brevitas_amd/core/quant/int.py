@@ -234,19 +234,34 @@ class RescalingIntQuant(torch.nn.Module):
             raise NotImplementedError('calibration with quant_delay_steps')
         with torch.no_grad():
             fused = self._stats_plan(x, bit_width)
+            if pre_op in _fused.ACT_PRE_OPS and (fused is None or fused[1]['runtime'] is None or fused[0].nhwc
+                                                 or getattr(self, 'bvq_shard_group', None) is not None
+                                                 or not _fused.act_dtype_ok(x, pre_op) or x.data_ptr() % 16 != 0):
+                # sigmoid / tanh fold into the row-mapped statistic kernels only: materialise them elsewhere
+                x, pre_op = _fused.apply_pre_op(x, pre_op), nat.PRE_NONE
+                fused = self._stats_plan(x, bit_width)
             if fused is not None and fused[1]['runtime'] is not None:
                 sp, tmpl = fused
                 group = getattr(self, 'bvq_shard_group', None)
                 flat = _fused._memory_order(x, sp.channels, sp.nhwc)[0].reshape(-1)
                 stat, scale = _fused.stats_scale(flat, self.int_scaling_impl(bit_width), sp, group, pre_op)
                 tmpl['runtime'].update_running_stats(stat.view(sp.scaling_shape))
-                x_act = torch.relu(x) if pre_op == nat.PRE_RELU else x
+                x_act = _fused.apply_pre_op(x, pre_op)
             else:
-                x_act = torch.relu(x) if pre_op == nat.PRE_RELU else x
+                x_act = _fused.apply_pre_op(x, pre_op)
                 threshold = self.scaling_impl(x_act)
                 scale = threshold / self.int_scaling_impl(bit_width)
             zero_point = self.zero_point_impl(x_act, scale, bit_width)
         return x_act, scale, zero_point, bit_width
+
+    def _learned_forward(self, x: Tensor, bit_width: Tensor, learned, pre_op: int):
+        """learned scale (steady state of the default activation quantizers): one launch for the scale, the
+        quantizer kernel; in backward the scale's own chain rides on the last reduction launch"""
+        value, min_val, p, thr_div, scale_dtype, qmin, qmax, round_mode, clamp_ste = learned
+        y, scale = _fused.LearnedScaleFakeQuantFn.apply(x, value, p, min_val, thr_div, scale_dtype, qmin, qmax,
+                                                        round_mode, clamp_ste, pre_op)
+        zero_point = self.zero_point_impl(x, scale, bit_width)
+        return y, scale, zero_point, bit_width
 
     def bvq_forward_pre(self, x: Tensor, pre_op: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
         """forward(pre_op(x)) -- FusedActivationQuantProxy.forward (B/proxy/runtime_quant.py:80-84) -- with
@@ -256,6 +271,17 @@ class RescalingIntQuant(torch.nn.Module):
         if getattr(self, 'bvq_collect_only', False):
             return self._collect_only(x, pre_op, bit_width)
         fused = self._stats_plan(x, bit_width)
+        if pre_op in _fused.ACT_PRE_OPS:
+            # sigmoid / tanh (csrc/bvq_act.h) fold into the quantizer kernels of a scale that does not read x: a learned
+            # one here, a constant one or frozen statistics in the block below (IntQuant decides what it covers).
+            # Stats-scaled graphs and batch-sharded quantizers materialise the activation.
+            shard = getattr(self, 'bvq_shard_group', None) is not None
+            learned = self._learned_scale_args(x, bit_width) if fused is None and not shard else None
+            if learned is not None and _fused.act_fusable(x, learned[2], pre_op):
+                return self._learned_forward(x, bit_width, learned, pre_op)
+            if fused is not None or shard or learned is not None:
+                x, pre_op = _fused.apply_pre_op(x, pre_op), nat.PRE_NONE
+                fused = self._stats_plan(x, bit_width)
         if fused is None and pre_op != nat.PRE_NONE:
             if type(self.int_quant) is IntQuant and type(self.zero_point_impl) is ZeroZeroPoint \
                     and self._scale_ignores_input():
@@ -265,7 +291,7 @@ class RescalingIntQuant(torch.nn.Module):
                 zero_point = self.zero_point_impl(x, scale, bit_width)
                 y = self.int_quant.bvq_forward_pre(scale, zero_point, bit_width, x, pre_op)
                 return y, scale, zero_point, bit_width
-            x = torch.relu(x)  # not fusable here: materialise the activation like the reference does
+            x = _fused.apply_pre_op(x, pre_op)  # not fusable here: materialise the activation like the reference does
             pre_op = nat.PRE_NONE
         if fused is not None:
             sp, tmpl = fused
@@ -287,7 +313,7 @@ class RescalingIntQuant(torch.nn.Module):
                     return y, scale, zero_point, bit_width
                 fused = None  # list not covered by the list kernel: op by op
                 if pre_op != nat.PRE_NONE:
-                    x, pre_op = torch.relu(x), nat.PRE_NONE
+                    x, pre_op = _fused.apply_pre_op(x, pre_op), nat.PRE_NONE
         if fused is not None:
             sp, tmpl = fused
             if tmpl['post'] is not None:
@@ -322,13 +348,7 @@ class RescalingIntQuant(torch.nn.Module):
             return y, scale, zero_point, bit_width
         learned = self._learned_scale_args(x, bit_width)
         if learned is not None:
-            # learned scale (steady state of the default activation quantizers): one launch for the scale, the
-            # quantizer kernel; in backward the scale's own chain rides on the last reduction launch
-            value, min_val, p, thr_div, scale_dtype, qmin, qmax, round_mode, clamp_ste = learned
-            y, scale = _fused.LearnedScaleFakeQuantFn.apply(x, value, p, min_val, thr_div, scale_dtype, qmin, qmax,
-                                                            round_mode, clamp_ste, pre_op)
-            zero_point = self.zero_point_impl(x, scale, bit_width)
-            return y, scale, zero_point, bit_width
+            return self._learned_forward(x, bit_width, learned, pre_op)
         # generic orchestration (B/core/quant/int.py:157-163)
         threshold = self.scaling_impl(x)
         int_threshold = self.int_scaling_impl(bit_width)

@@ -155,13 +155,18 @@ class IntQuant(torch.nn.Module):
         """forward(scale, zero_point, bit_width, pre_op(x)) with the activation `pre_op`
         (include/bvq.h, bvq_pre_op) folded into the quantizer kernel when that kernel applies"""
         fa = self._fused_args(scale, zero_point, bit_width, x)
+        if pre_op in _fused.ACT_PRE_OPS and (fa is None or bit_width.requires_grad or zero_point.requires_grad
+                                             or not _fused.act_fusable(x, fa[0], pre_op)):
+            # sigmoid / tanh fold into the plain quantizer kernels only: materialise them for every other route
+            x, pre_op = _fused.apply_pre_op(x, pre_op), nat.PRE_NONE
+            fa = self._fused_args(scale, zero_point, bit_width, x)
         if fa is not None and not bit_width.requires_grad:
             p, qmin, qmax, round_mode, clamp_ste = fa
             y = _fused.FakeQuantFn.apply(x, scale, zero_point, p, qmin, qmax, round_mode, clamp_ste,
                                          nat.OUT_DEQUANT, pre_op)
             x_act = x  # only handed back while quantization is delayed; see below
             if pre_op != nat.PRE_NONE and not isinstance(self.delay_wrapper.delay_impl, _NoDelay):
-                x_act = torch.relu(x)
+                x_act = _fused.apply_pre_op(x, pre_op)
         else:
             bounds = self._fused_bounds_args(scale, zero_point, bit_width, x)
             if bounds is not None:
@@ -172,9 +177,9 @@ class IntQuant(torch.nn.Module):
                                                    self.max_int(bit_width), p, round_mode, clamp_ste, pre_op)
                 x_act = x
                 if pre_op != nat.PRE_NONE and not isinstance(self.delay_wrapper.delay_impl, _NoDelay):
-                    x_act = torch.relu(x)
+                    x_act = _fused.apply_pre_op(x, pre_op)
                 return self.delay_wrapper(x_act, y)
-            x_act = torch.relu(x) if pre_op == nat.PRE_RELU else x
+            x_act = _fused.apply_pre_op(x, pre_op)
             y_int = self.to_int(scale, zero_point, bit_width, x_act)
             y = y_int - zero_point
             y = y * scale

@@ -60,6 +60,20 @@ struct elem<f16_t> {
 
 static inline int dtype_size(int dt) { return dt == BVQ_F32 ? 4 : 2; }
 
+// the check of an entry that takes pre_op (bvq_pre_op) as an int and covers NONE and RELU only: sigmoid and tanh are
+// refused as not covered, never run as something else
+static inline int check_pre_op(int pre_op, const char* what) {
+  if (pre_op == BVQ_PRE_SIGMOID || pre_op == BVQ_PRE_TANH) {
+    set_error("%s: pre_op %d (sigmoid / tanh) is not covered by this entry", what, pre_op);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (pre_op != BVQ_PRE_NONE && pre_op != BVQ_PRE_RELU) {
+    set_error("%s: bad pre_op %d", what, pre_op);
+    return BVQ_ERR_INVALID;
+  }
+  return BVQ_OK;
+}
+
 // value -> float (exact widening)
 template <typename T>
 __device__ __forceinline__ float to_f(T v) {

@@ -50,6 +50,9 @@ struct QuantArgs {
   double* shard_msg;
   long long* shard_pos;
   int32_t shard_rank;
+  // x is passed through the activation BVQ_PRE_SIGMOID / BVQ_PRE_TANH first (bvq_act.h; 0: neither).  Last, so that the
+  // kernels that do not read it keep their argument layout.
+  int32_t pre_act;
 };
 
 #ifndef BVQ_FWD_UNROLL
@@ -303,7 +306,8 @@ struct ColsLane {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static int validate(const bvq_quant_desc* d) {
+// act: the entry covers the activations of bvq_act.h (sigmoid, tanh); every other entry refuses them
+static int validate(const bvq_quant_desc* d, bool act = false) {
   if (!d) {
     set_error("null descriptor");
     return BVQ_ERR_INVALID;
@@ -313,9 +317,13 @@ static int validate(const bvq_quant_desc* d) {
               (long long)d->inner);
     return BVQ_ERR_INVALID;
   }
-  if (d->pre_op != BVQ_PRE_NONE && d->pre_op != BVQ_PRE_RELU) {
+  if (d->pre_op < BVQ_PRE_NONE || d->pre_op > BVQ_PRE_TANH) {
     set_error("bad pre_op %d", d->pre_op);
     return BVQ_ERR_INVALID;
+  }
+  if (d->pre_op >= BVQ_PRE_SIGMOID && !act) {
+    set_error("pre_op %d (sigmoid / tanh) is not covered by this entry", d->pre_op);
+    return BVQ_ERR_UNSUPPORTED;
   }
   if (d->codes_dtype < BVQ_CODES_I32 || d->codes_dtype > BVQ_CODES_U8) {
     set_error("bad codes_dtype %d", d->codes_dtype);
@@ -365,6 +373,7 @@ static void fill_args(QuantArgs& a, const bvq_quant_desc* d) {
   a.out_int = d->out_kind == BVQ_OUT_INT;
   a.round_mode = d->round_mode;
   a.pre_relu = d->pre_op == BVQ_PRE_RELU;
+  a.pre_act = d->pre_op >= BVQ_PRE_SIGMOID ? d->pre_op : 0;
   a.codes_dtype = d->codes_dtype;
 }
 

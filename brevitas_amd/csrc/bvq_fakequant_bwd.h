@@ -2,6 +2,7 @@
 // finish (arrival), the column-mapped kernel, the finishing kernels, and the launch_bwd template whose instantiations
 // are spread over bvq_fakequant_bwd_{bf16,f16,f32}.hip so that they build in parallel.
 #pragma once
+#include "bvq_act.h"
 #include "bvq_fakequant.h"
 
 namespace bvq {
@@ -288,8 +289,10 @@ __device__ __forceinline__ void bwd_arrive(const QuantArgs& a, const Unit& u, fl
   channel_finish<XT, PRE>(a, u.channel, lane);
 }
 
-// NT: cache policy of the loads of g and the stores of dx; NTX: of the loads of x (the same unless stated)
-template <typename XT, typename CT, int VEC, int RM, int MODE, bool NT, bool ZP0, bool PRE, bool NTX = NT, typename Div>
+// NT: cache policy of the loads of g and the stores of dx; NTX: of the loads of x (the same unless stated); ACT: the
+// activation of bvq_act.h applied to x first (0: none; PRE is the ReLU), kBwdDx / kBwdDs only
+template <typename XT, typename CT, int VEC, int RM, int MODE, bool NT, bool ZP0, bool PRE, bool NTX = NT, int ACT = 0,
+          typename Div>
 __device__ __forceinline__ void bwd_unit(const QuantArgs& a, const Unit& u, const Div& div, float s,
                                          float z, float qmin, float qmax) {
   const int lane = threadIdx.x & 63;
@@ -325,6 +328,13 @@ __device__ __forceinline__ void bwd_unit(const QuantArgs& a, const Unit& u, cons
       for (int k = 0; k < VEC; k += 2) {
         const f2 xraw = widen2<XT>(xv.v[k], xv.v[k + 1]);
         constexpr bool kSame16 = sizeof(CT) == 2 && sizeof(XT) == 2;  // then XT is CT (dispatch pairs)
+        if constexpr (ACT != 0) {
+          const f2 av = act_rnd2<XT, ACT>(xraw);
+          const f2 d = bwd_elem2<CT, RM, MODE, ZP0, kSame16, true>(av, widen2<CT>(gv.v[k], gv.v[k + 1]), div, s, z, qmin,
+                                                                  qmax, clamp_ste, mode, ds_acc2, dzp_acc2, dq_acc2);
+          pack2<XT>(act_bwd_rnd2<XT, ACT>(d, av), dv.v[k], dv.v[k + 1]);
+          continue;
+        }
         f2 d = bwd_elem2<CT, RM, MODE, ZP0, kSame16, true>(PRE ? relu2(xraw) : xraw, widen2<CT>(gv.v[k], gv.v[k + 1]),
                                             div, s, z, qmin, qmax, clamp_ste, mode, ds_acc2, dzp_acc2, dq_acc2);
         if constexpr (PRE) d = xraw > splat2(0.f) ? d : splat2(0.f);  // torch.relu backward: grad * (x > 0)
@@ -334,9 +344,11 @@ __device__ __forceinline__ void bwd_unit(const QuantArgs& a, const Unit& u, cons
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
         const float xraw = to_f<XT>(xv.v[k]);
-        float d = bwd_elem<CT, RM, MODE, ZP0>(PRE ? relu_f(xraw) : xraw, to_f<CT>(gv.v[k]), div, s, z,
+        const float xin = ACT != 0 ? act_rnd<XT, ACT>(xraw) : (PRE ? relu_f(xraw) : xraw);
+        float d = bwd_elem<CT, RM, MODE, ZP0>(xin, to_f<CT>(gv.v[k]), div, s, z,
                                               qmin, qmax, clamp_ste, mode, ds_acc, dzp_acc, dq_acc);
         if constexpr (PRE) d = xraw > 0.f ? d : 0.f;  // torch.relu backward: grad * (x > 0)
+        if constexpr (ACT != 0) d = act_bwd_rnd<XT, ACT>(d, xin);
         dv.v[k] = from_f<XT>(d);
       }
     }
@@ -463,9 +475,11 @@ __device__ __forceinline__ void bwd_unit(const QuantArgs& a, const Unit& u, cons
     const int64_t in_row = (int64_t)cur.cpr * VEC + tk;
     const int64_t i = (int64_t)tr * u.row_stride + in_row;
     const float xraw = to_f<XT>(xp[i]);
-    float d = bwd_elem<CT, RM, MODE, ZP0>(PRE ? relu_f(xraw) : xraw, to_f<CT>(gp[i]), div, s, z, qmin, qmax,
+    const float xin = ACT != 0 ? act_rnd<XT, ACT>(xraw) : (PRE ? relu_f(xraw) : xraw);
+    float d = bwd_elem<CT, RM, MODE, ZP0>(xin, to_f<CT>(gp[i]), div, s, z, qmin, qmax,
                                           clamp_ste, mode, ds_acc, dzp_acc, dq_acc);
     if constexpr (PRE) d = xraw > 0.f ? d : 0.f;
+    if constexpr (ACT != 0) d = act_bwd_rnd<XT, ACT>(d, xin);
     if constexpr (MODE == kBwdDsArrive)
       store_through<XT>(dxp + i, from_f<XT>(d));
     else
@@ -513,14 +527,16 @@ __device__ __forceinline__ void bwd_unit(const QuantArgs& a, const Unit& u, cons
 
 // one unit of the row-mapped backward with its channel's scale s and zero-point z: the division form and the
 // template variant chosen from them (fakequant_bwd_kernel, and the list form of bvq_weight_list.hip)
-template <typename XT, typename CT, int VEC, int RM, int MODE, bool NT, bool NTX = NT>
+template <typename XT, typename CT, int VEC, int RM, int MODE, bool NT, bool NTX = NT, int ACT = 0>
 __device__ __forceinline__ void bwd_unit_scaled(const QuantArgs& a, const Unit& u, float s, float z) {
   const float qmin = rnd<CT>(a.bounds ? a.bounds[0] : a.qmin), qmax = rnd<CT>(a.bounds ? a.bounds[1] : a.qmax);
   const bool zp0 = sizeof(CT) == 2 && zp_is_pos_zero(z);
-#define BVQ_BWD_UNIT(ZP0, PRE, DIV) bwd_unit<XT, CT, VEC, RM, MODE, NT, ZP0, PRE, NTX>(a, u, DIV, s, z, qmin, qmax)
+#define BVQ_BWD_UNIT(ZP0, PRE, DIV) bwd_unit<XT, CT, VEC, RM, MODE, NT, ZP0, PRE, NTX, ACT>(a, u, DIV, s, z, qmin, qmax)
 #define BVQ_BWD_PRE(ZP0, DIV)      \
   do {                             \
-    if (a.pre_relu)                \
+    if constexpr (ACT != 0)        \
+      BVQ_BWD_UNIT(ZP0, false, DIV); \
+    else if (a.pre_relu)           \
       BVQ_BWD_UNIT(ZP0, true, DIV); \
     else                           \
       BVQ_BWD_UNIT(ZP0, false, DIV); \
@@ -562,13 +578,13 @@ __device__ __forceinline__ void bwd_unit_scaled(const QuantArgs& a, const Unit& 
 }
 
 // (96 scalar registers: one more would cost a resident workgroup per CU -- MI355X_MICROARCH.md, Residency)
-template <typename XT, typename CT, int VEC, int RM, int MODE, bool NT, bool NTX = NT>
+template <typename XT, typename CT, int VEC, int RM, int MODE, bool NT, bool NTX = NT, int ACT = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96), amdgpu_waves_per_eu(BVQ_BWD_WAVES, 8))) void fakequant_bwd_kernel(QuantArgs a) {
   const Unit u = locate_unit(a.t);
   if (!u.valid) return;
   float s, z;
   load_scale_zp<CT>(a, u.channel, s, z);
-  bwd_unit_scaled<XT, CT, VEC, RM, MODE, NT, NTX>(a, u, s, z);
+  bwd_unit_scaled<XT, CT, VEC, RM, MODE, NT, NTX, ACT>(a, u, s, z);
 }
 
 
@@ -897,6 +913,20 @@ static inline Tiling bwd_tiling(int64_t outer, int32_t channels, int64_t row_len
 // two-launch route
 template <typename XT, typename CT>
 int launch_bwd(const QuantArgs& a, int vec, int mode, bool nt, hipStream_t st) {
+  if (a.pre_act != 0) {  // bvq_act.h: x and compute dtype alike, dx and dscale only (the entry has checked)
+    if constexpr (std::is_same_v<XT, CT>) {
+      return with_value<kBwdDx, kBwdDs>(mode, [&](auto m) {
+        return with_value<BVQ_PRE_SIGMOID, BVQ_PRE_TANH>(a.pre_act, [&](auto ac) {
+          return with_stream_variant<elem<XT>::vec>("bvq_fakequant_bwd", vec, a.round_mode, nt, [&](auto v, auto rm, auto ntc) {
+            fakequant_bwd_kernel<XT, CT, v, rm, decltype(m)::value, ntc, ntc, ac><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+          });
+        });
+      });
+    } else {
+      set_error("bvq_fakequant_bwd: pre_op %d needs x and compute dtype alike", a.pre_act);
+      return BVQ_ERR_UNSUPPORTED;
+    }
+  }
   return with_value<kBwdDx, kBwdDs, kBwdDsDzp, kBwdDsBounds, kBwdDsArrive, kBwdDsTies>(mode, [&](auto m) {
     constexpr int MODE = decltype(m)::value;
     return with_stream_variant<elem<XT>::vec, MODE == kBwdDsArrive>(

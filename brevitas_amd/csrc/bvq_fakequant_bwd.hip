@@ -30,7 +30,7 @@ static int64_t bwd_units(const bvq_quant_desc* d) {
 }
 
 extern "C" int64_t bvq_fakequant_bwd_workspace_bytes(const bvq_quant_desc* d) {
-  if (validate(d)) return -1;
+  if (validate(d, true)) return -1;
   int64_t outer, row_len;
   int32_t channels;
   rows_of(d, outer, row_len, channels);
@@ -48,8 +48,14 @@ static int fakequant_bwd_impl(const bvq_quant_desc* d, const void* g, const void
                              int64_t* tie_info, void* workspace, int64_t workspace_bytes, bvq_stream_t stream,
                              const LearnedScaleEpilogue* epilogue, const float* bounds = nullptr,
                              float* dbounds = nullptr) {
-  int rc = validate(d);
+  int rc = validate(d, true);
   if (rc) return rc;
+  const bool act = d->pre_op >= BVQ_PRE_SIGMOID;  // bvq_act.h: the row-mapped kernel, dx and dscale only
+  if (act && (tie_stat || dzp || bounds || dbounds || d->x_dtype != d->ct_dtype)) {
+    set_error("bvq_fakequant_bwd: pre_op %d covers dx and dscale in x's dtype only (no ties, dzp or bounds)",
+              d->pre_op);
+    return BVQ_ERR_UNSUPPORTED;
+  }
   const int64_t n = d->outer * d->channels * d->inner;
   hipStream_t st = (hipStream_t)stream;
   int64_t outer, row_len;
@@ -83,7 +89,7 @@ static int fakequant_bwd_impl(const bvq_quant_desc* d, const void* g, const void
     set_error("bvq_fakequant_bwd: the bound gradients ride on the dscale variant (dscale set, dzp / tie_stat null)");
     return BVQ_ERR_UNSUPPORTED;
   }
-  if (!dzp && !bounds) {
+  if (!dzp && !bounds && !act) {
     const ColsPlan cp = cols_quant_plan(d, x, g, dx, !dscale && !tie_stat, true);
     if (cp.ok) {
       const int64_t need = dscale ? (cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L * (int64_t)sizeof(float) : 0;
@@ -313,6 +319,7 @@ extern "C" int bvq_shard_unpack_deposit(int dtype, const void* x, void* dx, cons
   gs.scale_dtype = scale_dtype;
   gs.quot_dtype = quot_dtype;
   gs.int_threshold = (float)int_threshold;
+  if (const int prc = check_pre_op(pre_op, "bvq_shard_unpack_deposit")) return prc;
   gs.pre_relu = pre_op == BVQ_PRE_RELU;
   const dim3 grid((unsigned)((channels + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;

@@ -7,6 +7,7 @@
 // HBM-bound: algorithmic bytes per element are
 //   forward  sizeof(x) + sizeof(y)          backward  sizeof(g) + sizeof(x) + sizeof(dx).
 
+#include "bvq_act.h"
 #include "bvq_fakequant.h"
 #include "bvq_stat_epilogue.h"
 
@@ -64,8 +65,10 @@ __device__ __forceinline__ void store_codes(void* base, int codes_dtype, int64_t
   }
 }
 
-// NT: cache policy of the stores of y; NTL: of the loads of x (the same unless stated)
-template <typename XT, typename CT, int VEC, int RM, bool NT, bool ZP0, bool PRE, bool NTL = NT, typename Div>
+// NT: cache policy of the stores of y; NTL: of the loads of x (the same unless stated); ACT: the activation of
+// bvq_act.h applied to x first (0: none; PRE is the ReLU)
+template <typename XT, typename CT, int VEC, int RM, bool NT, bool ZP0, bool PRE, bool NTL = NT, int ACT = 0,
+          typename Div>
 __device__ __forceinline__ void fwd_unit(const QuantArgs& a, const Unit& u, const Div& div, float s,
                                          float z, float qmin, float qmax) {
   const int lane = threadIdx.x & 63;
@@ -99,6 +102,7 @@ __device__ __forceinline__ void fwd_unit(const QuantArgs& a, const Unit& u, cons
           for (int k = 0; k < VEC; k += 2) {
             f2 xf = widen2<XT>(xv[j].v[k], xv[j].v[k + 1]);
             if constexpr (PRE) xf = relu2(xf);
+            if constexpr (ACT != 0) xf = act_rnd2<XT, ACT>(xf);
             f2 q2;
             const f2 r = fwd_elem2<CT, RM, ZP0>(xf, div, s, z, qmin, qmax, out_int, mode, q2);
             pack2<CT>(r, yv.v[k], yv.v[k + 1]);
@@ -108,7 +112,8 @@ __device__ __forceinline__ void fwd_unit(const QuantArgs& a, const Unit& u, cons
         } else {
 #pragma unroll
           for (int k = 0; k < VEC; ++k) {
-            const float xf = PRE ? relu_f(to_f<XT>(xv[j].v[k])) : to_f<XT>(xv[j].v[k]);
+            float xf = PRE ? relu_f(to_f<XT>(xv[j].v[k])) : to_f<XT>(xv[j].v[k]);
+            if constexpr (ACT != 0) xf = act_rnd<XT, ACT>(xf);
             const float r = fwd_elem<CT, RM, ZP0>(xf, div, s, z, qmin, qmax, out_int, mode, qv[k]);
             yv.v[k] = from_f<CT>(r);
           }
@@ -124,14 +129,15 @@ __device__ __forceinline__ void fwd_unit(const QuantArgs& a, const Unit& u, cons
     const int32_t tr = e / tail, tk = e - tr * tail;
     const int64_t i = (int64_t)tr * u.row_stride + (int64_t)cur.cpr * VEC + tk;
     float q;
-    const float xf = PRE ? relu_f(to_f<XT>(xp[i])) : to_f<XT>(xp[i]);
+    float xf = PRE ? relu_f(to_f<XT>(xp[i])) : to_f<XT>(xp[i]);
+    if constexpr (ACT != 0) xf = act_rnd<XT, ACT>(xf);
     const float r = fwd_elem<CT, RM, ZP0>(xf, div, s, z, qmin, qmax, out_int, mode, q);
     if (yp) yp[i] = from_f<CT>(r);
     if (cp) store_codes<1>(cp, a.codes_dtype, u.base + i, &q);
   }
 }
 
-template <typename XT, typename CT, int VEC, int RM, bool NT, bool NTL = NT>
+template <typename XT, typename CT, int VEC, int RM, bool NT, bool NTL = NT, int ACT = 0>
 __global__ __launch_bounds__(kBlock) void fakequant_fwd_kernel(QuantArgs a) {
   const Unit u = locate_unit(a.t);
   if (!u.valid) return;
@@ -142,10 +148,12 @@ __global__ __launch_bounds__(kBlock) void fakequant_fwd_kernel(QuantArgs a) {
   // wave-uniform choices: fused pre-activation, zero zero-point (16-bit compute types: saves two
   // re-roundings per element), and (bf16) the reciprocal fast path
   const bool zp0 = sizeof(CT) == 2 && zp_is_pos_zero(z);
-#define BVQ_FWD_UNIT(ZP0, PRE, DIV) fwd_unit<XT, CT, VEC, RM, NT, ZP0, PRE, NTL>(a, u, DIV, s, z, qmin, qmax)
+#define BVQ_FWD_UNIT(ZP0, PRE, DIV) fwd_unit<XT, CT, VEC, RM, NT, ZP0, PRE, NTL, ACT>(a, u, DIV, s, z, qmin, qmax)
 #define BVQ_FWD_PRE(ZP0, DIV)      \
   do {                             \
-    if (a.pre_relu)                \
+    if constexpr (ACT != 0)        \
+      BVQ_FWD_UNIT(ZP0, false, DIV); \
+    else if (a.pre_relu)           \
       BVQ_FWD_UNIT(ZP0, true, DIV); \
     else                           \
       BVQ_FWD_UNIT(ZP0, false, DIV); \
@@ -686,15 +694,21 @@ using namespace bvq;
 
 static int fakequant_fwd_impl(const bvq_quant_desc* d, const void* x, const void* scale, const void* zp, void* y,
                              void* codes, const float* bounds, bvq_stream_t stream) {
-  int rc = validate(d);
+  int rc = validate(d, true);
   if (rc) return rc;
+  const bool act = d->pre_op >= BVQ_PRE_SIGMOID;  // bvq_act.h: the row-mapped kernel, dequantized output only
+  if (act && (codes || bounds || !y || d->out_kind != BVQ_OUT_DEQUANT || d->x_dtype != d->ct_dtype)) {
+    set_error("bvq_fakequant_fwd: pre_op %d needs the dequantized output in x's dtype, no codes, no device bounds",
+              d->pre_op);
+    return BVQ_ERR_UNSUPPORTED;
+  }
   const int64_t n = d->outer * d->channels * d->inner;
   if (n == 0) return BVQ_OK;
   if (!x || !scale || !zp || (!y && !codes)) {
     set_error("bvq_fakequant_fwd: null pointer");
     return BVQ_ERR_INVALID;
   }
-  if (y && !codes && !bounds) {
+  if (y && !codes && !bounds && !act) {
     const ColsPlan cp = cols_quant_plan(d, x, y, nullptr, true, false, kColsFwdVec16);
     if (cp.ok) {
       ColsQuantArgs ca = {};
@@ -729,6 +743,17 @@ static int fakequant_fwd_impl(const bvq_quant_desc* d, const void* x, const void
   fill_args(a, d);
   hipStream_t st = (hipStream_t)stream;
   const bool nt = n * (int64_t)(dtype_size(d->x_dtype) + dtype_size(d->ct_dtype)) >= nt_threshold_bytes();
+  if (act) {
+    rc = with_dtype(d->x_dtype, [&](auto xt) {
+      using XT = typename decltype(xt)::type;
+      return with_value<BVQ_PRE_SIGMOID, BVQ_PRE_TANH>(d->pre_op, [&](auto ac) {
+        return with_stream_variant<elem<XT>::vec>("bvq_fakequant_fwd", vec, a.round_mode, nt, [&](auto v, auto rm, auto ntc) {
+          fakequant_fwd_kernel<XT, XT, v, rm, ntc, ntc, ac><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+        });
+      });
+    });
+    return rc ? rc : check_launch("bvq_fakequant_fwd");
+  }
   rc = with_pair(d->x_dtype, d->ct_dtype, [&](auto xt, auto ct) {
     using XT = typename decltype(xt)::type;
     return with_stream_variant<elem<XT>::vec>("bvq_fakequant_fwd", vec, a.round_mode, nt, [&](auto v, auto rm, auto ntc) {
@@ -1028,3 +1053,40 @@ extern "C" int bvq_selftest_div_f16r(const float* a, int32_t n_a, const float* s
   return check_launch("bvq_selftest_div_f16r");
 }
 
+
+// self-test of the fused activations (bvq_act.h): act(x) and its backward, element by element, as the quantizer kernels
+// compute them
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void selftest_pre_op_kernel(const T* __restrict__ x, const T* __restrict__ g,
+                                                              T* __restrict__ act_out, T* __restrict__ dact_out, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float a = act_rnd<T, ACT>(to_f<T>(x[i]));
+    act_out[i] = from_f<T>(a);
+    dact_out[i] = from_f<T>(act_bwd_rnd<T, ACT>(to_f<T>(g[i]), a));
+  }
+}
+
+extern "C" int bvq_selftest_pre_op(int pre_op, int dtype, const void* x, const void* g, void* act_out, void* dact_out,
+                                   int64_t n, bvq_stream_t stream) {
+  if (!x || !g || !act_out || !dact_out || n < 0) {
+    set_error("bvq_selftest_pre_op: bad argument");
+    return BVQ_ERR_INVALID;
+  }
+  if (pre_op != BVQ_PRE_SIGMOID && pre_op != BVQ_PRE_TANH) {
+    set_error("bvq_selftest_pre_op: pre_op %d has no bvq_act.h form", pre_op);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (n == 0) return BVQ_OK;
+  int64_t nb = (n + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_value<BVQ_PRE_SIGMOID, BVQ_PRE_TANH>(pre_op, [&](auto ac) {
+      selftest_pre_op_kernel<T, ac><<<dim3((unsigned)nb), dim3(256), 0, st>>>(
+          reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(g), reinterpret_cast<T*>(act_out),
+          reinterpret_cast<T*>(dact_out), n);
+    });
+  });
+  return rc ? rc : check_launch("bvq_selftest_pre_op");
+}

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "bvq_common.h"
+#include "bvq_act.h"
 #include "bvq_ties.h"
 #include "bvq_sums.h"
 #include "bvq_stat_epilogue.h"
@@ -28,7 +29,13 @@ struct StatArgs {
   float* pivot;      // moments: [channels] the value the sums are shifted by (written by the kernel)
 };
 
-template <typename T, int VEC, bool NT, bool RELU>
+// ACT: the activation of bvq_act.h applied to x first (0: none; RELU is the ReLU)
+template <typename T, int ACT>
+__device__ __forceinline__ uint32_t act_abs_bits(T v) {
+  return abs_bits<T>(from_f<T>(act_rnd<T, ACT>(to_f<T>(v))));
+}
+
+template <typename T, int VEC, bool NT, bool RELU, int ACT = 0>
 __global__ __launch_bounds__(kBlock) void absmax_kernel(StatArgs a) {
   const Unit u = locate_unit(a.t);
   if (!u.valid) return;
@@ -52,7 +59,7 @@ __global__ __launch_bounds__(kBlock) void absmax_kernel(StatArgs a) {
       if (ok[j]) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-          const uint32_t b = pre_abs_bits<T, RELU>(xv[j].v[k]);
+          const uint32_t b = ACT != 0 ? act_abs_bits<T, ACT>(xv[j].v[k]) : pre_abs_bits<T, RELU>(xv[j].v[k]);
           m = b > m ? b : m;
         }
       }
@@ -62,14 +69,15 @@ __global__ __launch_bounds__(kBlock) void absmax_kernel(StatArgs a) {
   const int32_t tail = (int32_t)(u.len - (int64_t)cur.cpr * VEC);
   for (int32_t e = lane; e < u.nrows * tail; e += kWave) {
     const int32_t r = e / tail, k = e - r * tail;
-    const uint32_t b = pre_abs_bits<T, RELU>(xp[(int64_t)r * u.row_stride + (int64_t)cur.cpr * VEC + k]);
+    const T xe = xp[(int64_t)r * u.row_stride + (int64_t)cur.cpr * VEC + k];
+    const uint32_t b = ACT != 0 ? act_abs_bits<T, ACT>(xe) : pre_abs_bits<T, RELU>(xe);
     m = b > m ? b : m;
   }
   m = wave_max_u32(m);
   if (lane == 0) a.part_a[u.id] = m;
 }
 
-template <typename T, int VEC, bool NT, bool RELU>
+template <typename T, int VEC, bool NT, bool RELU, int ACT = 0>
 __global__ __launch_bounds__(kBlock) void minmax_kernel(StatArgs a) {
   const Unit u = locate_unit(a.t);
   if (!u.valid) return;
@@ -94,7 +102,8 @@ __global__ __launch_bounds__(kBlock) void minmax_kernel(StatArgs a) {
       if (ok[j]) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-          const float f = RELU ? relu_f(to_f<T>(xv[j].v[k])) : to_f<T>(xv[j].v[k]);
+          float f = RELU ? relu_f(to_f<T>(xv[j].v[k])) : to_f<T>(xv[j].v[k]);
+          if constexpr (ACT != 0) f = act_rnd<T, ACT>(f);
           nan |= (f != f) ? 1u : 0u;
           mx = fmaxf(mx, f);
           mn = fminf(mn, f);
@@ -106,7 +115,8 @@ __global__ __launch_bounds__(kBlock) void minmax_kernel(StatArgs a) {
   for (int32_t e = lane; e < u.nrows * tail; e += kWave) {
     const int32_t r = e / tail, k = e - r * tail;
     const T xe = xp[(int64_t)r * u.row_stride + (int64_t)cur.cpr * VEC + k];
-    const float f = RELU ? relu_f(to_f<T>(xe)) : to_f<T>(xe);
+    float f = RELU ? relu_f(to_f<T>(xe)) : to_f<T>(xe);
+    if constexpr (ACT != 0) f = act_rnd<T, ACT>(f);
     nan |= (f != f) ? 1u : 0u;
     mx = fmaxf(mx, f);
     mn = fminf(mn, f);
@@ -1033,10 +1043,12 @@ extern "C" int64_t bvq_stats_workspace_bytes(int kind, int dtype, int64_t outer,
 static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t outer, int64_t channels,
                       int64_t inner, int out_dtype, void* out, const ScaleEpilogue& ep, void* workspace,
                       int64_t workspace_bytes, bvq_stream_t stream) {
-  if (pre_op != BVQ_PRE_NONE && pre_op != BVQ_PRE_RELU) {
+  if (pre_op < BVQ_PRE_NONE || pre_op > BVQ_PRE_TANH) {
     set_error("bvq_stats: bad pre_op %d", pre_op);
     return BVQ_ERR_INVALID;
   }
+  // sigmoid / tanh (bvq_act.h): the row-mapped statistic kernels + the finishing launch, nothing else
+  const bool act = pre_op >= BVQ_PRE_SIGMOID;
   if (bad_dtype(dtype) || bad_dtype(out_dtype) || outer < 0 || channels < 1 || inner < 0 ||
       (kind != BVQ_STAT_ABSMAX && kind != BVQ_STAT_MINMAX)) {
     set_error("bvq_stats: bad argument");
@@ -1059,7 +1071,7 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
   bool nt = n * (int64_t)dtype_size(dtype) >= nt_threshold_bytes();
   // channel axis last (or nearly): column-mapped units, same finishing kernel
   const ColsPlan cp =
-      (reinterpret_cast<uintptr_t>(x) & 15) == 0 ? cols_plan(dtype, outer, channels, inner) : ColsPlan{};
+      (reinterpret_cast<uintptr_t>(x) & 15) == 0 && !act ? cols_plan(dtype, outer, channels, inner) : ColsPlan{};
   if (cp.ok) {
     const int64_t width = (kind == BVQ_STAT_MINMAX ? 2 : 1) * cp.L;  // entries per partial row
     if (workspace_bytes < (cp.prows + cols_fold_scratch_rows(cp.prows)) * width * (int64_t)sizeof(uint32_t)) {
@@ -1099,7 +1111,7 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
   // kernel of the one-launch route -- the partials then fit ONE finishing launch (the short-unit tiling leaves ~10^4-10^5
   // partials and needs two): [8192,8192] bf16 34 -> 26 us, profiles/r03_onepass.txt section 5.
   const bool long_units = kind == BVQ_STAT_ABSMAX && channels == 1 && vec == 16 / dtype_size(dtype) &&
-                          a.t.units > kFinishSlice;
+                          a.t.units > kFinishSlice && !act;
   if (long_units) {
     const int64_t quantum = (int64_t)kWave * vec;
     int64_t piece = (a.t.row_len + kFinishSlice - 1) / kFinishSlice;
@@ -1127,6 +1139,18 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
       using T = typename decltype(t)::type;
       return with_nt_relu(nt, pre_op == BVQ_PRE_RELU, [&](auto ntc, auto relu) {
         absmax_onepass_kernel<T, elem<T>::vec, ntc, relu><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a, r, no_ep);
+      });
+    });
+  } else if (act) {
+    rc = with_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      return with_value<BVQ_PRE_SIGMOID, BVQ_PRE_TANH>(pre_op, [&](auto ac) {
+        return with_read_variant<elem<T>::vec>(vec, nt, [&](auto v, auto ntc) {
+          if (kind == BVQ_STAT_ABSMAX)
+            absmax_kernel<T, v, ntc, false, ac><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+          else
+            minmax_kernel<T, v, ntc, false, ac><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+        });
       });
     });
   } else {
@@ -1260,10 +1284,7 @@ extern "C" int bvq_absmax_scale_onepass(int pre_op, int dtype, const void* x, in
                                         double int_threshold, int scale_dtype, void* scale_out, int run_dtype,
                                         void* running, double momentum, int first_batch, uint32_t* arrive,
                                         int64_t arrive_words, bvq_stream_t stream) {
-  if (pre_op != BVQ_PRE_NONE && pre_op != BVQ_PRE_RELU) {
-    set_error("bvq_absmax_scale_onepass: bad pre_op %d", pre_op);
-    return BVQ_ERR_INVALID;
-  }
+  if (const int prc = check_pre_op(pre_op, "bvq_absmax_scale_onepass")) return prc;
   if (bad_dtype(dtype) || bad_dtype(stat_dtype) || (scale_out && bad_dtype(scale_dtype)) ||
       (running && bad_dtype(run_dtype)) || (scale_out && !(int_threshold == int_threshold))) {
     set_error("bvq_absmax_scale_onepass: bad argument");
@@ -1879,6 +1900,7 @@ extern "C" int bvq_stat_tie_apply(int match, int pre_op, int dtype, const void* 
   hipStream_t st = (hipStream_t)stream;
   GstatSrc src = {};
   src.p = gstat;
+  if (const int prc = check_pre_op(pre_op, "bvq_stat_tie_apply")) return prc;
   src.pre_relu = pre_op == BVQ_PRE_RELU;
   const int first_only = (match & BVQ_MATCH_FIRST) != 0;
   match &= ~BVQ_MATCH_FIRST;
@@ -1916,6 +1938,7 @@ extern "C" int bvq_stat_tie_apply_dscale(int pre_op, int dtype, const void* x, c
   src.scale_dtype = scale_dtype;
   src.quot_dtype = quot_dtype;
   src.int_threshold = (float)int_threshold;
+  if (const int prc = check_pre_op(pre_op, "bvq_stat_tie_apply_dscale")) return prc;
   src.pre_relu = pre_op == BVQ_PRE_RELU;
   rc = with_dtype(dtype, [&](auto t) {
     run_tie_apply<typename decltype(t)::type, BVQ_MATCH_ABS>(x, stat, src, reinterpret_cast<const unsigned long long*>(tie_info),

@@ -9,10 +9,12 @@ from typing import Callable, Optional
 import torch
 import torch.nn.functional as F
 
+from brevitas_amd.core.function_wrapper import Identity
 from brevitas_amd.core.quant import RescalingIntQuant
 from brevitas_amd.core.quant.weight_group import WeightQuantGroup
 
-__all__ = ['QuantConv2d', 'QuantLinear', 'QuantIdentity', 'WeightQuantGroup']
+__all__ = ['QuantConv2d', 'QuantLinear', 'QuantIdentity', 'QuantReLU', 'QuantSigmoid', 'QuantTanh', 'QuantHardTanh',
+           'WeightQuantGroup']
 
 WeightQuantFactory = Callable[[torch.nn.Parameter], RescalingIntQuant]
 
@@ -101,3 +103,76 @@ class QuantIdentity(torch.nn.Module):
 
     def forward(self, x):
         return self.act_quant(x)[0]
+
+
+_DEFAULT = object()  # act_quant not given: the layer's default quantizer
+
+
+class _QuantActivation(torch.nn.Module):
+    """A non-linear activation followed by its quantizer (QuantNLAL, B/nn/quant_activation.py:14-100, with the proxy of
+    B/proxy/runtime_quant.py:102-164): `act_quant` is a tensor_quant module, or None for the plain activation.  The
+    quantized form owns a FusedActivationQuantProxy (`act_quant`), which folds ReLU, sigmoid and tanh into the
+    quantizer's kernels where they apply; forward returns the dequantized tensor."""
+
+    def __init__(self, act_impl: torch.nn.Module, act_quant: Optional[torch.nn.Module]):
+        super().__init__()
+        from brevitas_amd.proxy import FusedActivationQuantProxy
+        self.act_impl = act_impl
+        if act_quant is None:
+            self.act_quant = None
+        else:
+            # the quantizer's clamp replaces a HardTanh (_is_act_enabled, B/proxy/runtime_quant.py:38-45)
+            fused_act = Identity() if isinstance(act_impl, torch.nn.Hardtanh) else act_impl
+            self.act_quant = FusedActivationQuantProxy(fused_act, act_quant)
+
+    def forward(self, x):
+        if self.act_quant is None:
+            return self.act_impl(x)
+        return self.act_quant(x)[0]
+
+
+def _default(act_quant, factory):
+    return factory() if act_quant is _DEFAULT else act_quant
+
+
+class QuantReLU(_QuantActivation):
+    """nn.ReLU + act_quant (default Uint8ActPerTensorFloat)"""
+
+    def __init__(self, act_quant=_DEFAULT):
+        from brevitas_amd.quant import Uint8ActPerTensorFloat
+        super().__init__(torch.nn.ReLU(), _default(act_quant, Uint8ActPerTensorFloat))
+
+
+class QuantSigmoid(_QuantActivation):
+    """nn.Sigmoid + act_quant (default Uint8ActPerTensorFloat)"""
+
+    def __init__(self, act_quant=_DEFAULT):
+        from brevitas_amd.quant import Uint8ActPerTensorFloat
+        super().__init__(torch.nn.Sigmoid(), _default(act_quant, Uint8ActPerTensorFloat))
+
+
+class QuantTanh(_QuantActivation):
+    """nn.Tanh + act_quant (default Int8ActPerTensorFloat)"""
+
+    def __init__(self, act_quant=_DEFAULT):
+        from brevitas_amd.quant import Int8ActPerTensorFloat
+        super().__init__(torch.nn.Tanh(), _default(act_quant, Int8ActPerTensorFloat))
+
+
+class QuantHardTanh(_QuantActivation):
+    """nn.Hardtanh(min_val, max_val) + act_quant (default Int8ActPerTensorFloatMinMaxInit(min_val, max_val)).  With a
+    quantizer the HardTanh itself is dropped -- the quantizer's clamp replaces it -- except in a calibration forward,
+    which hands on hardtanh(x) as the reference's calibration hook does (B/graph/calibrate.py:112-123)."""
+
+    def __init__(self, min_val: float = -1.0, max_val: float = 1.0, act_quant=_DEFAULT):
+        from brevitas_amd.quant import Int8ActPerTensorFloatMinMaxInit
+        if act_quant is _DEFAULT:
+            act_quant = Int8ActPerTensorFloatMinMaxInit(min_val, max_val)
+        super().__init__(torch.nn.Hardtanh(min_val, max_val), act_quant)
+        self.min_val, self.max_val = float(min_val), float(max_val)
+
+    def forward(self, x):
+        y = super().forward(x)
+        if self.act_quant is not None and getattr(self.act_quant.tensor_quant, 'bvq_collect_only', False):
+            y = F.hardtanh(y, self.min_val, self.max_val)
+        return y

@@ -1,9 +1,10 @@
 """The one proxy-level module on the hot path: activation function fused with its quantizer.
 
 FusedActivationQuantProxy (drop-in for B/proxy/runtime_quant.py:73-84) applies `activation_impl`
-and then `tensor_quant`.  When the activation is ReLU (QuantReLU, the dominant pattern) and the
-quantizer is brevitas_amd's RescalingIntQuant, the activation is folded into the statistic and
-quantizer kernels: its own read+write pass and its backward pass disappear.  Every other
+and then `tensor_quant`.  When the activation is ReLU (QuantReLU, the dominant pattern), sigmoid or tanh and
+the quantizer is brevitas_amd's RescalingIntQuant, the activation is folded into the statistic and
+quantizer kernels where they cover the quantizer's route: its own read+write pass and its
+backward pass disappear.  Every other
 combination runs the two modules one after the other, like the reference.
 """
 import torch
@@ -20,6 +21,10 @@ def _pre_op_of(activation_impl):
         return nat.PRE_NONE
     if type(activation_impl) is torch.nn.ReLU:
         return nat.PRE_RELU
+    if type(activation_impl) is torch.nn.Sigmoid:
+        return nat.PRE_SIGMOID
+    if type(activation_impl) is torch.nn.Tanh:
+        return nat.PRE_TANH
     return None
 
 

@@ -25,6 +25,7 @@ __all__ = ['Int8WeightPerChannelFloat', 'Int4WeightPerChannelFloat', 'Int8Weight
            'Int8ActPerTensorFloat', 'Uint8ActPerTensorFloat', 'Int8ActPerChannelFloat',
            'ShiftedUint8WeightPerTensorFloat', 'ShiftedUint8WeightPerChannelFloat', 'ShiftedUint8ActPerTensorFloat',
            'Int8WeightPerTensorFixedPoint', 'Int8WeightPerChannelFixedPoint', 'Int8ActPerTensorFixedPoint',
+           'Int8ActPerTensorFloatMinMaxInit', 'Uint8ActPerTensorFloatMaxInit',
            'Uint8ActPerTensorFixedPoint', 'Uint8ActPerTensorFixedPointMaxInit', 'Int8Bias', 'Int16Bias', 'Int24Bias',
            'Int32Bias', 'Int8BiasPerTensorFloatInternalScaling', 'Int8BiasPerTensorFixedPointInternalScaling']
 
@@ -109,6 +110,27 @@ def Uint8ActPerTensorFloat(scaling_impl_type: str = 'parameter_from_stats', coll
     """unsigned variant for post-ReLU activations (B/quant/scaled_int.py:183-193)"""
     return _act_quant(False, bit_width, scaling_impl_type, collect_stats_steps, None, scaling_init,
                       scaling_stats_op)
+
+
+def _act_min_max_init(signed: bool, min_val: float, max_val: float, bit_width: int) -> RescalingIntQuant:
+    # MinMaxScalingInit (B/quant/solver/act.py:17-23): a float32 scalar max(|min_val|, |max_val|)
+    init = torch.tensor(max(abs(float(min_val)), abs(float(max_val))))
+    return RescalingIntQuant(
+        IntQuant(narrow_range=False, signed=signed, float_to_int_impl=RoundSte(), tensor_clamp_impl=TensorClamp()),
+        ParameterScaling(init, None, FloatRestrictValue(), None),
+        IntScaling(signed=signed, narrow_range=False), ZeroZeroPoint(), BitWidthConst(bit_width))
+
+
+def Int8ActPerTensorFloatMinMaxInit(min_val: float, max_val: float, bit_width: int = 8) -> RescalingIntQuant:
+    """IntQuant + ParamMinMaxInitScaling + PerTensorFloatScaling8bit + ActQuantSolver (B/quant/scaled_int.py:32-46):
+    a learned per-tensor scale initialised to max(|min_val|, |max_val|) / 2^(b-1); the default of QuantHardTanh"""
+    return _act_min_max_init(True, min_val, max_val, bit_width)
+
+
+def Uint8ActPerTensorFloatMaxInit(max_val: float, bit_width: int = 8) -> RescalingIntQuant:
+    """UintQuant + ParamMinMaxInitScaling + PerTensorFloatScaling8bit + ActQuantSolver (B/quant/scaled_int.py:49-62):
+    min_val = 0, a learned per-tensor scale initialised to |max_val| / (2^b - 1)"""
+    return _act_min_max_init(False, 0.0, max_val, bit_width)
 
 
 def Int8ActPerChannelFloat(channels: int, scaling_impl_type: str = 'stats', collect_stats_steps: int = 300,

@@ -86,8 +86,13 @@ typedef enum bvq_scalar_mode { BVQ_SCALAR_OPMATH = 0, BVQ_SCALAR_CAST = 1 } bvq_
 /* Elementwise activation applied to x BEFORE the statistic / the quantizer, fused into the same
  * kernels: FusedActivationQuantProxy.forward = tensor_quant(activation_impl(x))
  * (B/proxy/runtime_quant.py:73-84).  RELU: torch.relu forward (NaN and -0.0 pass), backward
- * grad * (x > 0) (threshold_backward). */
-typedef enum bvq_pre_op { BVQ_PRE_NONE = 0, BVQ_PRE_RELU = 1 } bvq_pre_op;
+ * grad * (x > 0) (threshold_backward).  SIGMOID / TANH: torch.sigmoid / torch.tanh in float opmath, rounded to
+ * x's dtype; backward sigmoid_backward / tanh_backward with torch's rounding (brevitas_amd/csrc/bvq_act.h).
+ * SIGMOID and TANH are covered, with x and the compute dtype alike, by bvq_fakequant_fwd (dequantized output),
+ * bvq_fakequant_bwd (dx and dscale), bvq_fakequant_bwd_learned, and the row-mapped abs-max / min-max statistic of
+ * bvq_stats_pre, bvq_absmax_scale and bvq_absmax_scale_running; every other entry fails with BVQ_ERR_UNSUPPORTED on
+ * them. */
+typedef enum bvq_pre_op { BVQ_PRE_NONE = 0, BVQ_PRE_RELU = 1, BVQ_PRE_SIGMOID = 2, BVQ_PRE_TANH = 3 } bvq_pre_op;
 
 /* element type of the integer codes bvq_fakequant_fwd can emit: what QuantTensor.int() returns
  * (B/quant_tensor/__init__.py:174-187: int8 / uint8 up to 8 bits, int32 above) and what the QCDQ export
@@ -668,6 +673,13 @@ int bvq_weight_quant_list_bwd(int dtype, int scale_dtype, int quot_dtype, int ro
  * tests compare every float16 numerator x every float16 scale in [2^-14, 2^14] with a / s (tests/test_gpu_fastdiv.py). */
 int bvq_selftest_div_f16r(const float* a, int32_t n_a, const float* scales, int32_t n_s, float* out,
                           bvq_stream_t stream);
+
+/* Diagnostic entry (no reference counterpart): the fused activation pre_op (BVQ_PRE_SIGMOID / BVQ_PRE_TANH) as the
+ * quantizer kernels compute it, element by element on n elements of dtype: act_out[i] = act(x[i]) and
+ * dact_out[i] = act_backward(g[i], act_out[i]), both rounded to dtype, so that the tests can compare them with
+ * torch.sigmoid / torch.tanh and their autograd on the device. */
+int bvq_selftest_pre_op(int pre_op, int dtype, const void* x, const void* g, void* act_out, void* dact_out, int64_t n,
+                        bvq_stream_t stream);
 
 #ifdef __cplusplus
 }
