@@ -930,10 +930,11 @@ def fakequant_fwd_bounds(desc, x, scale, zp, bounds):
 
 
 def fakequant_bwd_bounds(desc, g, x, scale, zp, bounds, need_dbounds):
-    """-> (dx, dscale float32 [n], dbounds float32 [2, n] or None): n = channels or 1"""
+    """-> (dx, dscale float32 [n], dbounds float32 [2, n] or None): n = channels when the scale OR the zero-point is
+    per-channel, else 1 -- the kernel sums per channel in either case (like bvq_fakequant_bwd)"""
     dev = require_device(g, x, scale, zp, bounds)
     dx = torch.empty_like(x)
-    nsum = int(desc.channels) if (desc.scale_per_channel and desc.channels > 1) else 1
+    nsum = int(desc.channels) if ((desc.scale_per_channel or desc.zp_per_channel) and desc.channels > 1) else 1
     ds = torch.empty(nsum, dtype=torch.float32, device=dev)
     db = torch.empty(2, nsum, dtype=torch.float32, device=dev) if need_dbounds else None
     wsb = int(lib.bvq_fakequant_bwd_workspace_bytes(ctypes.byref(desc)))

@@ -230,6 +230,21 @@ def fakequant_bwd(desc, g, x, scale, zp):
     return dx, ds, dz
 
 
+def fakequant_bwd_bounds(desc, g, x, scale, zp):
+    """-> float32 [2, n]: the gradients tensor_clamp sends to its tensor bounds, d(qmin) per channel then d(qmax) per
+    channel (n = channels when scale or zero-point is per-channel, else 1); zeros with a straight-through clamp.
+    desc.qmin / qmax are the bounds."""
+    g = _c(g, desc.ct_dtype)
+    x = _c(x, desc.x_dtype)
+    scale = _c(scale, desc.scale_dtype)
+    zp = _c(zp, desc.zp_dtype)
+    pc = (desc.scale_per_channel or desc.zp_per_channel) and desc.channels > 1
+    nsum = desc.channels if pc else 1
+    db = np.empty(2 * nsum, dtype=np.float32)
+    lib().orc_fakequant_bwd_bounds(ctypes.byref(desc), _ptr(g), _ptr(x), _ptr(scale), _ptr(zp), _ptr(db))
+    return db.reshape(2, nsum)
+
+
 def variant_fwd(desc, x, scale, pre_scale=None, zp=None, pre_zp=None):
     """BinaryQuant / ClampedBinaryQuant / TernaryQuant / DecoupledIntQuant / TruncIntQuant forward -> y (ct dtype)"""
     x = _c(x, desc.x_dtype)

@@ -185,3 +185,75 @@ def test_doctests():
     c = pick('ternary_doctest')[0]
     y, scale, zp, bw = TernaryQuant(ConstScaling(1.0), 0.5).to(DEV)(c.torch('x', DEV))
     assert y.tolist() == [0.0, -1.0, 1.0] and float(scale) == 1.0 and float(zp) == 0.0 and float(bw) == 2.0
+
+
+def _sums_close(got, want, name):
+    """float32 sums in another order: the form and limit of test_gpu_fuzz.py"""
+    got, want = got.double().cpu().reshape(-1), want.double().cpu().reshape(-1)
+    mag = float(want.abs().max())
+    assert bool(((got - want).abs() <= 2e-4 * (want.abs() + mag + 1.0)).all()), (name, got[:4], want[:4])
+
+
+def _large_step(kind, shape, channels_last):
+    """one forward and backward of `kind` on a seeded float32 tensor -> (y, dx, parameter gradients)"""
+    from brevitas_amd.core.bit_width import BitWidthConst
+    from brevitas_amd.core.function_wrapper import RoundSte, TensorClamp
+    from brevitas_amd.core.quant import BinaryQuant, ClampedBinaryQuant, DecoupledIntQuant, TernaryQuant, TruncIntQuant
+    from brevitas_amd.core.scaling import ParameterScaling
+    gen = torch.Generator().manual_seed(11)
+    ch = shape[1]
+    v = torch.rand(1, ch, 1, 1, generator=gen) * 0.5 + 0.25
+    x = torch.randn(shape, generator=gen)
+    g = torch.randn(shape, generator=gen).to(DEV)
+    x = x.to(DEV)
+    if channels_last:
+        x = x.contiguous(memory_format=torch.channels_last)
+    x.requires_grad_(True)
+    if kind in ('binary', 'clamped_binary', 'ternary'):
+        q = {'binary': lambda: BinaryQuant(ParameterScaling(v, tuple(v.shape))),
+             'clamped_binary': lambda: ClampedBinaryQuant(ParameterScaling(v, tuple(v.shape)),
+                                                          tensor_clamp_impl=TensorClamp()),
+             'ternary': lambda: TernaryQuant(ParameterScaling(v, tuple(v.shape)), 0.6)}[kind]().to(DEV)
+        y = q(x)[0]
+        params = [q.scaling_impl.value]
+    elif kind == 'decoupled':
+        dq = DecoupledIntQuant(narrow_range=False, signed=True, tensor_clamp_impl=TensorClamp()).to(DEV)
+        pre_scale = (v * 0.1).to(DEV).requires_grad_(True)
+        scale = (v * 0.12).to(DEV).requires_grad_(True)
+        t = lambda s: torch.tensor(s, device=DEV)  # noqa: E731
+        y = dq(pre_scale, t(1.), scale, t(2.), BitWidthConst(4).to(DEV)(), x)
+        params = [scale, pre_scale]
+    else:
+        tq = TruncIntQuant(RoundSte(), BitWidthConst(5)).to(DEV)
+        scale = torch.tensor(0.05, device=DEV, requires_grad=True)
+        y = tq(x * 4, scale, torch.tensor(0., device=DEV), BitWidthConst(8).to(DEV)())[0]
+        params = [scale]
+    y.backward(g)
+    return y.detach(), x.grad, [p.grad for p in params]
+
+
+@pytest.mark.parametrize('layout', ['nchw', 'channels_last'])
+@pytest.mark.parametrize('kind', ['binary', 'clamped_binary', 'ternary', 'decoupled', 'trunc'])
+def test_large_fused_route_equals_op_by_op(kind, layout, monkeypatch):
+    """float32 [32,64,28,28] (and a channels_last tensor): the fused kernels and the op-by-op route on the device give
+    the same y and dx bits and the same parameter gradients up to the order of the float32 sums; the NCHW case takes
+    the kernels"""
+    import brevitas_amd.config as config
+    from brevitas_amd import _native as nat
+    shape, cl = ((32, 64, 28, 28), False) if layout == 'nchw' else ((8, 64, 28, 28), True)
+    calls = []
+    for name in ('variant_fwd', 'variant_bwd'):
+        real = getattr(nat, name)
+        monkeypatch.setattr(nat, name, lambda *a, _r=real, _n=name, **k: (calls.append(_n), _r(*a, **k))[1])
+    monkeypatch.setattr(config, 'FUSED_PATHS', True)
+    y1, dx1, p1 = _large_step(kind, shape, cl)
+    if not cl:
+        assert calls == ['variant_fwd', 'variant_bwd'], calls
+    calls.clear()
+    monkeypatch.setattr(config, 'FUSED_PATHS', False)
+    y0, dx0, p0 = _large_step(kind, shape, cl)
+    assert calls == []
+    assert torch.equal(y1, y0), 'y'
+    assert torch.equal(dx1, dx0), 'dx'
+    for i, (a, b) in enumerate(zip(p1, p0)):
+        _sums_close(a, b, 'parameter %d' % i)
