@@ -77,26 +77,16 @@ __device__ __forceinline__ float add_rounded_pair_bf16(float acc, f2 v) {
   const bf16x2 ones = {(bf16_t)1.0f, (bf16_t)1.0f};
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_convertvector(v, bf16x2), ones, acc, false);
 }
-// {acc.x + RN_bf16(v.x), acc.y + RN_bf16(v.y)}: the column-mapped kernels keep one sum per element of the pair.
-// The selectors {1, 0} and {0, 1} must live in registers the compiler cannot see through: as a constant, {1.0bf16, 0}
-// = 0x00003f80 is emitted as the inline constant "1.0", which the instruction reads as 0x3f800000 = {0, 1.0bf16}
-// (ROCm 7.2 / gfx950: both sums then received the pair's second element).  make_dot_sel() once per kernel.
-struct DotSel {
-  uint32_t lo, hi;      // bf16 {1, 0}, {0, 1}
-  uint32_t lo16, hi16;  // float16 {1, 0}, {0, 1}
-};
-__device__ __forceinline__ DotSel make_dot_sel() {
-  DotSel d = {0x00003f80u, 0x3f800000u, 0x00003c00u, 0x3c000000u};
-  asm volatile("" : "+s"(d.lo), "+s"(d.hi), "+s"(d.lo16), "+s"(d.hi16));
-  return d;
-}
-__device__ __forceinline__ f2 add_rounded_lanes_bf16(f2 acc, f2 v, const DotSel& sel) {
+// {acc.x + RN_bf16(v.x), acc.y + RN_bf16(v.y)}: the column-mapped kernels keep one sum per element of the pair -- the
+// packed conversion, then the two halves widened by a shift and a mask.  (Not a dot product with {1, 0} / {0, 1}
+// selectors: that adds 0 * the other element, a NaN when the other column's term is an inf or a NaN, and one column's
+// non-finite gradient made its pair neighbour's channel sum NaN.)
+__device__ __forceinline__ f2 add_rounded_lanes_bf16(f2 acc, f2 v) {
   typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-  const bf16x2 p = __builtin_convertvector(v, bf16x2);
-  return f2{__builtin_amdgcn_fdot2_f32_bf16(p, __builtin_bit_cast(bf16x2, sel.lo), acc.x, false),
-            __builtin_amdgcn_fdot2_f32_bf16(p, __builtin_bit_cast(bf16x2, sel.hi), acc.y, false)};
+  const uint32_t p = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+  return f2{acc.x + __builtin_bit_cast(float, p << 16), acc.y + __builtin_bit_cast(float, p & 0xffff0000u)};
 }
-// float16: the same with v_dot2_f32_f16 (the selectors kept out of the compiler's sight like the bf16 ones)
+// float16: the pair sum with v_dot2_f32_f16
 #ifndef BVQ_BWD_LEAN_F16
 #define BVQ_BWD_LEAN_F16 1
 #endif
@@ -106,18 +96,18 @@ __device__ __forceinline__ float add_rounded_pair_f16(float acc, f2 v) {
   const f16x2 ones = {(f16_t)1.0f, (f16_t)1.0f};
   return __builtin_amdgcn_fdot2(__builtin_convertvector(v, f16x2), ones, acc, false);
 }
-__device__ __forceinline__ f2 add_rounded_lanes_f16(f2 acc, f2 v, const DotSel& sel) {
+// {acc.x + RN_f16(v.x), acc.y + RN_f16(v.y)}: the packed conversion, then each half widened (no selector dot product,
+// as for bf16)
+__device__ __forceinline__ f2 add_rounded_lanes_f16(f2 acc, f2 v) {
   typedef f16_t f16x2 __attribute__((ext_vector_type(2)));
   const f16x2 p = __builtin_convertvector(v, f16x2);
-  return f2{__builtin_amdgcn_fdot2(p, __builtin_bit_cast(f16x2, sel.lo16), acc.x, false),
-            __builtin_amdgcn_fdot2(p, __builtin_bit_cast(f16x2, sel.hi16), acc.y, false)};
+  return f2{acc.x + (float)p.x, acc.y + (float)p.y};
 }
 // MIX: the caller adds the two halves of ds_acc up in the end (row-mapped units: one channel per wave), so the sums
 // of the pair's elements may share an accumulator; otherwise ds_acc.x / .y stay the sums of element x / y.
 template <typename CT, int RM, int MODE, bool ZP0, bool SAME16, bool MIX = false, typename Div, typename S>
 __device__ __forceinline__ f2 bwd_elem2(f2 xf, f2 gf, const Div& div, S s, S z, float qmin, float qmax,
-                                        bool clamp_ste, int mode, f2& ds_acc, f2& dzp_acc, f2& dq_acc,
-                                        const DotSel& sel = DotSel{}) {
+                                        bool clamp_ste, int mode, f2& ds_acc, f2& dzp_acc, f2& dq_acc) {
   const f2 t1 = rnd2<CT>(div(xf));
   constexpr bool kLean = BVQ_BWD_LEAN && MODE != kBwdDsBounds;
   const f2 t2 = ZP0 ? (kLean ? t1 : t1 + 0.f) : rnd2<CT>(t1 + z);
@@ -152,15 +142,15 @@ __device__ __forceinline__ f2 bwd_elem2(f2 xf, f2 gf, const Div& div, S s, S z, 
       const float a2 = add_rounded_pair_bf16(ds_acc.y, -dt * rnd2<CT>(div(t1)));
       ds_acc = f2{a1, a2};
     } else if constexpr (kLean && elem<CT>::id == BVQ_BF16) {
-      ds_acc = add_rounded_lanes_bf16(ds_acc, gf * t5, sel);
-      ds_acc = add_rounded_lanes_bf16(ds_acc, -dt * rnd2<CT>(div(t1)), sel);
+      ds_acc = add_rounded_lanes_bf16(ds_acc, gf * t5);
+      ds_acc = add_rounded_lanes_bf16(ds_acc, -dt * rnd2<CT>(div(t1)));
     } else if constexpr (kLean && BVQ_BWD_LEAN_F16 && elem<CT>::id == BVQ_F16 && MIX) {
       const float a1 = add_rounded_pair_f16(ds_acc.x, gf * t5);
       const float a2 = add_rounded_pair_f16(ds_acc.y, -dt * rnd2<CT>(div(t1)));
       ds_acc = f2{a1, a2};
     } else if constexpr (kLean && BVQ_BWD_LEAN_F16 && elem<CT>::id == BVQ_F16) {
-      ds_acc = add_rounded_lanes_f16(ds_acc, gf * t5, sel);
-      ds_acc = add_rounded_lanes_f16(ds_acc, -dt * rnd2<CT>(div(t1)), sel);
+      ds_acc = add_rounded_lanes_f16(ds_acc, gf * t5);
+      ds_acc = add_rounded_lanes_f16(ds_acc, -dt * rnd2<CT>(div(t1)));
     } else {
       const f2 term1 = rnd2<CT>(gf * t5);
       const f2 term2 = rnd2<CT>(-dt * rnd2<CT>(div(t1)));
@@ -638,7 +628,6 @@ __device__ __forceinline__ void cols_bwd_rows(const ColsQuantArgs& a, const Cols
   const bool ties = a.tie_stat != nullptr;
   const bool clamp_ste = a.clamp_ste != 0;
   const int mode = a.round_mode;
-  const DotSel dsel = make_dot_sel();
   // the work on one row of this lane's columns
   auto row_work = [&](const vec_t<T, VEC>& xr, const vec_t<T, VEC>& gr, uint32_t off) {
     vec_t<T, VEC> dv;
@@ -650,13 +639,13 @@ __device__ __forceinline__ void cols_bwd_rows(const ColsQuantArgs& a, const Cols
       f2 d;
       if constexpr (FAST && elem<T>::id == BVQ_F16)
         d = bwd_elem2<T, RM, kBwdDs, ZP0, kSame16>(xin, gf, BVQ_DIVF16V{ln.s2[k / 2], r2[k / 2]}, ln.s2[k / 2], ln.z2[k / 2],
-                                                   qmin, qmax, clamp_ste, mode, ds2[k / 2], dz_unused, dz_unused, dsel);
+                                                   qmin, qmax, clamp_ste, mode, ds2[k / 2], dz_unused, dz_unused);
       else if constexpr (FAST)
         d = bwd_elem2<T, RM, kBwdDs, ZP0, kSame16>(xin, gf, DivBf16V{r2[k / 2]}, ln.s2[k / 2], ln.z2[k / 2], qmin, qmax,
-                                                   clamp_ste, mode, ds2[k / 2], dz_unused, dz_unused, dsel);
+                                                   clamp_ste, mode, ds2[k / 2], dz_unused, dz_unused);
       else
         d = bwd_elem2<T, RM, kBwdDs, ZP0, kSame16>(xin, gf, DivExactV{ln.s2[k / 2]}, ln.s2[k / 2], ln.z2[k / 2], qmin,
-                                                   qmax, clamp_ste, mode, ds2[k / 2], dz_unused, dz_unused, dsel);
+                                                   qmax, clamp_ste, mode, ds2[k / 2], dz_unused, dz_unused);
       if constexpr (PRE) d = xraw > splat2(0.f) ? d : splat2(0.f);  // torch.relu backward: grad * (x > 0)
       pack2<T>(d, dv.v[k], dv.v[k + 1]);
     }

@@ -29,6 +29,15 @@ static int64_t bwd_units(const bvq_quant_desc* d) {
   return a > b ? a : b;
 }
 
+// the column-mapped backward's scale-gradient workspace: the partial rows and their fold (floats), then, 8-byte aligned,
+// the double-precision middle stage of the per-channel sums (rows of more than kSumSlice columns per channel)
+static int64_t cols_bwd_mid_off(const ColsPlan& cp) {
+  return (((cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L * (int64_t)sizeof(float) + 7) / 8) * 8;
+}
+static int64_t cols_bwd_sum_bytes(const ColsPlan& cp, int64_t inner, int64_t channels) {
+  return cols_bwd_mid_off(cp) + channel_sums_mid_bytes(inner, channels);
+}
+
 extern "C" int64_t bvq_fakequant_bwd_workspace_bytes(const bvq_quant_desc* d) {
   if (validate(d, true)) return -1;
   int64_t outer, row_len;
@@ -38,8 +47,8 @@ extern "C" int64_t bvq_fakequant_bwd_workspace_bytes(const bvq_quant_desc* d) {
   const int64_t mid = channel_sums_mid_bytes(units / channels + 1, channels) + 16;
   int64_t bytes = 3 * units * (int64_t)sizeof(float) + mid + 256;  // (a third partial array: bvq_fakequant_bwd_bounds)
   const ColsPlan cp = cols_quant_plan(d, nullptr, nullptr, nullptr, false, true);
-  if (cp.ok && (cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L * (int64_t)sizeof(float) + 256 > bytes)
-    bytes = (cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L * (int64_t)sizeof(float) + 256;
+  if (cp.ok && cols_bwd_sum_bytes(cp, d->inner, channels) + 256 > bytes)
+    bytes = cols_bwd_sum_bytes(cp, d->inner, channels) + 256;
   return bytes;
 }
 
@@ -92,7 +101,7 @@ static int fakequant_bwd_impl(const bvq_quant_desc* d, const void* g, const void
   if (!dzp && !bounds && !act) {
     const ColsPlan cp = cols_quant_plan(d, x, g, dx, !dscale && !tie_stat, true);
     if (cp.ok) {
-      const int64_t need = dscale ? (cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L * (int64_t)sizeof(float) : 0;
+      const int64_t need = dscale ? cols_bwd_sum_bytes(cp, d->inner, channels) : 0;
       if (dscale && (!workspace || workspace_bytes < need)) {
         set_error("bvq_fakequant_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
         return BVQ_ERR_WORKSPACE;
@@ -117,7 +126,8 @@ static int fakequant_bwd_impl(const bvq_quant_desc* d, const void* g, const void
         float* folded = nullptr;
         launch_cols_fold_sum_min(ca.ds_part, nullptr, cp.prows, cp.L, ca.ds_part + cp.prows * cp.L, nullptr, &folded,
                                  nullptr, st);
-        launch_channel_sums(folded, nullptr, dscale, nullptr, 1, channels, d->inner, nullptr, st, epilogue);
+        launch_channel_sums(folded, nullptr, dscale, nullptr, 1, channels, d->inner,
+                            reinterpret_cast<char*>(workspace) + cols_bwd_mid_off(cp), st, epilogue);
         rc = check_launch("bvq_fakequant_bwd/cols_sum");
       }
       return rc;

@@ -230,6 +230,21 @@ def fakequant_bwd(desc, g, x, scale, zp):
     return dx, ds, dz
 
 
+def fakequant_bwd_abs(desc, g, x, scale, zp):
+    """-> (abs_dscale, abs_dzp) float64 [n]: per channel, the sum of |term| over the terms fakequant_bwd adds up for dscale
+    and dzp (n as for dscale) -- the scale of a float32 summation error that other channels do not dominate"""
+    g = _c(g, desc.ct_dtype)
+    x = _c(x, desc.x_dtype)
+    scale = _c(scale, desc.scale_dtype)
+    zp = _c(zp, desc.zp_dtype)
+    pc = (desc.scale_per_channel or desc.zp_per_channel) and desc.channels > 1
+    nsum = desc.channels if pc else 1
+    a_s = np.empty(nsum, dtype=np.float64)
+    a_z = np.empty(nsum, dtype=np.float64)
+    lib().orc_fakequant_bwd_abs(ctypes.byref(desc), _ptr(g), _ptr(x), _ptr(scale), _ptr(zp), _ptr(a_s), _ptr(a_z))
+    return a_s, a_z
+
+
 def fakequant_bwd_bounds(desc, g, x, scale, zp):
     """-> float32 [2, n]: the gradients tensor_clamp sends to its tensor bounds, d(qmin) per channel then d(qmax) per
     channel (n = channels when scale or zero-point is per-channel, else 1); zeros with a straight-through clamp.
