@@ -27,6 +27,8 @@ MATCH_FIRST = 16  # OR-ed: only the first attaining element, even for a whole-te
 PRE_NONE, PRE_RELU, PRE_SIGMOID, PRE_TANH = 0, 1, 2, 3
 CODES_I32, CODES_I8, CODES_U8 = 0, 1, 2
 CLUSTER_FORCE_FALLBACK = 1  # BVQ_CLUSTER_FORCE_FALLBACK: tests only
+# the `form` of bvq_absmax_fakequant_cluster_form (developers, tests)
+CLUSTER_AUTO, CLUSTER_WALK, CLUSTER_ONESHOT = range(3)
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
 ABI_VERSION = 2
 
@@ -46,7 +48,8 @@ EXPORTS = (
     'bvq_fakequant_bwd_stats_onepass', 'bvq_scale_from_stat_running', 'bvq_fakequant_bwd_shard',
     'bvq_shard_unpack_deposit', 'bvq_absmax_list_supported', 'bvq_absmax_scale_list', 'bvq_weight_list_supported',
     'bvq_weight_quant_list_fwd', 'bvq_weight_quant_list_bwd_workspace_bytes', 'bvq_weight_quant_list_bwd',
-    'bvq_absmax_fakequant_cluster_supported', 'bvq_absmax_fakequant_cluster', 'bvq_selftest_pre_op')
+    'bvq_absmax_fakequant_cluster_supported', 'bvq_absmax_fakequant_cluster', 'bvq_absmax_fakequant_cluster_form',
+    'bvq_selftest_pre_op')
 
 
 class QuantDesc(ctypes.Structure):
@@ -167,6 +170,8 @@ def _load(path=None, strict=True):
         'bvq_absmax_fakequant_cluster_supported': (i64, [ctypes.POINTER(QuantDesc), vp, vp]),
         'bvq_absmax_fakequant_cluster': (i32, [ctypes.POINTER(QuantDesc), vp, dbl, i32, dbl, vp, vp, i32, vp, dbl, i32, vp,
                                                vp, i64, i32, vp, vp]),
+        'bvq_absmax_fakequant_cluster_form': (i32, [ctypes.POINTER(QuantDesc), vp, dbl, i32, dbl, vp, vp, i32, vp, dbl, i32,
+                                                    vp, vp, i64, i32, vp, i32, vp, vp]),
         'bvq_fakequant_bwd_learned': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, i32, dbl, i32, dbl, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
@@ -449,11 +454,13 @@ def stats_fakequant_fwd(desc, x, min_val, int_threshold, scale_dtype):
 
 
 def absmax_fakequant_cluster(desc, x, min_val, int_threshold, scale_dtype, running=None, momentum=0.0,
-                             first_batch=False, flags=0, fallbacks=None):
+                             first_batch=False, flags=0, fallbacks=None, form=CLUSTER_AUTO, stamps=None):
     """abs-max statistic, scale, running statistic and quantize-dequantize in ONE launch for channels held by a cluster
     of workgroups (x read once) -> (stat, scale, y), the bits of absmax_scale + fakequant_fwd; or None when the shape is
     not covered or there is no arrival buffer (capturing, ONEPASS off): the caller takes the two-call route.
-    fallbacks: optional int32 device counter of the workgroups that read their channel themselves."""
+    fallbacks: optional int32 device counter of the workgroups that read their channel themselves.
+    form (developers, tests): CLUSTER_AUTO, or the form of the kernel to run instead of the library's choice for the
+    shape; stamps: int64 [channels * members * 6] for a library built with -DBVQ_CLUSTER_STAMPS."""
     dev = require_device(x)
     assert x.is_contiguous()
     y = torch.empty_like(x)
@@ -469,11 +476,14 @@ def absmax_fakequant_cluster(desc, x, min_val, int_threshold, scale_dtype, runni
         scale = torch.empty(desc.channels, dtype=scale_dtype, device=dev)
         if _timer is not None:
             _timer.before('bvq_stats_fakequant_fwd')
-        check(lib.bvq_absmax_fakequant_cluster(
-            ctypes.byref(desc), ptr(x), float(min_val or 0.0), int(bool(min_val)), float(int_threshold), ptr(stat),
-            ptr(scale), dtype_code(running.dtype) if running is not None else 0, ptr(running), float(momentum),
-            int(first_batch), ptr(y), ptr(arrive), arrive.numel(), int(flags), ptr(fallbacks), st),
-            'bvq_absmax_fakequant_cluster')
+        args = (ctypes.byref(desc), ptr(x), float(min_val or 0.0), int(bool(min_val)), float(int_threshold), ptr(stat),
+                ptr(scale), dtype_code(running.dtype) if running is not None else 0, ptr(running), float(momentum),
+                int(first_batch), ptr(y), ptr(arrive), arrive.numel(), int(flags), ptr(fallbacks))
+        if form == CLUSTER_AUTO and stamps is None:
+            check(lib.bvq_absmax_fakequant_cluster(*args, st), 'bvq_absmax_fakequant_cluster')
+        else:
+            check(lib.bvq_absmax_fakequant_cluster_form(*args, int(form), ptr(stamps), st),
+                  'bvq_absmax_fakequant_cluster_form')
         if _timer is not None:
             _timer.after('bvq_stats_fakequant_fwd')
     return stat, scale, y

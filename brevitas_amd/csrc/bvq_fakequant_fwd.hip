@@ -342,8 +342,8 @@ __device__ __forceinline__ void store_stat_scale(void* stat_out, void* scale_out
     reinterpret_cast<f16_t*>(scale_out)[c] = (f16_t)s;
 }
 
-template <typename T, int RM, bool PRE, typename Div>
-__device__ __forceinline__ void fused_quantize(const vec_t<T, elem<T>::vec> (&xv)[kFusedSlots], const bool (&ok)[kFusedSlots],
+template <typename T, int RM, bool PRE, typename Div, typename Ok>
+__device__ __forceinline__ void fused_quantize(const vec_t<T, elem<T>::vec> (&xv)[kFusedSlots], const Ok& ok,
                                                T* __restrict__ yp, int lane, const Div& div, float s,
                                                float qmin, float qmax, int mode) {
   constexpr int VEC = elem<T>::vec;
@@ -395,10 +395,40 @@ __device__ __forceinline__ void fused_load(const FusedArgs& a, int32_t c, int r,
     xv[j] = load_vec<T, VEC, true>(ok[j] ? xp + (int64_t)(lane + kWave * j) * VEC : reinterpret_cast<const T*>(a.x));
 }
 
-// ... and its maximum |x| key (this lane's)
+// The same two for a kernel short of registers (the cluster forward below): the slots of a wave's slice as ONE count of
+// chunks, every ok[j] a compare where it is used instead of eight lane masks held in registers; and a load whose
+// address is the slice's (wave-uniform) start plus a 32-bit lane offset (slots that are not in the row read the slice's
+// first chunk and are never used)
+struct SlotCount {
+  int lane, nch;
+  __device__ __forceinline__ bool operator[](int j) const { return lane + kWave * j < nch; }
+};
+__device__ __forceinline__ void fused_slice(const FusedArgs& a, int q, int lane, int& r, int& sl, SlotCount& ok) {
+  const bool active = q < a.slices;
+  r = active ? q / a.spr : 0;
+  sl = active ? q - r * a.spr : 0;
+  const int left = a.cpr - sl * kFusedSliceChunks;
+  ok.lane = lane;
+  ok.nch = active ? (left < kFusedSliceChunks ? left : kFusedSliceChunks) : 0;
+}
 template <typename T>
+__device__ __forceinline__ void fused_load(const FusedArgs& a, int32_t c, int r, int sl, const SlotCount& ok, int lane,
+                                           vec_t<T, elem<T>::vec> (&xv)[kFusedSlots]) {
+  constexpr int VEC = elem<T>::vec;
+  const int64_t base = ((int64_t)r * a.channels + c) * a.inner + (int64_t)sl * kFusedSliceChunks * VEC;
+  const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + base;
+  // opaque to the optimizer: the eight lane offsets are recomputed at every call (a few VALU instructions) instead of
+  // being hoisted out of the caller's channel loop into eight more registers
+  asm volatile("" : "+v"(lane));
+#pragma unroll
+  for (int j = 0; j < kFusedSlots; ++j)
+    xv[j] = load_vec<T, VEC, true>(xp + (lane + kWave * j < ok.nch ? (uint32_t)(lane + kWave * j) * VEC : 0u));
+}
+
+// ... and its maximum |x| key (this lane's)
+template <typename T, typename Ok>
 __device__ __forceinline__ uint32_t fused_key(const FusedArgs& a, const vec_t<T, elem<T>::vec> (&xv)[kFusedSlots],
-                                              const bool (&ok)[kFusedSlots]) {
+                                              const Ok& ok) {
   uint32_t m = 0;
 #pragma unroll
   for (int j = 0; j < kFusedSlots; ++j) {
@@ -412,11 +442,30 @@ __device__ __forceinline__ uint32_t fused_key(const FusedArgs& a, const vec_t<T,
   }
   return m;
 }
+// (SlotCount, float32: a select per slot instead of a branch -- what keeps the cluster kernel within 64 registers;
+// the 16-bit types are within them with the branches above and far beyond with the selects)
+template <typename T, std::enable_if_t<sizeof(T) == 4, int> = 0>
+__device__ __forceinline__ uint32_t fused_key(const FusedArgs& a, const vec_t<T, elem<T>::vec> (&xv)[kFusedSlots],
+                                              const SlotCount& ok) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int j = 0; j < kFusedSlots; ++j) {
+    uint32_t mj = 0;
+#pragma unroll
+    for (int k = 0; k < elem<T>::vec; ++k) {
+      const uint32_t b = a.pre_relu ? pre_abs_bits<T, true>(xv[j].v[k]) : pre_abs_bits<T, false>(xv[j].v[k]);
+      mj = b > mj ? b : mj;
+    }
+    mj = ok[j] ? mj : 0u;
+    m = mj > m ? mj : m;
+  }
+  return m;
+}
 
 // phase 2 of a channel: quantize what the registers still hold with the scale s
-template <typename T, int RM>
+template <typename T, int RM, typename Ok>
 __device__ __forceinline__ void fused_apply(const FusedArgs& a, int32_t c, int r, int sl,
-                                            const vec_t<T, elem<T>::vec> (&xv)[kFusedSlots], const bool (&ok)[kFusedSlots],
+                                            const vec_t<T, elem<T>::vec> (&xv)[kFusedSlots], const Ok& ok,
                                             float s, float qmin, float qmax, int lane) {
   constexpr int VEC = elem<T>::vec;
   const int64_t base = ((int64_t)r * a.channels + c) * a.inner + (int64_t)sl * kFusedSliceChunks * VEC;
@@ -527,41 +576,40 @@ __global__ __launch_bounds__(kFusedMaxWaves * kWave) void fused_list_fakequant_k
 // statistic + quantizer in ONE kernel, channels held by a CLUSTER of workgroups
 // ------------------------------------------------------------------------------------------------
 // A channel that does not fit one workgroup's registers ([256,512,56,56] bf16: 1.53 MiB) is held by `members`
-// workgroups at once, one slice (fused_slice) per wave, so x is still read once.  The members agree on the channel's
-// maximum through one 32-bit word each: every member folds its key in LDS, its wave 0 publishes the key (tagged, one
-// agent-scope store: the word is the data and its own flag, so no release fence; cdna_hip_programming §6 Guideline 16
-// R2) and then sweeps the cluster's words with one relaxed agent-scope load per lane (one member per lane, s_sleep
-// between passes) while the other waves wait at the barrier -- and every wave already has the NEXT channel's loads in
-// flight.  A persistent grid of clusters walks the channels: cluster k takes k, k + nclusters, ...
+// workgroups of 16 waves at once, one slice (fused_slice) per wave, so x is still read once.  The members agree on the
+// channel's maximum through one 32-bit word each: every member folds its key in LDS, its wave 0 publishes the key
+// (tagged, one agent-scope store: the word is the data and its own flag, so no release fence; cdna_hip_programming §6
+// Guideline 16 R2) and then sweeps the cluster's words with one relaxed agent-scope load per lane (one member per lane,
+// s_sleep between passes) while the other waves wait at the barrier.
+//
+// The kernel needs at most 64 VGPRs, so TWO 1024-thread workgroups are resident per CU: while one sweeps and quantizes,
+// the other one loads, which is where the overlap of loads, exchange and stores comes from (an earlier form kept a second
+// register set with the next channel's loads in flight in ONE workgroup per CU: 109 VGPRs, slower on every measured
+// shape, removed; profiles/cluster_fwd.md).  Two walks over the channels, chosen by cluster_plan through nclusters:
+//   walking   a persistent grid of (resident workgroups / members) clusters; cluster k takes channels k, k + nclusters, ...
+//   one-shot  nclusters = channels: a grid of channels x members workgroups, each handles one channel and exits, and a
+//             slot refills the moment a workgroup retires.
+// One-shot placement: members of a cluster have consecutive block ids, and the dispatcher starts the blocks of an XCD
+// in order, so every member of the lowest unfinished cluster is resident or next in its XCD's queue, and every
+// workgroup resident ahead of it belongs to a lower cluster and finishes without it.  HIP does not promise that order:
+// it is relied on for speed only.  If it fails, the budget below ends the wait, the fallback gives the same bits, and
+// every workgroup still terminates.  No cooperative launch (+15-19 us per call), no wait without a bound.
 //
 // Never an unbounded wait: the sweep has a budget on the constant-rate clock (s_memrealtime, 100 MHz); when it runs
 // out (partners not resident, or the test bit BVQ_CLUSTER_FORCE_FALLBACK) the workgroup reads every row of the channel
-// itself.  A max is exact and order-independent, so that gives the same bits; the workgroup has already published, so
-// its partners still finish.
+// itself (cluster_fallback_key).  A max is exact and order-independent, so that gives the same bits; the workgroup has
+// already published, so its partners still finish.
 //
 // Arrival words (zero on entry, handed back as zeros): key[c * members + i] for member i of channel c, then dep[c]:
 // every member adds one to dep[c] once it has its maximum (after its sweep's loads returned, or, on the fallback, after
 // its own key store has been written through: s_waitcnt vmcnt(0)); the member whose add completes the count knows no
 // partner still reads channel c's words and zeroes them.  Member 0 writes the statistic, scale and running statistic
 // (absmax_epilogue: the bits of bvq_absmax_scale_onepass).
-// (profiles/cluster_fwd.md, [256,512,56,56] bf16: 16 waves 0.352 ms, 8 waves 0.363; without the prefetch 0.409 at
-//  16 waves per CU, 0.365 at 24 -- 110 VGPRs with it, 73 without)
-#ifndef BVQ_CLUSTER_WAVES
-#define BVQ_CLUSTER_WAVES 16  // waves per workgroup: 16 workgroups per headline channel
-#endif
-#ifndef BVQ_CLUSTER_WAVES_PER_CU
-#define BVQ_CLUSTER_WAVES_PER_CU 16  // resident waves per CU the grid is sized for (4 per SIMD: <= 128 VGPRs)
-#endif
-#ifndef BVQ_CLUSTER_PREFETCH
-#define BVQ_CLUSTER_PREFETCH 1  // the next channel's loads are issued before the sweep for this one
-#endif
-constexpr int kClusterWaves = BVQ_CLUSTER_WAVES;
-constexpr int kClusterWavesPerCu = BVQ_CLUSTER_WAVES_PER_CU;
-constexpr bool kClusterPrefetch = BVQ_CLUSTER_PREFETCH != 0;
+constexpr int kClusterWaves = 16;                   // waves per workgroup: one member is 16 slices and one key word
 constexpr int kClusterMaxMembers = kWave;           // one sweeping lane per member
 constexpr uint32_t kClusterTag = 0x80000000u;       // abs keys never have the top bit set
 constexpr uint64_t kClusterBudgetTicks = 200000;    // 2 ms of s_memrealtime (100 MHz) before the fallback
-static_assert(kClusterWaves >= 1 && kClusterWaves * kWave <= 1024, "BVQ_CLUSTER_WAVES");
+enum { kClusterAuto = 0, kClusterWalk = 1, kClusterOneShot = 2 };  // the `form` of bvq_absmax_fakequant_cluster_form
 
 struct ClusterArgs {
   FusedArgs f;        // the tensor (f.stat_out / f.scale_out unused: the epilogue writes the outputs)
@@ -572,10 +620,73 @@ struct ClusterArgs {
   uint32_t* dep;      // [channels]
   uint32_t* fallbacks;  // nullable: fallbacks taken
   int32_t members, nclusters, force_fallback;
+#ifdef BVQ_CLUSTER_STAMPS
+  uint64_t* stamps;   // nullable: [channels][members][kClusterStamps] s_memrealtime ticks (developer builds only)
+#endif
 };
 
+// BVQ_CLUSTER_STAMPS (developer builds, never the product library): wave 0 of every workgroup reads the constant-rate
+// clock at the start of a round and at five points of it, and writes the six values with ordinary vector stores at the
+// round's end (tools/cluster_phases.py turns them into per-phase medians)
+constexpr int kClusterStamps = 6;  // round start | loads landed | key published | sweep done | quantizer done, stores issued | words handed back
+#ifdef BVQ_CLUSTER_STAMPS
+#define BVQ_CLUSTER_STAMP(k) \
+  do {                       \
+    if (wave == 0) tk[k] = __builtin_amdgcn_s_memrealtime(); \
+  } while (0)
+#else
+#define BVQ_CLUSTER_STAMP(k) \
+  do {                       \
+  } while (0)
+#endif
+
+// wave_max_u32 of a whole wave without the six lane-index registers of its ds_bpermute form (the kernel has none
+// to spare): four DPP steps leave every row of 16 lanes with its maximum, four lane reads fold the rows
+__device__ __forceinline__ uint32_t cluster_wave_max(uint32_t v) {
+#define BVQ_DPP_MAX(ctrl)                                                                       \
+  do {                                                                                          \
+    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, 0xf, 0xf, false); \
+    v = o > v ? o : v;                                                                          \
+  } while (0)
+  BVQ_DPP_MAX(0xB1);   // quad_perm:[1,0,3,2]
+  BVQ_DPP_MAX(0x4E);   // quad_perm:[2,3,0,1]
+  BVQ_DPP_MAX(0x141);  // row_half_mirror
+  BVQ_DPP_MAX(0x140);  // row_mirror
+#undef BVQ_DPP_MAX
+  const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), b = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
+  const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), d = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+  const uint32_t ab = a > b ? a : b, cd = c > d ? c : d;
+  return ab > cd ? ab : cd;
+}
+
+// The fallback: the maximum |x| key of every row of channel c, read by this workgroup alone, one chunk per lane at a
+// time.  Cold, and written so that it needs a handful of registers next to the channel slice the caller still holds.
+template <typename T>
+__device__ __forceinline__ uint32_t cluster_fallback_key(const FusedArgs& a, int32_t c, int wave, int lane) {
+  constexpr int VEC = elem<T>::vec;
+  uint32_t fm = 0;
+  for (int q = wave; q < a.slices; q += kClusterWaves) {  // (wave-uniform)
+    const int fr = q / a.spr, fsl = q - fr * a.spr;
+    const int left = a.cpr - fsl * kFusedSliceChunks;
+    const int nch = left < kFusedSliceChunks ? left : kFusedSliceChunks;
+    const T* xp = reinterpret_cast<const T*>(a.x) + ((int64_t)fr * a.channels + c) * a.inner +
+                  (int64_t)fsl * kFusedSliceChunks * VEC;
+#pragma clang loop unroll(disable)
+    for (int i = lane; i < nch; i += kWave) {
+      const vec_t<T, VEC> u = load_vec<T, VEC, false>(xp + (int64_t)i * VEC);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const uint32_t b = a.pre_relu ? pre_abs_bits<T, true>(u.v[k]) : pre_abs_bits<T, false>(u.v[k]);
+        fm = b > fm ? b : fm;
+      }
+    }
+  }
+  return cluster_wave_max(fm);
+}
+
+// (the second launch bound is waves per SIMD: 8 = two workgroups of 16 waves per CU, at most 64 VGPRs)
 template <typename T, int RM>
-__global__ __launch_bounds__(kClusterWaves * kWave, kClusterWavesPerCu / 4) void cluster_absmax_fakequant_kernel(ClusterArgs ca) {
+__global__ __launch_bounds__(kClusterWaves * kWave, 8) void cluster_absmax_fakequant_kernel(ClusterArgs ca) {
   constexpr int VEC = elem<T>::vec;
   __shared__ uint32_t sh_max[kClusterWaves];
   __shared__ uint32_t sh_stat, sh_ok;
@@ -585,16 +696,21 @@ __global__ __launch_bounds__(kClusterWaves * kWave, kClusterWavesPerCu / 4) void
   const int32_t members = ca.members;
   const int32_t member = (int32_t)blockIdx.x % members, cluster = (int32_t)blockIdx.x / members;
   int r, sl;
-  bool ok[kFusedSlots];
+  SlotCount ok;
   fused_slice(a, member * kClusterWaves + wave, lane, r, sl, ok);
   const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
   int32_t c = cluster;
   if (c >= a.channels) return;  // (workgroup-uniform)
+#ifdef BVQ_CLUSTER_STAMPS
+  uint64_t tk[kClusterStamps] = {};
+#endif
+  BVQ_CLUSTER_STAMP(0);
   vec_t<T, VEC> xv[kFusedSlots];
   fused_load<T>(a, c, r, sl, ok, lane, xv);
   for (; c < a.channels; c += ca.nclusters) {
-    const uint32_t m = wave_max_u32(fused_key<T>(a, xv, ok));
+    const uint32_t m = cluster_wave_max(fused_key<T>(a, xv, ok));
     if (lane == 0) sh_max[wave] = m;
+    BVQ_CLUSTER_STAMP(1);
     __syncthreads();
     uint32_t* const keys = ca.key + (int64_t)c * members;
     if (wave == 0) {
@@ -602,9 +718,8 @@ __global__ __launch_bounds__(kClusterWaves * kWave, kClusterWavesPerCu / 4) void
       for (int w = 0; w < kClusterWaves; ++w) bm = sh_max[w] > bm ? sh_max[w] : bm;
       if (lane == 0) __hip_atomic_store(keys + member, bm | kClusterTag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    BVQ_CLUSTER_STAMP(2);
     const int32_t cn = c + ca.nclusters;
-    vec_t<T, VEC> xn[kFusedSlots];
-    if (kClusterPrefetch && cn < a.channels) fused_load<T>(a, cn, r, sl, ok, lane, xn);
     if (wave == 0) {
       bool done = false;
       uint32_t v = 0;
@@ -620,32 +735,15 @@ __global__ __launch_bounds__(kClusterWaves * kWave, kClusterWavesPerCu / 4) void
           __builtin_amdgcn_s_sleep(2);
         }
       }
-      v = wave_max_u32(v) & ~kClusterTag;
+      v = cluster_wave_max(v) & ~kClusterTag;
       if (lane == 0) {
         sh_stat = v;
         sh_ok = done ? 1u : 0u;
       }
     }
     __syncthreads();
-    if (!sh_ok) {  // (workgroup-uniform) the fallback: every row of the channel, one chunk at a time
-      uint32_t fm = 0;
-      for (int q = wave; q < a.slices; q += kClusterWaves) {
-        int fr, fsl;
-        bool fok[kFusedSlots];
-        fused_slice(a, q, lane, fr, fsl, fok);
-        const T* xp = reinterpret_cast<const T*>(a.x) + ((int64_t)fr * a.channels + c) * a.inner +
-                      (int64_t)fsl * kFusedSliceChunks * VEC;
-        for (int j = 0; j < kFusedSlots; ++j) {
-          if (!fok[j]) break;
-          const vec_t<T, VEC> u = load_vec<T, VEC, false>(xp + (int64_t)(lane + kWave * j) * VEC);
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) {
-            const uint32_t b = a.pre_relu ? pre_abs_bits<T, true>(u.v[k]) : pre_abs_bits<T, false>(u.v[k]);
-            fm = b > fm ? b : fm;
-          }
-        }
-      }
-      fm = wave_max_u32(fm);
+    if (!sh_ok) {  // (workgroup-uniform) the fallback
+      const uint32_t fm = cluster_fallback_key<T>(a, c, wave, lane);
       if (lane == 0) sh_max[wave] = fm;
       __syncthreads();
       if (threadIdx.x == 0) {
@@ -656,6 +754,7 @@ __global__ __launch_bounds__(kClusterWaves * kWave, kClusterWavesPerCu / 4) void
       }
       __syncthreads();
     }
+    BVQ_CLUSTER_STAMP(3);
     const uint32_t key = sh_stat;
     // departure: this member no longer reads channel c's words (on the fallback its key store is drained first, so
     // that the zeroing below cannot overtake it)
@@ -669,7 +768,27 @@ __global__ __launch_bounds__(kClusterWaves * kWave, kClusterWavesPerCu / 4) void
     float stat;
     const float s = scale_from_key<T>(key, a.use_min, a.min_val, a.int_threshold, a.scale_dtype, stat);
     if (member == 0 && threadIdx.x == 0) absmax_epilogue(ca.stat_out, ca.in_dtype, ca.in_dtype, ca.ep, c, key);
-    fused_apply<T, RM>(a, c, r, sl, xv, ok, s, qmin, qmax, lane);
+    if constexpr (RM == kAnyRM && elem<T>::id == BVQ_BF16) {
+      // bfloat16: the rounding mode chosen once per round, not inside every pair of elements.  Straight-line
+      // quantizers are what keeps this instance within 64 registers (float16 and float32 are within them with the
+      // switch inside, and float16 is not with it here: tools/kernel_resources.py)
+      switch (a.round_mode) {
+#define BVQ_CLUSTER_APPLY(M)                                              \
+  case M:                                                                 \
+    fused_apply<T, M>(a, c, r, sl, xv, ok, s, qmin, qmax, lane); \
+    break
+        BVQ_CLUSTER_APPLY(BVQ_ROUND);
+        BVQ_CLUSTER_APPLY(BVQ_FLOOR);
+        BVQ_CLUSTER_APPLY(BVQ_CEIL);
+        BVQ_CLUSTER_APPLY(BVQ_ROUND_TO_ZERO);
+        default:
+          fused_apply<T, BVQ_DPU_ROUND>(a, c, r, sl, xv, ok, s, qmin, qmax, lane);
+#undef BVQ_CLUSTER_APPLY
+      }
+    } else {
+      fused_apply<T, RM>(a, c, r, sl, xv, ok, s, qmin, qmax, lane);
+    }
+    BVQ_CLUSTER_STAMP(4);
     if (wave == 0) {
       before = __builtin_amdgcn_readfirstlane(before);
       if (before + 1 == (uint32_t)members) {  // the last departure hands the channel's words back as zeros
@@ -677,16 +796,20 @@ __global__ __launch_bounds__(kClusterWaves * kWave, kClusterWavesPerCu / 4) void
         if (lane == 0) __hip_atomic_store(ca.dep + c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
-    if (cn < a.channels) {
-      if constexpr (kClusterPrefetch) {
+#ifdef BVQ_CLUSTER_STAMPS
+    BVQ_CLUSTER_STAMP(5);
+    if (ca.stamps && wave == 0 && lane < kClusterStamps) {
+      uint64_t t = tk[0];
 #pragma unroll
-        for (int j = 0; j < kFusedSlots; ++j) xv[j] = xn[j];
-      } else {
-        fused_load<T>(a, cn, r, sl, ok, lane, xv);
-      }
+      for (int k = 1; k < kClusterStamps; ++k) t = lane == k ? tk[k] : t;
+      ca.stamps[((int64_t)c * members + member) * kClusterStamps + lane] = t;
     }
+    if (wave == 0) tk[0] = tk[5];  // the next round starts where this one ended
+#endif
+    if (cn < a.channels) fused_load<T>(a, cn, r, sl, ok, lane, xv);
   }
 }
+#undef BVQ_CLUSTER_STAMP
 
 }  // namespace bvq
 
@@ -907,7 +1030,8 @@ struct ClusterPlan {
   int64_t words;  // arrival words
 };
 
-static bool cluster_plan(const bvq_quant_desc* d, const void* x, const void* y, ClusterPlan& cp) {
+// form: kClusterAuto, or the form a developer / test asks for (bvq_absmax_fakequant_cluster_form)
+static bool cluster_plan(const bvq_quant_desc* d, const void* x, const void* y, ClusterPlan& cp, int form = kClusterAuto) {
   if (!(d->scale_per_channel && d->channels > 1) || d->channels >= ((int64_t)1 << 31)) return false;
   const FusedShape f = fused_shape(d, x, y);
   if (!f.ok) return false;
@@ -925,10 +1049,21 @@ static bool cluster_plan(const bvq_quant_desc* d, const void* x, const void* y, 
   cp.p.slices = (int32_t)slices;
   cp.p.waves = kClusterWaves;
   cp.members = (int32_t)members;
-  // persistent grid: whole clusters within the resident workgroups (kClusterWavesPerCu waves per CU)
-  const int64_t resident = (int64_t)num_cus() * kClusterWavesPerCu / kClusterWaves;
-  int64_t nc = resident / members;
+  // persistent grid: whole clusters within the resident workgroups (two per CU)
+  int64_t nc = (int64_t)num_cus() * 2 / members;
   nc = nc < 1 ? 1 : (nc > f.channels ? f.channels : nc);
+  // The rule, from tools/cluster_ab.py --forms walk,oneshot (profiles/cluster_fwd.md, rows of 392 chunks): up to 4
+  // rounds per walking cluster the walk is level or ahead (2 rounds: 6 %), from 8 rounds on the one-shot grid is level
+  // or ahead (8 rounds: 0-5 %, 16 rounds, the headline: 8 %).  Rows of 98 chunks, which leave four fifths of a slice
+  // empty, keep the walk (6-9 % ahead at 16 rounds: a workgroup's start is not paid back by 25 KB of work); the
+  // boundary between the two measured row lengths is put at half a slice.
+  if (form == kClusterAuto) {
+    const int64_t row_chunks = cpr < kFusedSliceChunks ? cpr : kFusedSliceChunks;
+    const bool oneshot = f.channels > 4 * nc && 2 * row_chunks >= kFusedSliceChunks;
+    form = oneshot ? kClusterOneShot : kClusterWalk;
+  }
+  if (form == kClusterOneShot && f.channels * members > ((int64_t)1 << 30)) form = kClusterWalk;  // grid size
+  if (form == kClusterOneShot) nc = f.channels;  // a cluster per channel
   cp.nclusters = (int32_t)nc;
   cp.p.nblocks = (int32_t)(nc * members);
   cp.words = f.channels * (members + 1);
@@ -941,11 +1076,10 @@ extern "C" int64_t bvq_absmax_fakequant_cluster_supported(const bvq_quant_desc* 
   return cluster_plan(d, x, y, cp) ? cp.words : 0;
 }
 
-extern "C" int bvq_absmax_fakequant_cluster(const bvq_quant_desc* d, const void* x, double min_val, int use_min,
-                                            double int_threshold, void* stat_out, void* scale_out, int run_dtype,
-                                            void* running, double momentum, int first_batch, void* y, uint32_t* arrive,
-                                            int64_t arrive_words, int flags, uint32_t* fallbacks,
-                                            bvq_stream_t stream) {
+static int cluster_impl(const bvq_quant_desc* d, const void* x, double min_val, int use_min, double int_threshold,
+                        void* stat_out, void* scale_out, int run_dtype, void* running, double momentum, int first_batch,
+                        void* y, uint32_t* arrive, int64_t arrive_words, int flags, uint32_t* fallbacks, int form,
+                        uint64_t* stamps, bvq_stream_t stream) {
   int rc = validate(d);
   if (rc) return rc;
   if (!x || !y || !stat_out || !scale_out || !arrive) {
@@ -958,8 +1092,18 @@ extern "C" int bvq_absmax_fakequant_cluster(const bvq_quant_desc* d, const void*
     set_error("bvq_absmax_fakequant_cluster: bad argument");
     return BVQ_ERR_INVALID;
   }
+  if (form < kClusterAuto || form > kClusterOneShot) {
+    set_error("bvq_absmax_fakequant_cluster: form %d", form);
+    return BVQ_ERR_INVALID;
+  }
+#ifndef BVQ_CLUSTER_STAMPS
+  if (stamps) {
+    set_error("bvq_absmax_fakequant_cluster: this library was built without BVQ_CLUSTER_STAMPS");
+    return BVQ_ERR_UNSUPPORTED;
+  }
+#endif
   ClusterPlan cp;
-  if (!cluster_plan(d, x, y, cp)) {
+  if (!cluster_plan(d, x, y, cp, form)) {
     set_error("bvq_absmax_fakequant_cluster: shape / layout not covered (bvq_absmax_fakequant_cluster_supported)");
     return BVQ_ERR_UNSUPPORTED;
   }
@@ -991,11 +1135,33 @@ extern "C" int bvq_absmax_fakequant_cluster(const bvq_quant_desc* d, const void*
   ca.members = cp.members;
   ca.nclusters = cp.nclusters;
   ca.force_fallback = (flags & BVQ_CLUSTER_FORCE_FALLBACK) ? 1 : 0;
+#ifdef BVQ_CLUSTER_STAMPS
+  ca.stamps = stamps;
+#endif
   hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)cp.p.nblocks), block(kClusterWaves * kWave);
   rc = with_cols_variant(d, false, [&](auto t, auto rm, auto) {
-    cluster_absmax_fakequant_kernel<typename decltype(t)::type, rm><<<dim3((unsigned)cp.p.nblocks), dim3(kClusterWaves * kWave), 0, st>>>(ca);
+    cluster_absmax_fakequant_kernel<typename decltype(t)::type, rm><<<grid, block, 0, st>>>(ca);
   });
   return rc ? rc : check_launch("bvq_absmax_fakequant_cluster");
+}
+
+extern "C" int bvq_absmax_fakequant_cluster(const bvq_quant_desc* d, const void* x, double min_val, int use_min,
+                                            double int_threshold, void* stat_out, void* scale_out, int run_dtype,
+                                            void* running, double momentum, int first_batch, void* y, uint32_t* arrive,
+                                            int64_t arrive_words, int flags, uint32_t* fallbacks,
+                                            bvq_stream_t stream) {
+  return cluster_impl(d, x, min_val, use_min, int_threshold, stat_out, scale_out, run_dtype, running, momentum,
+                      first_batch, y, arrive, arrive_words, flags, fallbacks, kClusterAuto, nullptr, stream);
+}
+
+extern "C" int bvq_absmax_fakequant_cluster_form(const bvq_quant_desc* d, const void* x, double min_val, int use_min,
+                                                 double int_threshold, void* stat_out, void* scale_out, int run_dtype,
+                                                 void* running, double momentum, int first_batch, void* y,
+                                                 uint32_t* arrive, int64_t arrive_words, int flags, uint32_t* fallbacks,
+                                                 int form, uint64_t* stamps, bvq_stream_t stream) {
+  return cluster_impl(d, x, min_val, use_min, int_threshold, stat_out, scale_out, run_dtype, running, momentum,
+                      first_batch, y, arrive, arrive_words, flags, fallbacks, form, stamps, stream);
 }
 
 namespace bvq {

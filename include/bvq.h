@@ -480,7 +480,7 @@ int bvq_stats_fakequant_fwd(const bvq_quant_desc* desc, const void* x, double mi
 
 /* The same AbsMax -> scale -> IntQuant in ONE launch (x read once) for channels that do NOT fit one workgroup: each
  * channel is held in registers by a CLUSTER of workgroups, which agree on its maximum through one arrival word each;
- * a persistent grid of clusters walks the channels.  stat_out [channels] in x's dtype, scale_out [channels] in
+ * a persistent grid of clusters walks the channels, or (many channels per cluster) every channel has its own.  stat_out [channels] in x's dtype, scale_out [channels] in
  * desc->scale_dtype, running (nullable, [channels] of run_dtype: the running average of bvq_absmax_scale_onepass) and
  * y are the bits of bvq_absmax_scale_onepass + bvq_fakequant_fwd on the same descriptor.  A workgroup never waits
  * without a bound: past a time budget it reads the whole channel itself (same bits; `fallbacks`, nullable, counts
@@ -496,6 +496,16 @@ int bvq_absmax_fakequant_cluster(const bvq_quant_desc* desc, const void* x, doub
                                  double int_threshold, void* stat_out, void* scale_out, int run_dtype, void* running,
                                  double momentum, int first_batch, void* y, uint32_t* arrive, int64_t arrive_words,
                                  int flags, uint32_t* fallbacks, bvq_stream_t stream);
+/* Developer / test entry: the same call with the form of the kernel named instead of chosen per shape.
+ * form: 0 the library's choice for the shape (= bvq_absmax_fakequant_cluster), 1 a persistent grid of clusters
+ * walking the channels, 2 one-shot: one workgroup per (channel, member).  Both forms give the same bits and use the
+ * same arrival words.  stamps: null, except with a library built with
+ * -DBVQ_CLUSTER_STAMPS (tools/cluster_phases.py): [channels][members][6] clock ticks of every round. */
+int bvq_absmax_fakequant_cluster_form(const bvq_quant_desc* desc, const void* x, double min_val, int use_min,
+                                      double int_threshold, void* stat_out, void* scale_out, int run_dtype,
+                                      void* running, double momentum, int first_batch, void* y, uint32_t* arrive,
+                                      int64_t arrive_words, int flags, uint32_t* fallbacks, int form, uint64_t* stamps,
+                                      bvq_stream_t stream);
 
 /* bytes of scratch bvq_fakequant_bwd needs */
 int64_t bvq_fakequant_bwd_workspace_bytes(const bvq_quant_desc* desc);
