@@ -49,7 +49,7 @@ EXPORTS = (
     'bvq_shard_unpack_deposit', 'bvq_absmax_list_supported', 'bvq_absmax_scale_list', 'bvq_weight_list_supported',
     'bvq_weight_quant_list_fwd', 'bvq_weight_quant_list_bwd_workspace_bytes', 'bvq_weight_quant_list_bwd',
     'bvq_absmax_fakequant_cluster_supported', 'bvq_absmax_fakequant_cluster', 'bvq_absmax_fakequant_cluster_form',
-    'bvq_selftest_pre_op')
+    'bvq_selftest_pre_op', 'bvq_group_quant_supported', 'bvq_group_quant_fwd', 'bvq_group_quant_bwd')
 
 
 class QuantDesc(ctypes.Structure):
@@ -172,6 +172,9 @@ def _load(path=None, strict=True):
                                                vp, i64, i32, vp, vp]),
         'bvq_absmax_fakequant_cluster_form': (i32, [ctypes.POINTER(QuantDesc), vp, dbl, i32, dbl, vp, vp, i32, vp, dbl, i32,
                                                     vp, vp, i64, i32, vp, i32, vp, vp]),
+        'bvq_group_quant_supported': (i32, [ctypes.POINTER(QuantDesc), vp]),
+        'bvq_group_quant_fwd': (i32, [ctypes.POINTER(QuantDesc), vp, dbl, i32, dbl, vp, vp, vp, vp]),
+        'bvq_group_quant_bwd': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, dbl, i32, dbl, vp, vp]),
         'bvq_fakequant_bwd_learned': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, i32, dbl, i32, dbl, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
@@ -451,6 +454,47 @@ def stats_fakequant_fwd(desc, x, min_val, int_threshold, scale_dtype):
         if _timer is not None:
             _timer.after('bvq_stats_fakequant_fwd')
     return stat, scale, y
+
+
+def group_quant_supported(desc, x):
+    """the group-wise kernels cover this descriptor (outer 1, channels = groups, inner = group size) and tensor"""
+    return bool(lib.bvq_group_quant_supported(ctypes.byref(desc), ptr(x)))
+
+
+def group_quant_fwd(desc, x, min_val, thr_div):
+    """abs-max per group, scale and quantize-dequantize in ONE launch -> (y like x, scale [groups], stat [groups])"""
+    dev = require_device(x)
+    assert x.is_contiguous()
+    groups = int(desc.channels)
+    y = torch.empty_like(x)
+    scale = torch.empty(groups, dtype=x.dtype, device=dev)
+    stat = torch.empty(groups, dtype=x.dtype, device=dev)
+    with _DeviceGuard(dev):
+        if _timer is not None:
+            _timer.before('bvq_group_quant_fwd')
+        check(lib.bvq_group_quant_fwd(ctypes.byref(desc), ptr(x), float(min_val or 0.0), int(bool(min_val)),
+                                      float(thr_div), ptr(y), ptr(scale), ptr(stat), stream_ptr(dev)),
+              'bvq_group_quant_fwd')
+        if _timer is not None:
+            _timer.after('bvq_group_quant_fwd')
+    return y, scale, stat
+
+
+def group_quant_bwd(desc, g, x, scale, stat, gscale, min_val, thr_div):
+    """backward of group_quant_fwd in ONE launch -> dx (the statistic's gradient of every group deposited on the first
+    element attaining it); gscale: None, or the gradient arriving through `scale`, [groups] in x's dtype"""
+    dev = require_device(g, x, scale, stat, gscale)
+    assert g.is_contiguous() and x.is_contiguous() and (gscale is None or gscale.is_contiguous())
+    dx = torch.empty_like(x)
+    with _DeviceGuard(dev):
+        if _timer is not None:
+            _timer.before('bvq_group_quant_bwd')
+        check(lib.bvq_group_quant_bwd(ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(stat), ptr(gscale),
+                                      float(min_val or 0.0), int(bool(min_val)), float(thr_div), ptr(dx),
+                                      stream_ptr(dev)), 'bvq_group_quant_bwd')
+        if _timer is not None:
+            _timer.after('bvq_group_quant_bwd')
+    return dx
 
 
 def absmax_fakequant_cluster(desc, x, min_val, int_threshold, scale_dtype, running=None, momentum=0.0,

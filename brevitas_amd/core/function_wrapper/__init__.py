@@ -17,5 +17,6 @@ Identity, PowerOfTwo, LogTwo, InplaceLogTwo = _misc.Identity, _misc.PowerOfTwo, 
 # statistic input views
 PermuteDims, StatsInputViewShapeImpl = _shape.PermuteDims, _shape.StatsInputViewShapeImpl
 OverTensorView, OverOutputChannelView = _shape.OverTensorView, _shape.OverOutputChannelView
+OverSubChannelBlockView = _shape.OverSubChannelBlockView
 OverBatchOverTensorView = _shape.OverBatchOverTensorView
 OverBatchOverOutputChannelView = _shape.OverBatchOverOutputChannelView

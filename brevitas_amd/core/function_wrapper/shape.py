@@ -60,6 +60,19 @@ class OverOutputChannelView(torch.nn.Module):
         return dims[0] if rest == sorted(rest) else -1
 
 
+class OverSubChannelBlockView(torch.nn.Module):
+    """[groups, group_size] view of a tensor whose groups are `group_size` consecutive elements in memory order: the
+    statistic's input of a group-wise weight quantizer (one scale per group of each output channel's flattened
+    trailing dimensions)"""
+
+    def __init__(self, group_size: int) -> None:
+        super().__init__()
+        self.bvq_group_size = int(group_size)
+
+    def forward(self, x: torch.Tensor):
+        return x.reshape(-1, self.bvq_group_size)
+
+
 class OverBatchOverTensorView(torch.nn.Module):
 
     def forward(self, x: torch.Tensor):

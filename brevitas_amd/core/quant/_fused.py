@@ -504,6 +504,42 @@ class StatsFakeQuantFn(Function):
         return dx, None, None, None, None, None, None, None, None, None
 
 
+class GroupStatsFakeQuantFn(Function):
+    """Group-wise weights: AbsMax per group of `group_size` consecutive elements -> clamp_min(min_val) -> / int_threshold
+    -> IntQuant with a zero zero-point, x -> (y like x, scale [groups, 1]).  One launch each way (csrc/bvq_group_quant.hip):
+    a group lives in a fraction of one wave, so the statistic, the scale gradient and the arg-max deposit never leave
+    registers.  The caller has checked what the kernels cover (GroupwiseRescalingIntQuant._group_plan)."""
+
+    @staticmethod
+    def forward(ctx, x, group_size, min_val, int_threshold, qmin, qmax, clamp_ste):
+        ctx.set_materialize_grads(False)  # an unused `scale` output must not cost a zero-fill + add
+        code = nat.dtype_code(x.dtype)
+        desc = nat.QuantDesc(1, x.numel() // group_size, group_size, code, code, code, nat.F32, 1, 0, qmin, qmax,
+                             nat.ROUND, scalar_mode(), int(clamp_ste), nat.OUT_DEQUANT, nat.PRE_NONE)
+        # a dimensioned threshold keeps its dtype: the 0-dim float32 int_threshold is converted to it
+        thr_div = _as_dtype_value(int_threshold, x.dtype)
+        y, scale, stat = nat.group_quant_fwd(desc, x, min_val, thr_div)
+        ctx.desc, ctx.min_val, ctx.thr_div = desc, min_val, thr_div
+        ctx.save_for_backward(x, scale, stat)
+        return y, scale.view(-1, 1)
+
+    @staticmethod
+    def backward(ctx, gy, gscale):
+        x, scale, stat = ctx.saved_tensors
+        if gy is None:  # only `scale` was used downstream
+            if gscale is None:
+                return (None,) * 7
+            gy = torch.zeros_like(x)
+        else:
+            gy = gy.to(x.dtype).contiguous()
+        if gscale is not None:
+            gscale = gscale.to(x.dtype).reshape(-1).contiguous()
+        if gy.data_ptr() % 16 != 0:
+            gy = gy.clone()
+        dx = nat.group_quant_bwd(ctx.desc, gy, x, scale, stat, gscale, ctx.min_val, ctx.thr_div)
+        return (dx,) + (None,) * 6
+
+
 class StatsGraphFakeQuantFn(Function):
     """AbsMax statistic -> ANY scale-shaped map (`post`: a _StatsScaling with affine rescaling, a power-of-two
     restriction, ...) -> / int_threshold -> IntQuant, zero zero-point (B/core/scaling/runtime.py:19-72,

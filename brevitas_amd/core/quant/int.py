@@ -19,7 +19,7 @@ from torch import Tensor
 from torch.nn import Module
 
 import brevitas_amd.config as config
-from brevitas_amd.core.function_wrapper.shape import OverOutputChannelView, OverTensorView
+from brevitas_amd.core.function_wrapper.shape import OverOutputChannelView, OverSubChannelBlockView, OverTensorView
 from brevitas_amd.core.quant import _fused
 from brevitas_amd.core.quant.delay import _NoDelay
 from brevitas_amd.core.quant.int_base import IntQuant
@@ -356,6 +356,106 @@ class RescalingIntQuant(torch.nn.Module):
         zero_point = self.zero_point_impl(x, scale, bit_width)
         y = self.int_quant(scale, zero_point, bit_width, x)
         return y, scale, zero_point, bit_width
+
+
+class GroupwiseRescalingIntQuant(RescalingIntQuant):
+    """RescalingIntQuant with one scale per `group_size` consecutive elements of each output channel's flattened
+    trailing dimensions: the sub-modules (same attribute names, same state-dict keys, nothing new) applied to the input
+    regrouped as [groups, group_size], y reshaped back to x's shape and the scale to (x.shape[0], K / group_size, 1),
+    K = x.numel() / x.shape[0].
+
+    One recognised graph runs as one kernel each way (_fused.GroupStatsFakeQuantFn): the AbsMax statistic of exactly the
+    tracked weight over OverSubChannelBlockView(group_size), a plain lower bound, IntQuant with half-even rounding and
+    a zero zero-point, on a contiguous 16-byte-aligned device tensor with a group size the kernels cover.  Everything
+    else takes the generic route below.  Inside `with WeightQuantGroup(...)` such a quantizer keeps its own route."""
+
+    def __init__(self, int_quant: Module, scaling_impl: Module, int_scaling_impl: Module, zero_point_impl: Module,
+                 bit_width_impl: Module, group_size: int):
+        super().__init__(int_quant, scaling_impl, int_scaling_impl, zero_point_impl, bit_width_impl)
+        if int(group_size) < 1:
+            raise ValueError('group_size must be positive, got %r' % (group_size,))
+        self.group_size = int(group_size)
+
+    def _group_template(self, bit_width: Tensor):
+        """structural part of the fused-graph recognition, cached like RescalingIntQuant._stats_template"""
+        iq, sc = self.int_quant, self.scaling_impl
+        bw = getattr(bit_width, 'bvq_host_value', None)
+        key = (config.FUSED_PATHS, self.group_size, id(iq), id(sc), id(self.zero_point_impl),
+               id(self.int_scaling_impl), bw, id(getattr(iq, 'float_to_int_impl', None)),
+               id(getattr(iq, 'tensor_clamp_impl', None)),
+               id(getattr(getattr(iq, 'delay_wrapper', None), 'delay_impl', None)))
+        cached = self.__dict__.get('_bvq_group_template')
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        tmpl = self._build_group_template(bw)
+        self.__dict__['_bvq_group_template'] = (key, tmpl)
+        return tmpl
+
+    def _build_group_template(self, bw):
+        if not config.FUSED_PATHS or bw is None:
+            return None
+        iq, sc = self.int_quant, self.scaling_impl
+        if type(iq) is not IntQuant or not isinstance(iq.delay_wrapper.delay_impl, _NoDelay):
+            return None
+        if getattr(iq.float_to_int_impl, 'bvq_round_mode', None) != nat.ROUND or \
+                getattr(iq.tensor_clamp_impl, 'bvq_clamp_ste', None) is None:
+            return None
+        if type(self.zero_point_impl) is not ZeroZeroPoint or type(self.int_scaling_impl) is not IntScaling:
+            return None
+        if type(sc) is not StatsFromParameterScaling:
+            return None
+        pls = sc.parameter_list_stats
+        view, stats = pls.first_tracked_param.view_shape_impl, pls.stats
+        if pls.extra_tracked_params_list is not None or type(view) is not OverSubChannelBlockView or \
+                view.bvq_group_size != self.group_size:
+            return None
+        if type(stats.stats_impl) is not AbsMax or stats.stats_impl.stats_reduce_dim not in (1, -1):
+            return None
+        min_val = sc.stats_scaling_impl.bvq_plain_min_val()
+        if min_val is None or self.group_size not in (16, 32, 64, 128, 256):
+            return None
+        qmin, qmax = int_range_host(iq.signed, iq.narrow_range, bw)
+        return dict(weight=pls.first_tracked_param.parameter, shape=tuple(stats.stats_output_shape), min_val=min_val,
+                    int_thr=self.int_scaling_impl.host_value(bw), qmin=qmin, qmax=qmax,
+                    clamp_ste=iq.tensor_clamp_impl.bvq_clamp_ste)
+
+    def _group_plan(self, x: Tensor, bit_width: Tensor):
+        """the template if the one-kernel route applies to this input, else None"""
+        if not x.is_cuda or x.dtype not in _fused._FLOATS or not x.is_contiguous() or x.data_ptr() % 16 != 0:
+            return None
+        tmpl = self._group_template(bit_width)
+        if tmpl is None:
+            return None
+        w = tmpl['weight']
+        if not (w is x or (w.data_ptr() == x.data_ptr() and w.shape == x.shape and w.stride() == x.stride()
+                           and w.dtype == x.dtype)):
+            return None  # the statistic is taken of another tensor than the one being quantized
+        if tmpl['shape'] != (x.numel() // self.group_size, 1):
+            return None
+        return tmpl
+
+    def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        g = self.group_size
+        if x.dim() < 2 or x.shape[0] == 0 or (x.numel() // x.shape[0]) % g != 0:
+            raise ValueError('group-wise quantizer: a tensor of shape %s has no whole groups of %d elements per output '
+                             'channel (at least 2 dimensions, numel / shape[0] a multiple of the group size)'
+                             % (tuple(x.shape), g))
+        bit_width = self.msb_clamp_bit_width_impl()
+        tmpl = self._group_plan(x, bit_width)
+        if tmpl is not None:
+            y, scale = _fused.GroupStatsFakeQuantFn.apply(x, g, tmpl['min_val'], tmpl['int_thr'], tmpl['qmin'],
+                                                          tmpl['qmax'], tmpl['clamp_ste'])
+        else:
+            # the existing modules on the regrouped tensor (the reference's own sequence, B/core/quant/int.py:157-163)
+            xg = x.reshape(-1, g)
+            threshold = self.scaling_impl(xg)
+            scale = threshold / self.int_scaling_impl(bit_width)
+            y = self.int_quant(scale, self.zero_point_impl(xg, scale, bit_width), bit_width, xg)
+        scale = scale.reshape(x.shape[0], -1, 1)
+        return y.reshape(x.shape), scale, self.zero_point_impl(x, scale, bit_width), bit_width
+
+    def bvq_forward_pre(self, x: Tensor, pre_op: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        return self.forward(_fused.apply_pre_op(x, pre_op))
 
 
 class PrescaledRestrictIntQuantWithInputBitWidth(torch.nn.Module):

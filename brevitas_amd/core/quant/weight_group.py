@@ -32,7 +32,7 @@ import torch
 from brevitas_amd import _native as nat
 from brevitas_amd.core.quant import _fused
 from brevitas_amd.core.quant import int as _int
-from brevitas_amd.core.quant.int import RescalingIntQuant
+from brevitas_amd.core.quant.int import GroupwiseRescalingIntQuant, RescalingIntQuant
 
 __all__ = ['WeightQuantGroup']
 
@@ -119,7 +119,8 @@ class WeightQuantGroup:
         self._members: List[_Member] = []
         self._names = []
         for m in module.modules():
-            if isinstance(m, RescalingIntQuant):
+            # (a group-wise quantizer is no member: it keeps its own one-kernel route)
+            if isinstance(m, RescalingIntQuant) and not isinstance(m, GroupwiseRescalingIntQuant):
                 tmpl = m._stats_template(m.msb_clamp_bit_width_impl())
                 w = tmpl.get('weight') if tmpl is not None else None
                 self._members.append(_Member(m, owners.get(id(w)) if w is not None else None))

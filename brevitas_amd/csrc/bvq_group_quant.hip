@@ -1,0 +1,419 @@
+// bvq_group_quant.hip -- group-wise weight quantizer: one scale per `group_size` consecutive elements, statistic,
+// scale, quantization, scale gradient and arg-max deposit inside registers, one launch each way.
+//
+// The tensor is walked as a flat stream of 16-byte lane accesses.  A group of g elements occupies
+// L = g * sizeof(T) / 16 ADJACENT lanes of one wave load (2..32 lanes for 16-bit types, 4..64 for float32), and 64 / L
+// groups share a load; L divides 64, so a group never straddles two loads.  Everything a group needs from its other
+// elements -- the abs-max, the two sums of the scale gradient, the first element attaining the abs-max -- is a
+// SEGMENTED butterfly over those L lanes (__shfl_xor with offsets L/2 .. 1: every lane of the segment ends with the
+// same bits, in a fixed order).  No LDS, no atomics, no partials, no workspace, no second launch.
+//   forward   reads x, writes y                (+ 2 * bytes(x) / g for scale and stat)
+//   backward  reads g and x, writes dx once    (+ bytes(x) / g for stat)
+// Results are the bits of the per-channel kernels on the tensor regrouped as [groups, g] (bvq_stats_fakequant_fwd,
+// bvq_fakequant_bwd_stats); only the ORDER in which a group's float32 scale-gradient terms are added differs, which
+// can move the deposited element by a rounding.
+#include "bvq_fakequant_bwd.h"
+#include "bvq_stat_epilogue.h"
+
+namespace bvq {
+
+#ifndef BVQ_GROUP_FWD_DEPTH
+#define BVQ_GROUP_FWD_DEPTH 4  // wave loads of x in flight per wave
+#endif
+#ifndef BVQ_GROUP_BWD_DEPTH
+#define BVQ_GROUP_BWD_DEPTH 2  // wave loads of x and of g in flight per wave
+#endif
+constexpr int kGroupFwdDepth = BVQ_GROUP_FWD_DEPTH;
+constexpr int kGroupBwdDepth = BVQ_GROUP_BWD_DEPTH;
+
+struct GroupArgs {
+  const void* x;
+  const void* g;       // bwd
+  void* y;             // fwd: y, bwd: dx
+  void* scale;         // fwd: [groups] out
+  void* stat;          // fwd: [groups] out, bwd: in
+  const void* gscale;  // bwd, nullable: gradient arriving through the returned scale, [groups]
+  int64_t chunks;      // 16-byte chunks of the tensor = groups * L
+  float qmin, qmax, min_val, thr_div;
+  int32_t use_min, clamp_ste;
+};
+
+template <int L>
+__device__ __forceinline__ uint32_t seg_max_u32(uint32_t v) {
+#pragma unroll
+  for (int off = L / 2; off > 0; off >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)v, off, kWave);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+template <int L>
+__device__ __forceinline__ uint32_t seg_min_u32(uint32_t v) {
+#pragma unroll
+  for (int off = L / 2; off > 0; off >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)v, off, kWave);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+// a + b is commutative, so both partners of every exchange compute the same bits: the sum is the same in every lane
+// of the segment, and from run to run
+template <int L>
+__device__ __forceinline__ float seg_sum(float v) {
+#pragma unroll
+  for (int off = L / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  return v;
+}
+
+// largest |x| key (abs_bits<T>) of one 16-byte chunk: sign-cleared bit patterns, so a NaN wins and propagates
+template <typename T>
+__device__ __forceinline__ uint32_t chunk_key(const vec_t<T, elem<T>::vec>& xv) {
+  constexpr int VEC = elem<T>::vec;
+  if constexpr (sizeof(T) == 2) {
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    const vec_t<uint32_t, VEC / 2> w = __builtin_bit_cast(vec_t<uint32_t, VEC / 2>, xv);
+    u16x2 m2 = {0, 0};
+#pragma unroll
+    for (int k = 0; k < VEC / 2; ++k)
+      m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(u16x2, w.v[k] & 0x7fff7fffu));
+    const uint32_t m16 = m2.x > m2.y ? m2.x : m2.y;
+    return elem<T>::id == BVQ_BF16 ? (m16 << 16) : m16;
+  } else {
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const uint32_t b = abs_bits<T>(xv.v[k]);
+      m = b > m ? b : m;
+    }
+    return m;
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ float key_value(uint32_t key) {
+  if constexpr (elem<T>::id == BVQ_F16)
+    return (float)__builtin_bit_cast(f16_t, (uint16_t)key);
+  else
+    return __builtin_bit_cast(float, key);
+}
+
+// statistic -> scale with the rounding points of the scale epilogue (bvq_stat_epilogue.h): clamp_min, then the
+// quotient rounded to the scale's dtype, which is x's here
+template <typename T>
+__device__ __forceinline__ float group_scale(float stat, bool use_min, float min_val, float thr_div) {
+  const float thr = (use_min && stat < min_val) ? min_val : stat;  // NaN passes, like torch.clamp_min
+  return rnd<T>(thr / thr_div);
+}
+
+// the forward chain of IntQuant on a pair (the rounding points of bvq_quant_math.h; the last rounding is the caller's
+// pack2<T>).  16-bit types: the zero-point is +0, "+ zp" only turns -0 into +0 and "- zp" is the identity.
+template <typename T, typename Div>
+__device__ __forceinline__ f2 group_fwd_pair(f2 xf, const Div& div, float s, float qmin, float qmax) {
+  f2 t = rnd2<T>(div(xf));
+  t = t + 0.f;
+  t = round_op2<T, BVQ_ROUND>(t);
+  const f2 q = clamp_where2(t, qmin, qmax);
+  return sizeof(T) == 2 ? q * s : rnd2<T>(q - 0.f) * s;
+}
+
+template <typename T, bool NT, typename Div>
+__device__ __forceinline__ void group_fwd_chunk(const vec_t<T, elem<T>::vec>& xv, buf_t by, uint32_t off,
+                                                const Div& div, float s, float qmin, float qmax) {
+  constexpr int VEC = elem<T>::vec;
+  vec_t<T, VEC> yv;
+#pragma unroll
+  for (int k = 0; k < VEC; k += 2) {
+    const f2 r = group_fwd_pair<T>(widen2<T>(xv.v[k], xv.v[k + 1]), div, s, qmin, qmax);
+    pack2<T>(r, yv.v[k], yv.v[k + 1]);
+  }
+  buf_store<T, VEC, NT>(by, off, yv);  // dropped past the tensor's end
+}
+
+// every lane's scale suits the reciprocal form of its dtype (bvq_fakequant.h): decided per wave load, and the two
+// forms agree wherever the fast one is valid, so the choice cannot change a bit
+template <typename T>
+__device__ __forceinline__ bool wave_fast_div(float s) {
+  if constexpr (elem<T>::id == BVQ_BF16)
+    return __builtin_amdgcn_ballot_w64(!bf16_scale_ok(s)) == 0;
+  else if constexpr (elem<T>::id == BVQ_F16)
+    return __builtin_amdgcn_ballot_w64(!f16_scale_ok(s)) == 0;
+  else
+    return false;
+}
+template <typename T>
+using FastDiv = std::conditional_t<elem<T>::id == BVQ_BF16, DivBf16, DivF16R>;
+template <typename T>
+__device__ __forceinline__ FastDiv<T> fast_div(float s) {
+  if constexpr (elem<T>::id == BVQ_BF16)
+    return DivBf16{1.0f / s};
+  else
+    return DivF16R{s, 1.0f / s};
+}
+
+// the wave's window of the tensor: kD wave loads from chunk c0 on, seen through buffer descriptors whose extents end
+// with the tensor -- lanes past the end read zeros without a memory access and their stores are dropped, so the walk
+// has no tail branch.  The tensor is whole groups, so a group is either inside or outside as a whole.
+template <typename T, int L, int kD>
+struct GroupWindow {
+  int64_t c0;
+  uint32_t nch, ngr;
+  __device__ __forceinline__ bool init(const GroupArgs& a) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    c0 = ((int64_t)blockIdx.x * kWavesPerBlock + wave) * (kD * kWave);
+    if (c0 >= a.chunks) return false;
+    const int64_t left = a.chunks - c0;
+    nch = (uint32_t)(left < kD * kWave ? left : kD * kWave);
+    ngr = nch / L;
+    return true;
+  }
+  __device__ __forceinline__ buf_t elems(const void* p) const {
+    return make_buf(reinterpret_cast<const T*>(p) + c0 * elem<T>::vec, nch * 16u);
+  }
+  __device__ __forceinline__ buf_t groups(const void* p) const {
+    return make_buf(reinterpret_cast<const T*>(p) + c0 / L, ngr * (uint32_t)sizeof(T));
+  }
+};
+
+template <typename T, int L, bool NT>
+__global__ __launch_bounds__(kBlock) void group_quant_fwd_kernel(GroupArgs a) {
+  constexpr int VEC = elem<T>::vec, kD = kGroupFwdDepth;
+  GroupWindow<T, L, kD> w;
+  if (!w.init(a)) return;
+  const int lane = threadIdx.x & 63;
+  const buf_t bx = w.elems(a.x), by = w.elems(a.y), bs = w.groups(a.scale), bt = w.groups(a.stat);
+  const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
+  vec_t<T, VEC> xv[kD];
+#pragma unroll
+  for (int j = 0; j < kD; ++j) xv[j] = buf_load<T, VEC, NT>(bx, (uint32_t)(j * kWave + lane) * 16u);
+#pragma unroll
+  for (int j = 0; j < kD; ++j) {
+    if ((uint32_t)(j * kWave) >= w.nch) break;  // wave-uniform: a load no lane has is not worked on
+    const float stat = key_value<T>(seg_max_u32<L>(chunk_key<T>(xv[j])));
+    const float s = group_scale<T>(stat, a.use_min != 0, a.min_val, a.thr_div);
+    // one lane per segment writes the two small outputs (vector stores; dropped for the groups past the end)
+    const uint32_t goff = (lane & (L - 1)) == 0 ? (uint32_t)(j * (kWave / L) + lane / L) * (uint32_t)sizeof(T) : kBufSkip;
+    vec_t<T, 1> sv, tv;
+    sv.v[0] = from_f<T>(s);
+    tv.v[0] = from_f<T>(stat);  // exact: stat is a value of T
+    buf_store<T, 1>(bs, goff, sv);
+    buf_store<T, 1>(bt, goff, tv);
+    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
+    if constexpr (sizeof(T) == 2) {
+      if (wave_fast_div<T>(s)) {
+        group_fwd_chunk<T, NT>(xv[j], by, off, fast_div<T>(s), s, qmin, qmax);
+        continue;
+      }
+    }
+    group_fwd_chunk<T, NT>(xv[j], by, off, DivExact{s}, s, qmin, qmax);
+  }
+}
+
+// One chunk of the backward: dx and the two rounded scale-gradient terms per element exactly as the per-channel
+// backward of the stats-scaled graph computes them (bwd_elem2, kBwdDs), the group's sum, the statistic's gradient
+// with the rounding points of bwd_stats_finish_kernel, and its deposit on the first element attaining the statistic.
+template <typename T, int L, bool NT, typename Div>
+__device__ __forceinline__ void group_bwd_chunk(const GroupArgs& a, const vec_t<T, elem<T>::vec>& xv,
+                                                const vec_t<T, elem<T>::vec>& gv, buf_t bd, uint32_t off, int lane,
+                                                const Div& div, float s, float stat, float gsc, float qmin,
+                                                float qmax) {
+  constexpr int VEC = elem<T>::vec;
+  constexpr bool kZp0 = sizeof(T) == 2, kSame16 = sizeof(T) == 2;
+  const bool clamp_ste = a.clamp_ste != 0;
+  f2 ds2 = splat2(0.f), unused1 = splat2(0.f), unused2 = splat2(0.f);
+  vec_t<T, VEC> dv;
+#pragma unroll
+  for (int k = 0; k < VEC; k += 2) {
+    const f2 d = bwd_elem2<T, BVQ_ROUND, kBwdDs, kZp0, kSame16, true>(
+        widen2<T>(xv.v[k], xv.v[k + 1]), widen2<T>(gv.v[k], gv.v[k + 1]), div, s, 0.f, qmin, qmax, clamp_ste,
+        BVQ_ROUND, ds2, unused1, unused2);
+    pack2<T>(d, dv.v[k], dv.v[k + 1]);
+  }
+  const float ds = seg_sum<L>(ds2.x + ds2.y);
+  // dscale (+ the gradient arriving through `scale`) -> the statistic's gradient: scale = clamp_min_ste(stat) / thr_div,
+  // every torch op rounding to the scale's dtype (T); the straight-through clamp passes it on
+  float v = rnd<T>(ds);
+  if (a.gscale) v = rnd<T>(v + gsc);
+  const float dstat = rnd<T>(v / a.thr_div);
+  // first element of the group whose |x| is the statistic: segment-wide minimum over lane * VEC + index
+  const uint32_t skey = abs_bits<T>(from_f<T>(stat));
+  const uint32_t e0 = (uint32_t)(lane & (L - 1)) * VEC;
+  uint32_t first = ~0u;
+#pragma unroll
+  for (int k = VEC - 1; k >= 0; --k) first = abs_bits<T>(xv.v[k]) == skey ? e0 + k : first;
+  first = seg_min_u32<L>(first);  // ~0: no element equals the statistic (a NaN of another pattern)
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    // the owning lane adds sign(x) * dstat to its already rounded dx element: the deposit's two roundings
+    const float dep = to_f<T>(dv.v[k]) + deposit<T, BVQ_MATCH_ABS>(dstat, xv.v[k]);
+    dv.v[k] = first == e0 + k ? from_f<T>(dep) : dv.v[k];
+  }
+  buf_store<T, VEC, NT>(bd, off, dv);
+}
+
+template <typename T, int L, bool NT>
+__global__ __launch_bounds__(kBlock) void group_quant_bwd_kernel(GroupArgs a) {
+  constexpr int VEC = elem<T>::vec, kD = kGroupBwdDepth;
+  GroupWindow<T, L, kD> w;
+  if (!w.init(a)) return;
+  const int lane = threadIdx.x & 63;
+  const buf_t bx = w.elems(a.x), bg = w.elems(a.g), bd = w.elems(a.y), bt = w.groups(a.stat);
+  const buf_t bgs = w.groups(a.gscale ? a.gscale : a.stat);
+  const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
+  vec_t<T, VEC> xv[kD], gv[kD];
+  vec_t<T, 1> tv[kD], gsv[kD];
+#pragma unroll
+  for (int j = 0; j < kD; ++j) {
+    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
+    const uint32_t goff = (uint32_t)(j * (kWave / L) + lane / L) * (uint32_t)sizeof(T);  // one address per segment
+    xv[j] = buf_load<T, VEC, NT>(bx, off);
+    gv[j] = buf_load<T, VEC, NT>(bg, off);
+    tv[j] = buf_load<T, 1>(bt, goff);
+    gsv[j] = buf_load<T, 1>(bgs, goff);
+  }
+#pragma unroll
+  for (int j = 0; j < kD; ++j) {
+    if ((uint32_t)(j * kWave) >= w.nch) break;  // wave-uniform
+    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
+    const float stat = to_f<T>(tv[j].v[0]);
+    // the forward's scale from the saved statistic: the same arithmetic, the saved bits
+    const float s = group_scale<T>(stat, a.use_min != 0, a.min_val, a.thr_div);
+    const float gsc = to_f<T>(gsv[j].v[0]);
+    if constexpr (sizeof(T) == 2) {
+      if (wave_fast_div<T>(s)) {
+        group_bwd_chunk<T, L, NT>(a, xv[j], gv[j], bd, off, lane, fast_div<T>(s), s, stat, gsc, qmin, qmax);
+        continue;
+      }
+    }
+    group_bwd_chunk<T, L, NT>(a, xv[j], gv[j], bd, off, lane, DivExact{s}, s, stat, gsc, qmin, qmax);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// what the kernels cover, apart from the pointers: BVQ_OK, or the error with its text
+static int group_check(const bvq_quant_desc* d, const char* what) {
+  int rc = validate(d);
+  if (rc) return rc;
+  if (d->outer != 1 || d->channels < 1 || !d->scale_per_channel || d->zp_per_channel) {
+    set_error("%s: the descriptor of a grouped tensor is outer 1, channels = groups, inner = group size, one scale per "
+              "channel and one zero-point", what);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (d->inner != 16 && d->inner != 32 && d->inner != 64 && d->inner != 128 && d->inner != 256) {
+    set_error("%s: group size %lld (16, 32, 64, 128 or 256)", what, (long long)d->inner);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (d->round_mode != BVQ_ROUND) {
+    set_error("%s: round_mode %d (half-even rounding only)", what, d->round_mode);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (d->x_dtype != d->ct_dtype || d->scale_dtype != d->x_dtype) {
+    set_error("%s: x, compute and scale dtype must agree (x=%d ct=%d scale=%d)", what, d->x_dtype, d->ct_dtype,
+              d->scale_dtype);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (d->pre_op != BVQ_PRE_NONE) {
+    set_error("%s: pre_op %d is not covered", what, d->pre_op);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (d->out_kind != BVQ_OUT_DEQUANT) {
+    set_error("%s: integer output is not covered", what);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  return BVQ_OK;
+}
+
+static GroupArgs group_args(const bvq_quant_desc* d, double min_val, int use_min, double thr_div) {
+  GroupArgs a = {};
+  a.chunks = d->channels * (d->inner * dtype_size(d->x_dtype) / 16);
+  a.qmin = d->qmin;
+  a.qmax = d->qmax;
+  a.min_val = round_host((float)min_val, d->x_dtype);  // python scalar -> the statistic's dtype
+  a.thr_div = (float)thr_div;
+  a.use_min = use_min;
+  a.clamp_ste = d->clamp_ste;
+  return a;
+}
+
+static unsigned group_grid(int64_t chunks, int depth) {
+  const int64_t per_block = (int64_t)kWavesPerBlock * depth * kWave;
+  return (unsigned)((chunks + per_block - 1) / per_block);
+}
+
+// f(type_tag<T>, int_c<L>, std::bool_constant<NT>) for the lanes per group of d's dtype and group size
+template <typename F>
+static int with_group_variant(const bvq_quant_desc* d, bool nt, F&& f) {
+  const int lanes = (int)(d->inner * dtype_size(d->x_dtype) / 16);
+  return with_dtype(d->x_dtype, [&](auto t) {
+    return with_bool(nt, [&](auto ntc) {
+      if constexpr (sizeof(typename decltype(t)::type) == 2)
+        return with_value<2, 4, 8, 16, 32>(lanes, [&](auto l) { return call_rc(f, t, l, ntc); });
+      else
+        return with_value<4, 8, 16, 32, 64>(lanes, [&](auto l) { return call_rc(f, t, l, ntc); });
+    });
+  });
+}
+
+}  // namespace bvq
+
+using namespace bvq;
+
+extern "C" int bvq_group_quant_supported(const bvq_quant_desc* d, const void* x) {
+  if (group_check(d, "bvq_group_quant_supported")) return 0;
+  return x && aligned16(x) ? 1 : 0;
+}
+
+extern "C" int bvq_group_quant_fwd(const bvq_quant_desc* d, const void* x, double min_val, int use_min, double thr_div,
+                                   void* y, void* scale, void* stat, bvq_stream_t stream) {
+  int rc = group_check(d, "bvq_group_quant_fwd");
+  if (rc) return rc;
+  if (!x || !y || !scale || !stat) {
+    set_error("bvq_group_quant_fwd: null pointer");
+    return BVQ_ERR_INVALID;
+  }
+  if (!aligned16(x) || !aligned16(y)) {
+    set_error("bvq_group_quant_fwd: x and y must lie on 16-byte boundaries");
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  GroupArgs a = group_args(d, min_val, use_min, thr_div);
+  a.x = x;
+  a.y = y;
+  a.scale = scale;
+  a.stat = stat;
+  const bool nt = a.chunks * 32 >= nt_threshold_bytes();  // x read + y written
+  rc = with_group_variant(d, nt, [&](auto t, auto l, auto ntc) {
+    group_quant_fwd_kernel<typename decltype(t)::type, l, ntc>
+        <<<group_grid(a.chunks, kGroupFwdDepth), kBlock, 0, (hipStream_t)stream>>>(a);
+  });
+  return rc ? rc : check_launch("bvq_group_quant_fwd");
+}
+
+extern "C" int bvq_group_quant_bwd(const bvq_quant_desc* d, const void* g, const void* x, const void* scale,
+                                   const void* stat, const void* gscale, double min_val, int use_min, double thr_div,
+                                   void* dx, bvq_stream_t stream) {
+  int rc = group_check(d, "bvq_group_quant_bwd");
+  if (rc) return rc;
+  if (!g || !x || !scale || !stat || !dx) {
+    set_error("bvq_group_quant_bwd: null pointer");
+    return BVQ_ERR_INVALID;
+  }
+  if (!aligned16(g) || !aligned16(x) || !aligned16(dx)) {
+    set_error("bvq_group_quant_bwd: g, x and dx must lie on 16-byte boundaries");
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  GroupArgs a = group_args(d, min_val, use_min, thr_div);
+  a.x = x;
+  a.g = g;
+  a.y = dx;
+  a.stat = const_cast<void*>(stat);
+  a.gscale = gscale;
+  const bool nt = a.chunks * 48 >= nt_threshold_bytes();  // g and x read, dx written
+  rc = with_group_variant(d, nt, [&](auto t, auto l, auto ntc) {
+    group_quant_bwd_kernel<typename decltype(t)::type, l, ntc>
+        <<<group_grid(a.chunks, kGroupBwdDepth), kBlock, 0, (hipStream_t)stream>>>(a);
+  });
+  return rc ? rc : check_launch("bvq_group_quant_bwd");
+}

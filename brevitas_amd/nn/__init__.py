@@ -30,6 +30,12 @@ class _QuantWeightMixin:
         if bias_quant is not None and self.bias is not None and not isinstance(bias_quant, torch.nn.Module):
             bias_quant = bias_quant(self.bias)
         self.bias_quant = bias_quant if self.bias is not None else None
+        from brevitas_amd.core.quant.int import GroupwiseRescalingIntQuant, PrescaledRestrictIntQuant
+        if isinstance(self.weight_quant, GroupwiseRescalingIntQuant) and \
+                isinstance(self.bias_quant, PrescaledRestrictIntQuant):
+            # one scale per group of input weights: the accumulator the bias is added to has no single scale
+            raise ValueError('a group-wise weight quantizer cannot be combined with an externally scaled bias quantizer '
+                             '(Int8Bias ... Int32Bias); use a bias quantizer with internal scaling')
 
     def _quant_all(self, x):
         """-> (x, w, bias) as the float op consumes them (B/nn/quant_layer.py:302-333)"""

@@ -11,9 +11,9 @@ from typing import List, Optional, Sequence, Union
 import torch
 
 from brevitas_amd.core.bit_width import BitWidthConst
-from brevitas_amd.core.function_wrapper import (CeilSte, OverOutputChannelView, OverTensorView, RoundSte, TensorClamp,
-                                                TensorClampSte)
-from brevitas_amd.core.quant import IntQuant, PrescaledRestrictIntQuant, RescalingIntQuant
+from brevitas_amd.core.function_wrapper import (CeilSte, OverOutputChannelView, OverSubChannelBlockView, OverTensorView,
+                                                RoundSte, TensorClamp, TensorClampSte)
+from brevitas_amd.core.quant import GroupwiseRescalingIntQuant, IntQuant, PrescaledRestrictIntQuant, RescalingIntQuant
 from brevitas_amd.core.restrict_val import FloatRestrictValue, PowerOfTwoRestrictValue
 from brevitas_amd.core.scaling import (IntScaling, ParameterFromRuntimeStatsScaling, ParameterScaling,
                                        PowerOfTwoIntScaling, RuntimeStatsScaling, StatsFromParameterScaling)
@@ -21,7 +21,8 @@ from brevitas_amd.core.stats import (AbsMax, AbsMinMax, AbsPercentile, NegativeM
                                      PercentileInterval)
 from brevitas_amd.core.zero_point import ParameterFromRuntimeZeroPoint, StatsFromParameterZeroPoint, ZeroZeroPoint
 
-__all__ = ['Int8WeightPerChannelFloat', 'Int4WeightPerChannelFloat', 'Int8WeightPerTensorFloat',
+__all__ = ['Int8WeightPerChannelFloat', 'Int4WeightPerChannelFloat', 'Int8WeightPerGroupFloat',
+           'Int4WeightPerGroupFloat', 'Int8WeightPerTensorFloat',
            'Int8ActPerTensorFloat', 'Uint8ActPerTensorFloat', 'Int8ActPerChannelFloat',
            'ShiftedUint8WeightPerTensorFloat', 'ShiftedUint8WeightPerChannelFloat', 'ShiftedUint8ActPerTensorFloat',
            'Int8WeightPerTensorFixedPoint', 'Int8WeightPerChannelFixedPoint', 'Int8ActPerTensorFixedPoint',
@@ -54,6 +55,34 @@ def Int8WeightPerChannelFloat(weights: Union[torch.nn.Parameter, Sequence[torch.
 def Int4WeightPerChannelFloat(weights) -> RescalingIntQuant:
     """not in this reference snapshot; defined as Int8WeightPerChannelFloat with bit_width = 4"""
     return Int8WeightPerChannelFloat(weights, bit_width=4)
+
+
+def Int8WeightPerGroupFloat(weights: Union[torch.nn.Parameter, Sequence[torch.nn.Parameter]], group_size: int = 128,
+                            bit_width: int = 8) -> GroupwiseRescalingIntQuant:
+    """Int8WeightPerChannelFloat with one scale per `group_size` consecutive input weights of each output channel
+    (Int8WeightPerGroupFloat of later Brevitas releases; not in this reference snapshot): the per-channel graph on the
+    weight regrouped as [out * K / group_size, group_size], K = Cin * kh * kw in memory order.  y has the weight's
+    shape, scale is (out, K / group_size, 1).  In a layer: weight_quant=functools.partial(Int8WeightPerGroupFloat,
+    group_size=64).  One tracked weight only: the groups of several weights do not line up."""
+    tracked = _params(weights)
+    if len(tracked) != 1:
+        raise ValueError('a group-wise weight quantizer tracks exactly one weight, got a list of %d' % len(tracked))
+    w = tracked[0]
+    group_size = int(group_size)
+    if w.dim() < 2 or group_size < 1 or (w.numel() // max(w.shape[0], 1)) % group_size != 0:
+        raise ValueError('a weight of shape %s has no whole groups of %d elements per output channel'
+                         % (tuple(w.shape), group_size))
+    shape = (w.numel() // group_size, 1)
+    return GroupwiseRescalingIntQuant(
+        IntQuant(narrow_range=True, signed=True, float_to_int_impl=RoundSte(), tensor_clamp_impl=TensorClampSte()),
+        StatsFromParameterScaling(AbsMax(1), OverSubChannelBlockView(group_size), 1, tracked, FloatRestrictValue(),
+                                  shape, affine_rescaling=False, scaling_min_val=SCALING_MIN_VAL),
+        IntScaling(signed=True, narrow_range=True), ZeroZeroPoint(), BitWidthConst(bit_width), group_size)
+
+
+def Int4WeightPerGroupFloat(weights, group_size: int = 128) -> GroupwiseRescalingIntQuant:
+    """Int8WeightPerGroupFloat with bit_width = 4: the usual weight-only format of LLM-sized linear layers"""
+    return Int8WeightPerGroupFloat(weights, group_size=group_size, bit_width=4)
 
 
 def Int8WeightPerTensorFloat(weights, bit_width: int = 8) -> RescalingIntQuant:

@@ -677,6 +677,30 @@ int bvq_weight_quant_list_bwd(int dtype, int scale_dtype, int quot_dtype, int ro
                               const bvq_weight_item* items, void* workspace, int64_t workspace_bytes, uint32_t* arrive,
                               int64_t arrive_words, bvq_stream_t stream);
 
+/* ---- group-wise weights: one scale per group of consecutive elements ------------------------------------------------
+ * A weight [out, K] with one scale per `group_size` consecutive elements of each row is, in memory, [groups, group_size]
+ * with one scale per row.  The descriptor says so: outer = 1, channels = groups, inner = group_size, scale_per_channel,
+ * x_dtype = ct_dtype = scale_dtype, zero zero-point.  The results are those of bvq_stats_fakequant_fwd and
+ * bvq_fakequant_bwd_stats on that descriptor; what differs is the kernel: a group lives in a fraction of one wave, so
+ * statistic, scale, quantization, scale gradient and arg-max deposit stay in registers -- ONE launch each way, no
+ * workspace, no atomics.  Only the order in which a group's float32 scale-gradient terms are added differs from the
+ * per-channel kernels (the deposited element can move by a rounding).
+ *   bvq_group_quant_fwd: AbsMax per group -> clamp_min(min_val) (use_min) -> / thr_div (the value the division sees,
+ *     rounded to the scale's dtype by the caller) -> quantize-dequantize.  y like x; scale, stat: [groups] in x's dtype.
+ *   bvq_group_quant_bwd: dx = the quantizer's input gradient + the statistic's gradient of each group on the first
+ *     element attaining it.  stat: the forward's output (the scale is derived from it again, same bits; `scale` is not
+ *     read).  gscale (nullable, [groups] in x's dtype): a gradient arriving through the returned scale, added to the
+ *     group's scale gradient before it becomes the statistic's.  The clamp_min is straight-through, as in the
+ *     per-channel route.
+ * Covered: group_size 16, 32, 64, 128 or 256; BVQ_ROUND; BVQ_PRE_NONE; BVQ_OUT_DEQUANT; every tensor pointer on a
+ * 16-byte boundary.  Anything else returns BVQ_ERR_UNSUPPORTED with a bvq_last_error() text, found before anything
+ * touches the device; bvq_group_quant_supported answers 1 / 0 for a descriptor and x. */
+int bvq_group_quant_supported(const bvq_quant_desc* desc, const void* x);
+int bvq_group_quant_fwd(const bvq_quant_desc* desc, const void* x, double min_val, int use_min, double thr_div, void* y,
+                        void* scale, void* stat, bvq_stream_t stream);
+int bvq_group_quant_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* scale, const void* stat,
+                        const void* gscale, double min_val, int use_min, double thr_div, void* dx, bvq_stream_t stream);
+
 /* Diagnostic entry (no reference counterpart): the float32 quotient the float16 quantizer kernels compute for a
  * numerator a[i] and a scale scales[j] -- the product with the correctly rounded reciprocal, corrected by one exact
  * remainder step (brevitas_amd/csrc/bvq_fakequant.h, DivF16R) -- out[j * n_a + i], float32 device buffers.  The
