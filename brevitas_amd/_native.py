@@ -29,6 +29,9 @@ CODES_I32, CODES_I8, CODES_U8 = 0, 1, 2
 CLUSTER_FORCE_FALLBACK = 1  # BVQ_CLUSTER_FORCE_FALLBACK: tests only
 # the `form` of bvq_absmax_fakequant_cluster_form (developers, tests)
 CLUSTER_AUTO, CLUSTER_WALK, CLUSTER_ONESHOT = range(3)
+# bvq_mx_format, bvq_mx_scale_rule
+MX_E4M3, MX_E5M2, MX_E3M2, MX_E2M3, MX_E2M1, MX_INT8 = range(6)
+MX_FLOOR, MX_CEIL = 0, 1
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
 ABI_VERSION = 2
 
@@ -49,7 +52,8 @@ EXPORTS = (
     'bvq_shard_unpack_deposit', 'bvq_absmax_list_supported', 'bvq_absmax_scale_list', 'bvq_weight_list_supported',
     'bvq_weight_quant_list_fwd', 'bvq_weight_quant_list_bwd_workspace_bytes', 'bvq_weight_quant_list_bwd',
     'bvq_absmax_fakequant_cluster_supported', 'bvq_absmax_fakequant_cluster', 'bvq_absmax_fakequant_cluster_form',
-    'bvq_selftest_pre_op', 'bvq_group_quant_supported', 'bvq_group_quant_fwd', 'bvq_group_quant_bwd')
+    'bvq_selftest_pre_op', 'bvq_group_quant_supported', 'bvq_group_quant_fwd', 'bvq_group_quant_bwd',
+    'bvq_mx_quant_supported', 'bvq_mx_quant_fwd', 'bvq_mx_quant_bwd')
 
 
 class QuantDesc(ctypes.Structure):
@@ -175,6 +179,9 @@ def _load(path=None, strict=True):
         'bvq_group_quant_supported': (i32, [ctypes.POINTER(QuantDesc), vp]),
         'bvq_group_quant_fwd': (i32, [ctypes.POINTER(QuantDesc), vp, dbl, i32, dbl, vp, vp, vp, vp]),
         'bvq_group_quant_bwd': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, dbl, i32, dbl, vp, vp]),
+        'bvq_mx_quant_supported': (i32, [i32, i64, i32, i32, vp]),
+        'bvq_mx_quant_fwd': (i32, [i32, i64, i32, i32, i32, vp, vp, vp, vp]),
+        'bvq_mx_quant_bwd': (i32, [i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         'bvq_fakequant_bwd_learned': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, i32, dbl, i32, dbl, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
@@ -494,6 +501,49 @@ def group_quant_bwd(desc, g, x, scale, stat, gscale, min_val, thr_div):
                                       stream_ptr(dev)), 'bvq_group_quant_bwd')
         if _timer is not None:
             _timer.after('bvq_group_quant_bwd')
+    return dx
+
+
+def mx_quant_supported(x, group_size, fmt):
+    """the MX kernels cover this tensor (dtype, whole groups, 16-byte aligned), group size and format"""
+    code = _DTYPES.get(x.dtype)
+    if code is None or x.numel() == 0 or x.numel() % group_size:
+        return False
+    return bool(lib.bvq_mx_quant_supported(code, x.numel() // group_size, int(group_size), int(fmt), ptr(x)))
+
+
+def mx_quant_fwd(x, group_size, fmt, scale_rule):
+    """MX block-scaled quantize-dequantize in ONE launch -> (y like x, float32 scale [groups])"""
+    dev = require_device(x)
+    assert x.is_contiguous() and x.numel() % group_size == 0
+    groups = x.numel() // group_size
+    y = torch.empty_like(x)
+    scale = torch.empty(groups, dtype=torch.float32, device=dev)
+    with _DeviceGuard(dev):
+        if _timer is not None:
+            _timer.before('bvq_mx_quant_fwd')
+        check(lib.bvq_mx_quant_fwd(dtype_code(x.dtype), groups, int(group_size), int(fmt), int(scale_rule), ptr(x),
+                                   ptr(y), ptr(scale), stream_ptr(dev)), 'bvq_mx_quant_fwd')
+        if _timer is not None:
+            _timer.after('bvq_mx_quant_fwd')
+    return y, scale
+
+
+def mx_quant_bwd(g, x, gscale, group_size, fmt, scale_rule, clamp_ste):
+    """backward of mx_quant_fwd in ONE launch -> dx; gscale: None, or the float32 [groups] gradient arriving through the
+    returned scale.  The group's abs-max and exponent are recomputed from x."""
+    dev = require_device(g, x, gscale)
+    assert g.is_contiguous() and x.is_contiguous() and g.dtype == x.dtype
+    assert gscale is None or (gscale.is_contiguous() and gscale.dtype == torch.float32)
+    dx = torch.empty_like(x)
+    with _DeviceGuard(dev):
+        if _timer is not None:
+            _timer.before('bvq_mx_quant_bwd')
+        check(lib.bvq_mx_quant_bwd(dtype_code(x.dtype), x.numel() // group_size, int(group_size), int(fmt),
+                                   int(scale_rule), int(bool(clamp_ste)), ptr(g), ptr(x), ptr(gscale), ptr(dx),
+                                   stream_ptr(dev)), 'bvq_mx_quant_bwd')
+        if _timer is not None:
+            _timer.after('bvq_mx_quant_bwd')
     return dx
 
 

@@ -3,4 +3,5 @@ from .delay import DelayWrapper
 from .int import (DecoupledRescalingIntQuant, GroupwiseRescalingIntQuant, PrescaledRestrictIntQuant,
                   PrescaledRestrictIntQuantWithInputBitWidth, RescalingIntQuant, TruncIntQuant)
 from .int_base import DecoupledIntQuant, IntQuant
+from .mx import MXQuant
 from .ternary import TernaryQuant

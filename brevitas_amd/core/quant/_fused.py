@@ -540,6 +540,37 @@ class GroupStatsFakeQuantFn(Function):
         return (dx,) + (None,) * 6
 
 
+class MXQuantFn(Function):
+    """MX block-scaled quantizer (core/quant/mx.py): x -> (y like x, float32 scale [groups]).  One launch each way
+    (csrc/bvq_mx_quant.hip); the backward recomputes each group's abs-max and exponent from x, so only x is saved.  The
+    caller has checked what the kernels cover (MXQuant.fused_route)."""
+
+    @staticmethod
+    def forward(ctx, x, group_size, fmt, scale_rule, clamp_ste):
+        ctx.set_materialize_grads(False)  # an unused `scale` output must not cost a zero-fill
+        y, scale = nat.mx_quant_fwd(x, group_size, fmt, scale_rule)
+        ctx.args = (group_size, fmt, scale_rule, clamp_ste)
+        ctx.save_for_backward(x)
+        return y, scale
+
+    @staticmethod
+    def backward(ctx, gy, gscale):
+        x, = ctx.saved_tensors
+        if gy is None:  # only `scale` was used downstream
+            if gscale is None:
+                return (None,) * 5
+            gy = torch.zeros_like(x)
+        else:
+            gy = gy.to(x.dtype).contiguous()
+        if gscale is not None:
+            gscale = gscale.to(torch.float32).reshape(-1).contiguous()
+            if gscale.data_ptr() % 16 != 0:
+                gscale = gscale.clone()
+        if gy.data_ptr() % 16 != 0:
+            gy = gy.clone()
+        return (nat.mx_quant_bwd(gy, x, gscale, *ctx.args),) + (None,) * 4
+
+
 class StatsGraphFakeQuantFn(Function):
     """AbsMax statistic -> ANY scale-shaped map (`post`: a _StatsScaling with affine rescaling, a power-of-two
     restriction, ...) -> / int_threshold -> IntQuant, zero zero-point (B/core/scaling/runtime.py:19-72,

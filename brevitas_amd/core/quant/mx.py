@@ -1,0 +1,222 @@
+"""OCP Microscaling (MX) block-scaled quantizers: groups of `group_size` consecutive elements share one power-of-two
+scale, the elements are minifloats (FP8 E4M3 / E5M2, FP6 E3M2 / E2M3, FP4 E2M1) or MXINT8.  Not in the reference
+snapshot (later Brevitas releases: MXFloat8e4m3Weight, MXFloat8e4m3Act, MXInt8Weight ...); the definition is
+include/bvq.h, "MX block-scaled quantizers", restated here as the composed route.
+
+Per group, in float32 (x of float32, bfloat16 or float16 widened exactly):
+    a  = max |x_i|                                   a NaN or Inf: scale and every y_i are NaN
+    E  = floor(log2 a) - emax                        ('floor', the OCP rule; read from a's exponent, no log2 call)
+         + 1 if a > max_val * 2^E                    ('ceil': the smallest power of two with which nothing saturates)
+    E  = clamp(E, -126, 127)                         a == 0 counts as E = -inf; the scale is a normal float32, the E8M0
+                                                     code of 2^-127 is never produced
+    p_i = x_i * 2^-E                                 exact
+    r_i = p_i rounded half-even to the format's unbounded grid, quantum 2^(max(floor(log2 |p_i|), emin) - m)
+          (MXINT8: 2^-6); the sign of p_i is kept, also on a zero
+    q_i = clamp(r_i, -max_val, max_val)              inside_i = |r_i| <= max_val
+    y_i = T(q_i * 2^E)                               scale = 2^E as float32 for every T
+Backward (gy through y, gs through the returned scale), mask_i = inside_i or clamp_ste:
+    dx_i = gy_i * mask_i
+    S    = sum_i gy_i * (q_i - p_i * mask_i)         float32
+    da   = (gs + S) * (2^E / a)                      the floor / ceil of the exponent is straight-through; no da when
+                                                     a == 0, E was clamped or a is not finite
+    dx_k += sign(x_k) * da                           at the first k of the group with |x_k| == a
+
+Routes: on a ROCm device, for a covered dtype and group size, a contiguous 16-byte aligned tensor and
+config.FUSED_PATHS, one kernel each way (_fused.MXQuantFn, csrc/bvq_mx_quant.hip).  Everything else -- CPU tensors,
+FUSED_PATHS off, other group sizes, misaligned views -- runs the composed route below: the same definition as ONE
+autograd.Function of plain torch ops, the same bits on the CPU and on the device.
+"""
+from typing import NamedTuple, Optional, Tuple
+
+import torch
+from torch import Tensor
+from torch.autograd import Function
+
+import brevitas_amd.config as config
+from brevitas_amd import _native as nat
+from brevitas_amd.core.utils import StatelessBuffer
+
+from . import _fused
+
+__all__ = ['MXQuant', 'MX_FORMATS', 'MXFormat']
+
+
+class MXFormat(NamedTuple):
+    code: int            # bvq_mx_format
+    mantissa_bits: int   # fractional bits of the fixed quantum for int8
+    emin: Optional[int]  # smallest normal exponent; None: a fixed quantum of 2^-mantissa_bits (MXINT8)
+    emax: int
+    max_val: float
+    bit_width: int
+
+
+MX_FORMATS = {
+    'e4m3': MXFormat(nat.MX_E4M3, 3, -6, 8, 448.0, 8),
+    'e5m2': MXFormat(nat.MX_E5M2, 2, -14, 15, 57344.0, 8),
+    'e3m2': MXFormat(nat.MX_E3M2, 2, -2, 4, 28.0, 6),
+    'e2m3': MXFormat(nat.MX_E2M3, 3, 0, 2, 7.5, 6),
+    'e2m1': MXFormat(nat.MX_E2M1, 1, 0, 2, 6.0, 4),
+    'int8': MXFormat(nat.MX_INT8, 6, None, 0, 127.0 / 64.0, 8),
+}
+SCALE_RULES = {'floor': nat.MX_FLOOR, 'ceil': nat.MX_CEIL}
+FUSED_GROUP_SIZES = (16, 32, 64, 128, 256)
+_E_MIN, _E_MAX = -126, 127
+
+
+def _pow2(k: Tensor) -> Tensor:
+    """2^k as float32 for an int32 tensor k in [-126, 127]: the exponent field, no arithmetic"""
+    return ((k + 127) << 23).view(torch.float32)
+
+
+def _floor_log2(v: Tensor) -> Tensor:
+    """floor(log2 |v|) as int32 from the exponent (subnormals included); v == 0 gives -1"""
+    return torch.frexp(v)[1].to(torch.int32) - 1
+
+
+def _ordered_sum(t: Tensor) -> Tensor:
+    """[groups, g] -> [groups, 1], float32 additions in an order fixed by g alone (halves folded onto each other while
+    the width is even, the rest left to right): element-wise adds only, so the CPU and the device give the same bits"""
+    while t.shape[1] > 1 and t.shape[1] % 2 == 0:
+        h = t.shape[1] // 2
+        t = t[:, :h] + t[:, h:]
+    s = t[:, 0:1]
+    for j in range(1, t.shape[1]):
+        s = s + t[:, j:j + 1]
+    return s
+
+
+def _group_terms(x2: Tensor, fmt: MXFormat, ceil: bool):
+    """the forward of the definition on float32 [groups, g] -> dict of its intermediate tensors"""
+    ax = x2.abs()
+    a = ax.amax(dim=1, keepdim=True)
+    finite = torch.isfinite(a)
+    a_f = torch.where(finite, a, torch.ones_like(a))
+    mant, ex = torch.frexp(a_f)              # a = mant * 2^ex, mant in [0.5, 1)
+    e = ex.to(torch.int32) - 1 - fmt.emax
+    if ceil:                                 # a * 2^-E = mant * 2^(emax + 1), exact
+        e = e + (mant * float(2 ** (fmt.emax + 1)) > fmt.max_val).to(torch.int32)
+    e = torch.where(a_f == 0, torch.full_like(e, -(1 << 20)), e)
+    ec = e.clamp(_E_MIN, _E_MAX)
+    no_da = (ec != e) | ~finite              # a == 0, E clamped, a not finite
+    big_x = _pow2(ec)
+    # x * 2^-E with normal powers of two only: -E in [-127, 126] is split into a factor >= 2^-126 and 1 or 1/2
+    h1 = (-ec).clamp(min=_E_MIN)
+    p = x2 * _pow2(h1) * _pow2(-ec - h1)
+    nan = torch.full_like(a, float('nan'))
+    p = torch.where(finite, p, nan)
+    if fmt.emin is None:
+        qe = torch.full_like(p, -fmt.mantissa_bits, dtype=torch.int32)
+    else:
+        qe = _floor_log2(torch.where(finite, p, torch.zeros_like(p))).clamp(min=fmt.emin, max=_E_MAX) - fmt.mantissa_bits
+    r = torch.round(p * _pow2(-qe)) * _pow2(qe)       # half-even; -0 stays -0
+    q = r.clamp(-fmt.max_val, fmt.max_val)
+    inside = r.abs() <= fmt.max_val
+    return dict(ax=ax, a=a, finite=finite, no_da=no_da, X=big_x, p=p, q=q, inside=inside, nan=nan)
+
+
+class MXComposedFn(Function):
+    """the definition as plain torch ops: x (contiguous, whole groups of g in memory order) -> (y like x, scale
+    float32 [groups])"""
+
+    @staticmethod
+    def forward(ctx, x, g, fmt, ceil, clamp_ste):
+        ctx.set_materialize_grads(False)
+        t = _group_terms(x.reshape(-1, g).float(), fmt, ceil)
+        y = torch.where(t['finite'], t['q'] * t['X'], t['nan']).to(x.dtype)
+        scale = torch.where(t['finite'], t['X'], t['nan']).reshape(-1)
+        ctx.args = (g, fmt, ceil, clamp_ste)
+        ctx.save_for_backward(x)
+        return y.reshape(x.shape), scale
+
+    @staticmethod
+    def backward(ctx, gy, gs):
+        x, = ctx.saved_tensors
+        g, fmt, ceil, clamp_ste = ctx.args
+        if gy is None and gs is None:
+            return (None,) * 5
+        x2 = x.reshape(-1, g).float()
+        t = _group_terms(x2, fmt, ceil)
+        gy2 = torch.zeros_like(x2) if gy is None else gy.reshape(-1, g).float()
+        zero = torch.zeros_like(x2)
+        mask = torch.ones_like(t['inside']) if clamp_ste else t['inside']
+        dx = torch.where(mask, gy2, zero)
+        s = _ordered_sum(gy2 * (t['q'] - torch.where(mask, t['p'], zero)))
+        if gs is not None:
+            s = gs.reshape(-1, 1).float() + s
+        dep = ~t['no_da']
+        a_safe = torch.where(dep, t['a'], torch.ones_like(t['a']))
+        da = s * (t['X'] / a_safe)
+        first = (t['ax'] == t['a']).to(torch.uint8).argmax(dim=1, keepdim=True)  # the first of the attaining elements
+        cur = dx.gather(1, first)
+        dx.scatter_(1, first, torch.where(dep, cur + torch.sign(x2.gather(1, first)) * da, cur))
+        return dx.to(x.dtype).reshape(x.shape), None, None, None, None
+
+
+class MXQuant(torch.nn.Module):
+    """x -> (y, scale, zero_point, bit_width) of an MX format.  Stateless: no parameters, no buffers in the state dict.
+
+    group_axis 'flat' (weights): groups of each output channel's flattened trailing dimensions, K = numel / shape[0],
+    scale (shape[0], K / g, 1).  'last' (activations): groups along the last dimension, scale shape[:-1] + (last / g, 1).
+    scale is float32 for every input dtype (a float16 scale could not hold 2^-39)."""
+
+    def __init__(self, element_format: str, group_size: int = 32, scale_rule: str = 'floor', clamp_ste: bool = False,
+                 group_axis: str = 'flat'):
+        super().__init__()
+        if element_format not in MX_FORMATS:
+            raise ValueError('element_format %r (one of %s)' % (element_format, ', '.join(MX_FORMATS)))
+        if scale_rule not in SCALE_RULES:
+            raise ValueError("scale_rule %r ('floor' or 'ceil')" % (scale_rule,))
+        if group_axis not in ('flat', 'last'):
+            raise ValueError("group_axis %r ('flat' or 'last')" % (group_axis,))
+        if int(group_size) < 1:
+            raise ValueError('group_size must be positive, got %r' % (group_size,))
+        self.element_format, self.format = element_format, MX_FORMATS[element_format]
+        self.group_size, self.scale_rule, self.clamp_ste = int(group_size), scale_rule, bool(clamp_ste)
+        self.group_axis = group_axis
+        self.zero_point = StatelessBuffer(torch.tensor(0.0))
+        self.bit_width = StatelessBuffer(torch.tensor(float(self.format.bit_width)))
+
+    def extra_repr(self):
+        return '%s, group_size=%d, scale_rule=%s, clamp_ste=%s, group_axis=%s' % (
+            self.element_format, self.group_size, self.scale_rule, self.clamp_ste, self.group_axis)
+
+    def _bit_width(self) -> Tensor:
+        t = self.bit_width()
+        t.bvq_host_value = self.format.bit_width
+        return t
+
+    def _scale_shape(self, x: Tensor) -> Tuple[int, ...]:
+        g = self.group_size
+        if self.group_axis == 'flat':
+            if x.dim() < 2 or x.shape[0] == 0 or (x.numel() // x.shape[0]) % g != 0:
+                raise ValueError('MX quantizer: a tensor of shape %s has no whole groups of %d elements per output '
+                                 'channel (at least 2 dimensions, numel / shape[0] a multiple of the group size)'
+                                 % (tuple(x.shape), g))
+            return (x.shape[0], x.numel() // x.shape[0] // g, 1)
+        if x.dim() < 1 or x.shape[-1] == 0 or x.shape[-1] % g != 0:
+            raise ValueError('MX quantizer: the last dimension of a tensor of shape %s is no multiple of the group size '
+                             '%d' % (tuple(x.shape), g))
+        return tuple(x.shape[:-1]) + (x.shape[-1] // g, 1)
+
+    def fused_route(self, x: Tensor) -> bool:
+        """the one-kernel route applies to this (contiguous) tensor"""
+        return bool(config.FUSED_PATHS and x.is_cuda and x.dtype in _fused._FLOATS
+                    and self.group_size in FUSED_GROUP_SIZES and x.data_ptr() % 16 == 0 and x.numel() > 0)
+
+    def forward(self, x: Tensor) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor], Tensor]:
+        bit_width = self._bit_width()
+        if getattr(self, 'bvq_collect_only', False):   # calibration: nothing to collect, the tensor passes untouched
+            return x, None, None, bit_width
+        if x.dtype not in _fused._FLOATS:
+            raise ValueError('MX quantizer: dtype %s (float32, bfloat16, float16)' % x.dtype)
+        shape = self._scale_shape(x)
+        xc = x.contiguous()
+        if self.fused_route(xc):
+            y, scale = _fused.MXQuantFn.apply(xc, self.group_size, self.format.code, SCALE_RULES[self.scale_rule],
+                                              self.clamp_ste)
+        else:
+            y, scale = MXComposedFn.apply(xc, self.group_size, self.format, self.scale_rule == 'ceil', self.clamp_ste)
+        return y, scale.reshape(shape), self.zero_point(), bit_width
+
+    def bvq_forward_pre(self, x: Tensor, pre_op: int) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor], Tensor]:
+        return self.forward(_fused.apply_pre_op(x, pre_op))

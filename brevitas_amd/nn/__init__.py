@@ -31,7 +31,8 @@ class _QuantWeightMixin:
             bias_quant = bias_quant(self.bias)
         self.bias_quant = bias_quant if self.bias is not None else None
         from brevitas_amd.core.quant.int import GroupwiseRescalingIntQuant, PrescaledRestrictIntQuant
-        if isinstance(self.weight_quant, GroupwiseRescalingIntQuant) and \
+        from brevitas_amd.core.quant.mx import MXQuant
+        if isinstance(self.weight_quant, (GroupwiseRescalingIntQuant, MXQuant)) and \
                 isinstance(self.bias_quant, PrescaledRestrictIntQuant):
             # one scale per group of input weights: the accumulator the bias is added to has no single scale
             raise ValueError('a group-wise weight quantizer cannot be combined with an externally scaled bias quantizer '

@@ -13,7 +13,8 @@ import torch
 from brevitas_amd.core.bit_width import BitWidthConst
 from brevitas_amd.core.function_wrapper import (CeilSte, OverOutputChannelView, OverSubChannelBlockView, OverTensorView,
                                                 RoundSte, TensorClamp, TensorClampSte)
-from brevitas_amd.core.quant import GroupwiseRescalingIntQuant, IntQuant, PrescaledRestrictIntQuant, RescalingIntQuant
+from brevitas_amd.core.quant import (GroupwiseRescalingIntQuant, IntQuant, MXQuant, PrescaledRestrictIntQuant,
+                                     RescalingIntQuant)
 from brevitas_amd.core.restrict_val import FloatRestrictValue, PowerOfTwoRestrictValue
 from brevitas_amd.core.scaling import (IntScaling, ParameterFromRuntimeStatsScaling, ParameterScaling,
                                        PowerOfTwoIntScaling, RuntimeStatsScaling, StatsFromParameterScaling)
@@ -28,7 +29,10 @@ __all__ = ['Int8WeightPerChannelFloat', 'Int4WeightPerChannelFloat', 'Int8Weight
            'Int8WeightPerTensorFixedPoint', 'Int8WeightPerChannelFixedPoint', 'Int8ActPerTensorFixedPoint',
            'Int8ActPerTensorFloatMinMaxInit', 'Uint8ActPerTensorFloatMaxInit',
            'Uint8ActPerTensorFixedPoint', 'Uint8ActPerTensorFixedPointMaxInit', 'Int8Bias', 'Int16Bias', 'Int24Bias',
-           'Int32Bias', 'Int8BiasPerTensorFloatInternalScaling', 'Int8BiasPerTensorFixedPointInternalScaling']
+           'Int32Bias', 'Int8BiasPerTensorFloatInternalScaling', 'Int8BiasPerTensorFixedPointInternalScaling',
+           'MXFloat8e4m3Weight', 'MXFloat8e5m2Weight', 'MXFloat6e3m2Weight', 'MXFloat6e2m3Weight', 'MXFloat4e2m1Weight',
+           'MXInt8Weight', 'MXFloat8e4m3Act', 'MXFloat8e5m2Act', 'MXFloat6e3m2Act', 'MXFloat6e2m3Act', 'MXFloat4e2m1Act',
+           'MXInt8Act']
 
 SCALING_MIN_VAL = 1e-10  # B/quant/base.py:115-123, 169-182
 
@@ -83,6 +87,77 @@ def Int8WeightPerGroupFloat(weights: Union[torch.nn.Parameter, Sequence[torch.nn
 def Int4WeightPerGroupFloat(weights, group_size: int = 128) -> GroupwiseRescalingIntQuant:
     """Int8WeightPerGroupFloat with bit_width = 4: the usual weight-only format of LLM-sized linear layers"""
     return Int8WeightPerGroupFloat(weights, group_size=group_size, bit_width=4)
+
+
+def _mx_weight(element_format: str, weights, group_size: int, scale_rule: str) -> MXQuant:
+    """an MX weight quantizer (core/quant/mx.py; MXFloat8e4m3Weight ... of later Brevitas releases, not in this
+    reference snapshot): groups of `group_size` consecutive input weights of each output channel, K = Cin * kh * kw in
+    memory order, share one power-of-two scale; straight-through clamp, as the integer weight quantizers.  y has the
+    weight's shape, scale is float32 (out, K / group_size, 1).  One tracked weight, its shape checked here."""
+    tracked = _params(weights)
+    if len(tracked) != 1:
+        raise ValueError('an MX weight quantizer tracks exactly one weight, got a list of %d' % len(tracked))
+    w = tracked[0]
+    group_size = int(group_size)
+    if w.dim() < 2 or group_size < 1 or (w.numel() // max(w.shape[0], 1)) % group_size != 0:
+        raise ValueError('a weight of shape %s has no whole groups of %d elements per output channel'
+                         % (tuple(w.shape), group_size))
+    return MXQuant(element_format, group_size=group_size, scale_rule=scale_rule, clamp_ste=True, group_axis='flat')
+
+
+def _mx_act(element_format: str, group_size: int, scale_rule: str) -> MXQuant:
+    """an MX activation quantizer: dynamic, one power-of-two scale per `group_size` elements of the last dimension,
+    plain clamp; scale is float32 x.shape[:-1] + (x.shape[-1] / group_size, 1)"""
+    return MXQuant(element_format, group_size=int(group_size), scale_rule=scale_rule, clamp_ste=False,
+                   group_axis='last')
+
+
+def MXFloat8e4m3Weight(weights, group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_weight('e4m3', weights, group_size, scale_rule)
+
+
+def MXFloat8e5m2Weight(weights, group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_weight('e5m2', weights, group_size, scale_rule)
+
+
+def MXFloat6e3m2Weight(weights, group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_weight('e3m2', weights, group_size, scale_rule)
+
+
+def MXFloat6e2m3Weight(weights, group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_weight('e2m3', weights, group_size, scale_rule)
+
+
+def MXFloat4e2m1Weight(weights, group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_weight('e2m1', weights, group_size, scale_rule)
+
+
+def MXInt8Weight(weights, group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_weight('int8', weights, group_size, scale_rule)
+
+
+def MXFloat8e4m3Act(group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_act('e4m3', group_size, scale_rule)
+
+
+def MXFloat8e5m2Act(group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_act('e5m2', group_size, scale_rule)
+
+
+def MXFloat6e3m2Act(group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_act('e3m2', group_size, scale_rule)
+
+
+def MXFloat6e2m3Act(group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_act('e2m3', group_size, scale_rule)
+
+
+def MXFloat4e2m1Act(group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_act('e2m1', group_size, scale_rule)
+
+
+def MXInt8Act(group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
+    return _mx_act('int8', group_size, scale_rule)
 
 
 def Int8WeightPerTensorFloat(weights, bit_width: int = 8) -> RescalingIntQuant:

@@ -701,6 +701,46 @@ int bvq_group_quant_fwd(const bvq_quant_desc* desc, const void* x, double min_va
 int bvq_group_quant_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* scale, const void* stat,
                         const void* gscale, double min_val, int use_min, double thr_div, void* dx, bvq_stream_t stream);
 
+/* ---- MX block-scaled quantizers: groups sharing one power-of-two scale, minifloat or MXINT8 elements -----------------
+ * The OCP Microscaling formats the gfx950 matrix units take natively, as quantize-dequantize for training (no
+ * reference counterpart; later Brevitas releases: MXFloat8e4m3Weight, MXFloat8e4m3Act, MXInt8Weight ...).  x is
+ * contiguous, dtype T, cut into `groups` groups of `group_size` consecutive elements.  Element formats (exponent bits
+ * e, mantissa bits m, emin = 2 - 2^(e-1)):
+ *     E4M3 (OCP FP8, no inf)  emax  8, max_val 448      E3M2  emax 4, max_val 28      E2M1  emax 2, max_val 6
+ *     E5M2                    emax 15, max_val 57344    E2M3  emax 2, max_val 7.5     INT8  k / 64, |k| <= 127, emax 0
+ * Forward, per group, in float32 and exact up to the last step:
+ *     a   = max |x_i|; a NaN or Inf: scale and every y_i of the group are NaN
+ *     E   = floor(log2 a) - emax (BVQ_MX_FLOOR, the OCP rule; read from a's exponent), + 1 if a > max_val * 2^E
+ *           (BVQ_MX_CEIL: the smallest power of two with which nothing saturates); a == 0 counts as -inf; then
+ *           clamped to [-126, 127]: the scale is always a normal float32 and the E8M0 code of 2^-127 never arises
+ *     p_i = x_i * 2^-E (ldexp)
+ *     r_i = p_i rounded half-even to a multiple of 2^(max(floor(log2 |p_i|), emin) - m) (INT8: of 2^-6), sign kept
+ *     q_i = clamp(r_i, -max_val, max_val), inside_i = |r_i| <= max_val
+ *     y_i = T(q_i * 2^E), scale = 2^E as float32 for every T
+ * Backward (g through y; gscale, nullable float32 [groups], through the returned scale), mask_i = inside_i or clamp_ste:
+ *     dx_i = g_i * mask_i;  S = sum_i g_i * (q_i - p_i * mask_i) in float32;  da = (gscale + S) * (2^E / a), the floor /
+ *     ceil of the exponent taken straight-through, and no da when a == 0, E was clamped or a is not finite;
+ *     sign(x_k) * da is added to dx_k at the first k of the group with |x_k| == a.
+ * One launch each way on the walk of the group-wise kernels: no workspace, no atomics; the backward recomputes a and E
+ * from x.  The order in which a group's float32 terms are added is fixed by the kernel (segmented butterfly).
+ * Covered: float32 / bfloat16 / float16; group_size 16, 32, 64, 128 or 256; every tensor pointer on a 16-byte boundary.
+ * Anything else returns BVQ_ERR_UNSUPPORTED with a bvq_last_error() text, found before anything touches the device;
+ * bvq_mx_quant_supported answers 1 / 0.  Emitting packed element codes and E8M0 scale bytes is not part of this. */
+typedef enum bvq_mx_format {
+  BVQ_MX_E4M3 = 0,
+  BVQ_MX_E5M2 = 1,
+  BVQ_MX_E3M2 = 2,
+  BVQ_MX_E2M3 = 3,
+  BVQ_MX_E2M1 = 4,
+  BVQ_MX_INT8 = 5
+} bvq_mx_format;
+typedef enum bvq_mx_scale_rule { BVQ_MX_FLOOR = 0, BVQ_MX_CEIL = 1 } bvq_mx_scale_rule;
+int bvq_mx_quant_supported(int dtype, int64_t groups, int group_size, int format, const void* x);
+int bvq_mx_quant_fwd(int dtype, int64_t groups, int group_size, int format, int scale_rule, const void* x, void* y,
+                     void* scale, bvq_stream_t stream);
+int bvq_mx_quant_bwd(int dtype, int64_t groups, int group_size, int format, int scale_rule, int clamp_ste,
+                     const void* g, const void* x, const void* gscale, void* dx, bvq_stream_t stream);
+
 /* Diagnostic entry (no reference counterpart): the float32 quotient the float16 quantizer kernels compute for a
  * numerator a[i] and a scale scales[j] -- the product with the correctly rounded reciprocal, corrected by one exact
  * remainder step (brevitas_amd/csrc/bvq_fakequant.h, DivF16R) -- out[j * n_a + i], float32 device buffers.  The
