@@ -53,7 +53,8 @@ EXPORTS = (
     'bvq_weight_quant_list_fwd', 'bvq_weight_quant_list_bwd_workspace_bytes', 'bvq_weight_quant_list_bwd',
     'bvq_absmax_fakequant_cluster_supported', 'bvq_absmax_fakequant_cluster', 'bvq_absmax_fakequant_cluster_form',
     'bvq_selftest_pre_op', 'bvq_group_quant_supported', 'bvq_group_quant_fwd', 'bvq_group_quant_bwd',
-    'bvq_mx_quant_supported', 'bvq_mx_quant_fwd', 'bvq_mx_quant_bwd')
+    'bvq_mx_quant_supported', 'bvq_mx_quant_fwd', 'bvq_mx_quant_bwd', 'bvq_mx_encode_supported', 'bvq_mx_encode',
+    'bvq_mx_decode')
 
 
 class QuantDesc(ctypes.Structure):
@@ -182,6 +183,9 @@ def _load(path=None, strict=True):
         'bvq_mx_quant_supported': (i32, [i32, i64, i32, i32, vp]),
         'bvq_mx_quant_fwd': (i32, [i32, i64, i32, i32, i32, vp, vp, vp, vp]),
         'bvq_mx_quant_bwd': (i32, [i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+        'bvq_mx_encode_supported': (i32, [i32, i64, i32, i32, vp]),
+        'bvq_mx_encode': (i32, [i32, i64, i32, i32, i32, vp, vp, vp, vp]),
+        'bvq_mx_decode': (i32, [i32, i64, i32, i32, vp, vp, vp, vp]),
         'bvq_fakequant_bwd_learned': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, i32, dbl, i32, dbl, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
@@ -545,6 +549,50 @@ def mx_quant_bwd(g, x, gscale, group_size, fmt, scale_rule, clamp_ste):
         if _timer is not None:
             _timer.after('bvq_mx_quant_bwd')
     return dx
+
+
+MX_CODE_BITS = (8, 8, 6, 6, 4, 8)  # per bvq_mx_format
+
+
+def mx_encode(x, group_size, fmt, scale_rule, codes=None, scale_e8m0=None):
+    """packed MX element codes and E8M0 scale bytes of x in ONE launch -> (uint8 codes [numel * bits / 8], uint8 scale
+    bytes [groups]); codes / scale_e8m0: contiguous uint8 outputs of exactly those sizes to write into"""
+    dev = require_device(x, codes, scale_e8m0)
+    assert x.is_contiguous() and x.numel() % group_size == 0
+    groups = x.numel() // group_size
+    nbytes = x.numel() * MX_CODE_BITS[fmt] // 8
+    if codes is None:
+        codes = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if scale_e8m0 is None:
+        scale_e8m0 = torch.empty(groups, dtype=torch.uint8, device=dev)
+    for t, n in ((codes, nbytes), (scale_e8m0, groups)):
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n
+    with _DeviceGuard(dev):
+        if _timer is not None:
+            _timer.before('bvq_mx_encode')
+        check(lib.bvq_mx_encode(dtype_code(x.dtype), groups, int(group_size), int(fmt), int(scale_rule), ptr(x),
+                                ptr(codes), ptr(scale_e8m0), stream_ptr(dev)), 'bvq_mx_encode')
+        if _timer is not None:
+            _timer.after('bvq_mx_encode')
+    return codes, scale_e8m0
+
+
+def mx_decode(codes, scale_e8m0, group_size, fmt, dtype):
+    """the values of packed MX codes and E8M0 scale bytes in ONE launch -> y of `dtype`, [groups * group_size]"""
+    dev = require_device(codes, scale_e8m0)
+    groups = scale_e8m0.numel()
+    n = groups * group_size
+    for t, m in ((codes, n * MX_CODE_BITS[fmt] // 8), (scale_e8m0, groups)):
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == m
+    y = torch.empty(n, dtype=dtype, device=dev)
+    with _DeviceGuard(dev):
+        if _timer is not None:
+            _timer.before('bvq_mx_decode')
+        check(lib.bvq_mx_decode(dtype_code(dtype), groups, int(group_size), int(fmt), ptr(codes), ptr(scale_e8m0),
+                                ptr(y), stream_ptr(dev)), 'bvq_mx_decode')
+        if _timer is not None:
+            _timer.after('bvq_mx_decode')
+    return y
 
 
 def absmax_fakequant_cluster(desc, x, min_val, int_threshold, scale_dtype, running=None, momentum=0.0,

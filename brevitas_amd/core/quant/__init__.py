@@ -3,5 +3,5 @@ from .delay import DelayWrapper
 from .int import (DecoupledRescalingIntQuant, GroupwiseRescalingIntQuant, PrescaledRestrictIntQuant,
                   PrescaledRestrictIntQuantWithInputBitWidth, RescalingIntQuant, TruncIntQuant)
 from .int_base import DecoupledIntQuant, IntQuant
-from .mx import MXQuant
+from .mx import MXPacked, MXQuant, mx_dequantize
 from .ternary import TernaryQuant

@@ -25,6 +25,11 @@ Routes: on a ROCm device, for a covered dtype and group size, a contiguous 16-by
 config.FUSED_PATHS, one kernel each way (_fused.MXQuantFn, csrc/bvq_mx_quant.hip).  Everything else -- CPU tensors,
 FUSED_PATHS off, other group sizes, misaligned views -- runs the composed route below: the same definition as ONE
 autograd.Function of plain torch ops, the same bits on the CPU and on the device.
+
+The wire format (include/bvq.h, "MX wire format"): MXQuant.to_mx_codes(x) gives the same q_i and E as packed element
+codes and E8M0 scale bytes (MXPacked), MXQuant.from_mx_codes / mx_dequantize read them back; the same two routes, one
+kernel each way (bvq_mx_encode, bvq_mx_decode) or plain integer tensor ops with the same bytes on the CPU and on the
+device.  Not differentiable.
 """
 from typing import NamedTuple, Optional, Tuple
 
@@ -38,7 +43,7 @@ from brevitas_amd.core.utils import StatelessBuffer
 
 from . import _fused
 
-__all__ = ['MXQuant', 'MX_FORMATS', 'MXFormat']
+__all__ = ['MXQuant', 'MX_FORMATS', 'MXFormat', 'MXPacked', 'mx_dequantize']
 
 
 class MXFormat(NamedTuple):
@@ -152,6 +157,86 @@ class MXComposedFn(Function):
         return dx.to(x.dtype).reshape(x.shape), None, None, None, None
 
 
+class MXPacked(NamedTuple):
+    """a tensor in the MX wire format"""
+    codes: Tensor          # uint8: shape[:-1] + (shape[-1] * bits // 8,) for 'last', (shape[0], K * bits // 8) for 'flat'
+    scale_e8m0: Tensor     # uint8: the shape of the float scale without its trailing 1
+    element_format: str
+    group_size: int
+    shape: Tuple[int, ...]  # of the tensor that was encoded
+    group_axis: str
+
+
+def _code_bias(fmt: MXFormat) -> int:
+    return 1 - fmt.emin
+
+
+def _composed_encode(x: Tensor, g: int, fmt: MXFormat, ceil: bool) -> Tuple[Tensor, Tensor]:
+    """x (contiguous, whole groups of g in memory order) -> (uint8 codes [numel * bits / 8], uint8 scale bytes [groups])"""
+    t = _group_terms(x.reshape(-1, g).float(), fmt, ceil)
+    finite = t['finite']
+    scale = torch.where(finite, t['X'].view(torch.int32) >> 23, torch.full_like(t['X'], 0xff, dtype=torch.int32))
+    q = torch.where(finite, t['q'], torch.zeros_like(t['q']))
+    if fmt.emin is None:
+        code = (q * 64.0).to(torch.int32) & 0xff        # exact; -0 becomes 0
+    else:
+        m, w = fmt.mantissa_bits, fmt.bit_width
+        bits = q.view(torch.int32)
+        ab = bits & 0x7fffffff
+        normal = (ab >> (23 - m)) - ((127 - _code_bias(fmt)) << m)
+        sub = (q.abs() * float(2 ** (m - fmt.emin))).to(torch.int32)    # |q| / 2^(emin - m), an integer
+        code = torch.where(ab < ((fmt.emin + 127) << 23), sub, normal) | (((bits >> 31) & 1) << (w - 1))
+    code = code.reshape(-1)
+    if fmt.bit_width == 8:
+        packed = code
+    elif fmt.bit_width == 4:
+        c = code.view(-1, 2)
+        packed = c[:, 0] | (c[:, 1] << 4)
+    else:                                               # 6 bits: 4 codes are 24 bits, 3 bytes, little-endian
+        c = code.view(-1, 4)
+        word = c[:, 0] | (c[:, 1] << 6) | (c[:, 2] << 12) | (c[:, 3] << 18)
+        packed = torch.stack([word & 0xff, (word >> 8) & 0xff, word >> 16], dim=1).reshape(-1)
+    return packed.to(torch.uint8), scale.reshape(-1).to(torch.uint8)
+
+
+def _composed_decode(codes: Tensor, scale_e8m0: Tensor, g: int, fmt: MXFormat, dtype) -> Tensor:
+    """uint8 codes [n * bits / 8], uint8 scale bytes [n / g] -> the values, dtype [n]"""
+    b = codes.to(torch.int32)
+    if fmt.bit_width == 8:
+        code = b
+    elif fmt.bit_width == 4:
+        code = torch.stack([b & 0xf, b >> 4], dim=1).reshape(-1)
+    else:
+        b = b.view(-1, 3)
+        word = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        code = torch.stack([word & 0x3f, (word >> 6) & 0x3f, (word >> 12) & 0x3f, word >> 18], dim=1).reshape(-1)
+    if fmt.emin is None:
+        v = (((code + 128) & 0xff) - 128).float() * (1.0 / 64.0)
+    else:
+        m, w = fmt.mantissa_bits, fmt.bit_width
+        mag = code & ((1 << (w - 1)) - 1)
+        field, man = mag >> m, mag & ((1 << m) - 1)
+        bits = (mag << (23 - m)) + ((127 - _code_bias(fmt)) << 23)
+        sub = (man.float() * float(2.0 ** (fmt.emin - m))).view(torch.int32)
+        bits = torch.where(field == 0, sub, bits)
+        if fmt.code == nat.MX_E4M3:
+            bits = torch.where(mag == 0x7f, torch.full_like(bits, 0x7fc00000), bits)
+        elif fmt.code == nat.MX_E5M2:
+            bits = torch.where(field == 31, torch.where(man == 0, 0x7f800000, 0x7fc00000).to(torch.int32), bits)
+        v = (bits | ((code >> (w - 1)) << 31)).view(torch.float32)
+    # v * 2^(byte - 127) with normal powers of two only: the exponent is split into one >= -126 and 0 or -1
+    e = scale_e8m0.to(torch.int32).reshape(-1, 1) - 127
+    h1 = e.clamp(min=_E_MIN)
+    y = v.view(-1, g) * _pow2(h1) * _pow2(e - h1)
+    y = torch.where(e == 128, torch.full_like(y, float('nan')), y)
+    return y.to(dtype).reshape(-1)
+
+
+def mx_dequantize(packed: MXPacked, dtype=torch.float32) -> Tensor:
+    """the tensor an MXPacked holds, as `dtype`"""
+    return MXQuant(packed.element_format, packed.group_size, group_axis=packed.group_axis).from_mx_codes(packed, dtype)
+
+
 class MXQuant(torch.nn.Module):
     """x -> (y, scale, zero_point, bit_width) of an MX format.  Stateless: no parameters, no buffers in the state dict.
 
@@ -220,3 +305,63 @@ class MXQuant(torch.nn.Module):
 
     def bvq_forward_pre(self, x: Tensor, pre_op: int) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor], Tensor]:
         return self.forward(_fused.apply_pre_op(x, pre_op))
+
+    # ---- the wire format -------------------------------------------------------------------------------------------
+
+    def _codes_shape(self, shape: Tuple[int, ...]) -> Tuple[int, ...]:
+        bits = self.format.bit_width
+        if self.group_axis == 'flat':
+            k = 1
+            for d in shape[1:]:
+                k *= d
+            row, lead = k, (shape[0],)
+        else:
+            row, lead = shape[-1], tuple(shape[:-1])
+        if row * bits % 8:
+            raise ValueError('MX quantizer: %d elements of %d bits per row of a tensor of shape %s are no whole bytes'
+                             % (row, bits, tuple(shape)))
+        return lead + (row * bits // 8,)
+
+    @torch.no_grad()
+    def to_mx_codes(self, x: Tensor) -> MXPacked:
+        """x -> its packed element codes and E8M0 scale bytes: the q_i and E of forward(x).  Not differentiable."""
+        if x.dtype not in _fused._FLOATS:
+            raise ValueError('MX quantizer: dtype %s (float32, bfloat16, float16)' % x.dtype)
+        scale_shape = self._scale_shape(x)[:-1]
+        codes_shape = self._codes_shape(tuple(x.shape))
+        xc = x.detach().contiguous()
+        if self.fused_route(xc):
+            codes, scale = nat.mx_encode(xc, self.group_size, self.format.code, SCALE_RULES[self.scale_rule])
+        else:
+            codes, scale = _composed_encode(xc, self.group_size, self.format, self.scale_rule == 'ceil')
+        return MXPacked(codes.reshape(codes_shape), scale.reshape(scale_shape), self.element_format, self.group_size,
+                        tuple(x.shape), self.group_axis)
+
+    @torch.no_grad()
+    def from_mx_codes(self, packed: MXPacked, dtype=torch.float32) -> Tensor:
+        """the tensor `packed` holds, as `dtype`: on to_mx_codes(x) the bits of forward(x)[0] (a negative zero of
+        MXINT8 comes back positive).  Any byte pattern is decoded."""
+        if dtype not in _fused._FLOATS:
+            raise ValueError('MX quantizer: dtype %s (float32, bfloat16, float16)' % dtype)
+        if (packed.element_format, packed.group_size, packed.group_axis) != \
+                (self.element_format, self.group_size, self.group_axis):
+            raise ValueError('MX quantizer (%s): packed tensor of format %s, group size %d, group_axis %s'
+                             % (self.extra_repr(), packed.element_format, packed.group_size, packed.group_axis))
+        shape = tuple(packed.shape)
+        n = 1
+        for d in shape:
+            n *= d
+        codes, scale = packed.codes, packed.scale_e8m0
+        if codes.dtype != torch.uint8 or scale.dtype != torch.uint8:
+            raise ValueError('MX quantizer: codes and scale_e8m0 are uint8, got %s and %s' % (codes.dtype, scale.dtype))
+        if n == 0 or n % self.group_size or codes.numel() * 8 != n * self.format.bit_width or \
+                scale.numel() * self.group_size != n or codes.device != scale.device:
+            raise ValueError('MX quantizer: %d code bytes and %d scale bytes do not hold a tensor of shape %s in %s with '
+                             'groups of %d' % (codes.numel(), scale.numel(), shape, self.element_format, self.group_size))
+        codes, scale = codes.contiguous().reshape(-1), scale.contiguous().reshape(-1)
+        if config.FUSED_PATHS and codes.is_cuda and self.group_size in FUSED_GROUP_SIZES and \
+                codes.data_ptr() % 16 == 0 and scale.data_ptr() % 16 == 0:
+            y = nat.mx_decode(codes, scale, self.group_size, self.format.code, dtype)
+        else:
+            y = _composed_decode(codes, scale, self.group_size, self.format, dtype)
+        return y.reshape(shape)

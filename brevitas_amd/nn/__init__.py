@@ -63,6 +63,14 @@ class _QuantWeightMixin:
             return self.weight, None, None, None
         return self.weight_quant(self.weight)
 
+    def packed_weight(self):
+        """-> MXPacked: the weight as packed MX element codes and E8M0 scale bytes (an MX weight quantizer only)"""
+        from brevitas_amd.core.quant.mx import MXQuant
+        if not isinstance(self.weight_quant, MXQuant):
+            raise TypeError('packed_weight: the weight quantizer %s is no MX quantizer'
+                            % type(self.weight_quant).__name__)
+        return self.weight_quant.to_mx_codes(self.weight)
+
     def quant_input(self, x):
         return self.input_quant(x)[0] if self.input_quant is not None else x
 

@@ -725,7 +725,8 @@ int bvq_group_quant_bwd(const bvq_quant_desc* desc, const void* g, const void* x
  * from x.  The order in which a group's float32 terms are added is fixed by the kernel (segmented butterfly).
  * Covered: float32 / bfloat16 / float16; group_size 16, 32, 64, 128 or 256; every tensor pointer on a 16-byte boundary.
  * Anything else returns BVQ_ERR_UNSUPPORTED with a bvq_last_error() text, found before anything touches the device;
- * bvq_mx_quant_supported answers 1 / 0.  Emitting packed element codes and E8M0 scale bytes is not part of this. */
+ * bvq_mx_quant_supported answers 1 / 0.  The packed element codes and E8M0 scale bytes of the same q_i and E are
+ * the "MX wire format" section below (bvq_mx_encode, bvq_mx_decode). */
 typedef enum bvq_mx_format {
   BVQ_MX_E4M3 = 0,
   BVQ_MX_E5M2 = 1,
@@ -740,6 +741,46 @@ int bvq_mx_quant_fwd(int dtype, int64_t groups, int group_size, int format, int 
                      void* scale, bvq_stream_t stream);
 int bvq_mx_quant_bwd(int dtype, int64_t groups, int group_size, int format, int scale_rule, int clamp_ste,
                      const void* g, const void* x, const void* gscale, void* dx, bvq_stream_t stream);
+
+/* ---- MX wire format: packed element codes and E8M0 scale bytes (OCP Microscaling v1.0) ----------------------------------
+ * With q_i and E of the MX section above (its steps unchanged):
+ * Scale byte (E8M0), one per group: E + 127, which lies in [1, 254]; 0xFF for a group whose abs-max is NaN or Inf.
+ *     Byte 0 (2^-127) is never produced: E is clamped to -126.
+ * Element code of q_i: sign bit on top, then the exponent field, then the mantissa field.
+ *     format  code width  bias  max_val -> code
+ *     E4M3    8 bits       7    448   -> 0x7E
+ *     E5M2    8 bits      15    57344 -> 0x7B
+ *     E3M2    6 bits       3    28    -> 0x1F
+ *     E2M3    6 bits       1    7.5   -> 0x1F
+ *     E2M1    4 bits       1    6     -> 0x7
+ *     |q_i| below 2^emin is a subnormal code (exponent field 0); the sign of q_i is kept on a zero; the NaN and Inf
+ *     codes of E4M3 and E5M2 are never produced.  MXINT8: the two's-complement int8 k = q_i * 64, |k| <= 127; a
+ *     negative zero becomes 0.  Every element code of a group that is not finite is 0: its scale byte 0xFF makes the
+ *     block NaN.
+ * Packing, in memory order, with the group boundaries of the fake-quantizer:
+ *     8-bit formats  one byte per element
+ *     E2M1           two elements per byte: element 2j in bits 0-3, element 2j + 1 in bits 4-7
+ *     E3M2, E2M3     a dense little-endian bit stream: element j of the tensor occupies bits [6j, 6j + 6), so 4
+ *                    elements fill 3 bytes and a group of 32 fills 24
+ *     A tensor of n elements gives n * bits / 8 code bytes and n / group_size scale bytes.
+ * Decode is the inverse on ANY byte pattern, not only those the encoder emits: scale byte 0 reads as 2^-127 and 0xFF
+ * makes every element of the group NaN; the E4M3 codes 0x7F and 0xFF read as NaN; E5M2 codes with exponent field 31
+ * read as +-Inf (mantissa 0) or NaN; MXINT8 -128 reads as -2.0.  y_i = T(v_i * 2^E) with the product in float32; it is
+ * exact (v_i has at most 7 significant bits, and the smallest magnitude of any format times 2^-127 is 2^-143).  On the
+ * encoder's own output the result is therefore the y of bvq_mx_quant_fwd bit for bit, with two exceptions: a NaN equals
+ * any NaN, and a negative zero of MXINT8 comes back positive.
+ * bvq_mx_encode: one launch on the walk of bvq_mx_quant_fwd with the same arithmetic for E and q_i; x is read once, the
+ * codes and the scale bytes are written once (16-byte and dword stores assembled across lanes; byte stores only for a
+ * last scale dword that the tensor ends inside), nothing is written past n * bits / 8 code bytes and `groups` scale
+ * bytes; no workspace, no atomics.  bvq_mx_decode: one launch, codes and scale bytes -> y of dtype T.
+ * Covered, both ways: float32 / bfloat16 / float16; group_size 16, 32, 64, 128 or 256; x, codes, scale_e8m0 and y on
+ * 16-byte boundaries.  Anything else returns BVQ_ERR_UNSUPPORTED with a bvq_last_error() text, found before anything
+ * touches the device; bvq_mx_encode_supported answers 1 / 0. */
+int bvq_mx_encode_supported(int dtype, int64_t groups, int group_size, int format, const void* x);
+int bvq_mx_encode(int dtype, int64_t groups, int group_size, int format, int scale_rule, const void* x, void* codes,
+                  void* scale_e8m0, bvq_stream_t stream);
+int bvq_mx_decode(int dtype, int64_t groups, int group_size, int format, const void* codes, const void* scale_e8m0,
+                  void* y, bvq_stream_t stream);
 
 /* Diagnostic entry (no reference counterpart): the float32 quotient the float16 quantizer kernels compute for a
  * numerator a[i] and a scale scales[j] -- the product with the correctly rounded reciprocal, corrected by one exact
