@@ -54,7 +54,7 @@ EXPORTS = (
     'bvq_absmax_fakequant_cluster_supported', 'bvq_absmax_fakequant_cluster', 'bvq_absmax_fakequant_cluster_form',
     'bvq_selftest_pre_op', 'bvq_group_quant_supported', 'bvq_group_quant_fwd', 'bvq_group_quant_bwd',
     'bvq_mx_quant_supported', 'bvq_mx_quant_fwd', 'bvq_mx_quant_bwd', 'bvq_mx_encode_supported', 'bvq_mx_encode',
-    'bvq_mx_decode')
+    'bvq_mx_decode', 'bvq_nt_threshold_bytes')
 
 
 class QuantDesc(ctypes.Structure):
@@ -107,6 +107,7 @@ def _load(path=None, strict=True):
     lib.bvq_abi_version.restype = i32
     lib.bvq_last_error.restype = ctypes.c_char_p
     sig = {
+        'bvq_nt_threshold_bytes': (i64, []),
         'bvq_unary': (i32, [i32, i32, vp, vp, i64, vp]),
         'bvq_scalar_clamp': (i32, [i32, vp, vp, i64, dbl, i32, dbl, i32, vp]),
         'bvq_tensor_clamp': (i32, [i32, vp, vp, vp, i32, vp, i64, vp]),

@@ -504,6 +504,16 @@ class StatsFakeQuantFn(Function):
         return dx, None, None, None, None, None, None, None, None, None
 
 
+def group_quant_call(x: Tensor, group_size: int, int_threshold: float, qmin: float, qmax: float, clamp_ste):
+    """-> (descriptor, threshold divisor) that nat.group_quant_fwd / group_quant_bwd take for x in groups of `group_size`
+    (GroupStatsFakeQuantFn, and the tests that launch the kernels through those wrappers)"""
+    code = nat.dtype_code(x.dtype)
+    desc = nat.QuantDesc(1, x.numel() // group_size, group_size, code, code, code, nat.F32, 1, 0, qmin, qmax,
+                         nat.ROUND, scalar_mode(), int(clamp_ste), nat.OUT_DEQUANT, nat.PRE_NONE)
+    # a dimensioned threshold keeps its dtype: the 0-dim float32 int_threshold is converted to it
+    return desc, _as_dtype_value(int_threshold, x.dtype)
+
+
 class GroupStatsFakeQuantFn(Function):
     """Group-wise weights: AbsMax per group of `group_size` consecutive elements -> clamp_min(min_val) -> / int_threshold
     -> IntQuant with a zero zero-point, x -> (y like x, scale [groups, 1]).  One launch each way (csrc/bvq_group_quant.hip):
@@ -513,11 +523,7 @@ class GroupStatsFakeQuantFn(Function):
     @staticmethod
     def forward(ctx, x, group_size, min_val, int_threshold, qmin, qmax, clamp_ste):
         ctx.set_materialize_grads(False)  # an unused `scale` output must not cost a zero-fill + add
-        code = nat.dtype_code(x.dtype)
-        desc = nat.QuantDesc(1, x.numel() // group_size, group_size, code, code, code, nat.F32, 1, 0, qmin, qmax,
-                             nat.ROUND, scalar_mode(), int(clamp_ste), nat.OUT_DEQUANT, nat.PRE_NONE)
-        # a dimensioned threshold keeps its dtype: the 0-dim float32 int_threshold is converted to it
-        thr_div = _as_dtype_value(int_threshold, x.dtype)
+        desc, thr_div = group_quant_call(x, group_size, int_threshold, qmin, qmax, clamp_ste)
         y, scale, stat = nat.group_quant_fwd(desc, x, min_val, thr_div)
         ctx.desc, ctx.min_val, ctx.thr_div = desc, min_val, thr_div
         ctx.save_for_backward(x, scale, stat)

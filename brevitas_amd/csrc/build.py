@@ -1,6 +1,6 @@
 """Build libbvq.so (the C-ABI HIP library) in-tree for gfx950.
 
-    python -m brevitas_amd.csrc.build [--force]
+    python -m brevitas_amd.csrc.build [--force] [--nt0]
 
 hipcc cross-compiles without a GPU; the resulting brevitas_amd/libbvq.so is git-ignored but travels
 to the GPU box with the source snapshot.
@@ -111,6 +111,47 @@ def build(force=False, verbose=False, defines=(), out=None):
     return lib_path
 
 
+NT0_LIB = os.path.join(PKG, 'libbvq_nt0.so')
+NT0_DEFINE = 'BVQ_NT_BYTES=0'
+
+
+def build_nt0(force=False, verbose=False):
+    """The forced-NT variant for the tests (tests/test_gpu_group_walk.py): the library with a non-temporal threshold of
+    0 bytes, so every entry point launches its NT = true kernels at any size -> brevitas_amd/libbvq_nt0.so.  The
+    threshold lives in bvq_common.hip alone: that file is compiled again with -DBVQ_NT_BYTES=0 into an object directory
+    of its own and linked with the other objects of the normal build, which this runs after."""
+    obj_dir = os.path.join(OBJ_DIR, 'nt0')
+    stamp = os.path.join(obj_dir, 'stamp')
+    dig = _digest() + ' ' + NT0_DEFINE + ' -Bsymbolic'
+    if not force and os.path.exists(NT0_LIB) and os.path.exists(stamp):
+        with open(stamp) as fh:
+            if fh.read().strip() == dig:
+                return NT0_LIB
+    others = [os.path.join(OBJ_DIR, objname) for src, _, objname in SOURCES if src != 'bvq_common.hip']
+    if source_digest() is None or not all(os.path.exists(o) for o in others):
+        build(force=True, verbose=verbose)   # (objects are not kept with a library that was copied here)
+    os.makedirs(obj_dir, exist_ok=True)
+    hipcc = _hipcc()
+    obj = os.path.join(obj_dir, 'bvq_common.o')
+    cmd = [hipcc] + FLAGS + ['-D' + NT0_DEFINE, '-c', os.path.join(CSRC, 'bvq_common.hip'), '-o', obj]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError('hipcc failed on bvq_common.hip (%s):\n%s\n%s' % (NT0_DEFINE, r.stdout, r.stderr))
+    # -Bsymbolic: the variant's references to its own symbols bind inside it.  Both libraries export every internal
+    # symbol, and once the package's libbvq.so is in the global scope (the C++ autograd node re-opens it RTLD_GLOBAL) a
+    # plain link would bind the variant's calls of nt_threshold_bytes() -- and its kernels' host stubs -- to that copy
+    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,-Bsymbolic', '-o', NT0_LIB + '.tmp', obj] + others
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError('link failed:\n%s\n%s' % (r.stdout, r.stderr))
+    os.replace(NT0_LIB + '.tmp', NT0_LIB)
+    with open(stamp, 'w') as fh:
+        fh.write(dig)
+    return NT0_LIB
+
+
 AUTOGRAD_SO = os.path.join(PKG, '_bvq_autograd.so')
 
 
@@ -147,3 +188,5 @@ if __name__ == '__main__':
     outs = [a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--out=')]
     print(build(force='--force' in sys.argv, verbose='-v' in sys.argv, defines=defs,
                 out=os.path.abspath(outs[0]) if outs else None))
+    if '--nt0' in sys.argv:
+        print(build_nt0(force='--force' in sys.argv, verbose='-v' in sys.argv))

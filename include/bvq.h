@@ -136,6 +136,9 @@ typedef struct bvq_quant_desc {
 int bvq_abi_version(void);
 /* message of the calling thread's last failing call ("" if none) */
 const char* bvq_last_error(void);
+/* bytes of traffic from which an entry point launches the non-temporal variant of its kernels (the cache policy changes
+ * no value): 256 MiB in the shipped library, 0 in the forced-NT build the tests load (csrc/build.py, build_nt0) */
+int64_t bvq_nt_threshold_bytes(void);
 
 /* ---- elementwise STE namespace (seam 1) ----------------------------------------------------
  * Forward math of torch.ops.autograd_ste_ops.<name>_impl / brevitas.ops.autograd_ste_ops.<name>_impl

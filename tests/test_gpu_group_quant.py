@@ -22,8 +22,10 @@ MANT = {'f32': 23, 'bf16': 7, 'f16': 10}
 MIN_EXP = {'f32': -126, 'bf16': -126, 'f16': -14}
 # [out, K], group size: less than one wave load in every dtype; a whole wave per float32 group with a ragged last
 # wave; a number of groups that is no multiple of the groups per load; several waves, workgroups and the full depth
-SHAPES = [((3, 64), 16), ((5, 512), 256), ((7, 96), 32), ((64, 4096), 128)]
-shapes = pytest.mark.parametrize('shape,g', SHAPES, ids=['3x64-g16', '5x512-g256', '7x96-g32', '64x4096-g128'])
+# and 27 groups of 64, ragged in every dtype
+SHAPES = [((3, 64), 16), ((5, 512), 256), ((7, 96), 32), ((64, 4096), 128), ((9, 192), 64)]
+shapes = pytest.mark.parametrize('shape,g', SHAPES, ids=['3x64-g16', '5x512-g256', '7x96-g32', '64x4096-g128',
+                                                         '9x192-g64'])
 dtypes = pytest.mark.parametrize('dn', ['f32', 'bf16', 'f16'])
 
 

@@ -22,9 +22,9 @@ DEV = 'cuda:0'
 # the last dimension -- and 15 groups of 16: the scale bytes end inside a dword, and the 120 FP4 code bytes of float32
 # inside 16 bytes
 SHAPES = [((3, 64), 16, 'flat'), ((5, 512), 256, 'flat'), ((7, 96), 32, 'flat'), ((64, 4096), 128, 'flat'),
-          ((2, 5, 64), 32, 'last'), ((3, 80), 16, 'flat')]
+          ((2, 5, 64), 32, 'last'), ((3, 80), 16, 'flat'), ((9, 192), 64, 'flat')]   # and 27 ragged groups of 64
 shapes = pytest.mark.parametrize('shape,g,axis', SHAPES, ids=['3x64-g16', '5x512-g256', '7x96-g32', '64x4096-g128',
-                                                              '2x5x64-g32-last', '3x80-g16'])
+                                                              '2x5x64-g32-last', '3x80-g16', '9x192-g64'])
 dtypes = pytest.mark.parametrize('dn', ['f32', 'bf16', 'f16'])
 
 

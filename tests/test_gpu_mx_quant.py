@@ -18,9 +18,10 @@ DEV = 'cuda:0'
 # ragged last wave; a number of groups that is no multiple of the groups per load; several workgroups at full depth;
 # and groups along the last dimension of an activation
 SHAPES = [((3, 64), 16, 'flat'), ((5, 512), 256, 'flat'), ((7, 96), 32, 'flat'), ((64, 4096), 128, 'flat'),
-          ((2, 5, 64), 32, 'last')]
+          ((2, 5, 64), 32, 'last'), ((9, 192), 64, 'flat')]     # and 27 groups of 64, ragged in every dtype
 shapes = pytest.mark.parametrize('shape,g,axis', SHAPES,
-                                 ids=['3x64-g16', '5x512-g256', '7x96-g32', '64x4096-g128', '2x5x64-g32-last'])
+                                 ids=['3x64-g16', '5x512-g256', '7x96-g32', '64x4096-g128', '2x5x64-g32-last',
+                                      '9x192-g64'])
 dtypes = pytest.mark.parametrize('dn', ['f32', 'bf16', 'f16'])
 
 
