@@ -37,26 +37,6 @@ ABI_VERSION = 2
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
-EXPORTS = (
-    'bvq_abi_version', 'bvq_last_error', 'bvq_unary', 'bvq_stats_pre', 'bvq_scalar_clamp', 'bvq_tensor_clamp',
-    'bvq_tensor_clamp_bwd', 'bvq_abs_binary_sign_grad_bwd', 'bvq_stats_workspace_bytes', 'bvq_stats',
-    'bvq_absmax_scale', 'bvq_running_stats_update', 'bvq_scale_from_stat', 'bvq_shard_pack', 'bvq_shard_unpack', 'bvq_abs_moments_workspace_bytes', 'bvq_abs_moments',
-    'bvq_abs_affine_bwd', 'bvq_kth_workspace_bytes', 'bvq_kth_value', 'bvq_kth_pair', 'bvq_kth_passes',
-    'bvq_kth_hist_offset', 'bvq_kth_begin', 'bvq_kth_hist', 'bvq_kth_pick', 'bvq_kth_finish', 'bvq_stat_bwd', 'bvq_tie_info_bytes', 'bvq_stat_tie_scan', 'bvq_stat_tie_apply', 'bvq_stat_tie_apply_dscale', 'bvq_fakequant_fwd', 'bvq_stats_fakequant_fwd_workspace_bytes', 'bvq_stats_fakequant_fwd',
-    'bvq_fakequant_bwd_workspace_bytes', 'bvq_fakequant_bwd_stats_workspace_bytes', 'bvq_fakequant_bwd_stats', 'bvq_fakequant_bwd',
-    'bvq_learned_scale', 'bvq_fakequant_bwd_learned', 'bvq_variant_fwd', 'bvq_variant_bwd_workspace_bytes', 'bvq_variant_bwd',
-    'bvq_fakequant_fwd_bounds', 'bvq_fakequant_bwd_bounds', 'bvq_histc', 'bvq_absmax_scale_running', 'bvq_selftest_div_f16r',
-    'bvq_kthw_plan', 'bvq_kthw_begin', 'bvq_kthw_hist', 'bvq_kthw_pick', 'bvq_kthw_finish',
-    'bvq_absmax_onepass_supported', 'bvq_absmax_scale_onepass', 'bvq_fakequant_bwd_stats_onepass_supported',
-    'bvq_fakequant_bwd_stats_onepass', 'bvq_scale_from_stat_running', 'bvq_fakequant_bwd_shard',
-    'bvq_shard_unpack_deposit', 'bvq_absmax_list_supported', 'bvq_absmax_scale_list', 'bvq_weight_list_supported',
-    'bvq_weight_quant_list_fwd', 'bvq_weight_quant_list_bwd_workspace_bytes', 'bvq_weight_quant_list_bwd',
-    'bvq_absmax_fakequant_cluster_supported', 'bvq_absmax_fakequant_cluster', 'bvq_absmax_fakequant_cluster_form',
-    'bvq_selftest_pre_op', 'bvq_group_quant_supported', 'bvq_group_quant_fwd', 'bvq_group_quant_bwd',
-    'bvq_mx_quant_supported', 'bvq_mx_quant_fwd', 'bvq_mx_quant_bwd', 'bvq_mx_encode_supported', 'bvq_mx_encode',
-    'bvq_mx_decode', 'bvq_nt_threshold_bytes')
-
-
 class QuantDesc(ctypes.Structure):
     """bvq_quant_desc of include/bvq.h"""
     _fields_ = [
@@ -96,6 +76,99 @@ class BvqError(RuntimeError):
     pass
 
 
+# The signature of every entry of include/bvq.h that takes arguments: name -> (restype, argtypes).
+# tests/test_cabi_symbols.py holds it against the header's prototypes.
+_vp, _i64, _i32, _dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
+_qd, _vd = ctypes.POINTER(QuantDesc), ctypes.POINTER(VariantDesc)
+_SIG = {
+    'bvq_nt_threshold_bytes': (_i64, []),
+    'bvq_unary': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp]),
+    'bvq_scalar_clamp': (_i32, [_i32, _vp, _vp, _i64, _dbl, _i32, _dbl, _i32, _vp]),
+    'bvq_tensor_clamp': (_i32, [_i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
+    'bvq_tensor_clamp_bwd': (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
+    'bvq_abs_binary_sign_grad_bwd': (_i32, [_i32, _vp, _vp, _vp, _i64, _vp]),
+    'bvq_stats_workspace_bytes': (_i64, [_i32, _i32, _i64, _i64, _i64]),
+    'bvq_stats': (_i32, [_i32, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
+    'bvq_stats_pre': (_i32, [_i32, _i32, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
+    'bvq_stat_bwd': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
+    'bvq_fakequant_fwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_stats_fakequant_fwd_workspace_bytes': (_i64, [_qd, _vp, _vp]),
+    'bvq_stats_fakequant_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'bvq_fakequant_bwd_workspace_bytes': (_i64, [_qd]),
+    'bvq_fakequant_bwd_stats_workspace_bytes': (_i64, [_qd]),
+    'bvq_fakequant_bwd_stats': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _vp, _i64, _vp]),
+    'bvq_fakequant_bwd_stats_onepass_supported': (_i32, [_qd]),
+    'bvq_fakequant_bwd_stats_onepass': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _vp, _i64, _vp, _i64, _vp]),
+    'bvq_absmax_scale': (_i32, [_i32, _i32, _vp, _i64, _i64, _i64, _vp, _dbl, _i32, _dbl, _i32, _vp, _vp, _i64, _vp]),
+    'bvq_absmax_scale_running': (_i32, [_i32, _i32, _vp, _i64, _i64, _i64, _vp, _dbl, _i32, _dbl, _i32, _vp, _i32, _vp, _dbl, _i32, _vp, _i64, _vp]),
+    'bvq_absmax_onepass_supported': (_i32, [_i32, _vp, _i64, _i64, _i64]),
+    'bvq_absmax_scale_onepass': (_i32, [_i32, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _dbl, _i32, _dbl, _i32, _vp, _i32, _vp, _dbl, _i32, _vp, _i64, _vp]),
+    'bvq_absmax_list_supported': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp]),
+    'bvq_absmax_scale_list': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _vp, _dbl, _i32, _dbl, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),
+    'bvq_running_stats_update': (_i32, [_i32, _vp, _i32, _vp, _i64, _dbl, _i32, _vp]),
+    'bvq_scale_from_stat': (_i32, [_vp, _i64, _i32, _vp, _dbl, _i32, _dbl, _i32, _vp, _vp]),
+    'bvq_scale_from_stat_running': (_i32, [_vp, _i64, _i32, _vp, _dbl, _i32, _dbl, _i32, _vp, _i32, _vp, _dbl, _i32, _vp]),
+    'bvq_fakequant_bwd_shard': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp]),
+    'bvq_shard_unpack_deposit': (_i32, [_i32, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i64, _i32, _dbl, _i32, _i32, _vp, _vp]),
+    'bvq_shard_pack': (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    'bvq_shard_unpack': (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'bvq_abs_moments_workspace_bytes': (_i64, [_i32, _i64, _i64, _i64]),
+    'bvq_abs_moments': (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    'bvq_abs_affine_bwd': (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    'bvq_kth_workspace_bytes': (_i64, [_i32, _i64, _i64, _i64]),
+    'bvq_kth_value': (_i32, [_i32, _i32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    'bvq_kth_pair': (_i32, [_i32, _i32, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    'bvq_kth_passes': (_i32, [_i32]),
+    'bvq_kth_hist_offset': (_i64, [_i32, _i64, _i32]),
+    'bvq_kth_begin': (_i32, [_i32, _i64, _i32, _i64, _dbl, _vp, _i64, _vp]),
+    'bvq_kth_hist': (_i32, [_i32, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
+    'bvq_kth_pick': (_i32, [_i32, _i64, _i32, _i32, _dbl, _vp, _i64, _vp]),
+    'bvq_kth_finish': (_i32, [_i32, _i32, _i64, _vp, _vp, _i64, _vp]),
+    'bvq_kthw_plan': (_i32, [_i32, _i32, _i32, _vp, _vp]),
+    'bvq_kthw_begin': (_i32, [_i32, _i32, _vp, _i64, _vp]),
+    'bvq_kthw_hist': (_i32, [_i32, _i32, _vp, _i64, _i32, _vp, _i64, _vp]),
+    'bvq_kthw_pick': (_i32, [_i32, _i32, _i32, _i32, _i64, _dbl, _vp, _i64, _vp]),
+    'bvq_kthw_finish': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp]),
+    'bvq_tie_info_bytes': (_i64, [_i64]),
+    'bvq_stat_tie_scan': (_i32, [_i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    'bvq_stat_tie_apply': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
+    'bvq_stat_tie_apply_dscale': (_i32, [_i32, _i32, _vp, _vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    'bvq_fakequant_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'bvq_learned_scale': (_i32, [_i32, _vp, _i64, _dbl, _i32, _dbl, _i32, _vp, _vp]),
+    'bvq_histc': (_i32, [_i32, _vp, _i64, _vp, _i32, _vp, _vp]),
+    'bvq_selftest_div_f16r': (_i32, [_vp, _i32, _vp, _i32, _vp, _vp]),
+    'bvq_selftest_pre_op': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'bvq_fakequant_fwd_bounds': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_fakequant_bwd_bounds': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'bvq_variant_fwd': (_i32, [_vd, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_variant_bwd_workspace_bytes': (_i64, [_vd]),
+    'bvq_variant_bwd': (_i32, [_vd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'bvq_weight_list_supported': (_i32, [_i32, _i32, _i32, _vp, _i64]),
+    'bvq_weight_quant_list_fwd': (_i32, [_i32, _i32, _i32, _i32, _vp, _vp]),
+    'bvq_weight_quant_list_bwd_workspace_bytes': (_i64, [_i32, _i32, _vp]),
+    'bvq_weight_quant_list_bwd': (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),
+    'bvq_absmax_fakequant_cluster_supported': (_i64, [_qd, _vp, _vp]),
+    'bvq_absmax_fakequant_cluster': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _i32, _vp, _dbl, _i32, _vp,
+                                            _vp, _i64, _i32, _vp, _vp]),
+    'bvq_absmax_fakequant_cluster_form': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _i32, _vp, _dbl, _i32,
+                                                 _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    'bvq_group_quant_supported': (_i32, [_qd, _vp]),
+    'bvq_group_quant_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp]),
+    'bvq_group_quant_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
+    'bvq_mx_quant_supported': (_i32, [_i32, _i64, _i32, _i32, _vp]),
+    'bvq_mx_quant_fwd': (_i32, [_i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'bvq_mx_quant_bwd': (_i32, [_i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_mx_encode_supported': (_i32, [_i32, _i64, _i32, _i32, _vp]),
+    'bvq_mx_encode': (_i32, [_i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'bvq_mx_decode': (_i32, [_i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'bvq_fakequant_bwd_learned': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _i64, _vp]),
+}
+
+EXPORTS = ('bvq_abi_version', 'bvq_last_error') + tuple(_SIG)
+
+_TORCH_DTYPES = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
+
+
 def _load(path=None, strict=True):
     path = path or LIB_PATH
     if not os.path.exists(path):
@@ -103,93 +176,9 @@ def _load(path=None, strict=True):
             'brevitas_amd: %s is missing. Build it with `python -m brevitas_amd.csrc.build` '
             '(needs hipcc, gfx950). There is no fallback backend.' % path)
     lib = ctypes.CDLL(path)
-    vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
-    lib.bvq_abi_version.restype = i32
+    lib.bvq_abi_version.restype = _i32
     lib.bvq_last_error.restype = ctypes.c_char_p
-    sig = {
-        'bvq_nt_threshold_bytes': (i64, []),
-        'bvq_unary': (i32, [i32, i32, vp, vp, i64, vp]),
-        'bvq_scalar_clamp': (i32, [i32, vp, vp, i64, dbl, i32, dbl, i32, vp]),
-        'bvq_tensor_clamp': (i32, [i32, vp, vp, vp, i32, vp, i64, vp]),
-        'bvq_tensor_clamp_bwd': (i32, [i32, vp, vp, vp, vp, i32, vp, i64, vp]),
-        'bvq_abs_binary_sign_grad_bwd': (i32, [i32, vp, vp, vp, i64, vp]),
-        'bvq_stats_workspace_bytes': (i64, [i32, i32, i64, i64, i64]),
-        'bvq_stats': (i32, [i32, i32, vp, i64, i64, i64, i32, vp, vp, i64, vp]),
-        'bvq_stats_pre': (i32, [i32, i32, i32, vp, i64, i64, i64, i32, vp, vp, i64, vp]),
-        'bvq_stat_bwd': (i32, [i32, i32, vp, vp, vp, vp, i64, i64, i64, i32, vp, i64, vp]),
-        'bvq_fakequant_fwd': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp]),
-        'bvq_stats_fakequant_fwd_workspace_bytes': (i64, [ctypes.POINTER(QuantDesc), vp, vp]),
-        'bvq_stats_fakequant_fwd': (i32, [ctypes.POINTER(QuantDesc), vp, dbl, i32, dbl, vp, vp, vp, vp, i64, vp]),
-        'bvq_fakequant_bwd_workspace_bytes': (i64, [ctypes.POINTER(QuantDesc)]),
-        'bvq_fakequant_bwd_stats_workspace_bytes': (i64, [ctypes.POINTER(QuantDesc)]),
-        'bvq_fakequant_bwd_stats': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, i32, dbl, i32, vp, i64, vp]),
-        'bvq_fakequant_bwd_stats_onepass_supported': (i32, [ctypes.POINTER(QuantDesc)]),
-        'bvq_fakequant_bwd_stats_onepass': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, i32, dbl, i32, vp, i64, vp, i64, vp]),
-        'bvq_absmax_scale': (i32, [i32, i32, vp, i64, i64, i64, vp, dbl, i32, dbl, i32, vp, vp, i64, vp]),
-        'bvq_absmax_scale_running': (i32, [i32, i32, vp, i64, i64, i64, vp, dbl, i32, dbl, i32, vp, i32, vp, dbl, i32, vp, i64, vp]),
-        'bvq_absmax_onepass_supported': (i32, [i32, vp, i64, i64, i64]),
-        'bvq_absmax_scale_onepass': (i32, [i32, i32, vp, i64, i64, i64, i32, vp, dbl, i32, dbl, i32, vp, i32, vp, dbl, i32, vp, i64, vp]),
-        'bvq_absmax_list_supported': (i32, [i32, i32, vp, vp, i64, vp]),
-        'bvq_absmax_scale_list': (i32, [i32, i32, vp, vp, i64, vp, vp, dbl, i32, dbl, i32, vp, vp, i64, vp, i64, vp]),
-        'bvq_running_stats_update': (i32, [i32, vp, i32, vp, i64, dbl, i32, vp]),
-        'bvq_scale_from_stat': (i32, [vp, i64, i32, vp, dbl, i32, dbl, i32, vp, vp]),
-        'bvq_scale_from_stat_running': (i32, [vp, i64, i32, vp, dbl, i32, dbl, i32, vp, i32, vp, dbl, i32, vp]),
-        'bvq_fakequant_bwd_shard': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp, i64, vp]),
-        'bvq_shard_unpack_deposit': (i32, [i32, vp, vp, vp, i32, i64, i32, vp, i64, i32, dbl, i32, i32, vp, vp]),
-        'bvq_shard_pack': (i32, [vp, vp, i64, i32, i32, vp, vp]),
-        'bvq_shard_unpack': (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp]),
-        'bvq_abs_moments_workspace_bytes': (i64, [i32, i64, i64, i64]),
-        'bvq_abs_moments': (i32, [i32, vp, i64, i64, i64, vp, vp, i64, vp]),
-        'bvq_abs_affine_bwd': (i32, [i32, vp, vp, vp, vp, i64, i64, i64, vp]),
-        'bvq_kth_workspace_bytes': (i64, [i32, i64, i64, i64]),
-        'bvq_kth_value': (i32, [i32, i32, vp, i64, i64, i64, i64, vp, vp, i64, vp]),
-        'bvq_kth_pair': (i32, [i32, i32, vp, i64, i64, i64, i64, i64, vp, vp, i64, vp]),
-        'bvq_kth_passes': (i32, [i32]),
-        'bvq_kth_hist_offset': (i64, [i32, i64, i32]),
-        'bvq_kth_begin': (i32, [i32, i64, i32, i64, dbl, vp, i64, vp]),
-        'bvq_kth_hist': (i32, [i32, i32, vp, i64, i64, i64, i32, vp, i64, vp]),
-        'bvq_kth_pick': (i32, [i32, i64, i32, i32, dbl, vp, i64, vp]),
-        'bvq_kth_finish': (i32, [i32, i32, i64, vp, vp, i64, vp]),
-        'bvq_kthw_plan': (i32, [i32, i32, i32, vp, vp]),
-        'bvq_kthw_begin': (i32, [i32, i32, vp, i64, vp]),
-        'bvq_kthw_hist': (i32, [i32, i32, vp, i64, i32, vp, i64, vp]),
-        'bvq_kthw_pick': (i32, [i32, i32, i32, i32, i64, dbl, vp, i64, vp]),
-        'bvq_kthw_finish': (i32, [i32, i32, vp, vp, i64, vp]),
-        'bvq_tie_info_bytes': (i64, [i64]),
-        'bvq_stat_tie_scan': (i32, [i32, i32, vp, vp, i64, i64, i64, vp, vp, vp]),
-        'bvq_stat_tie_apply': (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]),
-        'bvq_stat_tie_apply_dscale': (i32, [i32, i32, vp, vp, vp, i32, dbl, i32, vp, vp, vp, i64, i64, i64, vp]),
-        'bvq_fakequant_bwd': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
-        'bvq_learned_scale': (i32, [i32, vp, i64, dbl, i32, dbl, i32, vp, vp]),
-        'bvq_histc': (i32, [i32, vp, i64, vp, i32, vp, vp]),
-        'bvq_selftest_div_f16r': (i32, [vp, i32, vp, i32, vp, vp]),
-        'bvq_selftest_pre_op': (i32, [i32, i32, vp, vp, vp, vp, i64, vp]),
-        'bvq_fakequant_fwd_bounds': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp]),
-        'bvq_fakequant_bwd_bounds': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
-        'bvq_variant_fwd': (i32, [ctypes.POINTER(VariantDesc), vp, vp, vp, vp, vp, vp, vp]),
-        'bvq_variant_bwd_workspace_bytes': (i64, [ctypes.POINTER(VariantDesc)]),
-        'bvq_variant_bwd': (i32, [ctypes.POINTER(VariantDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
-        'bvq_weight_list_supported': (i32, [i32, i32, i32, vp, i64]),
-        'bvq_weight_quant_list_fwd': (i32, [i32, i32, i32, i32, vp, vp]),
-        'bvq_weight_quant_list_bwd_workspace_bytes': (i64, [i32, i32, vp]),
-        'bvq_weight_quant_list_bwd': (i32, [i32, i32, i32, i32, i32, vp, vp, i64, vp, i64, vp]),
-        'bvq_absmax_fakequant_cluster_supported': (i64, [ctypes.POINTER(QuantDesc), vp, vp]),
-        'bvq_absmax_fakequant_cluster': (i32, [ctypes.POINTER(QuantDesc), vp, dbl, i32, dbl, vp, vp, i32, vp, dbl, i32, vp,
-                                               vp, i64, i32, vp, vp]),
-        'bvq_absmax_fakequant_cluster_form': (i32, [ctypes.POINTER(QuantDesc), vp, dbl, i32, dbl, vp, vp, i32, vp, dbl, i32,
-                                                    vp, vp, i64, i32, vp, i32, vp, vp]),
-        'bvq_group_quant_supported': (i32, [ctypes.POINTER(QuantDesc), vp]),
-        'bvq_group_quant_fwd': (i32, [ctypes.POINTER(QuantDesc), vp, dbl, i32, dbl, vp, vp, vp, vp]),
-        'bvq_group_quant_bwd': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, dbl, i32, dbl, vp, vp]),
-        'bvq_mx_quant_supported': (i32, [i32, i64, i32, i32, vp]),
-        'bvq_mx_quant_fwd': (i32, [i32, i64, i32, i32, i32, vp, vp, vp, vp]),
-        'bvq_mx_quant_bwd': (i32, [i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
-        'bvq_mx_encode_supported': (i32, [i32, i64, i32, i32, vp]),
-        'bvq_mx_encode': (i32, [i32, i64, i32, i32, i32, vp, vp, vp, vp]),
-        'bvq_mx_decode': (i32, [i32, i64, i32, i32, vp, vp, vp, vp]),
-        'bvq_fakequant_bwd_learned': (i32, [ctypes.POINTER(QuantDesc), vp, vp, vp, vp, vp, vp, vp, i32, dbl, i32, dbl, vp, vp, vp, i64, vp]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in _SIG.items():
         fn = getattr(lib, name, None)
         if fn is None:
             if strict:
@@ -255,16 +244,20 @@ def ptr(t):
 
 
 class _DeviceGuard:
-    """`with torch.cuda.device(dev)` only when dev is not already current (the common case costs one call)"""
-    __slots__ = ('ctx',)
+    """`with torch.cuda.device(dev)` only when dev is not already current (the common case costs one call); yields the
+    current stream of dev, for a wrapper that needs it before its launch: `with _DeviceGuard(dev) as st:`, the arrival
+    buffer asked for and `_call(..., st)` made inside"""
+    __slots__ = ('ctx', 'dev')
 
     def __init__(self, dev):
         idx = dev.index
         self.ctx = None if idx is None or idx == torch.cuda.current_device() else torch.cuda.device(dev)
+        self.dev = dev
 
     def __enter__(self):
         if self.ctx is not None:
             self.ctx.__enter__()
+        return stream_ptr(self.dev)
 
     def __exit__(self, *exc):
         if self.ctx is not None:
@@ -273,13 +266,58 @@ class _DeviceGuard:
 
 
 # Optional measurement hook (bench.py): an object with before(name) / after(name), called around the
-# C-ABI calls listed below on the launching thread, e.g. to record HIP events on the current stream.
+# C-ABI calls that name a bracket (_launch / _call) on the launching thread, e.g. to record HIP events on the current
+# stream.
 _timer = None
 
 
 def set_kernel_timer(timer):
     global _timer
     _timer = timer
+
+
+def _call(name, bracket, *args):
+    """One C-ABI call on the current device: lib.<name>(*args), the stream already last in args; a non-zero return
+    raises BvqError naming the entry.  bracket: the name the kernel timer, if one is set, sees before and after the
+    call (a failing call raises before after()); None: the call is not timed.  Called by _launch, and directly by the
+    wrappers that hold a guard and its stream for their arrival buffer: `with _DeviceGuard(dev) as st:`."""
+    if bracket is not None and _timer is not None:
+        _timer.before(bracket)
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        check(rc, name)
+    if bracket is not None and _timer is not None:
+        _timer.after(bracket)
+
+
+def _launch(dev, name, bracket, *args):
+    """One launching C-ABI call, the whole protocol: _call on dev with dev's current stream as the last argument, where
+    every launching entry of include/bvq.h takes it.  (dev already current, the common case, costs one query.)"""
+    idx = dev.index
+    if idx is not None and idx != torch.cuda.current_device():
+        with _DeviceGuard(dev) as stream:
+            return _call(name, bracket, *args, stream)
+    _call(name, bracket, *args, stream_ptr(dev))
+
+
+def _workspace(dev, query, *args, floor=0):
+    """ask lib.<query>(*args) for a workspace size -> (uint8 tensor of max(size, floor) bytes, size)"""
+    wsb = int(getattr(lib, query)(*args))
+    if wsb < 0:
+        raise BvqError('%s: %s' % (query, last_error()))
+    return torch.empty(max(wsb, floor), dtype=torch.uint8, device=dev), wsb
+
+
+def _scale_args(min_val, int_threshold):
+    """(min_val, use_min, int_threshold) of a scale epilogue: no clamp_min for a min_val of None or 0"""
+    if min_val:
+        return float(min_val), 1, float(int_threshold)
+    return 0.0, 0, float(int_threshold)
+
+
+def _running_args(running, momentum, first_batch):
+    """(run_dtype, running, momentum, first_batch) of a running statistic; running None: none is kept"""
+    return dtype_code(running.dtype) if running is not None else 0, ptr(running), float(momentum), int(first_batch)
 
 
 # ---- arrival buffers of the one-launch kernels --------------------------------------------------------------------
@@ -312,8 +350,7 @@ def unary(op, x):
     dev = require_device(x)
     x = x.contiguous()
     y = torch.empty_like(x)
-    with _DeviceGuard(dev):
-        check(lib.bvq_unary(op, dtype_code(x.dtype), ptr(x), ptr(y), x.numel(), stream_ptr(dev)), 'bvq_unary')
+    _launch(dev, 'bvq_unary', None, op, dtype_code(x.dtype), ptr(x), ptr(y), x.numel())
     return y
 
 
@@ -321,11 +358,9 @@ def scalar_clamp(x, lo, hi):
     dev = require_device(x)
     x = x.contiguous()
     y = torch.empty_like(x)
-    with _DeviceGuard(dev):
-        check(lib.bvq_scalar_clamp(dtype_code(x.dtype), ptr(x), ptr(y), x.numel(),
-                                   0.0 if lo is None else float(lo), int(lo is not None),
-                                   0.0 if hi is None else float(hi), int(hi is not None), stream_ptr(dev)),
-              'bvq_scalar_clamp')
+    _launch(dev, 'bvq_scalar_clamp', None, dtype_code(x.dtype), ptr(x), ptr(y), x.numel(),
+            0.0 if lo is None else float(lo), int(lo is not None), 0.0 if hi is None else float(hi),
+            int(hi is not None))
     return y
 
 
@@ -343,9 +378,7 @@ def tensor_clamp(x, lo, hi, out=None):
     xc = x.contiguous()
     lo, hi, full = _bounds(xc, lo, hi)
     y = out if out is not None else torch.empty_like(xc)
-    with _DeviceGuard(dev):
-        check(lib.bvq_tensor_clamp(dtype_code(xc.dtype), ptr(xc), ptr(lo), ptr(hi), full, ptr(y), xc.numel(),
-                                   stream_ptr(dev)), 'bvq_tensor_clamp')
+    _launch(dev, 'bvq_tensor_clamp', None, dtype_code(xc.dtype), ptr(xc), ptr(lo), ptr(hi), full, ptr(y), xc.numel())
     return y
 
 
@@ -355,9 +388,8 @@ def tensor_clamp_bwd(g, x, lo, hi):
     g = g.to(xc.dtype).contiguous()
     lo, hi, full = _bounds(xc, lo, hi)
     dx = torch.empty_like(xc)
-    with _DeviceGuard(dev):
-        check(lib.bvq_tensor_clamp_bwd(dtype_code(xc.dtype), ptr(g), ptr(xc), ptr(lo), ptr(hi), full, ptr(dx),
-                                       xc.numel(), stream_ptr(dev)), 'bvq_tensor_clamp_bwd')
+    _launch(dev, 'bvq_tensor_clamp_bwd', None, dtype_code(xc.dtype), ptr(g), ptr(xc), ptr(lo), ptr(hi), full, ptr(dx),
+            xc.numel())
     return dx
 
 
@@ -366,10 +398,28 @@ def abs_binary_sign_grad_bwd(g, x):
     xc = x.contiguous()
     g = g.to(xc.dtype).contiguous()
     dx = torch.empty_like(xc)
-    with _DeviceGuard(dev):
-        check(lib.bvq_abs_binary_sign_grad_bwd(dtype_code(xc.dtype), ptr(g), ptr(xc), ptr(dx), xc.numel(),
-                                               stream_ptr(dev)), 'bvq_abs_binary_sign_grad_bwd')
+    _launch(dev, 'bvq_abs_binary_sign_grad_bwd', None, dtype_code(xc.dtype), ptr(g), ptr(xc), ptr(dx), xc.numel())
     return dx
+
+
+def _absmax_onepass(dev, pre_op, x, outer, channels, inner, stat, min_val=None, int_threshold=1.0, scale=None,
+                    running=None, momentum=0.0, first_batch=False):
+    """the one-launch abs-max (the statistic kernel's last-arriving wave per channel finishes it) into `stat`, where
+    the layout is covered and an arrival buffer is to be had -> whether it was launched; if not, the caller takes the
+    two-launch route.  scale: None, or the tensor that takes clamp_min(stat, min_val) / int_threshold; running: None,
+    or the running statistic folded with `stat` in the same launch"""
+    dt = dtype_code(x.dtype)
+    if pre_op not in (PRE_NONE, PRE_RELU) or not lib.bvq_absmax_onepass_supported(dt, ptr(x), outer, channels, inner):
+        return False
+    with _DeviceGuard(dev) as st:
+        arrive = arrival_buffer(dev, st, max(2 * channels, 18))
+        if arrive is None:
+            return False
+        _call('bvq_absmax_scale_onepass', 'bvq_stats', pre_op, dt, ptr(x), outer, channels, inner,
+              dtype_code(stat.dtype), ptr(stat), *_scale_args(min_val, int_threshold),
+              dtype_code(scale.dtype) if scale is not None else 0, ptr(scale),
+              *_running_args(running, momentum, first_batch), ptr(arrive), arrive.numel(), st)
+    return True
 
 
 def stats(kind, x, outer, channels, inner, out_f32=False, pre_op=PRE_NONE):
@@ -379,31 +429,11 @@ def stats(kind, x, outer, channels, inner, out_f32=False, pre_op=PRE_NONE):
     dt = dtype_code(x.dtype)
     nout = channels * (2 if kind == STAT_MINMAX else 1)
     out = torch.empty(nout, dtype=torch.float32 if out_f32 else x.dtype, device=dev)
-    if kind == STAT_ABSMAX and pre_op in (PRE_NONE, PRE_RELU) and \
-            lib.bvq_absmax_onepass_supported(dt, ptr(x), outer, channels, inner):
-        with _DeviceGuard(dev):
-            st = stream_ptr(dev)
-            arrive = arrival_buffer(dev, st, max(2 * channels, 18))
-            if arrive is not None:
-                if _timer is not None:
-                    _timer.before('bvq_stats')
-                check(lib.bvq_absmax_scale_onepass(pre_op, dt, ptr(x), outer, channels, inner, dtype_code(out.dtype),
-                                                   ptr(out), 0.0, 0, 1.0, 0, None, 0, None, 0.0, 0, ptr(arrive),
-                                                   arrive.numel(), st), 'bvq_absmax_scale_onepass')
-                if _timer is not None:
-                    _timer.after('bvq_stats')
-                return out
-    wsb = lib.bvq_stats_workspace_bytes(kind, dt, outer, channels, inner)
-    if wsb < 0:
-        raise BvqError('bvq_stats_workspace_bytes: bad arguments')
-    ws = torch.empty(max(int(wsb), 8), dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_stats')
-        check(lib.bvq_stats_pre(kind, pre_op, dt, ptr(x), outer, channels, inner, dtype_code(out.dtype), ptr(out),
-                                ptr(ws), ws.numel(), stream_ptr(dev)), 'bvq_stats')
-        if _timer is not None:
-            _timer.after('bvq_stats')
+    if kind == STAT_ABSMAX and _absmax_onepass(dev, pre_op, x, outer, channels, inner, out):
+        return out
+    ws, _ = _workspace(dev, 'bvq_stats_workspace_bytes', kind, dt, outer, channels, inner, floor=8)
+    _launch(dev, 'bvq_stats_pre', 'bvq_stats', kind, pre_op, dt, ptr(x), outer, channels, inner, dtype_code(out.dtype),
+            ptr(out), ptr(ws), ws.numel())
     return out
 
 
@@ -418,27 +448,19 @@ def stat_bwd(match, x, stat, gstat, outer, channels, inner, dx=None):
     if dx is None:
         dx = torch.empty_like(x)
     assert dx.is_contiguous() and dx.dtype == x.dtype
-    wsb = lib.bvq_stats_workspace_bytes(STAT_ABSMAX, dt, outer, channels, inner)
-    ws = torch.empty(max(int(wsb), 8), dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_stat_bwd(match, dt, ptr(x), ptr(stat), ptr(gstat), ptr(dx), outer, channels, inner,
-                               mode_add, ptr(ws), ws.numel(), stream_ptr(dev)), 'bvq_stat_bwd')
+    ws, _ = _workspace(dev, 'bvq_stats_workspace_bytes', STAT_ABSMAX, dt, outer, channels, inner, floor=8)
+    _launch(dev, 'bvq_stat_bwd', None, match, dt, ptr(x), ptr(stat), ptr(gstat), ptr(dx), outer, channels, inner,
+            mode_add, ptr(ws), ws.numel())
     return dx
 
 
 def fakequant_fwd(desc, x, scale, zp, want_codes=False, want_y=True):
     """-> y, (y, codes) or codes alone; codes have the element type of desc.codes_dtype"""
     dev = require_device(x, scale, zp)
-    ct = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}[desc.ct_dtype]
-    y = torch.empty(x.shape, dtype=ct, device=dev) if want_y else None
+    y = torch.empty(x.shape, dtype=_TORCH_DTYPES[desc.ct_dtype], device=dev) if want_y else None
     codes = torch.empty(x.shape, dtype=_CODES_TORCH[desc.codes_dtype], device=dev) if want_codes else None
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_fakequant_fwd')
-        check(lib.bvq_fakequant_fwd(ctypes.byref(desc), ptr(x), ptr(scale), ptr(zp), ptr(y), ptr(codes),
-                                    stream_ptr(dev)), 'bvq_fakequant_fwd')
-        if _timer is not None:
-            _timer.after('bvq_fakequant_fwd')
+    _launch(dev, 'bvq_fakequant_fwd', 'bvq_fakequant_fwd', ctypes.byref(desc), ptr(x), ptr(scale), ptr(zp), ptr(y),
+            ptr(codes))
     if not want_y:
         return codes
     return (y, codes) if want_codes else y
@@ -457,14 +479,8 @@ def stats_fakequant_fwd(desc, x, min_val, int_threshold, scale_dtype):
     stat = torch.empty(channels, dtype=x.dtype, device=dev)
     scale = torch.empty(channels, dtype=scale_dtype, device=dev)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_stats_fakequant_fwd')
-        check(lib.bvq_stats_fakequant_fwd(ctypes.byref(desc), ptr(x), float(min_val or 0.0), int(bool(min_val)),
-                                          float(int_threshold), ptr(stat), ptr(scale), ptr(y), ptr(ws), wsb,
-                                          stream_ptr(dev)), 'bvq_stats_fakequant_fwd')
-        if _timer is not None:
-            _timer.after('bvq_stats_fakequant_fwd')
+    _launch(dev, 'bvq_stats_fakequant_fwd', 'bvq_stats_fakequant_fwd', ctypes.byref(desc), ptr(x),
+            *_scale_args(min_val, int_threshold), ptr(stat), ptr(scale), ptr(y), ptr(ws), wsb)
     return stat, scale, y
 
 
@@ -481,14 +497,8 @@ def group_quant_fwd(desc, x, min_val, thr_div):
     y = torch.empty_like(x)
     scale = torch.empty(groups, dtype=x.dtype, device=dev)
     stat = torch.empty(groups, dtype=x.dtype, device=dev)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_group_quant_fwd')
-        check(lib.bvq_group_quant_fwd(ctypes.byref(desc), ptr(x), float(min_val or 0.0), int(bool(min_val)),
-                                      float(thr_div), ptr(y), ptr(scale), ptr(stat), stream_ptr(dev)),
-              'bvq_group_quant_fwd')
-        if _timer is not None:
-            _timer.after('bvq_group_quant_fwd')
+    _launch(dev, 'bvq_group_quant_fwd', 'bvq_group_quant_fwd', ctypes.byref(desc), ptr(x),
+            *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(stat))
     return y, scale, stat
 
 
@@ -498,14 +508,8 @@ def group_quant_bwd(desc, g, x, scale, stat, gscale, min_val, thr_div):
     dev = require_device(g, x, scale, stat, gscale)
     assert g.is_contiguous() and x.is_contiguous() and (gscale is None or gscale.is_contiguous())
     dx = torch.empty_like(x)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_group_quant_bwd')
-        check(lib.bvq_group_quant_bwd(ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(stat), ptr(gscale),
-                                      float(min_val or 0.0), int(bool(min_val)), float(thr_div), ptr(dx),
-                                      stream_ptr(dev)), 'bvq_group_quant_bwd')
-        if _timer is not None:
-            _timer.after('bvq_group_quant_bwd')
+    _launch(dev, 'bvq_group_quant_bwd', 'bvq_group_quant_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(scale),
+            ptr(stat), ptr(gscale), *_scale_args(min_val, thr_div), ptr(dx))
     return dx
 
 
@@ -524,13 +528,8 @@ def mx_quant_fwd(x, group_size, fmt, scale_rule):
     groups = x.numel() // group_size
     y = torch.empty_like(x)
     scale = torch.empty(groups, dtype=torch.float32, device=dev)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_mx_quant_fwd')
-        check(lib.bvq_mx_quant_fwd(dtype_code(x.dtype), groups, int(group_size), int(fmt), int(scale_rule), ptr(x),
-                                   ptr(y), ptr(scale), stream_ptr(dev)), 'bvq_mx_quant_fwd')
-        if _timer is not None:
-            _timer.after('bvq_mx_quant_fwd')
+    _launch(dev, 'bvq_mx_quant_fwd', 'bvq_mx_quant_fwd', dtype_code(x.dtype), groups, int(group_size), int(fmt),
+            int(scale_rule), ptr(x), ptr(y), ptr(scale))
     return y, scale
 
 
@@ -541,14 +540,8 @@ def mx_quant_bwd(g, x, gscale, group_size, fmt, scale_rule, clamp_ste):
     assert g.is_contiguous() and x.is_contiguous() and g.dtype == x.dtype
     assert gscale is None or (gscale.is_contiguous() and gscale.dtype == torch.float32)
     dx = torch.empty_like(x)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_mx_quant_bwd')
-        check(lib.bvq_mx_quant_bwd(dtype_code(x.dtype), x.numel() // group_size, int(group_size), int(fmt),
-                                   int(scale_rule), int(bool(clamp_ste)), ptr(g), ptr(x), ptr(gscale), ptr(dx),
-                                   stream_ptr(dev)), 'bvq_mx_quant_bwd')
-        if _timer is not None:
-            _timer.after('bvq_mx_quant_bwd')
+    _launch(dev, 'bvq_mx_quant_bwd', 'bvq_mx_quant_bwd', dtype_code(x.dtype), x.numel() // group_size, int(group_size),
+            int(fmt), int(scale_rule), int(bool(clamp_ste)), ptr(g), ptr(x), ptr(gscale), ptr(dx))
     return dx
 
 
@@ -568,13 +561,8 @@ def mx_encode(x, group_size, fmt, scale_rule, codes=None, scale_e8m0=None):
         scale_e8m0 = torch.empty(groups, dtype=torch.uint8, device=dev)
     for t, n in ((codes, nbytes), (scale_e8m0, groups)):
         assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_mx_encode')
-        check(lib.bvq_mx_encode(dtype_code(x.dtype), groups, int(group_size), int(fmt), int(scale_rule), ptr(x),
-                                ptr(codes), ptr(scale_e8m0), stream_ptr(dev)), 'bvq_mx_encode')
-        if _timer is not None:
-            _timer.after('bvq_mx_encode')
+    _launch(dev, 'bvq_mx_encode', 'bvq_mx_encode', dtype_code(x.dtype), groups, int(group_size), int(fmt),
+            int(scale_rule), ptr(x), ptr(codes), ptr(scale_e8m0))
     return codes, scale_e8m0
 
 
@@ -586,13 +574,8 @@ def mx_decode(codes, scale_e8m0, group_size, fmt, dtype):
     for t, m in ((codes, n * MX_CODE_BITS[fmt] // 8), (scale_e8m0, groups)):
         assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == m
     y = torch.empty(n, dtype=dtype, device=dev)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_mx_decode')
-        check(lib.bvq_mx_decode(dtype_code(dtype), groups, int(group_size), int(fmt), ptr(codes), ptr(scale_e8m0),
-                                ptr(y), stream_ptr(dev)), 'bvq_mx_decode')
-        if _timer is not None:
-            _timer.after('bvq_mx_decode')
+    _launch(dev, 'bvq_mx_decode', 'bvq_mx_decode', dtype_code(dtype), groups, int(group_size), int(fmt), ptr(codes),
+            ptr(scale_e8m0), ptr(y))
     return y
 
 
@@ -610,25 +593,19 @@ def absmax_fakequant_cluster(desc, x, min_val, int_threshold, scale_dtype, runni
     words = int(lib.bvq_absmax_fakequant_cluster_supported(ctypes.byref(desc), ptr(x), ptr(y)))
     if words <= 0:
         return None
-    with _DeviceGuard(dev):
-        st = stream_ptr(dev)
+    with _DeviceGuard(dev) as st:
         arrive = arrival_buffer(dev, st, words)
         if arrive is None:
             return None
         stat = torch.empty(desc.channels, dtype=x.dtype, device=dev)
         scale = torch.empty(desc.channels, dtype=scale_dtype, device=dev)
-        if _timer is not None:
-            _timer.before('bvq_stats_fakequant_fwd')
-        args = (ctypes.byref(desc), ptr(x), float(min_val or 0.0), int(bool(min_val)), float(int_threshold), ptr(stat),
-                ptr(scale), dtype_code(running.dtype) if running is not None else 0, ptr(running), float(momentum),
-                int(first_batch), ptr(y), ptr(arrive), arrive.numel(), int(flags), ptr(fallbacks))
+        args = (ctypes.byref(desc), ptr(x), *_scale_args(min_val, int_threshold), ptr(stat), ptr(scale),
+                *_running_args(running, momentum, first_batch), ptr(y), ptr(arrive), arrive.numel(), int(flags),
+                ptr(fallbacks))
         if form == CLUSTER_AUTO and stamps is None:
-            check(lib.bvq_absmax_fakequant_cluster(*args, st), 'bvq_absmax_fakequant_cluster')
+            _call('bvq_absmax_fakequant_cluster', 'bvq_stats_fakequant_fwd', *args, st)
         else:
-            check(lib.bvq_absmax_fakequant_cluster_form(*args, int(form), ptr(stamps), st),
-                  'bvq_absmax_fakequant_cluster_form')
-        if _timer is not None:
-            _timer.after('bvq_stats_fakequant_fwd')
+            _call('bvq_absmax_fakequant_cluster_form', 'bvq_stats_fakequant_fwd', *args, int(form), ptr(stamps), st)
     return stat, scale, y
 
 
@@ -646,8 +623,7 @@ def absmax_scale_list(xs, outers, channels, inners, min_val, int_threshold, scal
     ia = (ctypes.c_int64 * n)(*inners)
     if not lib.bvq_absmax_list_supported(dt, n, ptrs, oa, channels, ia):
         return None
-    with _DeviceGuard(dev):
-        st = stream_ptr(dev)
+    with _DeviceGuard(dev) as st:
         arrive = ws = None
         if channels > 1:
             arrive = arrival_buffer(dev, st, max(2 * channels, 18))
@@ -657,10 +633,9 @@ def absmax_scale_list(xs, outers, channels, inners, min_val, int_threshold, scal
             ws = torch.empty(1 << 14, dtype=torch.uint8, device=dev)
         stat = torch.empty(channels, dtype=xs[0].dtype, device=dev)
         scale = torch.empty(channels, dtype=scale_dtype, device=dev)
-        check(lib.bvq_absmax_scale_list(dt, n, ptrs, oa, channels, ia, ptr(stat), float(min_val or 0.0),
-                                        int(bool(min_val)), float(int_threshold), dtype_code(scale_dtype), ptr(scale),
-                                        ptr(arrive), arrive.numel() if arrive is not None else 0, ptr(ws),
-                                        ws.numel() if ws is not None else 0, st), 'bvq_absmax_scale_list')
+        _call('bvq_absmax_scale_list', None, dt, n, ptrs, oa, channels, ia, ptr(stat),
+              *_scale_args(min_val, int_threshold), dtype_code(scale_dtype), ptr(scale), ptr(arrive),
+              arrive.numel() if arrive is not None else 0, ptr(ws), ws.numel() if ws is not None else 0, st)
     return stat, scale
 
 
@@ -673,39 +648,17 @@ def absmax_scale(x, outer, channels, inner, min_val, int_threshold, scale_dtype,
     dt = dtype_code(x.dtype)
     stat = torch.empty(channels, dtype=x.dtype, device=dev)
     scale = torch.empty(channels, dtype=scale_dtype, device=dev)
-    if pre_op in (PRE_NONE, PRE_RELU) and lib.bvq_absmax_onepass_supported(dt, ptr(x), outer, channels, inner):
-        # one launch: the statistic kernel's last-arriving wave per channel finishes it
-        with _DeviceGuard(dev):
-            st = stream_ptr(dev)
-            arrive = arrival_buffer(dev, st, max(2 * channels, 18))
-            if arrive is not None:
-                if _timer is not None:
-                    _timer.before('bvq_stats')
-                check(lib.bvq_absmax_scale_onepass(
-                    pre_op, dt, ptr(x), outer, channels, inner, dt, ptr(stat), float(min_val or 0.0),
-                    int(bool(min_val)), float(int_threshold), dtype_code(scale_dtype), ptr(scale),
-                    dtype_code(running.dtype) if running is not None else 0, ptr(running), float(momentum),
-                    int(first_batch), ptr(arrive), arrive.numel(), st), 'bvq_absmax_scale_onepass')
-                if _timer is not None:
-                    _timer.after('bvq_stats')
-                return stat, scale
-    wsb = lib.bvq_stats_workspace_bytes(STAT_ABSMAX, dt, outer, channels, inner)
-    ws = torch.empty(max(int(wsb), 8), dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_stats')
-        if running is not None:
-            check(lib.bvq_absmax_scale_running(pre_op, dt, ptr(x), outer, channels, inner, ptr(stat),
-                                               float(min_val or 0.0), int(bool(min_val)), float(int_threshold),
-                                               dtype_code(scale_dtype), ptr(scale), dtype_code(running.dtype),
-                                               ptr(running), float(momentum), int(first_batch), ptr(ws), ws.numel(),
-                                               stream_ptr(dev)), 'bvq_absmax_scale_running')
-        else:
-            check(lib.bvq_absmax_scale(pre_op, dt, ptr(x), outer, channels, inner, ptr(stat), float(min_val or 0.0),
-                                       int(bool(min_val)), float(int_threshold), dtype_code(scale_dtype), ptr(scale),
-                                       ptr(ws), ws.numel(), stream_ptr(dev)), 'bvq_absmax_scale')
-        if _timer is not None:
-            _timer.after('bvq_stats')
+    if _absmax_onepass(dev, pre_op, x, outer, channels, inner, stat, min_val, int_threshold, scale, running, momentum,
+                       first_batch):
+        return stat, scale
+    scale_args = (*_scale_args(min_val, int_threshold), dtype_code(scale_dtype), ptr(scale))
+    ws, _ = _workspace(dev, 'bvq_stats_workspace_bytes', STAT_ABSMAX, dt, outer, channels, inner, floor=8)
+    if running is not None:
+        _launch(dev, 'bvq_absmax_scale_running', 'bvq_stats', pre_op, dt, ptr(x), outer, channels, inner, ptr(stat),
+                *scale_args, *_running_args(running, momentum, first_batch), ptr(ws), ws.numel())
+    else:
+        _launch(dev, 'bvq_absmax_scale', 'bvq_stats', pre_op, dt, ptr(x), outer, channels, inner, ptr(stat),
+                *scale_args, ptr(ws), ws.numel())
     return stat, scale
 
 
@@ -715,17 +668,9 @@ def kth_value(x, k, outer, channels, inner, abs_key):
     assert x.is_contiguous() and x.numel() == outer * channels * inner
     dt = dtype_code(x.dtype)
     out = torch.empty(channels, dtype=x.dtype, device=dev)
-    wsb = int(lib.bvq_kth_workspace_bytes(dt, outer, channels, inner))
-    if wsb < 0:
-        raise BvqError('bvq_kth_workspace_bytes: bad arguments')
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_kth_value')
-        check(lib.bvq_kth_value(int(abs_key), dt, ptr(x), outer, channels, inner, int(k), ptr(out), ptr(ws), wsb,
-                                stream_ptr(dev)), 'bvq_kth_value')
-        if _timer is not None:
-            _timer.after('bvq_kth_value')
+    ws, wsb = _workspace(dev, 'bvq_kth_workspace_bytes', dt, outer, channels, inner)
+    _launch(dev, 'bvq_kth_value', 'bvq_kth_value', int(abs_key), dt, ptr(x), outer, channels, inner, int(k), ptr(out),
+            ptr(ws), wsb)
     return out
 
 
@@ -735,13 +680,9 @@ def kth_pair(x, k_first, k_second, outer, channels, inner, abs_key):
     assert x.is_contiguous() and x.numel() == outer * channels * inner
     dt = dtype_code(x.dtype)
     out = torch.empty(2, channels, dtype=x.dtype, device=dev)
-    wsb = int(lib.bvq_kth_workspace_bytes(dt, outer, channels, inner))
-    if wsb < 0:
-        raise BvqError('bvq_kth_workspace_bytes: bad arguments')
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_kth_pair(int(abs_key), dt, ptr(x), outer, channels, inner, int(k_first), int(k_second), ptr(out),
-                               ptr(ws), wsb, stream_ptr(dev)), 'bvq_kth_pair')
+    ws, wsb = _workspace(dev, 'bvq_kth_workspace_bytes', dt, outer, channels, inner)
+    _launch(dev, 'bvq_kth_pair', None, int(abs_key), dt, ptr(x), outer, channels, inner, int(k_first), int(k_second),
+            ptr(out), ptr(ws), wsb)
     return out
 
 
@@ -758,12 +699,9 @@ def scale_from_stat(stat32, stat_dtype, min_val, int_threshold, scale_dtype, run
     n = stat32.numel()
     stat = torch.empty(n, dtype=stat_dtype, device=dev)
     scale = torch.empty(n, dtype=scale_dtype, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_scale_from_stat_running(
-            ptr(stat32), n, dtype_code(stat_dtype), ptr(stat), float(min_val or 0.0), int(bool(min_val)),
-            float(int_threshold), dtype_code(scale_dtype), ptr(scale),
-            dtype_code(running.dtype) if running is not None else 0, ptr(running), float(momentum), int(first_batch),
-            stream_ptr(dev)), 'bvq_scale_from_stat_running')
+    _launch(dev, 'bvq_scale_from_stat_running', None, ptr(stat32), n, dtype_code(stat_dtype), ptr(stat),
+            *_scale_args(min_val, int_threshold), dtype_code(scale_dtype), ptr(scale),
+            *_running_args(running, momentum, first_batch))
     return stat, scale
 
 
@@ -781,16 +719,11 @@ def fakequant_bwd_shard(desc, g, x, scale, zp, stat, rank):
     pos = torch.empty(ch, dtype=torch.int64, device=dev)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     stat = stat.to(x.dtype).contiguous()
-    with _DeviceGuard(dev):
-        st = stream_ptr(dev)
+    with _DeviceGuard(dev) as st:
         arrive = arrival_buffer(dev, st, ch) if ONEPASS_BWD else None
-        if _timer is not None:
-            _timer.before('bvq_fakequant_bwd')
-        check(lib.bvq_fakequant_bwd_shard(ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(zp), ptr(stat), ptr(dx),
-                                          ptr(msg), ptr(pos), int(rank), ptr(ws), wsb, ptr(arrive),
-                                          arrive.numel() if arrive is not None else 0, st), 'bvq_fakequant_bwd_shard')
-        if _timer is not None:
-            _timer.after('bvq_fakequant_bwd')
+        _call('bvq_fakequant_bwd_shard', 'bvq_fakequant_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(scale),
+              ptr(zp), ptr(stat), ptr(dx), ptr(msg), ptr(pos), int(rank), ptr(ws), wsb, ptr(arrive),
+              arrive.numel() if arrive is not None else 0, st)
     return dx, msg, pos
 
 
@@ -801,11 +734,9 @@ def shard_unpack_deposit(x, dx, gathered, world, channels, rank, first_pos, inne
     dev = require_device(x, dx, gathered, first_pos)
     assert gathered.dtype == torch.float64 and gathered.is_contiguous() and gathered.numel() == world * 2 * channels
     ds = torch.empty(channels, dtype=torch.float32, device=dev) if want_dscale else None
-    with _DeviceGuard(dev):
-        check(lib.bvq_shard_unpack_deposit(dtype_code(x.dtype), ptr(x), ptr(dx), ptr(gathered), int(world), channels,
-                                           int(rank), ptr(first_pos), inner, dtype_code(scale_dtype),
-                                           float(int_threshold), dtype_code(quot_dtype), pre_op, ptr(ds),
-                                           stream_ptr(dev)), 'bvq_shard_unpack_deposit')
+    _launch(dev, 'bvq_shard_unpack_deposit', None, dtype_code(x.dtype), ptr(x), ptr(dx), ptr(gathered), int(world),
+            channels, int(rank), ptr(first_pos), inner, dtype_code(scale_dtype), float(int_threshold),
+            dtype_code(quot_dtype), pre_op, ptr(ds))
     return ds
 
 
@@ -814,9 +745,7 @@ def shard_pack(ds, tie_info, channels, rank, per_channel):
     dev = require_device(ds, tie_info)
     assert ds.dtype == torch.float32 and ds.is_contiguous() and tie_info.dtype == torch.int64
     msg = torch.empty(2 * channels, dtype=torch.float64, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_shard_pack(ptr(ds), ptr(tie_info), channels, int(rank), int(per_channel), ptr(msg),
-                                 stream_ptr(dev)), 'bvq_shard_pack')
+    _launch(dev, 'bvq_shard_pack', None, ptr(ds), ptr(tie_info), channels, int(rank), int(per_channel), ptr(msg))
     return msg
 
 
@@ -826,9 +755,8 @@ def shard_unpack(gathered, world, channels, rank, per_channel, tie_info):
     assert gathered.dtype == torch.float64 and gathered.is_contiguous() and gathered.numel() == world * 2 * channels
     ds_total = torch.empty(channels, dtype=torch.float32, device=dev)
     total = None if per_channel else torch.empty(1, dtype=torch.int64, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_shard_unpack(ptr(gathered), int(world), channels, int(rank), int(per_channel), ptr(ds_total),
-                                   ptr(tie_info), ptr(total), stream_ptr(dev)), 'bvq_shard_unpack')
+    _launch(dev, 'bvq_shard_unpack', None, ptr(gathered), int(world), channels, int(rank), int(per_channel),
+            ptr(ds_total), ptr(tie_info), ptr(total))
     return ds_total, total
 
 
@@ -839,13 +767,8 @@ def abs_moments(x, outer, channels, inner):
     assert x.is_contiguous() and x.numel() == outer * channels * inner
     dt = dtype_code(x.dtype)
     sums = torch.empty(3 * channels, dtype=torch.float32, device=dev)
-    wsb = int(lib.bvq_abs_moments_workspace_bytes(dt, outer, channels, inner))
-    if wsb < 0:
-        raise BvqError('bvq_abs_moments_workspace_bytes: bad arguments')
-    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_abs_moments(dt, ptr(x), outer, channels, inner, ptr(sums), ptr(ws), wsb, stream_ptr(dev)),
-              'bvq_abs_moments')
+    ws, wsb = _workspace(dev, 'bvq_abs_moments_workspace_bytes', dt, outer, channels, inner, floor=8)
+    _launch(dev, 'bvq_abs_moments', None, dt, ptr(x), outer, channels, inner, ptr(sums), ptr(ws), wsb)
     return sums
 
 
@@ -855,9 +778,8 @@ def abs_affine_bwd(x, a, b, outer, channels, inner):
     assert x.is_contiguous() and a.dtype == torch.float32 and b.dtype == torch.float32
     assert a.numel() == channels and b.numel() == channels
     dx = torch.empty_like(x)
-    with _DeviceGuard(dev):
-        check(lib.bvq_abs_affine_bwd(dtype_code(x.dtype), ptr(x), ptr(a.contiguous()), ptr(b.contiguous()), ptr(dx),
-                                     outer, channels, inner, stream_ptr(dev)), 'bvq_abs_affine_bwd')
+    _launch(dev, 'bvq_abs_affine_bwd', None, dtype_code(x.dtype), ptr(x), ptr(a.contiguous()), ptr(b.contiguous()),
+            ptr(dx), outer, channels, inner)
     return dx
 
 
@@ -875,36 +797,28 @@ class KthSelectSteps:
         self.per_channel = outer * inner if channels > 1 else x.numel()  # elements per channel on THIS shard
         self.dt = dtype_code(x.dtype)
         self.passes = int(lib.bvq_kth_passes(self.dt))
-        self.wsb = int(lib.bvq_kth_workspace_bytes(self.dt, outer, channels, inner))
-        if self.wsb < 0:
-            raise BvqError('bvq_kth_workspace_bytes: bad arguments')
-        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device=self.dev)
+        self.ws, self.wsb = _workspace(self.dev, 'bvq_kth_workspace_bytes', self.dt, outer, channels, inner)
 
     def begin(self):
-        with _DeviceGuard(self.dev):
-            check(lib.bvq_kth_begin(self.dt, self.layout[1], self.rule, self.k, self.q, ptr(self.ws), self.wsb,
-                                    stream_ptr(self.dev)), 'bvq_kth_begin')
+        _launch(self.dev, 'bvq_kth_begin', None, self.dt, self.layout[1], self.rule, self.k, self.q, ptr(self.ws),
+                self.wsb)
 
     def hist(self, p):
         """histogram this shard's elements for pass p -> the [channels * 2048] counters (int32 view of the
         unsigned counters: a two's-complement sum over the shards is their unsigned sum)"""
         outer, channels, inner = self.layout
-        with _DeviceGuard(self.dev):
-            check(lib.bvq_kth_hist(self.abs_key, self.dt, ptr(self.x), outer, channels, inner, p, ptr(self.ws),
-                                   self.wsb, stream_ptr(self.dev)), 'bvq_kth_hist')
+        _launch(self.dev, 'bvq_kth_hist', None, self.abs_key, self.dt, ptr(self.x), outer, channels, inner, p,
+                ptr(self.ws), self.wsb)
         off = int(lib.bvq_kth_hist_offset(self.dt, channels, p))
         return self.ws[off:off + 4 * channels * _KBINS].view(torch.int32)
 
     def pick(self, p):
-        with _DeviceGuard(self.dev):
-            check(lib.bvq_kth_pick(self.dt, self.layout[1], p, self.rule, self.q, ptr(self.ws), self.wsb,
-                                   stream_ptr(self.dev)), 'bvq_kth_pick')
+        _launch(self.dev, 'bvq_kth_pick', None, self.dt, self.layout[1], p, self.rule, self.q, ptr(self.ws), self.wsb)
 
     def finish(self):
         out = torch.empty(self.layout[1], dtype=self.x.dtype, device=self.dev)
-        with _DeviceGuard(self.dev):
-            check(lib.bvq_kth_finish(self.abs_key, self.dt, self.layout[1], ptr(out), ptr(self.ws), self.wsb,
-                                     stream_ptr(self.dev)), 'bvq_kth_finish')
+        _launch(self.dev, 'bvq_kth_finish', None, self.abs_key, self.dt, self.layout[1], ptr(out), ptr(self.ws),
+                self.wsb)
         return out
 
 
@@ -921,34 +835,28 @@ class KthWideSteps:
         self.per_channel = x.numel()
         self.dt = dtype_code(x.dtype)
         self.passes = int(lib.bvq_kthw_plan(self.abs_key, self.dt, -1, None, None))
-        self.wsb = int(lib.bvq_kth_workspace_bytes(self.dt, 1, 1, max(x.numel(), 1)))
-        if self.passes < 1 or self.wsb < 0:
-            raise BvqError('bvq_kthw_plan / bvq_kth_workspace_bytes: bad arguments')
-        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device=self.dev)
+        if self.passes < 1:
+            raise BvqError('bvq_kthw_plan: bad arguments')
+        self.ws, self.wsb = _workspace(self.dev, 'bvq_kth_workspace_bytes', self.dt, 1, 1, max(x.numel(), 1))
 
     def begin(self):
-        with _DeviceGuard(self.dev):
-            check(lib.bvq_kthw_begin(self.abs_key, self.dt, ptr(self.ws), self.wsb, stream_ptr(self.dev)), 'bvq_kthw_begin')
+        _launch(self.dev, 'bvq_kthw_begin', None, self.abs_key, self.dt, ptr(self.ws), self.wsb)
 
     def hist(self, p):
         """-> the counters of pass p to be summed over the shards (int32 view of the unsigned counters)"""
-        with _DeviceGuard(self.dev):
-            check(lib.bvq_kthw_hist(self.abs_key, self.dt, ptr(self.x) if self.x.numel() else None, self.x.numel(), p,
-                                    ptr(self.ws), self.wsb, stream_ptr(self.dev)), 'bvq_kthw_hist')
+        _launch(self.dev, 'bvq_kthw_hist', None, self.abs_key, self.dt, ptr(self.x) if self.x.numel() else None,
+                self.x.numel(), p, ptr(self.ws), self.wsb)
         off, words = ctypes.c_int64(0), ctypes.c_int64(0)
         lib.bvq_kthw_plan(self.abs_key, self.dt, p, ctypes.byref(off), ctypes.byref(words))
         return self.ws[off.value:off.value + 4 * words.value].view(torch.int32)
 
     def pick(self, p):
-        with _DeviceGuard(self.dev):
-            check(lib.bvq_kthw_pick(self.abs_key, self.dt, p, self.rule, self.k, self.q, ptr(self.ws), self.wsb,
-                                    stream_ptr(self.dev)), 'bvq_kthw_pick')
+        _launch(self.dev, 'bvq_kthw_pick', None, self.abs_key, self.dt, p, self.rule, self.k, self.q, ptr(self.ws),
+                self.wsb)
 
     def finish(self):
         out = torch.empty(1, dtype=self.x.dtype, device=self.dev)
-        with _DeviceGuard(self.dev):
-            check(lib.bvq_kthw_finish(self.abs_key, self.dt, ptr(out), ptr(self.ws), self.wsb, stream_ptr(self.dev)),
-                  'bvq_kthw_finish')
+        _launch(self.dev, 'bvq_kthw_finish', None, self.abs_key, self.dt, ptr(out), ptr(self.ws), self.wsb)
         return out
 
 
@@ -957,10 +865,8 @@ def running_stats_update(running, stat, momentum, first_batch):
     dev = require_device(running, stat)
     assert running.is_contiguous() and running.numel() == stat.numel()
     stat = stat.contiguous()
-    with _DeviceGuard(dev):
-        check(lib.bvq_running_stats_update(dtype_code(running.dtype), ptr(running), dtype_code(stat.dtype),
-                                           ptr(stat), running.numel(), float(momentum), int(first_batch),
-                                           stream_ptr(dev)), 'bvq_running_stats_update')
+    _launch(dev, 'bvq_running_stats_update', None, dtype_code(running.dtype), ptr(running), dtype_code(stat.dtype),
+            ptr(stat), running.numel(), float(momentum), int(first_batch))
     return running
 
 
@@ -975,9 +881,8 @@ def stat_tie_scan(match, x, stat, outer, channels, inner, dx_zero_fill=None):
     assert x.is_contiguous()
     stat = stat.to(x.dtype).contiguous()
     info = tie_info_buffer(channels, dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_stat_tie_scan(match, dtype_code(x.dtype), ptr(x), ptr(stat), outer, channels, inner,
-                                    ptr(dx_zero_fill), ptr(info), stream_ptr(dev)), 'bvq_stat_tie_scan')
+    _launch(dev, 'bvq_stat_tie_scan', None, match, dtype_code(x.dtype), ptr(x), ptr(stat), outer, channels, inner,
+            ptr(dx_zero_fill), ptr(info))
     return info
 
 
@@ -987,10 +892,8 @@ def stat_tie_apply(match, x, stat, gstat, info, dx, outer, channels, inner, mode
     assert x.is_contiguous() and dx.is_contiguous() and dx.dtype == x.dtype
     stat = stat.to(x.dtype).contiguous()
     gstat = gstat.to(x.dtype).contiguous()
-    with _DeviceGuard(dev):
-        check(lib.bvq_stat_tie_apply(match, pre_op, dtype_code(x.dtype), ptr(x), ptr(stat), ptr(gstat), ptr(info),
-                                     ptr(total_ties), ptr(dx), outer, channels, inner, int(mode_add),
-                                     stream_ptr(dev)), 'bvq_stat_tie_apply')
+    _launch(dev, 'bvq_stat_tie_apply', None, match, pre_op, dtype_code(x.dtype), ptr(x), ptr(stat), ptr(gstat),
+            ptr(info), ptr(total_ties), ptr(dx), outer, channels, inner, int(mode_add))
     return dx
 
 
@@ -1000,11 +903,9 @@ def stat_tie_apply_dscale(x, stat, dscale, scale_dtype, int_threshold, quot_dtyp
     dev = require_device(x, stat, dscale, info, dx, total_ties)
     assert x.is_contiguous() and dx.is_contiguous() and dx.dtype == x.dtype and dscale.dtype == torch.float32
     stat = stat.to(x.dtype).contiguous()
-    with _DeviceGuard(dev):
-        check(lib.bvq_stat_tie_apply_dscale(pre_op, dtype_code(x.dtype), ptr(x), ptr(stat), ptr(dscale),
-                                            dtype_code(scale_dtype), float(int_threshold), dtype_code(quot_dtype),
-                                            ptr(info), ptr(total_ties), ptr(dx), outer, channels, inner,
-                                            stream_ptr(dev)), 'bvq_stat_tie_apply_dscale')
+    _launch(dev, 'bvq_stat_tie_apply_dscale', None, pre_op, dtype_code(x.dtype), ptr(x), ptr(stat), ptr(dscale),
+            dtype_code(scale_dtype), float(int_threshold), dtype_code(quot_dtype), ptr(info), ptr(total_ties), ptr(dx),
+            outer, channels, inner)
     return dx
 
 
@@ -1019,35 +920,27 @@ def fakequant_bwd_stats(desc, g, x, scale, zp, stat, scale_dtype, int_threshold,
     ds = torch.empty(int(desc.channels), dtype=torch.float32, device=dev)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     stat = stat.to(x.dtype).contiguous()
-    with _DeviceGuard(dev):
-        st = stream_ptr(dev)
+    with _DeviceGuard(dev) as st:
         arrive = None
         if ONEPASS_BWD and lib.bvq_fakequant_bwd_stats_onepass_supported(ctypes.byref(desc)):
             arrive = arrival_buffer(dev, st, int(desc.channels))
-        if _timer is not None:
-            _timer.before('bvq_fakequant_bwd')
         if arrive is not None:  # one launch: the wave that completes a channel finishes it
-            check(lib.bvq_fakequant_bwd_stats_onepass(ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(zp), ptr(stat),
-                                                      ptr(dx), ptr(ds), dtype_code(scale_dtype), float(int_threshold),
-                                                      dtype_code(quot_dtype), ptr(ws), wsb, ptr(arrive), arrive.numel(),
-                                                      st), 'bvq_fakequant_bwd_stats_onepass')
+            _call('bvq_fakequant_bwd_stats_onepass', 'bvq_fakequant_bwd', ctypes.byref(desc), ptr(g), ptr(x),
+                  ptr(scale), ptr(zp), ptr(stat), ptr(dx), ptr(ds), dtype_code(scale_dtype), float(int_threshold),
+                  dtype_code(quot_dtype), ptr(ws), wsb, ptr(arrive), arrive.numel(), st)
         else:
-            check(lib.bvq_fakequant_bwd_stats(ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(zp), ptr(stat), ptr(dx),
-                                              ptr(ds), dtype_code(scale_dtype), float(int_threshold),
-                                              dtype_code(quot_dtype), ptr(ws), wsb, st), 'bvq_fakequant_bwd_stats')
-        if _timer is not None:
-            _timer.after('bvq_fakequant_bwd')
+            _call('bvq_fakequant_bwd_stats', 'bvq_fakequant_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(scale),
+                  ptr(zp), ptr(stat), ptr(dx), ptr(ds), dtype_code(scale_dtype), float(int_threshold),
+                  dtype_code(quot_dtype), ptr(ws), wsb, st)
     return (dx, ds) if want_dscale else dx
 
 
 def variant_fwd(desc, x, scale, pre_scale=None, zp=None, pre_zp=None):
     """forward of the sign / decoupled / truncating quantizers (include/bvq.h, bvq_variant_fwd) -> y in desc.ct_dtype"""
     dev = require_device(x, scale, pre_scale, zp, pre_zp)
-    ct = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}[desc.ct_dtype]
-    y = torch.empty(x.shape, dtype=ct, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_variant_fwd(ctypes.byref(desc), ptr(x), ptr(scale), ptr(pre_scale), ptr(zp), ptr(pre_zp), ptr(y),
-                                  stream_ptr(dev)), 'bvq_variant_fwd')
+    y = torch.empty(x.shape, dtype=_TORCH_DTYPES[desc.ct_dtype], device=dev)
+    _launch(dev, 'bvq_variant_fwd', None, ctypes.byref(desc), ptr(x), ptr(scale), ptr(pre_scale), ptr(zp), ptr(pre_zp),
+            ptr(y))
     return y
 
 
@@ -1060,13 +953,9 @@ def variant_bwd(desc, g, x, scale, pre_scale=None, zp=None, pre_zp=None, need_ds
     dp = torch.empty(nsum, dtype=torch.float32, device=dev) if need_dpre else None
     ws, wsb = None, 0
     if need_dscale or need_dpre:
-        wsb = int(lib.bvq_variant_bwd_workspace_bytes(ctypes.byref(desc)))
-        if wsb < 0:
-            raise BvqError('bvq_variant_bwd_workspace_bytes: ' + last_error())
-        ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_variant_bwd(ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(pre_scale), ptr(zp), ptr(pre_zp),
-                                  ptr(dx), ptr(ds), ptr(dp), ptr(ws), wsb, stream_ptr(dev)), 'bvq_variant_bwd')
+        ws, wsb = _workspace(dev, 'bvq_variant_bwd_workspace_bytes', ctypes.byref(desc), floor=8)
+    _launch(dev, 'bvq_variant_bwd', None, ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(pre_scale), ptr(zp),
+            ptr(pre_zp), ptr(dx), ptr(ds), ptr(dp), ptr(ws), wsb)
     return dx, ds, dp
 
 
@@ -1074,11 +963,8 @@ def fakequant_fwd_bounds(desc, x, scale, zp, bounds):
     """bvq_fakequant_fwd with the integer range [qmin, qmax] read from the device (float32 [2]) -> y"""
     dev = require_device(x, scale, zp, bounds)
     assert bounds.dtype == torch.float32 and bounds.numel() == 2 and bounds.is_contiguous()
-    ct = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}[desc.ct_dtype]
-    y = torch.empty(x.shape, dtype=ct, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_fakequant_fwd_bounds(ctypes.byref(desc), ptr(x), ptr(scale), ptr(zp), ptr(bounds), ptr(y),
-                                           stream_ptr(dev)), 'bvq_fakequant_fwd_bounds')
+    y = torch.empty(x.shape, dtype=_TORCH_DTYPES[desc.ct_dtype], device=dev)
+    _launch(dev, 'bvq_fakequant_fwd_bounds', None, ctypes.byref(desc), ptr(x), ptr(scale), ptr(zp), ptr(bounds), ptr(y))
     return y
 
 
@@ -1090,13 +976,9 @@ def fakequant_bwd_bounds(desc, g, x, scale, zp, bounds, need_dbounds):
     nsum = int(desc.channels) if ((desc.scale_per_channel or desc.zp_per_channel) and desc.channels > 1) else 1
     ds = torch.empty(nsum, dtype=torch.float32, device=dev)
     db = torch.empty(2, nsum, dtype=torch.float32, device=dev) if need_dbounds else None
-    wsb = int(lib.bvq_fakequant_bwd_workspace_bytes(ctypes.byref(desc)))
-    if wsb < 0:
-        raise BvqError('bvq_fakequant_bwd_workspace_bytes: ' + last_error())
-    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_fakequant_bwd_bounds(ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(zp), ptr(bounds), ptr(dx),
-                                           ptr(ds), ptr(db), ptr(ws), wsb, stream_ptr(dev)), 'bvq_fakequant_bwd_bounds')
+    ws, wsb = _workspace(dev, 'bvq_fakequant_bwd_workspace_bytes', ctypes.byref(desc), floor=8)
+    _launch(dev, 'bvq_fakequant_bwd_bounds', None, ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(zp), ptr(bounds),
+            ptr(dx), ptr(ds), ptr(db), ptr(ws), wsb)
     return dx, ds, db
 
 
@@ -1105,9 +987,8 @@ def histc(x, absmax, bins):
     dev = require_device(x, absmax)
     x = x.contiguous()
     counts = torch.empty(bins, dtype=torch.int32, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_histc(dtype_code(x.dtype), ptr(x), x.numel(), ptr(absmax.to(x.dtype).reshape(1)), int(bins),
-                            ptr(counts), stream_ptr(dev)), 'bvq_histc')
+    _launch(dev, 'bvq_histc', None, dtype_code(x.dtype), ptr(x), x.numel(), ptr(absmax.to(x.dtype).reshape(1)),
+            int(bins), ptr(counts))
     return counts
 
 
@@ -1116,9 +997,7 @@ def selftest_div_f16r(a, scales):
     dev = require_device(a, scales)
     assert a.dtype == torch.float32 and scales.dtype == torch.float32 and a.is_contiguous() and scales.is_contiguous()
     out = torch.empty(scales.numel(), a.numel(), dtype=torch.float32, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_selftest_div_f16r(ptr(a), a.numel(), ptr(scales), scales.numel(), ptr(out), stream_ptr(dev)),
-              'bvq_selftest_div_f16r')
+    _launch(dev, 'bvq_selftest_div_f16r', None, ptr(a), a.numel(), ptr(scales), scales.numel(), ptr(out))
     return out
 
 
@@ -1129,9 +1008,7 @@ def selftest_pre_op(pre_op, x, g):
     assert x.dtype == g.dtype and x.shape == g.shape and x.is_contiguous() and g.is_contiguous()
     a = torch.empty_like(x)
     da = torch.empty_like(x)
-    with _DeviceGuard(dev):
-        check(lib.bvq_selftest_pre_op(pre_op, dtype_code(x.dtype), ptr(x), ptr(g), ptr(a), ptr(da), x.numel(),
-                                      stream_ptr(dev)), 'bvq_selftest_pre_op')
+    _launch(dev, 'bvq_selftest_pre_op', None, pre_op, dtype_code(x.dtype), ptr(x), ptr(g), ptr(a), ptr(da), x.numel())
     return a, da
 
 
@@ -1140,10 +1017,8 @@ def learned_scale(value, min_val, int_threshold, scale_dtype):
     dev = require_device(value)
     v = value.detach().reshape(-1).contiguous()
     scale = torch.empty(v.numel(), dtype=scale_dtype, device=dev)
-    with _DeviceGuard(dev):
-        check(lib.bvq_learned_scale(dtype_code(v.dtype), ptr(v), v.numel(), float(min_val or 0.0), int(bool(min_val)),
-                                    float(int_threshold), dtype_code(scale_dtype), ptr(scale), stream_ptr(dev)),
-              'bvq_learned_scale')
+    _launch(dev, 'bvq_learned_scale', None, dtype_code(v.dtype), ptr(v), v.numel(),
+            *_scale_args(min_val, int_threshold), dtype_code(scale_dtype), ptr(scale))
     return scale
 
 
@@ -1157,19 +1032,10 @@ def fakequant_bwd_learned(desc, g, x, scale, zp, value, min_val, int_threshold, 
     assert v.numel() == nsum and (gscale is None or (gscale.numel() == nsum and gscale.is_contiguous()))
     ds = torch.empty(nsum, dtype=torch.float32, device=dev)
     dv = torch.empty(nsum, dtype=v.dtype, device=dev)
-    wsb = int(lib.bvq_fakequant_bwd_workspace_bytes(ctypes.byref(desc)))
-    if wsb < 0:
-        raise BvqError('bvq_fakequant_bwd_workspace_bytes: ' + last_error())
-    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_fakequant_bwd')
-        check(lib.bvq_fakequant_bwd_learned(ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(zp), ptr(dx), ptr(ds),
-                                            ptr(v), dtype_code(v.dtype), float(min_val or 0.0), int(bool(min_val)),
-                                            float(int_threshold), ptr(gscale), ptr(dv), ptr(ws), wsb, stream_ptr(dev)),
-              'bvq_fakequant_bwd_learned')
-        if _timer is not None:
-            _timer.after('bvq_fakequant_bwd')
+    ws, wsb = _workspace(dev, 'bvq_fakequant_bwd_workspace_bytes', ctypes.byref(desc), floor=8)
+    _launch(dev, 'bvq_fakequant_bwd_learned', 'bvq_fakequant_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(scale),
+            ptr(zp), ptr(dx), ptr(ds), ptr(v), dtype_code(v.dtype), *_scale_args(min_val, int_threshold), ptr(gscale),
+            ptr(dv), ptr(ws), wsb)
     return dx, ds, dv
 
 
@@ -1185,21 +1051,11 @@ def fakequant_bwd(desc, g, x, scale, zp, need_dscale, need_dzp, tie_stat=None):
     if tie_stat is not None:
         tie_stat = tie_stat.to(x.dtype).contiguous()
         info = tie_info_buffer(desc.channels, dev)
-    ws = None
-    wsb = 0
+    ws, wsb = None, 0
     if need_dscale or need_dzp:
-        wsb = int(lib.bvq_fakequant_bwd_workspace_bytes(ctypes.byref(desc)))
-        if wsb < 0:
-            raise BvqError('bvq_fakequant_bwd_workspace_bytes: ' + last_error())
-        ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_fakequant_bwd')
-        check(lib.bvq_fakequant_bwd(ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(zp), ptr(dx), ptr(ds),
-                                    ptr(dz), ptr(tie_stat), ptr(info), ptr(ws), wsb, stream_ptr(dev)),
-              'bvq_fakequant_bwd')
-        if _timer is not None:
-            _timer.after('bvq_fakequant_bwd')
+        ws, wsb = _workspace(dev, 'bvq_fakequant_bwd_workspace_bytes', ctypes.byref(desc), floor=8)
+    _launch(dev, 'bvq_fakequant_bwd', 'bvq_fakequant_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(scale), ptr(zp),
+            ptr(dx), ptr(ds), ptr(dz), ptr(tie_stat), ptr(info), ptr(ws), wsb)
     if tie_stat is not None:
         return dx, ds, dz, info
     return dx, ds, dz
@@ -1245,14 +1101,8 @@ def weight_quant_list_fwd(items, first, xs, scale_dtype, round_mode):
         it.scale = ss
         ps += it.channels * es
         ss += it.channels * esc
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_weight_quant_list_fwd')
-        check(lib.bvq_weight_quant_list_fwd(dtype_code(dtype), dtype_code(scale_dtype), round_mode, n,
-                                            ctypes.addressof(items) + first * _ITEM, stream_ptr(dev)),
-              'bvq_weight_quant_list_fwd')
-        if _timer is not None:
-            _timer.after('bvq_weight_quant_list_fwd')
+    _launch(dev, 'bvq_weight_quant_list_fwd', 'bvq_weight_quant_list_fwd', dtype_code(dtype), dtype_code(scale_dtype),
+            round_mode, n, ctypes.addressof(items) + first * _ITEM)
     return ys, stat, scale
 
 
@@ -1265,35 +1115,27 @@ def weight_quant_list_bwd(items, first, gs, xs, stat_ptrs, scale_ptrs, scale_dty
     n = len(xs)
     dev = xs[0].device
     dtype = xs[0].dtype
-    st = stream_ptr(dev)
     channels = 0
     for i in range(first, first + n):
         channels += items[i].channels
-    arrive = arrival_buffer(dev, st, channels) if ONEPASS_BWD else None
-    if arrive is None:
-        return None
-    dxs = [torch.empty_like(x) for x in xs]
-    ds = torch.empty(channels, dtype=torch.float32, device=dev)
-    pd = ds.data_ptr()
-    for i in range(n):
-        it = items[first + i]
-        it.g = gs[i].data_ptr()
-        it.dx = dxs[i].data_ptr()
-        it.stat = stat_ptrs[i]
-        it.scale = scale_ptrs[i]
-        it.dscale = pd
-        pd += it.channels * 4
-    addr = ctypes.addressof(items) + first * _ITEM
-    wsb = int(lib.bvq_weight_quant_list_bwd_workspace_bytes(dtype_code(dtype), n, addr))
-    if wsb < 0:
-        raise BvqError('bvq_weight_quant_list_bwd_workspace_bytes: ' + last_error())
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    with _DeviceGuard(dev):
-        if _timer is not None:
-            _timer.before('bvq_weight_quant_list_bwd')
-        check(lib.bvq_weight_quant_list_bwd(dtype_code(dtype), dtype_code(scale_dtype), dtype_code(quot_dtype),
-                                            round_mode, n, addr, ptr(ws), wsb, ptr(arrive), arrive.numel(), st),
-              'bvq_weight_quant_list_bwd')
-        if _timer is not None:
-            _timer.after('bvq_weight_quant_list_bwd')
+    with _DeviceGuard(dev) as st:
+        arrive = arrival_buffer(dev, st, channels) if ONEPASS_BWD else None
+        if arrive is None:
+            return None
+        dxs = [torch.empty_like(x) for x in xs]
+        ds = torch.empty(channels, dtype=torch.float32, device=dev)
+        pd = ds.data_ptr()
+        for i in range(n):
+            it = items[first + i]
+            it.g = gs[i].data_ptr()
+            it.dx = dxs[i].data_ptr()
+            it.stat = stat_ptrs[i]
+            it.scale = scale_ptrs[i]
+            it.dscale = pd
+            pd += it.channels * 4
+        addr = ctypes.addressof(items) + first * _ITEM
+        ws, wsb = _workspace(dev, 'bvq_weight_quant_list_bwd_workspace_bytes', dtype_code(dtype), n, addr)
+        _call('bvq_weight_quant_list_bwd', 'bvq_weight_quant_list_bwd', dtype_code(dtype),
+              dtype_code(scale_dtype), dtype_code(quot_dtype), round_mode, n, addr, ptr(ws), wsb, ptr(arrive),
+              arrive.numel(), st)
     return dxs

@@ -223,6 +223,8 @@ __device__ __forceinline__ void buf_store(buf_t b, uint32_t byte_off, const vec_
 int64_t nt_threshold_bytes();
 // host-side float -> dtype -> float rounding (python scalars that torch converts to the tensor dtype)
 float round_host(float f, int dt);
+// a dtype argument of the C ABI that is none of BVQ_F32 / BVQ_BF16 / BVQ_F16
+inline bool bad_dtype(int dt) { return dt < BVQ_F32 || dt > BVQ_F16; }
 
 // read element 0 / element c of a scale-like buffer of runtime dtype as float (wave-uniform use)
 __device__ __forceinline__ float load_scalar_as_f(const void* p, int dt, int64_t idx) {

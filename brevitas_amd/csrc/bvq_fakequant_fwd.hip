@@ -1086,7 +1086,6 @@ static int cluster_impl(const bvq_quant_desc* d, const void* x, double min_val, 
     set_error("bvq_absmax_fakequant_cluster: null pointer");
     return BVQ_ERR_INVALID;
   }
-  auto bad_dtype = [](int dt) { return dt < BVQ_F32 || dt > BVQ_F16; };
   if ((running && bad_dtype(run_dtype)) || bad_dtype(d->scale_dtype) || !(int_threshold == int_threshold) ||
       (flags & ~BVQ_CLUSTER_FORCE_FALLBACK)) {
     set_error("bvq_absmax_fakequant_cluster: bad argument");
@@ -1114,19 +1113,9 @@ static int cluster_impl(const bvq_quant_desc* d, const void* x, double min_val, 
   }
   ClusterArgs ca = {};
   ca.f = fused_args(d, cp.p, x, y, stat_out, scale_out, min_val, use_min, int_threshold);
-  ca.ep.scale_out = scale_out;
-  ca.ep.scale_dtype = d->scale_dtype;
-  ca.ep.use_min = use_min;
-  ca.ep.min_val = ca.f.min_val;
-  ca.ep.int_threshold = ca.f.int_threshold;
-  if (running) {
-    ca.ep.running = running;
-    ca.ep.run_dtype = run_dtype;
-    ca.ep.first_batch = first_batch;
-    // as bvq_absmax_scale_onepass: torch's float32 (1 - momentum) and momentum
-    ca.ep.one_minus_m = (float)(1.0 - momentum);
-    ca.ep.momentum = (float)momentum;
-  }
+  // (the same min_val and int_threshold as ca.f's: both round them for the statistic's dtype, x's)
+  ca.ep = with_running(scale_epilogue(scale_out, d->scale_dtype, use_min, min_val, d->x_dtype, int_threshold),
+                       run_dtype, running, momentum, first_batch);
   ca.stat_out = stat_out;
   ca.in_dtype = d->x_dtype;
   ca.key = arrive;

@@ -506,7 +506,10 @@ static int sel_check(const char* who, int dtype, int64_t channels, const void* w
 static int64_t sel_scratch_offset(int dtype, int64_t channels) { return (sel_workspace_bytes(dtype, channels) + 255) / 256 * 256; }
 
 extern "C" int64_t bvq_kth_workspace_bytes(int dtype, int64_t outer, int64_t channels, int64_t inner) {
-  if (dtype < BVQ_F32 || dtype > BVQ_F16 || outer < 0 || channels < 1 || inner < 0) return -1;
+  if (dtype < BVQ_F32 || dtype > BVQ_F16 || outer < 0 || channels < 1 || inner < 0) {
+    set_error("bvq_kth_workspace_bytes: bad argument");
+    return -1;
+  }
   if (cols_plan(dtype, outer, channels, inner).ok)
     return sel_scratch_offset(dtype, channels) + outer * channels * inner * (int64_t)dtype_size(dtype) + 256;
   return sel_workspace_bytes(dtype, channels);

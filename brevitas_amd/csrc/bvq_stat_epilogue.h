@@ -34,6 +34,32 @@ struct ScaleEpilogue {
   float momentum, one_minus_m;
 };
 
+// The epilogue from the arguments of the C ABI (host side).  scale_epilogue: the scale part; min_val is a python scalar
+// that torch converts to the statistic's dtype.  A null scale_out gives the empty epilogue.
+inline ScaleEpilogue scale_epilogue(void* scale_out, int scale_dtype, int use_min, double min_val, int stat_dtype,
+                                    double int_threshold) {
+  ScaleEpilogue ep = {};
+  if (!scale_out) return ep;
+  ep.scale_out = scale_out;
+  ep.scale_dtype = scale_dtype;
+  ep.use_min = use_min;
+  ep.min_val = round_host((float)min_val, stat_dtype);
+  ep.int_threshold = (float)int_threshold;
+  return ep;
+}
+
+// with_running: `ep` and the running average; torch turns the python scalars (1 - momentum) and momentum into float32
+// for these dtypes (bvq_running_stats_update).  A null running adds nothing.
+inline ScaleEpilogue with_running(ScaleEpilogue ep, int run_dtype, void* running, double momentum, int first_batch) {
+  if (!running) return ep;
+  ep.running = running;
+  ep.run_dtype = run_dtype;
+  ep.first_batch = first_batch;
+  ep.one_minus_m = (float)(1.0 - momentum);
+  ep.momentum = (float)momentum;
+  return ep;
+}
+
 // running *= out (first batch)  |  running *= (1 - momentum); running += momentum * out -- every torch op rounds to
 // its result dtype: running's for the in-place ops, out's for momentum * out
 __device__ __forceinline__ float running_update(float r, float o, int run_dtype, int stat_dtype, float one_minus_m,

@@ -1023,11 +1023,12 @@ static void run_tie_apply(const void* x, const void* stat, GstatSrc gstat,
 
 using namespace bvq;
 
-static int bad_dtype(int dt) { return dt < BVQ_F32 || dt > BVQ_F16; }
-
 extern "C" int64_t bvq_stats_workspace_bytes(int kind, int dtype, int64_t outer, int64_t channels,
                                              int64_t inner) {
-  if (bad_dtype(dtype) || outer < 0 || channels < 1 || inner < 0) return -1;
+  if (bad_dtype(dtype) || outer < 0 || channels < 1 || inner < 0) {
+    set_error("bvq_stats_workspace_bytes: bad argument");
+    return -1;
+  }
   (void)kind;
   const int64_t units = worst_units(dtype, outer, channels, inner);
   const int64_t mid = channels * (int64_t)finish_splits(units / channels + 1);
@@ -1201,23 +1202,32 @@ extern "C" int bvq_stats_pre(int kind, int pre_op, int dtype, const void* x, int
                     workspace_bytes, stream);
 }
 
+// the body of bvq_absmax_scale (with_run false: no running statistic) and of bvq_absmax_scale_running (with_run: one
+// must be given); entry: the name the error text carries
+static int absmax_scale_impl(const char* entry, bool with_run, int pre_op, int dtype, const void* x, int64_t outer,
+                             int64_t channels, int64_t inner, void* stat_out, double min_val, int use_min,
+                             double int_threshold, int scale_dtype, void* scale_out, int run_dtype, void* running,
+                             double momentum, int first_batch, void* workspace, int64_t workspace_bytes,
+                             bvq_stream_t stream) {
+  if (bad_dtype(scale_dtype) || !scale_out || !(int_threshold == int_threshold) ||
+      (with_run && (bad_dtype(run_dtype) || !running))) {
+    set_error("%s: bad argument", entry);
+    return BVQ_ERR_INVALID;
+  }
+  const ScaleEpilogue ep = with_running(scale_epilogue(scale_out, scale_dtype, use_min, min_val, dtype, int_threshold),
+                                        run_dtype, running, momentum, first_batch);
+  return stats_impl(BVQ_STAT_ABSMAX, pre_op, dtype, x, outer, channels, inner, dtype, stat_out, ep, workspace,
+                    workspace_bytes, stream);
+}
+
 extern "C" int bvq_absmax_scale(int pre_op, int dtype, const void* x, int64_t outer, int64_t channels,
                                 int64_t inner,
                                 void* stat_out, double min_val, int use_min, double int_threshold,
                                 int scale_dtype, void* scale_out, void* workspace,
                                 int64_t workspace_bytes, bvq_stream_t stream) {
-  if (bad_dtype(scale_dtype) || !scale_out || !(int_threshold == int_threshold)) {
-    set_error("bvq_absmax_scale: bad argument");
-    return BVQ_ERR_INVALID;
-  }
-  ScaleEpilogue ep = {};
-  ep.scale_out = scale_out;
-  ep.scale_dtype = scale_dtype;
-  ep.use_min = use_min;
-  ep.min_val = round_host((float)min_val, dtype);  // python scalar -> the statistic's dtype
-  ep.int_threshold = (float)int_threshold;
-  return stats_impl(BVQ_STAT_ABSMAX, pre_op, dtype, x, outer, channels, inner, dtype, stat_out, ep, workspace,
-                    workspace_bytes, stream);
+  return absmax_scale_impl("bvq_absmax_scale", false, pre_op, dtype, x, outer, channels, inner, stat_out, min_val,
+                           use_min, int_threshold, scale_dtype, scale_out, BVQ_F32, nullptr, 0.0, 0, workspace,
+                           workspace_bytes, stream);
 }
 
 // Units of the one-launch abs-max: long ones.  Short rows (NCHW activations): as many rows of one channel per wave as
@@ -1323,22 +1333,8 @@ extern "C" int bvq_absmax_scale_onepass(int pre_op, int dtype, const void* x, in
   r.in_dtype = dtype;
   r.part = nullptr;
   const unsigned blocks = grid_for_units(a.t.units);
-  ScaleEpilogue ep = {};
-  if (scale_out) {
-    ep.scale_out = scale_out;
-    ep.scale_dtype = scale_dtype;
-    ep.use_min = use_min;
-    ep.min_val = round_host((float)min_val, dtype);  // python scalar -> the statistic's dtype
-    ep.int_threshold = (float)int_threshold;
-  }
-  if (running) {
-    ep.running = running;
-    ep.run_dtype = run_dtype;
-    ep.first_batch = first_batch;
-    // torch turns the python scalars (1 - momentum) and momentum into float32 for these dtypes (bvq_running_stats_update)
-    ep.one_minus_m = (float)(1.0 - momentum);
-    ep.momentum = (float)momentum;
-  }
+  const ScaleEpilogue ep = with_running(scale_epilogue(scale_out, scale_dtype, use_min, min_val, dtype, int_threshold),
+                                        run_dtype, running, momentum, first_batch);
   const int rc = with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
     constexpr int V = elem<T>::vec;
@@ -1470,14 +1466,7 @@ extern "C" int bvq_absmax_scale_list(int dtype, int n, const void* const* xs, co
   r.stat_dtype = dtype;
   r.in_dtype = dtype;
   r.part = channels == 1 ? reinterpret_cast<uint32_t*>(workspace) : nullptr;
-  ScaleEpilogue ep = {};
-  if (scale_out) {
-    ep.scale_out = scale_out;
-    ep.scale_dtype = scale_dtype;
-    ep.use_min = use_min;
-    ep.min_val = round_host((float)min_val, dtype);  // python scalar -> the statistic's dtype
-    ep.int_threshold = (float)int_threshold;
-  }
+  const ScaleEpilogue ep = scale_epilogue(scale_out, scale_dtype, use_min, min_val, dtype, int_threshold);
   const dim3 grid(grid_for_units(la.start[n])), block(kBlock);
   int rc = with_dtype(dtype, [&](auto t) {
     absmax_list_kernel<typename decltype(t)::type><<<grid, block, 0, st>>>(la, r, ep);
@@ -1496,28 +1485,16 @@ extern "C" int bvq_absmax_scale_running(int pre_op, int dtype, const void* x, in
                                         double int_threshold, int scale_dtype, void* scale_out, int run_dtype,
                                         void* running, double momentum, int first_batch, void* workspace,
                                         int64_t workspace_bytes, bvq_stream_t stream) {
-  if (bad_dtype(scale_dtype) || bad_dtype(run_dtype) || !scale_out || !running || !(int_threshold == int_threshold)) {
-    set_error("bvq_absmax_scale_running: bad argument");
-    return BVQ_ERR_INVALID;
-  }
-  ScaleEpilogue ep = {};
-  ep.scale_out = scale_out;
-  ep.scale_dtype = scale_dtype;
-  ep.use_min = use_min;
-  ep.min_val = round_host((float)min_val, dtype);
-  ep.int_threshold = (float)int_threshold;
-  ep.running = running;
-  ep.run_dtype = run_dtype;
-  ep.first_batch = first_batch;
-  // torch turns the python scalars (1 - momentum) and momentum into float32 for these dtypes (bvq_running_stats_update)
-  ep.one_minus_m = (float)(1.0 - momentum);
-  ep.momentum = (float)momentum;
-  return stats_impl(BVQ_STAT_ABSMAX, pre_op, dtype, x, outer, channels, inner, dtype, stat_out, ep, workspace,
-                    workspace_bytes, stream);
+  return absmax_scale_impl("bvq_absmax_scale_running", true, pre_op, dtype, x, outer, channels, inner, stat_out,
+                           min_val, use_min, int_threshold, scale_dtype, scale_out, run_dtype, running, momentum,
+                           first_batch, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t bvq_abs_moments_workspace_bytes(int dtype, int64_t outer, int64_t channels, int64_t inner) {
-  if (bad_dtype(dtype) || outer < 0 || channels < 1 || inner < 0) return -1;
+  if (bad_dtype(dtype) || outer < 0 || channels < 1 || inner < 0) {
+    set_error("bvq_abs_moments_workspace_bytes: bad argument");
+    return -1;
+  }
   const int64_t units = worst_units(dtype, outer, channels, inner);
   int64_t need = 2 * units * (int64_t)sizeof(float) + 8 + channel_sums_mid_bytes(units / channels + 1, channels) + 256;
   const ColsPlan cp = cols_plan(dtype, outer, channels, inner);
@@ -1686,19 +1663,9 @@ extern "C" int bvq_scale_from_stat_running(const float* stat32, int64_t channels
     set_error("bvq_scale_from_stat: bad argument");
     return BVQ_ERR_INVALID;
   }
-  ScaleEpilogue ep = {};
-  if (running) {
-    ep.running = running;
-    ep.run_dtype = run_dtype;
-    ep.first_batch = first_batch;
-    ep.one_minus_m = (float)(1.0 - momentum);
-    ep.momentum = (float)momentum;
-  }
-  ep.scale_out = scale_out;
-  ep.scale_dtype = scale_dtype;
-  ep.use_min = use_min;
-  ep.min_val = round_host((float)min_val, stat_dtype);
-  ep.int_threshold = (float)int_threshold;
+  const ScaleEpilogue ep =
+      with_running(scale_epilogue(scale_out, scale_dtype, use_min, min_val, stat_dtype, int_threshold), run_dtype,
+                   running, momentum, first_batch);
   scale_from_stat_kernel<<<dim3((unsigned)((channels + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
       stat32, stat_out, stat_dtype, ep, (int32_t)channels);
   return check_launch("bvq_scale_from_stat");
@@ -1791,12 +1758,7 @@ extern "C" int bvq_learned_scale(int value_dtype, const void* value, int64_t n, 
     set_error("bvq_learned_scale: bad argument");
     return BVQ_ERR_INVALID;
   }
-  ScaleEpilogue ep = {};
-  ep.scale_out = scale_out;
-  ep.scale_dtype = scale_dtype;
-  ep.use_min = use_min;
-  ep.min_val = round_host((float)min_val, value_dtype);
-  ep.int_threshold = (float)int_threshold;
+  const ScaleEpilogue ep = scale_epilogue(scale_out, scale_dtype, use_min, min_val, value_dtype, int_threshold);
   learned_scale_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(value, value_dtype, ep,
                                                                                                  (int32_t)n);
   return check_launch("bvq_learned_scale");

@@ -91,8 +91,6 @@ static bvq_quant_desc item_desc(int dtype, int scale_dtype, int round_mode, cons
   return d;
 }
 
-static bool bad_dtype(int t) { return t < BVQ_F32 || t > BVQ_F16; }
-
 // the checks that need no device; what: the entry's name.  fwd / bwd: the pointers that entry reads or writes.
 static int check_list(const char* what, int dtype, int n, const bvq_weight_item* items, bool fwd, bool bwd) {
   if (!items || n < 1 || n > BVQ_WEIGHT_LIST_MAX) {
