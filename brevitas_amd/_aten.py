@@ -193,6 +193,47 @@ def abs_mean_var(x, dim):
     return torch.mean(a, dim=dim), torch.var(a, dim=dim)
 
 
+# ---- group-wise clip search (core/quant/int.py: GroupwiseMSEIntQuant), the composed route --------------------
+# Both steps take the module's own sub-modules as two callables, so they run the same ops as the plain group-wise
+# quantizer: scale_of(threshold [groups, 1]) -> scale [groups, 1], quantize(scale) -> y [groups, g].  They serve CPU and
+# device tensors alike (the ops dispatch by themselves) and define what the one-launch kernels compute.
+
+def group_mse_threshold(stat, ratio):
+    """a candidate's threshold: the statistic times a float32 ratio (a Python float, or a float32 tensor with one ratio
+    per group), the product formed in float32 and rounded once to the statistic's dtype.  Differentiable in stat."""
+    if not torch.is_tensor(ratio):
+        ratio = torch.tensor(float(ratio), dtype=torch.float32, device=stat.device)
+    return (stat.float() * ratio).to(stat.dtype)
+
+
+def group_mse_index(xg, ratios, stat, scale_of, quantize):
+    """-> idx uint8 [groups]: per group the first candidate whose float32 squared error sum((y_i - x)^2) is strictly
+    below every earlier one's.  NaN errors (a NaN or Inf group) are below nothing: such a group keeps 0, as a group of
+    zeros does.  An explicit loop: argmin's order among ties is not defined."""
+    with torch.no_grad():
+        xf = xg.float()
+        idx = torch.zeros(xg.shape[0], dtype=torch.uint8, device=xg.device)
+        best = None
+        for i, r in enumerate(ratios):
+            d = quantize(scale_of(group_mse_threshold(stat, r))).float() - xf
+            e = (d * d).sum(dim=1)
+            if best is None:
+                best = e
+                continue
+            better = e < best
+            idx = torch.where(better, torch.full_like(idx, i), idx)
+            best = torch.where(better, e, best)
+    return idx
+
+
+def group_mse_quantize_at(ratios, idx, stat, scale_of, quantize):
+    """quantize every group at the candidate idx names -> (y [groups, g], scale [groups, 1]); idx is a constant,
+    everything else is differentiated by autograd through the sub-modules"""
+    table = torch.tensor([float(r) for r in ratios], dtype=torch.float32, device=stat.device)
+    scale = scale_of(group_mse_threshold(stat, table[idx.long()].reshape(stat.shape)))
+    return quantize(scale), scale
+
+
 import sys  # noqa: E402
 
 _SELF = sys.modules[__name__]

@@ -33,7 +33,7 @@ CLUSTER_AUTO, CLUSTER_WALK, CLUSTER_ONESHOT = range(3)
 MX_E4M3, MX_E5M2, MX_E3M2, MX_E2M3, MX_E2M1, MX_INT8 = range(6)
 MX_FLOOR, MX_CEIL = 0, 1
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -155,6 +155,9 @@ _SIG = {
     'bvq_group_quant_supported': (_i32, [_qd, _vp]),
     'bvq_group_quant_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp]),
     'bvq_group_quant_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
+    'bvq_group_mse_supported': (_i32, [_qd, _vp, _i32]),
+    'bvq_group_mse_fwd': (_i32, [_qd, _vp, _vp, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_group_mse_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _dbl, _vp, _vp]),
     'bvq_mx_quant_supported': (_i32, [_i32, _i64, _i32, _i32, _vp]),
     'bvq_mx_quant_fwd': (_i32, [_i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'bvq_mx_quant_bwd': (_i32, [_i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -510,6 +513,43 @@ def group_quant_bwd(desc, g, x, scale, stat, gscale, min_val, thr_div):
     dx = torch.empty_like(x)
     _launch(dev, 'bvq_group_quant_bwd', 'bvq_group_quant_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(scale),
             ptr(stat), ptr(gscale), *_scale_args(min_val, thr_div), ptr(dx))
+    return dx
+
+
+def mse_ratio_table(ratios):
+    """the host array of float32 candidate ratios that the bvq_group_mse_* entries take (keep it alive over the call)"""
+    return (ctypes.c_float * len(ratios))(*[float(r) for r in ratios])
+
+
+def group_mse_supported(desc, x, n_ratios):
+    """the clip-search group kernels cover this descriptor (as group_quant_supported), tensor and candidate count"""
+    return bool(lib.bvq_group_mse_supported(ctypes.byref(desc), ptr(x), int(n_ratios)))
+
+
+def group_mse_fwd(desc, x, table, min_val, thr_div):
+    """abs-max per group, the search over the candidate thresholds abs-max * table[i], scale and quantize-dequantize in
+    ONE launch -> (y like x, scale [groups], stat [groups], idx uint8 [groups]: the chosen candidate)"""
+    dev = require_device(x)
+    assert x.is_contiguous()
+    groups = int(desc.channels)
+    y = torch.empty_like(x)
+    scale = torch.empty(groups, dtype=x.dtype, device=dev)
+    stat = torch.empty(groups, dtype=x.dtype, device=dev)
+    idx = torch.empty(groups, dtype=torch.uint8, device=dev)
+    _launch(dev, 'bvq_group_mse_fwd', 'bvq_group_mse_fwd', ctypes.byref(desc), ptr(x), ctypes.addressof(table),
+            len(table), *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(stat), ptr(idx))
+    return y, scale, stat, idx
+
+
+def group_mse_bwd(desc, g, x, stat, idx, gscale, table, min_val, thr_div):
+    """backward of group_mse_fwd in ONE launch -> dx (idx is a constant; the statistic's gradient of every group, scaled
+    by the chosen ratio, deposited on the first element attaining the statistic); gscale as in group_quant_bwd"""
+    dev = require_device(g, x, stat, idx, gscale)
+    assert g.is_contiguous() and x.is_contiguous() and idx.is_contiguous() and idx.dtype == torch.uint8
+    assert gscale is None or gscale.is_contiguous()
+    dx = torch.empty_like(x)
+    _launch(dev, 'bvq_group_mse_bwd', 'bvq_group_mse_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(stat), ptr(idx),
+            ptr(gscale), ctypes.addressof(table), len(table), *_scale_args(min_val, thr_div), ptr(dx))
     return dx
 
 

@@ -1,7 +1,8 @@
 from .binary import BinaryQuant, ClampedBinaryQuant
 from .delay import DelayWrapper
-from .int import (DecoupledRescalingIntQuant, GroupwiseRescalingIntQuant, PrescaledRestrictIntQuant,
-                  PrescaledRestrictIntQuantWithInputBitWidth, RescalingIntQuant, TruncIntQuant)
+from .int import (DecoupledRescalingIntQuant, GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant,
+                  PrescaledRestrictIntQuant, PrescaledRestrictIntQuantWithInputBitWidth, RescalingIntQuant,
+                  TruncIntQuant)
 from .int_base import DecoupledIntQuant, IntQuant
 from .mx import MXPacked, MXQuant, mx_dequantize
 from .ternary import TernaryQuant

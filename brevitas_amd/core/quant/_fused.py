@@ -546,6 +546,40 @@ class GroupStatsFakeQuantFn(Function):
         return (dx,) + (None,) * 6
 
 
+class GroupMSEFakeQuantFn(Function):
+    """Group-wise weights with a searched clipping threshold (GroupwiseMSEIntQuant): GroupStatsFakeQuantFn with, per
+    group, the first of the candidate thresholds AbsMax * ratio_i that has the smallest squared quantization error,
+    x -> (y like x, scale [groups, 1], idx uint8 [groups]).  One launch each way (csrc/bvq_group_mse.hip): the search
+    runs on the registers that hold the group.  idx is a constant of the backward.  `table`: nat.mse_ratio_table.  The
+    caller has checked what the kernels cover (GroupwiseMSEIntQuant.forward)."""
+
+    @staticmethod
+    def forward(ctx, x, group_size, min_val, int_threshold, qmin, qmax, clamp_ste, table):
+        ctx.set_materialize_grads(False)  # an unused `scale` output must not cost a zero-fill + add
+        desc, thr_div = group_quant_call(x, group_size, int_threshold, qmin, qmax, clamp_ste)
+        y, scale, stat, idx = nat.group_mse_fwd(desc, x, table, min_val, thr_div)
+        ctx.desc, ctx.min_val, ctx.thr_div, ctx.table = desc, min_val, thr_div, table
+        ctx.save_for_backward(x, stat, idx)
+        ctx.mark_non_differentiable(idx)
+        return y, scale.view(-1, 1), idx
+
+    @staticmethod
+    def backward(ctx, gy, gscale, _gidx):
+        x, stat, idx = ctx.saved_tensors
+        if gy is None:  # only `scale` was used downstream
+            if gscale is None:
+                return (None,) * 8
+            gy = torch.zeros_like(x)
+        else:
+            gy = gy.to(x.dtype).contiguous()
+        if gscale is not None:
+            gscale = gscale.to(x.dtype).reshape(-1).contiguous()
+        if gy.data_ptr() % 16 != 0:
+            gy = gy.clone()
+        dx = nat.group_mse_bwd(ctx.desc, gy, x, stat, idx, gscale, ctx.table, ctx.min_val, ctx.thr_div)
+        return (dx,) + (None,) * 7
+
+
 class MXQuantFn(Function):
     """MX block-scaled quantizer (core/quant/mx.py): x -> (y like x, float32 scale [groups]).  One launch each way
     (csrc/bvq_mx_quant.hip); the backward recomputes each group's abs-max and exponent from x, so only x is saved.  The

@@ -12,7 +12,8 @@ ops + quantize kernel, with a backward that never materialises torch.max's dense
   * activations:  RuntimeStatsScaling(AbsMax) in training mode.
 Everything else takes the generic route below, which is the reference's own sequence.
 """
-from typing import Tuple
+import math
+from typing import Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -24,6 +25,7 @@ from brevitas_amd.core.quant import _fused
 from brevitas_amd.core.quant.delay import _NoDelay
 from brevitas_amd.core.quant.int_base import IntQuant
 from brevitas_amd.core.scaling.int_scaling import IntScaling
+from brevitas_amd import _aten
 from brevitas_amd import _native as nat
 from brevitas_amd.core.scaling.runtime import RuntimeStatsScaling, StatsFromParameterScaling
 from brevitas_amd.core.scaling.standalone import ConstScaling, ParameterFromRuntimeStatsScaling, ParameterScaling
@@ -434,12 +436,16 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
             return None
         return tmpl
 
-    def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    def _check_groups(self, x: Tensor) -> int:
         g = self.group_size
         if x.dim() < 2 or x.shape[0] == 0 or (x.numel() // x.shape[0]) % g != 0:
             raise ValueError('group-wise quantizer: a tensor of shape %s has no whole groups of %d elements per output '
                              'channel (at least 2 dimensions, numel / shape[0] a multiple of the group size)'
                              % (tuple(x.shape), g))
+        return g
+
+    def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        g = self._check_groups(x)
         bit_width = self.msb_clamp_bit_width_impl()
         tmpl = self._group_plan(x, bit_width)
         if tmpl is not None:
@@ -456,6 +462,97 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
 
     def bvq_forward_pre(self, x: Tensor, pre_op: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
         return self.forward(_fused.apply_pre_op(x, pre_op))
+
+
+def check_mse_ratios(ratios: Sequence[float]) -> Tuple[float, ...]:
+    """the candidate ratios of a clip search as a tuple of Python floats: at least one, the first exactly 1 (the abs-max
+    itself is always a candidate), every one finite and in (0, 1]"""
+    try:
+        out = tuple(float(r) for r in ratios)
+    except TypeError:
+        raise ValueError('mse_ratios must be a sequence of floats, got %r' % (ratios,))
+    if not out:
+        raise ValueError('mse_ratios is empty: the search needs at least the abs-max itself, [1.0]')
+    if out[0] != 1.0:
+        raise ValueError('mse_ratios[0] must be 1.0 (the abs-max itself is always the first candidate), got %r' % out[0])
+    for i, r in enumerate(out):
+        if not math.isfinite(r) or not 0.0 < r <= 1.0:
+            raise ValueError('mse_ratios[%d] = %r is not a finite value in (0, 1]' % (i, r))
+    return out
+
+
+class GroupwiseMSEIntQuant(GroupwiseRescalingIntQuant):
+    """GroupwiseRescalingIntQuant whose threshold is searched per group: of the candidates AbsMax * mse_ratios[i]
+    (mse_ratios[0] == 1) a group takes the first one with the smallest squared quantization error, in place of the
+    abs-max alone (the clip search of low-bit weight-only recipes).  DESIGN.md, "Group-wise clip search", states the
+    semantics; _aten.group_mse_index / group_mse_quantize_at are their composition from the sub-modules.  No parameter,
+    no buffer, the parent's state-dict keys.  `last_mse_index`: the candidates the last forward chose, uint8
+    [out, K / group_size] (a plain attribute; None before the first forward).
+
+    On the graph the parent recognises, with at most 64 candidates (bvq_group_mse_supported), search and quantization
+    run as one kernel each way (_fused.GroupMSEFakeQuantFn); everything else -- CPU tensors, other group sizes,
+    non-contiguous or misaligned weights, more candidates, config.FUSED_PATHS off -- takes the composed route.  The
+    chosen index is a constant of the backward on both."""
+
+    def __init__(self, int_quant: Module, scaling_impl: Module, int_scaling_impl: Module, zero_point_impl: Module,
+                 bit_width_impl: Module, group_size: int, mse_ratios: Sequence[float]):
+        super().__init__(int_quant, scaling_impl, int_scaling_impl, zero_point_impl, bit_width_impl, group_size)
+        if type(scaling_impl) is not StatsFromParameterScaling:
+            raise TypeError('GroupwiseMSEIntQuant searches around the statistic of StatsFromParameterScaling, got %s'
+                            % type(scaling_impl).__name__)
+        if not isinstance(int_quant.delay_wrapper.delay_impl, _NoDelay):
+            raise ValueError('GroupwiseMSEIntQuant: quant_delay_steps is not supported (the search quantizes the weight '
+                             'once per candidate)')
+        self.mse_ratios = check_mse_ratios(mse_ratios)
+        self.last_mse_index = None
+
+    def _mse_callables(self, x: Tensor, bit_width: Tensor):
+        """(xg, statistic [groups, 1], threshold -> scale, scale -> y) from the module's own sub-modules"""
+        xg = x.reshape(-1, self.group_size)
+        stat = self.scaling_impl.parameter_list_stats()
+        int_threshold = self.int_scaling_impl(bit_width)
+
+        def scale_of(threshold):
+            return self.scaling_impl.stats_scaling_impl(threshold) / int_threshold
+
+        def quantize(scale):
+            return self.int_quant(scale, self.zero_point_impl(xg, scale, bit_width), bit_width, xg)
+        return xg, stat, scale_of, quantize
+
+    def mse_index(self, x: Tensor) -> Tensor:
+        """the composed search alone -> uint8 [groups] (no gradient)"""
+        xg, stat, scale_of, quantize = self._mse_callables(x, self.msb_clamp_bit_width_impl())
+        return _aten.group_mse_index(xg, self.mse_ratios, stat, scale_of, quantize)
+
+    def quantize_at_index(self, x: Tensor, idx: Tensor) -> Tuple[Tensor, Tensor]:
+        """the composed route at given candidates (uint8 [groups], a constant) -> (y like x, scale (out, K / g, 1)),
+        differentiable through the sub-modules"""
+        self._check_groups(x)
+        xg, stat, scale_of, quantize = self._mse_callables(x, self.msb_clamp_bit_width_impl())
+        y, scale = _aten.group_mse_quantize_at(self.mse_ratios, idx.reshape(-1), stat, scale_of, quantize)
+        return y.reshape(x.shape), scale.reshape(x.shape[0], -1, 1)
+
+    def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        g = self._check_groups(x)
+        bit_width = self.msb_clamp_bit_width_impl()
+        tmpl = self._group_plan(x, bit_width)
+        if tmpl is not None:
+            desc, _ = _fused.group_quant_call(x, g, tmpl['int_thr'], tmpl['qmin'], tmpl['qmax'], tmpl['clamp_ste'])
+            if not nat.group_mse_supported(desc, x, len(self.mse_ratios)):
+                tmpl = None
+        if tmpl is not None:
+            table = self.__dict__.get('_bvq_mse_table')
+            if table is None:
+                table = self.__dict__['_bvq_mse_table'] = nat.mse_ratio_table(self.mse_ratios)
+            y, scale, idx = _fused.GroupMSEFakeQuantFn.apply(x, g, tmpl['min_val'], tmpl['int_thr'], tmpl['qmin'],
+                                                             tmpl['qmax'], tmpl['clamp_ste'], table)
+        else:
+            xg, stat, scale_of, quantize = self._mse_callables(x, bit_width)
+            idx = _aten.group_mse_index(xg, self.mse_ratios, stat, scale_of, quantize)
+            y, scale = _aten.group_mse_quantize_at(self.mse_ratios, idx, stat, scale_of, quantize)
+        self.last_mse_index = idx.reshape(x.shape[0], -1)
+        scale = scale.reshape(x.shape[0], -1, 1)
+        return y.reshape(x.shape), scale, self.zero_point_impl(x, scale, bit_width), bit_width
 
 
 class PrescaledRestrictIntQuantWithInputBitWidth(torch.nn.Module):

@@ -12,9 +12,7 @@
 // Results are the bits of the per-channel kernels on the tensor regrouped as [groups, g] (bvq_stats_fakequant_fwd,
 // bvq_fakequant_bwd_stats); only the ORDER in which a group's float32 scale-gradient terms are added differs, which
 // can move the deposited element by a rounding.
-#include "bvq_fakequant_bwd.h"
-#include "bvq_group_walk.h"  // the walk itself: segmented butterflies, chunk keys, the wave's window, the dispatch
-#include "bvq_stat_epilogue.h"
+#include "bvq_group_quant.h"  // the argument struct, the chunk bodies and the coverage check
 
 namespace bvq {
 
@@ -26,71 +24,6 @@ namespace bvq {
 #endif
 constexpr int kGroupFwdDepth = BVQ_GROUP_FWD_DEPTH;
 constexpr int kGroupBwdDepth = BVQ_GROUP_BWD_DEPTH;
-
-struct GroupArgs {
-  const void* x;
-  const void* g;       // bwd
-  void* y;             // fwd: y, bwd: dx
-  void* scale;         // fwd: [groups] out
-  void* stat;          // fwd: [groups] out, bwd: in
-  const void* gscale;  // bwd, nullable: gradient arriving through the returned scale, [groups]
-  int64_t chunks;      // 16-byte chunks of the tensor = groups * L
-  float qmin, qmax, min_val, thr_div;
-  int32_t use_min, clamp_ste;
-};
-
-// statistic -> scale with the rounding points of the scale epilogue (bvq_stat_epilogue.h): clamp_min, then the
-// quotient rounded to the scale's dtype, which is x's here
-template <typename T>
-__device__ __forceinline__ float group_scale(float stat, bool use_min, float min_val, float thr_div) {
-  const float thr = (use_min && stat < min_val) ? min_val : stat;  // NaN passes, like torch.clamp_min
-  return rnd<T>(thr / thr_div);
-}
-
-// the forward chain of IntQuant on a pair (the rounding points of bvq_quant_math.h; the last rounding is the caller's
-// pack2<T>).  16-bit types: the zero-point is +0, "+ zp" only turns -0 into +0 and "- zp" is the identity.
-template <typename T, typename Div>
-__device__ __forceinline__ f2 group_fwd_pair(f2 xf, const Div& div, float s, float qmin, float qmax) {
-  f2 t = rnd2<T>(div(xf));
-  t = t + 0.f;
-  t = round_op2<T, BVQ_ROUND>(t);
-  const f2 q = clamp_where2(t, qmin, qmax);
-  return sizeof(T) == 2 ? q * s : rnd2<T>(q - 0.f) * s;
-}
-
-template <typename T, bool NT, typename Div>
-__device__ __forceinline__ void group_fwd_chunk(const vec_t<T, elem<T>::vec>& xv, buf_t by, uint32_t off,
-                                                const Div& div, float s, float qmin, float qmax) {
-  constexpr int VEC = elem<T>::vec;
-  vec_t<T, VEC> yv;
-#pragma unroll
-  for (int k = 0; k < VEC; k += 2) {
-    const f2 r = group_fwd_pair<T>(widen2<T>(xv.v[k], xv.v[k + 1]), div, s, qmin, qmax);
-    pack2<T>(r, yv.v[k], yv.v[k + 1]);
-  }
-  buf_store<T, VEC, NT>(by, off, yv);  // dropped past the tensor's end
-}
-
-// every lane's scale suits the reciprocal form of its dtype (bvq_fakequant.h): decided per wave load, and the two
-// forms agree wherever the fast one is valid, so the choice cannot change a bit
-template <typename T>
-__device__ __forceinline__ bool wave_fast_div(float s) {
-  if constexpr (elem<T>::id == BVQ_BF16)
-    return __builtin_amdgcn_ballot_w64(!bf16_scale_ok(s)) == 0;
-  else if constexpr (elem<T>::id == BVQ_F16)
-    return __builtin_amdgcn_ballot_w64(!f16_scale_ok(s)) == 0;
-  else
-    return false;
-}
-template <typename T>
-using FastDiv = std::conditional_t<elem<T>::id == BVQ_BF16, DivBf16, DivF16R>;
-template <typename T>
-__device__ __forceinline__ FastDiv<T> fast_div(float s) {
-  if constexpr (elem<T>::id == BVQ_BF16)
-    return DivBf16{1.0f / s};
-  else
-    return DivF16R{s, 1.0f / s};
-}
 
 template <typename T, int L, bool NT>
 __global__ __launch_bounds__(kBlock) void group_quant_fwd_kernel(GroupArgs a) {
@@ -124,48 +57,6 @@ __global__ __launch_bounds__(kBlock) void group_quant_fwd_kernel(GroupArgs a) {
     }
     group_fwd_chunk<T, NT>(xv[j], by, off, DivExact{s}, s, qmin, qmax);
   }
-}
-
-// One chunk of the backward: dx and the two rounded scale-gradient terms per element exactly as the per-channel
-// backward of the stats-scaled graph computes them (bwd_elem2, kBwdDs), the group's sum, the statistic's gradient
-// with the rounding points of bwd_stats_finish_kernel, and its deposit on the first element attaining the statistic.
-template <typename T, int L, bool NT, typename Div>
-__device__ __forceinline__ void group_bwd_chunk(const GroupArgs& a, const vec_t<T, elem<T>::vec>& xv,
-                                                const vec_t<T, elem<T>::vec>& gv, buf_t bd, uint32_t off, int lane,
-                                                const Div& div, float s, float stat, float gsc, float qmin,
-                                                float qmax) {
-  constexpr int VEC = elem<T>::vec;
-  constexpr bool kZp0 = sizeof(T) == 2, kSame16 = sizeof(T) == 2;
-  const bool clamp_ste = a.clamp_ste != 0;
-  f2 ds2 = splat2(0.f), unused1 = splat2(0.f), unused2 = splat2(0.f);
-  vec_t<T, VEC> dv;
-#pragma unroll
-  for (int k = 0; k < VEC; k += 2) {
-    const f2 d = bwd_elem2<T, BVQ_ROUND, kBwdDs, kZp0, kSame16, true>(
-        widen2<T>(xv.v[k], xv.v[k + 1]), widen2<T>(gv.v[k], gv.v[k + 1]), div, s, 0.f, qmin, qmax, clamp_ste,
-        BVQ_ROUND, ds2, unused1, unused2);
-    pack2<T>(d, dv.v[k], dv.v[k + 1]);
-  }
-  const float ds = seg_sum<L>(ds2.x + ds2.y);
-  // dscale (+ the gradient arriving through `scale`) -> the statistic's gradient: scale = clamp_min_ste(stat) / thr_div,
-  // every torch op rounding to the scale's dtype (T); the straight-through clamp passes it on
-  float v = rnd<T>(ds);
-  if (a.gscale) v = rnd<T>(v + gsc);
-  const float dstat = rnd<T>(v / a.thr_div);
-  // first element of the group whose |x| is the statistic: segment-wide minimum over lane * VEC + index
-  const uint32_t skey = abs_bits<T>(from_f<T>(stat));
-  const uint32_t e0 = (uint32_t)(lane & (L - 1)) * VEC;
-  uint32_t first = ~0u;
-#pragma unroll
-  for (int k = VEC - 1; k >= 0; --k) first = abs_bits<T>(xv.v[k]) == skey ? e0 + k : first;
-  first = seg_min_u32<L>(first);  // ~0: no element equals the statistic (a NaN of another pattern)
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    // the owning lane adds sign(x) * dstat to its already rounded dx element: the deposit's two roundings
-    const float dep = to_f<T>(dv.v[k]) + deposit<T, BVQ_MATCH_ABS>(dstat, xv.v[k]);
-    dv.v[k] = first == e0 + k ? from_f<T>(dep) : dv.v[k];
-  }
-  buf_store<T, VEC, NT>(bd, off, dv);
 }
 
 template <typename T, int L, bool NT>
@@ -204,60 +95,6 @@ __global__ __launch_bounds__(kBlock) void group_quant_bwd_kernel(GroupArgs a) {
     }
     group_bwd_chunk<T, L, NT>(a, xv[j], gv[j], bd, off, lane, DivExact{s}, s, stat, gsc, qmin, qmax);
   }
-}
-
-// ------------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------------
-// what the kernels cover, apart from the pointers: BVQ_OK, or the error with its text
-static int group_check(const bvq_quant_desc* d, const char* what) {
-  int rc = validate(d);
-  if (rc) return rc;
-  if (d->outer != 1 || d->channels < 1 || !d->scale_per_channel || d->zp_per_channel) {
-    set_error("%s: the descriptor of a grouped tensor is outer 1, channels = groups, inner = group size, one scale per "
-              "channel and one zero-point", what);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (d->inner != 16 && d->inner != 32 && d->inner != 64 && d->inner != 128 && d->inner != 256) {
-    set_error("%s: group size %lld (16, 32, 64, 128 or 256)", what, (long long)d->inner);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (d->round_mode != BVQ_ROUND) {
-    set_error("%s: round_mode %d (half-even rounding only)", what, d->round_mode);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (d->x_dtype != d->ct_dtype || d->scale_dtype != d->x_dtype) {
-    set_error("%s: x, compute and scale dtype must agree (x=%d ct=%d scale=%d)", what, d->x_dtype, d->ct_dtype,
-              d->scale_dtype);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (d->pre_op != BVQ_PRE_NONE) {
-    set_error("%s: pre_op %d is not covered", what, d->pre_op);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (d->out_kind != BVQ_OUT_DEQUANT) {
-    set_error("%s: integer output is not covered", what);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  return BVQ_OK;
-}
-
-static GroupArgs group_args(const bvq_quant_desc* d, double min_val, int use_min, double thr_div) {
-  GroupArgs a = {};
-  a.chunks = d->channels * (d->inner * dtype_size(d->x_dtype) / 16);
-  a.qmin = d->qmin;
-  a.qmax = d->qmax;
-  a.min_val = round_host((float)min_val, d->x_dtype);  // python scalar -> the statistic's dtype
-  a.thr_div = (float)thr_div;
-  a.use_min = use_min;
-  a.clamp_ste = d->clamp_ste;
-  return a;
-}
-
-// f(type_tag<T>, int_c<L>, std::bool_constant<NT>) for the lanes per group of d's dtype and group size
-template <typename F>
-static int with_group_variant(const bvq_quant_desc* d, bool nt, F&& f) {
-  return with_group_variant(d->x_dtype, d->inner, nt, f);
 }
 
 }  // namespace bvq

@@ -13,8 +13,8 @@ import torch
 from brevitas_amd.core.bit_width import BitWidthConst
 from brevitas_amd.core.function_wrapper import (CeilSte, OverOutputChannelView, OverSubChannelBlockView, OverTensorView,
                                                 RoundSte, TensorClamp, TensorClampSte)
-from brevitas_amd.core.quant import (GroupwiseRescalingIntQuant, IntQuant, MXQuant, PrescaledRestrictIntQuant,
-                                     RescalingIntQuant)
+from brevitas_amd.core.quant import (GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant, IntQuant, MXQuant,
+                                     PrescaledRestrictIntQuant, RescalingIntQuant)
 from brevitas_amd.core.restrict_val import FloatRestrictValue, PowerOfTwoRestrictValue
 from brevitas_amd.core.scaling import (IntScaling, ParameterFromRuntimeStatsScaling, ParameterScaling,
                                        PowerOfTwoIntScaling, RuntimeStatsScaling, StatsFromParameterScaling)
@@ -23,7 +23,8 @@ from brevitas_amd.core.stats import (AbsMax, AbsMinMax, AbsPercentile, NegativeM
 from brevitas_amd.core.zero_point import ParameterFromRuntimeZeroPoint, StatsFromParameterZeroPoint, ZeroZeroPoint
 
 __all__ = ['Int8WeightPerChannelFloat', 'Int4WeightPerChannelFloat', 'Int8WeightPerGroupFloat',
-           'Int4WeightPerGroupFloat', 'Int8WeightPerTensorFloat',
+           'Int4WeightPerGroupFloat', 'Int8WeightPerGroupFloatMSE', 'Int4WeightPerGroupFloatMSE',
+           'Int8WeightPerTensorFloat',
            'Int8ActPerTensorFloat', 'Uint8ActPerTensorFloat', 'Int8ActPerChannelFloat',
            'ShiftedUint8WeightPerTensorFloat', 'ShiftedUint8WeightPerChannelFloat', 'ShiftedUint8ActPerTensorFloat',
            'Int8WeightPerTensorFixedPoint', 'Int8WeightPerChannelFixedPoint', 'Int8ActPerTensorFixedPoint',
@@ -61,13 +62,8 @@ def Int4WeightPerChannelFloat(weights) -> RescalingIntQuant:
     return Int8WeightPerChannelFloat(weights, bit_width=4)
 
 
-def Int8WeightPerGroupFloat(weights: Union[torch.nn.Parameter, Sequence[torch.nn.Parameter]], group_size: int = 128,
-                            bit_width: int = 8) -> GroupwiseRescalingIntQuant:
-    """Int8WeightPerChannelFloat with one scale per `group_size` consecutive input weights of each output channel
-    (Int8WeightPerGroupFloat of later Brevitas releases; not in this reference snapshot): the per-channel graph on the
-    weight regrouped as [out * K / group_size, group_size], K = Cin * kh * kw in memory order.  y has the weight's
-    shape, scale is (out, K / group_size, 1).  In a layer: weight_quant=functools.partial(Int8WeightPerGroupFloat,
-    group_size=64).  One tracked weight only: the groups of several weights do not line up."""
+def _group_weight_modules(weights, group_size: int, bit_width: int) -> tuple:
+    """the constructor arguments of GroupwiseRescalingIntQuant for one tracked weight, its shape checked here"""
     tracked = _params(weights)
     if len(tracked) != 1:
         raise ValueError('a group-wise weight quantizer tracks exactly one weight, got a list of %d' % len(tracked))
@@ -77,16 +73,50 @@ def Int8WeightPerGroupFloat(weights: Union[torch.nn.Parameter, Sequence[torch.nn
         raise ValueError('a weight of shape %s has no whole groups of %d elements per output channel'
                          % (tuple(w.shape), group_size))
     shape = (w.numel() // group_size, 1)
-    return GroupwiseRescalingIntQuant(
+    return (
         IntQuant(narrow_range=True, signed=True, float_to_int_impl=RoundSte(), tensor_clamp_impl=TensorClampSte()),
         StatsFromParameterScaling(AbsMax(1), OverSubChannelBlockView(group_size), 1, tracked, FloatRestrictValue(),
                                   shape, affine_rescaling=False, scaling_min_val=SCALING_MIN_VAL),
         IntScaling(signed=True, narrow_range=True), ZeroZeroPoint(), BitWidthConst(bit_width), group_size)
 
 
+def Int8WeightPerGroupFloat(weights: Union[torch.nn.Parameter, Sequence[torch.nn.Parameter]], group_size: int = 128,
+                            bit_width: int = 8) -> GroupwiseRescalingIntQuant:
+    """Int8WeightPerChannelFloat with one scale per `group_size` consecutive input weights of each output channel
+    (Int8WeightPerGroupFloat of later Brevitas releases; not in this reference snapshot): the per-channel graph on the
+    weight regrouped as [out * K / group_size, group_size], K = Cin * kh * kw in memory order.  y has the weight's
+    shape, scale is (out, K / group_size, 1).  In a layer: weight_quant=functools.partial(Int8WeightPerGroupFloat,
+    group_size=64).  One tracked weight only: the groups of several weights do not line up."""
+    return GroupwiseRescalingIntQuant(*_group_weight_modules(weights, group_size, bit_width))
+
+
 def Int4WeightPerGroupFloat(weights, group_size: int = 128) -> GroupwiseRescalingIntQuant:
     """Int8WeightPerGroupFloat with bit_width = 4: the usual weight-only format of LLM-sized linear layers"""
     return Int8WeightPerGroupFloat(weights, group_size=group_size, bit_width=4)
+
+
+def Int8WeightPerGroupFloatMSE(weights, group_size: int = 128, bit_width: int = 8, mse_iters: int = 20,
+                               mse_step: float = 0.025,
+                               mse_ratios: Optional[Sequence[float]] = None) -> GroupwiseMSEIntQuant:
+    """Int8WeightPerGroupFloat whose threshold is searched per group (core/quant/int.py: GroupwiseMSEIntQuant; the
+    `MSE` statistic of later Brevitas releases and the clip search of AWQ-style recipes, not in this reference
+    snapshot): of the candidates abs-max * ratio a group takes the first one with the smallest squared quantization
+    error.  ratios = [1 - i * mse_step for i in range(mse_iters)] unless `mse_ratios` lists them (the first is 1, every
+    one in (0, 1]).  Same outputs, state-dict keys and layer use as Int8WeightPerGroupFloat:
+    weight_quant=functools.partial(Int4WeightPerGroupFloatMSE, group_size=64); the chosen candidates of the last forward
+    are `last_mse_index`."""
+    if mse_ratios is None:
+        if int(mse_iters) < 1:
+            raise ValueError('mse_iters must be at least 1, got %r' % (mse_iters,))
+        mse_ratios = [1.0 - i * float(mse_step) for i in range(int(mse_iters))]
+    return GroupwiseMSEIntQuant(*_group_weight_modules(weights, group_size, bit_width), mse_ratios)
+
+
+def Int4WeightPerGroupFloatMSE(weights, group_size: int = 128, mse_iters: int = 20, mse_step: float = 0.025,
+                               mse_ratios: Optional[Sequence[float]] = None) -> GroupwiseMSEIntQuant:
+    """Int8WeightPerGroupFloatMSE with bit_width = 4: at 4 bits nearly every group clips below its abs-max"""
+    return Int8WeightPerGroupFloatMSE(weights, group_size=group_size, bit_width=4, mse_iters=mse_iters,
+                                      mse_step=mse_step, mse_ratios=mse_ratios)
 
 
 def _mx_weight(element_format: str, weights, group_size: int, scale_rule: str) -> MXQuant:

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 2
+#define BVQ_ABI_VERSION 3
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -703,6 +703,35 @@ int bvq_group_quant_fwd(const bvq_quant_desc* desc, const void* x, double min_va
                         void* scale, void* stat, bvq_stream_t stream);
 int bvq_group_quant_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* scale, const void* stat,
                         const void* gscale, double min_val, int use_min, double thr_div, void* dx, bvq_stream_t stream);
+
+/* ---- group-wise weights with a searched clipping threshold (MSE) -------------------------------------------------------
+ * The group-wise quantizer above with n candidate thresholds per group instead of the abs-max alone (the clip search
+ * of low-bit weight-only recipes; `MSE` statistic of later Brevitas releases, no reference counterpart).  Descriptor,
+ * min_val / use_min / thr_div, y, scale and stat as in bvq_group_quant_fwd.  ratios: a HOST array of n_ratios floats,
+ * copied into the kernel's arguments (nothing of it is read after the call returns); ratios[0] == 1, every ratio finite
+ * and in (0, 1], 1 <= n_ratios <= 64.  T is x's dtype.
+ * Forward, per group:
+ *     a   = max |x|                                      (stat, a value of T)
+ *     t_i = T(a * ratios[i])                             (product in float32, rounded once)
+ *     s_i = T(clamp_min(t_i, min_val) / thr_div)         (the scale of bvq_group_quant_fwd for the statistic t_i)
+ *     y_i = quantize-dequantize of the group at s_i      (the values of T that bvq_group_quant_fwd would store)
+ *     e_i = sum (float32(y_i) - float32(x))^2            (float32; added in the kernel's fixed butterfly order)
+ *     k   = the first i with e_i < e_j for every j < i   (strict: ties keep the earlier candidate; a group with a NaN or
+ *           Inf has NaN errors and keeps k = 0, a group of zeros keeps k = 0)
+ *   y = y_k, scale = s_k, stat = a, idx = k as uint8 [groups].
+ * Backward: k is a constant.  dx and the group's scale gradient v (+ gscale) as in bvq_group_quant_bwd at the scale
+ * s_k, derived again from stat and idx; dt = T(v / thr_div), da = T(dt * ratios[k]); sign(x) * da is added to the first
+ * element of the group with |x| == a.
+ * With ratios = {1} both entries compute the bits of bvq_group_quant_fwd / bvq_group_quant_bwd.
+ * One launch each way, no workspace, no atomics.  Covered: what the group-wise entries cover, and the ratios as above;
+ * anything else returns BVQ_ERR_UNSUPPORTED with a bvq_last_error() text, found before anything touches the device;
+ * bvq_group_mse_supported answers 1 / 0 for a descriptor, x and a candidate count. */
+int bvq_group_mse_supported(const bvq_quant_desc* desc, const void* x, int n_ratios);
+int bvq_group_mse_fwd(const bvq_quant_desc* desc, const void* x, const float* ratios, int n_ratios, double min_val,
+                      int use_min, double thr_div, void* y, void* scale, void* stat, void* idx, bvq_stream_t stream);
+int bvq_group_mse_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* stat, const void* idx,
+                      const void* gscale, const float* ratios, int n_ratios, double min_val, int use_min,
+                      double thr_div, void* dx, bvq_stream_t stream);
 
 /* ---- MX block-scaled quantizers: groups sharing one power-of-two scale, minifloat or MXINT8 elements -----------------
  * The OCP Microscaling formats the gfx950 matrix units take natively, as quantize-dequantize for training (no
