@@ -296,7 +296,7 @@ __device__ __forceinline__ void bwd_unit(const QuantArgs& a, const Unit& u, cons
   uint32_t stat_bits = 0;
   const bool per_channel = a.t.channels > 1;
   if constexpr (kTieMode<MODE>)
-    stat_bits = abs_bits<XT>(reinterpret_cast<const XT*>(a.tie_stat)[u.channel]);
+    stat_bits = stat_key<XT>(reinterpret_cast<const XT*>(a.tie_stat)[u.channel]);
 
   float ds_acc = 0.f, dzp_acc = 0.f, dq_acc = 0.f;
   uint32_t umax = 0;  // kBwdDsTies: largest |x| key this lane has seen in the unit's full chunks
@@ -715,7 +715,7 @@ __device__ __forceinline__ void cols_bwd_rows(const ColsQuantArgs& a, const Cols
 #pragma unroll
   for (int k = 0; k < VEC; ++k) {
     const int64_t col = (int64_t)ln.chunk * VEC + k;
-    sk[k] = abs_bits<T>(reinterpret_cast<const T*>(a.tie_stat)[col / a.inner]);
+    sk[k] = stat_key<T>(reinterpret_cast<const T*>(a.tie_stat)[col / a.inner]);
     uint32_t key;
     if constexpr (kSame16) {
       const uint32_t k16 = (k & 1) ? (um[k / 2] >> 16) : (um[k / 2] & 0xffffu);
@@ -876,7 +876,7 @@ __global__ void shard_unpack_deposit_kernel(const double* __restrict__ all, int3
   const float ds = (float)sum;
   if (dscale_total) dscale_total[c] = ds;
   const long long pos = first_pos[c];
-  if (owner != (double)rank || pos < 0) return;
+  if (owner != (double)rank || pos < 0 || !x) return;  // (x null: an empty shard, which owns nothing)
   float v = round_rt(ds, gs.scale_dtype);
   v = round_rt(v / gs.int_threshold, gs.quot_dtype);
   const float g = rnd<T>(v);

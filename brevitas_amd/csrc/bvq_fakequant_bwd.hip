@@ -318,9 +318,10 @@ extern "C" int bvq_shard_unpack_deposit(int dtype, const void* x, void* dx, cons
                                         int64_t channels, int rank, const int64_t* first_pos, int64_t inner,
                                         int scale_dtype, double int_threshold, int quot_dtype, int pre_op,
                                         float* dscale_total, bvq_stream_t stream) {
+  // (x and dx both null: an empty shard, which owns no deposit)
   if (dtype < BVQ_F32 || dtype > BVQ_F16 || scale_dtype < BVQ_F32 || scale_dtype > BVQ_F16 || quot_dtype < BVQ_F32 ||
-      quot_dtype > BVQ_F16 || channels < 1 || world < 1 || rank < 0 || rank >= world || inner < 1 || !x || !dx ||
-      !gathered || !first_pos || !(int_threshold == int_threshold)) {
+      quot_dtype > BVQ_F16 || channels < 1 || world < 1 || rank < 0 || rank >= world || inner < 1 ||
+      (x == nullptr) != (dx == nullptr) || !gathered || !first_pos || !(int_threshold == int_threshold)) {
     set_error("bvq_shard_unpack_deposit: bad argument");
     return BVQ_ERR_INVALID;
   }
@@ -360,6 +361,18 @@ static int bwd_stats_impl(const bvq_quant_desc* d, const void* g, const void* x,
   hipStream_t st = (hipStream_t)stream;
   const int32_t channels = (int32_t)d->channels;
   if (n == 0) {
+    if (shard) {  // an empty shard claims nothing: zero sums, no owner, no position (dscale is the entry's dummy)
+      QuantArgs fa = {};
+      fa.t.nob = 1;
+      fa.t.channels = channels;
+      fa.arrive_per_channel = 0;  // no partials: channel_finish reads none and writes acc = 0, pmin = ~0
+      fa.shard_msg = shard->msg;
+      fa.shard_pos = shard->pos;
+      fa.shard_rank = shard->rank;
+      const dim3 cgrid((unsigned)((channels + kWavesPerBlock - 1) / kWavesPerBlock));
+      channel_finish_kernel<float><<<cgrid, dim3(kBlock), 0, st>>>(fa);
+      return check_launch("bvq_fakequant_bwd_shard/empty");
+    }
     if (dscale) (void)hipMemsetAsync(dscale, 0, sizeof(float) * channels, st);
     return BVQ_OK;
   }

@@ -788,7 +788,7 @@ __global__ void running_stats_kernel(void* running, int run_dtype, const void* s
 template <typename T, int MATCH>
 __device__ __forceinline__ bool is_tie(T v, T stat) {
   if constexpr (MATCH == BVQ_MATCH_ABS) {
-    return abs_bits<T>(v) == abs_bits<T>(stat);
+    return abs_bits<T>(v) == stat_key<T>(stat);  // (a NaN statistic is attained by nothing)
   } else {
     return to_f<T>(v) == to_f<T>(stat);  // -0 == +0, NaN never matches (torch: input == value)
   }
@@ -958,7 +958,7 @@ __global__ __launch_bounds__(kBlock) void tie_apply_full_kernel(const void* x, c
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
     const T xv = xp[i];
     const bool tie = (gstat.pre_relu && MATCH == BVQ_MATCH_ABS)
-                         ? pre_abs_bits<T, true>(xv) == abs_bits<T>(sv)
+                         ? pre_abs_bits<T, true>(xv) == stat_key<T>(sv)
                          : is_tie<T, MATCH>(xv, sv);
     if (tie) {
       const float term = deposit<T, MATCH>(share, xv, gstat.pre_relu != 0);

@@ -43,6 +43,14 @@ __device__ __forceinline__ uint32_t abs_bits<f16_t>(f16_t v) {
   return (uint32_t)(__builtin_bit_cast(uint16_t, v) & 0x7fffu);
 }
 
+// the key a tie search compares the |x| keys with: the statistic's own, or -- a NaN statistic -- ~0, which is no key:
+// like torch's ==, a NaN is attained by nothing, not even by the NaN of the same bit pattern it was taken from
+template <typename T>
+__device__ __forceinline__ uint32_t stat_key(T stat) {
+  const uint32_t b = abs_bits<T>(stat);
+  return b > abs_bits<T>((T)__builtin_inff()) ? ~0u : b;
+}
+
 // torch.relu: x < 0 ? 0 : x  (NaN and -0.0 pass through unchanged)
 __device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
 

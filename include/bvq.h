@@ -280,6 +280,14 @@ int bvq_scale_from_stat_running(const float* stat32, int64_t channels, int stat_
  * bvq_fakequant_bwd_stats_onepass -- the streaming kernel's last-arriving wave per channel then writes the message
  * (one launch); without it, or on column-mapped layouts, a one-wave-per-channel launch follows the streaming kernel.
  * workspace: bvq_fakequant_bwd_stats_workspace_bytes.
+ * An EMPTY shard (outer = 0) is legal and claims nothing: message[c] = 0.0, message[channels + c] = 2^30 and
+ * first_pos[c] = -1 for every channel, written by one small launch; g, x, dx and the workspace are not touched and may
+ * be null.  bvq_shard_unpack_deposit takes such a shard's x and dx as two null pointers: it owns no deposit.  (Two null
+ * pointers skip the deposit on ANY rank, the owning one included, and still return BVQ_OK: pass them for an empty shard
+ * only.  One null pointer of the two is refused.)
+ * A NaN statistic is attained by nothing -- torch's ==, whatever the NaN's bit pattern -- so a NaN channel has no
+ * claim, no position and no deposit.  The same rule holds for every tie search of this library: tie_stat of
+ * bvq_fakequant_bwd, bvq_fakequant_bwd_stats, the weight lists, bvq_stat_tie_scan / bvq_stat_tie_apply and bvq_stat_bwd.
  * bvq_shard_unpack_deposit: from the gathered [world][2][channels] messages, per channel: dscale_total (nullable out)
  * = the double sum over the shards in rank order, rounded once (the same bits on every rank); on the shard that owns
  * the deposit (lowest claiming rank) dscale -> statistic's gradient (B/core/quant/int.py:160 backward, rounding points
