@@ -33,7 +33,7 @@ CLUSTER_AUTO, CLUSTER_WALK, CLUSTER_ONESHOT = range(3)
 MX_E4M3, MX_E5M2, MX_E3M2, MX_E2M3, MX_E2M1, MX_INT8 = range(6)
 MX_FLOOR, MX_CEIL = 0, 1
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -158,6 +158,9 @@ _SIG = {
     'bvq_group_mse_supported': (_i32, [_qd, _vp, _i32]),
     'bvq_group_mse_fwd': (_i32, [_qd, _vp, _vp, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
     'bvq_group_mse_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _dbl, _vp, _vp]),
+    'bvq_group_shifted_supported': (_i32, [_qd, _vp]),
+    'bvq_group_shifted_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_group_shifted_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
     'bvq_mx_quant_supported': (_i32, [_i32, _i64, _i32, _i32, _vp]),
     'bvq_mx_quant_fwd': (_i32, [_i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'bvq_mx_quant_bwd': (_i32, [_i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -550,6 +553,40 @@ def group_mse_bwd(desc, g, x, stat, idx, gscale, table, min_val, thr_div):
     dx = torch.empty_like(x)
     _launch(dev, 'bvq_group_mse_bwd', 'bvq_group_mse_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(stat), ptr(idx),
             ptr(gscale), ctypes.addressof(table), len(table), *_scale_args(min_val, thr_div), ptr(dx))
+    return dx
+
+
+def group_shifted_supported(desc, x):
+    """the asymmetric group-wise kernels cover this descriptor (that of group_quant_supported with one zero-point per
+    group in x's dtype) and tensor"""
+    return bool(lib.bvq_group_shifted_supported(ctypes.byref(desc), ptr(x)))
+
+
+def group_shifted_fwd(desc, x, min_val, thr_div):
+    """max and min per group, scale, integer zero-point and quantize-dequantize in ONE launch -> (y like x, scale [groups],
+    zp [groups], stat [2 * groups]: the maxima then the minima), all in x's dtype"""
+    dev = require_device(x)
+    assert x.is_contiguous()
+    groups = int(desc.channels)
+    y = torch.empty_like(x)
+    scale = torch.empty(groups, dtype=x.dtype, device=dev)
+    zp = torch.empty(groups, dtype=x.dtype, device=dev)
+    stat = torch.empty(2 * groups, dtype=x.dtype, device=dev)
+    _launch(dev, 'bvq_group_shifted_fwd', 'bvq_group_shifted_fwd', ctypes.byref(desc), ptr(x),
+            *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(zp), ptr(stat))
+    return y, scale, zp, stat
+
+
+def group_shifted_bwd(desc, g, x, stat, gscale, gzp, min_val, thr_div):
+    """backward of group_shifted_fwd in ONE launch -> dx (the gradients of a group's maximum and minimum deposited on the
+    first element equal to each); gscale / gzp: None, or the gradient arriving through `scale` / `zp`, [groups] in x's
+    dtype"""
+    dev = require_device(g, x, stat, gscale, gzp)
+    assert g.is_contiguous() and x.is_contiguous() and stat.is_contiguous()
+    assert (gscale is None or gscale.is_contiguous()) and (gzp is None or gzp.is_contiguous())
+    dx = torch.empty_like(x)
+    _launch(dev, 'bvq_group_shifted_bwd', 'bvq_group_shifted_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(stat),
+            ptr(gscale), ptr(gzp), *_scale_args(min_val, thr_div), ptr(dx))
     return dx
 
 

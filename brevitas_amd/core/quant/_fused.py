@@ -546,6 +546,51 @@ class GroupStatsFakeQuantFn(Function):
         return (dx,) + (None,) * 6
 
 
+def group_shifted_call(x: Tensor, group_size: int, int_threshold: float, qmin: float, qmax: float, clamp_ste):
+    """group_quant_call for the asymmetric kernels (nat.group_shifted_fwd / group_shifted_bwd): one zero-point per
+    group, in x's dtype"""
+    code = nat.dtype_code(x.dtype)
+    desc = nat.QuantDesc(1, x.numel() // group_size, group_size, code, code, code, code, 1, 1, qmin, qmax,
+                         nat.ROUND, scalar_mode(), int(clamp_ste), nat.OUT_DEQUANT, nat.PRE_NONE)
+    return desc, _as_dtype_value(int_threshold, x.dtype)
+
+
+class GroupShiftedFakeQuantFn(Function):
+    """Asymmetric group-wise weights: per group of `group_size` consecutive elements, scale = clamp_min(|max - min|,
+    min_val) / int_threshold, integer zero-point = to_int(-min(min, 0)), IntQuant with unsigned codes;
+    x -> (y like x, scale [groups, 1], zero_point [groups, 1]).  One launch each way (csrc/bvq_group_shifted.hip): both
+    statistics, both gradient sums and the two deposits stay in registers.  Gradients arriving through the returned
+    scale and zero-point join the group's sums.  The caller has checked what the kernels cover
+    (GroupwiseRescalingIntQuant._group_plan)."""
+
+    @staticmethod
+    def forward(ctx, x, group_size, min_val, int_threshold, qmin, qmax, clamp_ste):
+        ctx.set_materialize_grads(False)  # unused `scale` / `zero_point` outputs must not cost a zero-fill + add
+        desc, thr_div = group_shifted_call(x, group_size, int_threshold, qmin, qmax, clamp_ste)
+        y, scale, zp, stat = nat.group_shifted_fwd(desc, x, min_val, thr_div)
+        ctx.desc, ctx.min_val, ctx.thr_div = desc, min_val, thr_div
+        ctx.save_for_backward(x, stat)
+        return y, scale.view(-1, 1), zp.view(-1, 1)
+
+    @staticmethod
+    def backward(ctx, gy, gscale, gzp):
+        x, stat = ctx.saved_tensors
+        if gy is None:  # only `scale` / `zero_point` were used downstream
+            if gscale is None and gzp is None:
+                return (None,) * 7
+            gy = torch.zeros_like(x)
+        else:
+            gy = gy.to(x.dtype).contiguous()
+        if gscale is not None:
+            gscale = gscale.to(x.dtype).reshape(-1).contiguous()
+        if gzp is not None:
+            gzp = gzp.to(x.dtype).reshape(-1).contiguous()
+        if gy.data_ptr() % 16 != 0:
+            gy = gy.clone()
+        dx = nat.group_shifted_bwd(ctx.desc, gy, x, stat, gscale, gzp, ctx.min_val, ctx.thr_div)
+        return (dx,) + (None,) * 6
+
+
 class GroupMSEFakeQuantFn(Function):
     """Group-wise weights with a searched clipping threshold (GroupwiseMSEIntQuant): GroupStatsFakeQuantFn with, per
     group, the first of the candidate thresholds AbsMax * ratio_i that has the smallest squared quantization error,

@@ -29,8 +29,8 @@ from brevitas_amd import _aten
 from brevitas_amd import _native as nat
 from brevitas_amd.core.scaling.runtime import RuntimeStatsScaling, StatsFromParameterScaling
 from brevitas_amd.core.scaling.standalone import ConstScaling, ParameterFromRuntimeStatsScaling, ParameterScaling
-from brevitas_amd.core.stats.stats_op import AbsMax
-from brevitas_amd.core.zero_point import ZeroZeroPoint
+from brevitas_amd.core.stats.stats_op import AbsMax, AbsMinMax, NegativeMinOrZero
+from brevitas_amd.core.zero_point import StatsFromParameterZeroPoint, ZeroZeroPoint
 from brevitas_amd.function.ops import int_range_host
 
 
@@ -368,8 +368,16 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
 
     One recognised graph runs as one kernel each way (_fused.GroupStatsFakeQuantFn): the AbsMax statistic of exactly the
     tracked weight over OverSubChannelBlockView(group_size), a plain lower bound, IntQuant with half-even rounding and
-    a zero zero-point, on a contiguous 16-byte-aligned device tensor with a group size the kernels cover.  Everything
-    else takes the generic route below.  Inside `with WeightQuantGroup(...)` such a quantizer keeps its own route."""
+    a zero zero-point, on a contiguous 16-byte-aligned device tensor with a group size the kernels cover.  A second one
+    is the asymmetric graph (_fused.GroupShiftedFakeQuantFn): AbsMinMax scale and a StatsFromParameterZeroPoint
+    (NegativeMinOrZero, quantized) of the same weight over the same groups, unsigned full range; its zero-point comes
+    back integer-valued, in x's dtype and shaped like the scale.  Everything else takes the generic route below, which
+    computes a statistics-based zero-point once, on the regrouped tensor.  Inside `with WeightQuantGroup(...)` such a
+    quantizer keeps its own route.
+
+    The asymmetric graph is the reference's, as it is: the range is max - min, not max(max, 0) - min(min, 0), so a group
+    of positive values only gets zero-point 0 and clips its upper part, one of negative values only gets 2^b - 1 and
+    clips likewise, and a constant non-zero group gets the lower bound of the scale; y and the gradients stay finite."""
 
     def __init__(self, int_quant: Module, scaling_impl: Module, int_scaling_impl: Module, zero_point_impl: Module,
                  bit_width_impl: Module, group_size: int):
@@ -402,7 +410,9 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
         if getattr(iq.float_to_int_impl, 'bvq_round_mode', None) != nat.ROUND or \
                 getattr(iq.tensor_clamp_impl, 'bvq_clamp_ste', None) is None:
             return None
-        if type(self.zero_point_impl) is not ZeroZeroPoint or type(self.int_scaling_impl) is not IntScaling:
+        zpi = self.zero_point_impl
+        if type(zpi) not in (ZeroZeroPoint, StatsFromParameterZeroPoint) or \
+                type(self.int_scaling_impl) is not IntScaling:
             return None
         if type(sc) is not StatsFromParameterScaling:
             return None
@@ -411,15 +421,32 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
         if pls.extra_tracked_params_list is not None or type(view) is not OverSubChannelBlockView or \
                 view.bvq_group_size != self.group_size:
             return None
-        if type(stats.stats_impl) is not AbsMax or stats.stats_impl.stats_reduce_dim not in (1, -1):
+        shifted = type(zpi) is StatsFromParameterZeroPoint
+        if type(stats.stats_impl) is not (AbsMinMax if shifted else AbsMax) or \
+                stats.stats_impl.stats_reduce_dim not in (1, -1):
             return None
+        if shifted:
+            # the asymmetric graph: the zero-point is NegativeMinOrZero of the same weight over the same groups,
+            # quantized by this quantizer's own to_int, whose "+ min_int" is "+ 0" for the unsigned full range
+            zls, ssz = zpi.parameter_list_stats, zpi.scale_shift_zero_point
+            zview, zstats = zls.first_tracked_param.view_shape_impl, zls.stats
+            if zls.extra_tracked_params_list is not None or type(zview) is not OverSubChannelBlockView or \
+                    zview.bvq_group_size != self.group_size or \
+                    zls.first_tracked_param.parameter is not pls.first_tracked_param.parameter:
+                return None
+            if type(zstats.stats_impl) is not NegativeMinOrZero or \
+                    zstats.stats_impl.stats_reduce_dim not in (1, -1) or \
+                    tuple(zstats.stats_output_shape) != tuple(stats.stats_output_shape):
+                return None
+            if ssz.int_quant is not iq or not ssz.quantize_zero_point or iq.signed or iq.narrow_range:
+                return None
         min_val = sc.stats_scaling_impl.bvq_plain_min_val()
         if min_val is None or self.group_size not in (16, 32, 64, 128, 256):
             return None
         qmin, qmax = int_range_host(iq.signed, iq.narrow_range, bw)
         return dict(weight=pls.first_tracked_param.parameter, shape=tuple(stats.stats_output_shape), min_val=min_val,
                     int_thr=self.int_scaling_impl.host_value(bw), qmin=qmin, qmax=qmax,
-                    clamp_ste=iq.tensor_clamp_impl.bvq_clamp_ste)
+                    clamp_ste=iq.tensor_clamp_impl.bvq_clamp_ste, shifted=shifted)
 
     def _group_plan(self, x: Tensor, bit_width: Tensor):
         """the template if the one-kernel route applies to this input, else None"""
@@ -448,7 +475,11 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
         g = self._check_groups(x)
         bit_width = self.msb_clamp_bit_width_impl()
         tmpl = self._group_plan(x, bit_width)
-        if tmpl is not None:
+        zero_point = None
+        if tmpl is not None and tmpl['shifted']:
+            y, scale, zero_point = _fused.GroupShiftedFakeQuantFn.apply(
+                x, g, tmpl['min_val'], tmpl['int_thr'], tmpl['qmin'], tmpl['qmax'], tmpl['clamp_ste'])
+        elif tmpl is not None:
             y, scale = _fused.GroupStatsFakeQuantFn.apply(x, g, tmpl['min_val'], tmpl['int_thr'], tmpl['qmin'],
                                                           tmpl['qmax'], tmpl['clamp_ste'])
         else:
@@ -456,9 +487,16 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
             xg = x.reshape(-1, g)
             threshold = self.scaling_impl(xg)
             scale = threshold / self.int_scaling_impl(bit_width)
-            y = self.int_quant(scale, self.zero_point_impl(xg, scale, bit_width), bit_width, xg)
+            zp = self.zero_point_impl(xg, scale, bit_width)
+            y = self.int_quant(scale, zp, bit_width, xg)
+            if type(self.zero_point_impl) is not ZeroZeroPoint:
+                zero_point = zp  # a statistic of the groups, computed once: one value per group, like the scale
         scale = scale.reshape(x.shape[0], -1, 1)
-        return y.reshape(x.shape), scale, self.zero_point_impl(x, scale, bit_width), bit_width
+        if zero_point is None:
+            zero_point = self.zero_point_impl(x, scale, bit_width)
+        elif zero_point.numel() == scale.numel():
+            zero_point = zero_point.reshape(scale.shape)
+        return y.reshape(x.shape), scale, zero_point, bit_width
 
     def bvq_forward_pre(self, x: Tensor, pre_op: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
         return self.forward(_fused.apply_pre_op(x, pre_op))
@@ -536,6 +574,8 @@ class GroupwiseMSEIntQuant(GroupwiseRescalingIntQuant):
         g = self._check_groups(x)
         bit_width = self.msb_clamp_bit_width_impl()
         tmpl = self._group_plan(x, bit_width)
+        if tmpl is not None and tmpl['shifted']:
+            tmpl = None  # the clip search is built for the symmetric graph alone
         if tmpl is not None:
             desc, _ = _fused.group_quant_call(x, g, tmpl['int_thr'], tmpl['qmin'], tmpl['qmax'], tmpl['clamp_ste'])
             if not nat.group_mse_supported(desc, x, len(self.mse_ratios)):

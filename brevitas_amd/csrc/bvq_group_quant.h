@@ -32,23 +32,28 @@ __device__ __forceinline__ float group_scale(float stat, bool use_min, float min
 
 // the forward chain of IntQuant on a pair (the rounding points of bvq_quant_math.h; the last rounding is the caller's
 // pack2<T>).  16-bit types: the zero-point is +0, "+ zp" only turns -0 into +0 and "- zp" is the identity.
-template <typename T, typename Div>
-__device__ __forceinline__ f2 group_fwd_pair(f2 xf, const Div& div, float s, float qmin, float qmax) {
+// kZp: the group has a zero-point of its own (bvq_group_shifted.hip), added and subtracted with their roundings.
+template <typename T, bool kZp = false, typename Div>
+__device__ __forceinline__ f2 group_fwd_pair(f2 xf, const Div& div, float s, float qmin, float qmax, float zp = 0.f) {
   f2 t = rnd2<T>(div(xf));
-  t = t + 0.f;
+  if constexpr (kZp)
+    t = rnd2<T>(t + zp);
+  else
+    t = t + 0.f;
   t = round_op2<T, BVQ_ROUND>(t);
   const f2 q = clamp_where2(t, qmin, qmax);
+  if constexpr (kZp) return rnd2<T>(q - zp) * s;
   return sizeof(T) == 2 ? q * s : rnd2<T>(q - 0.f) * s;
 }
 
-template <typename T, bool NT, typename Div>
+template <typename T, bool NT, bool kZp = false, typename Div>
 __device__ __forceinline__ void group_fwd_chunk(const vec_t<T, elem<T>::vec>& xv, buf_t by, uint32_t off,
-                                                const Div& div, float s, float qmin, float qmax) {
+                                                const Div& div, float s, float qmin, float qmax, float zp = 0.f) {
   constexpr int VEC = elem<T>::vec;
   vec_t<T, VEC> yv;
 #pragma unroll
   for (int k = 0; k < VEC; k += 2) {
-    const f2 r = group_fwd_pair<T>(widen2<T>(xv.v[k], xv.v[k + 1]), div, s, qmin, qmax);
+    const f2 r = group_fwd_pair<T, kZp>(widen2<T>(xv.v[k], xv.v[k + 1]), div, s, qmin, qmax, zp);
     pack2<T>(r, yv.v[k], yv.v[k + 1]);
   }
   buf_store<T, VEC, NT>(by, off, yv);  // dropped past the tensor's end
@@ -124,12 +129,22 @@ __device__ __forceinline__ void group_bwd_chunk(const GroupArgs& a, const vec_t<
 // host side
 // ------------------------------------------------------------------------------------------------
 // what the kernels cover, apart from the pointers: BVQ_OK, or the error with its text
-static int group_check(const bvq_quant_desc* d, const char* what) {
+// shifted: the asymmetric quantizer (bvq_group_shifted.hip), one zero-point per group in x's dtype
+static int group_check(const bvq_quant_desc* d, const char* what, bool shifted = false) {
   int rc = validate(d);
   if (rc) return rc;
-  if (d->outer != 1 || d->channels < 1 || !d->scale_per_channel || d->zp_per_channel) {
+  if (shifted && (d->outer != 1 || d->channels < 1 || !d->scale_per_channel || !d->zp_per_channel)) {
+    set_error("%s: the descriptor of a grouped tensor with zero-points is outer 1, channels = groups, inner = group size, "
+              "one scale and one zero-point per channel", what);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (!shifted && (d->outer != 1 || d->channels < 1 || !d->scale_per_channel || d->zp_per_channel)) {
     set_error("%s: the descriptor of a grouped tensor is outer 1, channels = groups, inner = group size, one scale per "
               "channel and one zero-point", what);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (shifted && d->zp_dtype != d->x_dtype) {
+    set_error("%s: x and zero-point dtype must agree (x=%d zp=%d)", what, d->x_dtype, d->zp_dtype);
     return BVQ_ERR_UNSUPPORTED;
   }
   if (d->inner != 16 && d->inner != 32 && d->inner != 64 && d->inner != 128 && d->inner != 256) {

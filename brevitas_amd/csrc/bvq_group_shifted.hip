@@ -1,0 +1,345 @@
+// bvq_group_shifted.hip -- asymmetric group-wise weight quantizer: unsigned codes, one scale and one integer zero-point
+// per `group_size` consecutive elements (the 4-bit weight-only format of AWQ / GPTQ style checkpoints), one launch each
+// way on the sub-wave group walk of bvq_group_walk.h.
+//
+// The result is the per-channel asymmetric graph (AbsMinMax scale, NegativeMinOrZero zero-point quantized through the
+// quantizer's own to_int) on the tensor regrouped as [groups, g], every torch op rounding to x's dtype T:
+//   mx = max x, mn = min x
+//   scale = T(clamp_min(|T(mx - mn)|, min_val) / thr_div)
+//   m0 = mn <= 0 ? mn : 0;  zp = clamp(round(T(T(-m0 / scale) + 0)), qmin, qmax)
+//   q = clamp(round(T(T(x / scale) + zp)), qmin, qmax);  y = T(T(q - zp) * scale)
+// A group's two statistics are segmented butterflies over ordered integer keys of the signed values, the two gradient
+// sums of the backward (scale, zero-point) segmented float32 sums; the statistics' gradients land on the first element
+// equal to each (-0 equals +0).  No LDS, no atomics, no workspace, no second launch.
+//   forward   reads x, writes y                (+ 5 * bytes(x) / g for scale, zp and the two statistics)
+//   backward  reads g and x, writes dx once    (+ 2 * bytes(x) / g for the statistics, + gscale / gzp when given)
+// Only the ORDER in which a group's float32 gradient terms are added differs from the per-channel kernels, which can
+// move the two deposited elements by a rounding.
+#include "bvq_group_quant.h"  // the argument struct, the forward chain of a chunk and the coverage check
+
+namespace bvq {
+
+#ifndef BVQ_GROUP_SHIFTED_FWD_DEPTH
+#define BVQ_GROUP_SHIFTED_FWD_DEPTH 4  // wave loads of x in flight per wave
+#endif
+#ifndef BVQ_GROUP_SHIFTED_BWD_DEPTH
+#define BVQ_GROUP_SHIFTED_BWD_DEPTH 2  // wave loads of x and of g in flight per wave
+#endif
+constexpr int kShiftedFwdDepth = BVQ_GROUP_SHIFTED_FWD_DEPTH;
+constexpr int kShiftedBwdDepth = BVQ_GROUP_SHIFTED_BWD_DEPTH;
+
+// GroupArgs with `stat` holding [2 * groups] values, the maxima then the minima (as BVQ_STAT_MINMAX)
+struct GroupShiftedArgs : GroupArgs {
+  void* zp;         // fwd: [groups] out
+  const void* gzp;  // bwd, nullable: gradient arriving through the returned zero-point, [groups]
+};
+
+// Largest and smallest element of one 16-byte chunk as ORDERED keys: the sign-magnitude pattern b of a float mapped to
+// an integer that compares like the value (negative: magnitude bits flipped), then biased into unsigned order so that
+// seg_max_u32 / seg_min_u32 apply.  A NaN keeps its place at one of the two ends (positive above +inf, negative below
+// -inf), so it always survives one of the two reductions: shifted_stats() hands it to both statistics.  The keys of -0
+// and +0 differ by one; nothing reads that: the statistics are compared as VALUES from here on.
+template <typename T>
+__device__ __forceinline__ void chunk_minmax_keys(const vec_t<T, elem<T>::vec>& xv, uint32_t& kmax, uint32_t& kmin) {
+  constexpr int VEC = elem<T>::vec;
+  if constexpr (sizeof(T) == 2) {
+    typedef short i16x2 __attribute__((ext_vector_type(2)));
+    const vec_t<uint32_t, VEC / 2> w = __builtin_bit_cast(vec_t<uint32_t, VEC / 2>, xv);
+    i16x2 hi = {-32768, -32768}, lo = {32767, 32767};
+#pragma unroll
+    for (int k = 0; k < VEC / 2; ++k) {
+      const i16x2 b = __builtin_bit_cast(i16x2, w.v[k]);
+      const i16x2 key = b ^ ((b >> 15) & (short)0x7fff);  // signed order, two elements per word
+      hi = __builtin_elementwise_max(hi, key);
+      lo = __builtin_elementwise_min(lo, key);
+    }
+    const short mx = hi.x > hi.y ? hi.x : hi.y, mn = lo.x < lo.y ? lo.x : lo.y;
+    kmax = ((uint32_t)(uint16_t)mx) ^ 0x8000u;
+    kmin = ((uint32_t)(uint16_t)mn) ^ 0x8000u;
+  } else {
+    kmax = 0u;
+    kmin = ~0u;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const int32_t b = __builtin_bit_cast(int32_t, xv.v[k]);
+      const uint32_t key = (uint32_t)b ^ ((uint32_t)(b >> 31) | 0x80000000u);
+      kmax = key > kmax ? key : kmax;
+      kmin = key < kmin ? key : kmin;
+    }
+  }
+}
+
+// the value of T behind an ordered key
+template <typename T>
+__device__ __forceinline__ float ordered_key_value(uint32_t key) {
+  if constexpr (sizeof(T) == 2) {
+    const uint32_t k = key ^ 0x8000u;
+    const uint32_t b = ((k & 0x8000u) ? (k ^ 0x7fffu) : k) & 0xffffu;
+    if constexpr (elem<T>::id == BVQ_F16)
+      return (float)__builtin_bit_cast(f16_t, (uint16_t)b);
+    else
+      return __builtin_bit_cast(float, b << 16);
+  } else {
+    return __builtin_bit_cast(float, (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+  }
+}
+
+// the group's two statistics from the segment-wide keys; a NaN anywhere in the group is both, as torch.max / torch.min
+// propagate it
+template <typename T>
+__device__ __forceinline__ void shifted_stats(uint32_t kmax, uint32_t kmin, float& mx, float& mn) {
+  mx = ordered_key_value<T>(kmax);
+  mn = ordered_key_value<T>(kmin);
+  const bool nan = mx != mx || mn != mn;
+  mx = nan ? __builtin_nanf("") : mx;
+  mn = nan ? __builtin_nanf("") : mn;
+}
+
+// v + 0.0 of the torch ops that add a zero (the zero-point's "+ min_int", the dense zero gradients added to dx): only a
+// -0 changes, to +0.  On the bit pattern: written as a float add of a constant zero, the compiler may fold it into a
+// sign modifier of the next instruction, which keeps the -0.
+__device__ __forceinline__ float plus_zero(float v) {
+  return __builtin_bit_cast(uint32_t, v) == 0x80000000u ? 0.f : v;
+}
+
+// statistics -> scale and zero-point with the rounding points of the torch ops (scale: bvq_stat_epilogue.h through
+// group_scale; zero-point: IntQuant.to_int of -m0 with min_int = 0, bvq_quant_math.h).  d, u and r are what the backward
+// needs of the way there.
+struct ShiftedGroup {
+  float s, zp;
+  float d;  // T(mx - mn)
+  float u;  // T(-m0 / s)
+  float r;  // round(u + 0), before the clamp
+};
+template <typename T>
+__device__ __forceinline__ ShiftedGroup shifted_group(float mx, float mn, const GroupArgs& a, float qmin, float qmax) {
+  ShiftedGroup p;
+  p.d = rnd<T>(mx - mn);
+  p.s = group_scale<T>(__builtin_fabsf(p.d), a.use_min != 0, a.min_val, a.thr_div);
+  const float m0 = mn <= 0.f ? mn : 0.f;  // NegativeMinOrZero: a NaN minimum gives 0, the scale is NaN then anyway
+  p.u = rnd<T>(-m0 / p.s);
+  p.r = round_op<T, BVQ_ROUND>(plus_zero(p.u));  // "+ min_int": -0 becomes +0
+  p.zp = clamp_where(p.r, qmin, qmax);      // a NaN passes
+  return p;
+}
+
+template <typename T, int L, bool NT>
+__global__ __launch_bounds__(kBlock) void group_shifted_fwd_kernel(GroupShiftedArgs a) {
+  constexpr int VEC = elem<T>::vec, kD = kShiftedFwdDepth;
+  GroupWindow<T, L, kD> w;
+  if (!w.init(a)) return;
+  const int lane = threadIdx.x & 63;
+  const T* statp = reinterpret_cast<const T*>(a.stat);
+  const buf_t bx = w.elems(a.x), by = w.elems(a.y), bs = w.groups(a.scale), bz = w.groups(a.zp);
+  const buf_t btx = w.groups(statp), btn = w.groups(statp + a.chunks / L);
+  const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
+  vec_t<T, VEC> xv[kD];
+#pragma unroll
+  for (int j = 0; j < kD; ++j) xv[j] = buf_load<T, VEC, NT>(bx, (uint32_t)(j * kWave + lane) * 16u);
+#pragma unroll
+  for (int j = 0; j < kD; ++j) {
+    if ((uint32_t)(j * kWave) >= w.nch) break;  // wave-uniform: a load no lane has is not worked on
+    uint32_t kmax, kmin;
+    chunk_minmax_keys<T>(xv[j], kmax, kmin);
+    float mx, mn;
+    shifted_stats<T>(seg_max_u32<L>(kmax), seg_min_u32<L>(kmin), mx, mn);
+    const ShiftedGroup p = shifted_group<T>(mx, mn, a, qmin, qmax);
+    // one lane per segment writes the four small outputs (vector stores; dropped for the groups past the end)
+    const uint32_t goff = (lane & (L - 1)) == 0 ? (uint32_t)(j * (kWave / L) + lane / L) * (uint32_t)sizeof(T) : kBufSkip;
+    vec_t<T, 1> sv, zv, txv, tnv;
+    sv.v[0] = from_f<T>(p.s);
+    zv.v[0] = from_f<T>(p.zp);  // exact: an integer of the code range
+    txv.v[0] = from_f<T>(mx);   // exact: values of T
+    tnv.v[0] = from_f<T>(mn);
+    buf_store<T, 1>(bs, goff, sv);
+    buf_store<T, 1>(bz, goff, zv);
+    buf_store<T, 1>(btx, goff, txv);
+    buf_store<T, 1>(btn, goff, tnv);
+    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
+    if constexpr (sizeof(T) == 2) {
+      if (wave_fast_div<T>(p.s)) {
+        group_fwd_chunk<T, NT, true>(xv[j], by, off, fast_div<T>(p.s), p.s, qmin, qmax, p.zp);
+        continue;
+      }
+    }
+    group_fwd_chunk<T, NT, true>(xv[j], by, off, DivExact{p.s}, p.s, qmin, qmax, p.zp);
+  }
+}
+
+// One chunk of the backward: dx and the rounded gradient terms of scale and zero-point per element exactly as the
+// per-channel backward computes them (bwd_elem2, kBwdDsDzp), the group's two sums, then the autograd of the scale-shaped
+// torch ops of the graph, each rounding to T:
+//   zero-point   dzp (+ gzp) -> its own clamp (masked where it clipped unless straight-through) -> round (STE) -> "+ 0"
+//                -> u = n / s: dn = dzp / s to n = -m0, -dzp * ((n / s) / s) to the scale -> m0 -> mn where mn <= 0
+//   scale        ds (+ gscale) + the zero-point's share -> / thr_div -> clamp_min (STE) -> |d|: * sgn(d) -> d = mx - mn
+// and the deposits in the order the per-channel route adds its dense gradients to dx: the zero-point statistic's first
+// (on the first element equal to mn), then the scale statistic's (max and min, added to each other first where one
+// element is both).  Every element of dx has been through "+ 0" there, which turns a -0 into +0.
+template <typename T, int L, bool NT, typename Div>
+__device__ __forceinline__ void group_shifted_bwd_chunk(const GroupShiftedArgs& a, const vec_t<T, elem<T>::vec>& xv,
+                                                        const vec_t<T, elem<T>::vec>& gv, buf_t bd, uint32_t off,
+                                                        int lane, const Div& div, const ShiftedGroup& p, float mx,
+                                                        float mn, float gsc, float gzp, float qmin, float qmax) {
+  constexpr int VEC = elem<T>::vec;
+  const bool clamp_ste = a.clamp_ste != 0;
+  f2 ds2 = splat2(0.f), dz2 = splat2(0.f), unused = splat2(0.f);
+  vec_t<T, VEC> dv;
+#pragma unroll
+  for (int k = 0; k < VEC; k += 2) {
+    const f2 d = bwd_elem2<T, BVQ_ROUND, kBwdDsDzp, false, false, true>(
+        widen2<T>(xv.v[k], xv.v[k + 1]), widen2<T>(gv.v[k], gv.v[k + 1]), div, p.s, p.zp, qmin, qmax, clamp_ste,
+        BVQ_ROUND, ds2, dz2, unused);
+    pack2<T>(f2{plus_zero(d.x), plus_zero(d.y)}, dv.v[k], dv.v[k + 1]);  // (d is rounded to T: the conversion is exact)
+  }
+  const float ds = seg_sum<L>(ds2.x + ds2.y);
+  const float dzs = seg_sum<L>(dz2.x + dz2.y);
+  // the zero-point's gradient on its way back through to_int
+  float dzp = rnd<T>(dzs);
+  if (a.gzp) dzp = rnd<T>(dzp + gzp);
+  const bool zhi = p.r > qmax;
+  const bool zlo = (zhi ? qmax : p.r) < qmin;
+  const float dzi = (clamp_ste || !(zhi || zlo)) ? dzp : 0.f;
+  const float dn = rnd<T>(dzi / p.s);
+  const float dsz = rnd<T>(-dzi * rnd<T>(p.u / p.s));
+  // the scale's gradient: the quantizer's, the one arriving through `scale`, the zero-point's share, in that order
+  float v = rnd<T>(ds);
+  if (a.gscale) v = rnd<T>(v + gsc);
+  v = rnd<T>(v + dsz);
+  const float dthr = rnd<T>(v / a.thr_div);
+  const float dd = rnd<T>(dthr * sgn_f(p.d));  // abs: zero at 0, a constant group deposits nothing through it
+  const float dmn_z = mn <= 0.f ? -dn : 0.f;
+  // first element of the group equal to each statistic: segment-wide minimum over lane * VEC + index (a NaN statistic
+  // is equal to nothing)
+  const uint32_t e0 = (uint32_t)(lane & (L - 1)) * VEC;
+  uint32_t fmx = ~0u, fmn = ~0u;
+#pragma unroll
+  for (int k = VEC - 1; k >= 0; --k) {
+    const float xf = to_f<T>(xv.v[k]);
+    fmx = xf == mx ? e0 + k : fmx;
+    fmn = xf == mn ? e0 + k : fmn;
+  }
+  fmx = seg_min_u32<L>(fmx);
+  fmn = seg_min_u32<L>(fmn);
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    const bool is_mx = fmx == e0 + k, is_mn = fmn == e0 + k;
+    float val = to_f<T>(dv.v[k]);
+    val = is_mn ? rnd<T>(val + dmn_z) : val;
+    float dep = is_mx ? dd : 0.f;
+    dep = is_mn ? rnd<T>(dep - dd) : dep;
+    dv.v[k] = (is_mx || is_mn) ? from_f<T>(val + dep) : dv.v[k];
+  }
+  buf_store<T, VEC, NT>(bd, off, dv);
+}
+
+template <typename T, int L, bool NT>
+__global__ __launch_bounds__(kBlock) void group_shifted_bwd_kernel(GroupShiftedArgs a) {
+  constexpr int VEC = elem<T>::vec, kD = kShiftedBwdDepth;
+  GroupWindow<T, L, kD> w;
+  if (!w.init(a)) return;
+  const int lane = threadIdx.x & 63;
+  const T* statp = reinterpret_cast<const T*>(a.stat);
+  const buf_t bx = w.elems(a.x), bg = w.elems(a.g), bd = w.elems(a.y);
+  const buf_t btx = w.groups(statp), btn = w.groups(statp + a.chunks / L);
+  const buf_t bgs = w.groups(a.gscale ? a.gscale : a.stat), bgz = w.groups(a.gzp ? a.gzp : a.stat);
+  const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
+  vec_t<T, VEC> xv[kD], gv[kD];
+  vec_t<T, 1> txv[kD], tnv[kD], gsv[kD], gzv[kD];
+#pragma unroll
+  for (int j = 0; j < kD; ++j) {
+    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
+    const uint32_t goff = (uint32_t)(j * (kWave / L) + lane / L) * (uint32_t)sizeof(T);  // one address per segment
+    xv[j] = buf_load<T, VEC, NT>(bx, off);
+    gv[j] = buf_load<T, VEC, NT>(bg, off);
+    txv[j] = buf_load<T, 1>(btx, goff);
+    tnv[j] = buf_load<T, 1>(btn, goff);
+    gsv[j] = buf_load<T, 1>(bgs, goff);
+    gzv[j] = buf_load<T, 1>(bgz, goff);
+  }
+#pragma unroll
+  for (int j = 0; j < kD; ++j) {
+    if ((uint32_t)(j * kWave) >= w.nch) break;  // wave-uniform
+    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
+    const float mx = to_f<T>(txv[j].v[0]), mn = to_f<T>(tnv[j].v[0]);
+    // the forward's scale and zero-point from the saved statistics: the same arithmetic, the saved bits
+    const ShiftedGroup p = shifted_group<T>(mx, mn, a, qmin, qmax);
+    const float gsc = to_f<T>(gsv[j].v[0]), gzp = to_f<T>(gzv[j].v[0]);
+    if constexpr (sizeof(T) == 2) {
+      if (wave_fast_div<T>(p.s)) {
+        group_shifted_bwd_chunk<T, L, NT>(a, xv[j], gv[j], bd, off, lane, fast_div<T>(p.s), p, mx, mn, gsc, gzp, qmin,
+                                          qmax);
+        continue;
+      }
+    }
+    group_shifted_bwd_chunk<T, L, NT>(a, xv[j], gv[j], bd, off, lane, DivExact{p.s}, p, mx, mn, gsc, gzp, qmin, qmax);
+  }
+}
+
+static GroupShiftedArgs group_shifted_args(const bvq_quant_desc* d, double min_val, int use_min, double thr_div) {
+  GroupShiftedArgs a = {};
+  static_cast<GroupArgs&>(a) = group_args(d, min_val, use_min, thr_div);
+  return a;
+}
+
+}  // namespace bvq
+
+using namespace bvq;
+
+extern "C" int bvq_group_shifted_supported(const bvq_quant_desc* d, const void* x) {
+  if (group_check(d, "bvq_group_shifted_supported", true)) return 0;
+  return x && aligned16(x) ? 1 : 0;
+}
+
+extern "C" int bvq_group_shifted_fwd(const bvq_quant_desc* d, const void* x, double min_val, int use_min,
+                                     double thr_div, void* y, void* scale, void* zp, void* stat, bvq_stream_t stream) {
+  int rc = group_check(d, "bvq_group_shifted_fwd", true);
+  if (rc) return rc;
+  if (!x || !y || !scale || !zp || !stat) {
+    set_error("bvq_group_shifted_fwd: null pointer");
+    return BVQ_ERR_INVALID;
+  }
+  if (!aligned16(x) || !aligned16(y)) {
+    set_error("bvq_group_shifted_fwd: x and y must lie on 16-byte boundaries");
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  GroupShiftedArgs a = group_shifted_args(d, min_val, use_min, thr_div);
+  a.x = x;
+  a.y = y;
+  a.scale = scale;
+  a.zp = zp;
+  a.stat = stat;
+  const bool nt = a.chunks * 32 >= nt_threshold_bytes();  // x read + y written
+  rc = with_group_variant(d, nt, [&](auto t, auto l, auto ntc) {
+    group_shifted_fwd_kernel<typename decltype(t)::type, l, ntc>
+        <<<group_grid(a.chunks, kShiftedFwdDepth), kBlock, 0, (hipStream_t)stream>>>(a);
+  });
+  return rc ? rc : check_launch("bvq_group_shifted_fwd");
+}
+
+extern "C" int bvq_group_shifted_bwd(const bvq_quant_desc* d, const void* g, const void* x, const void* stat,
+                                     const void* gscale, const void* gzp, double min_val, int use_min, double thr_div,
+                                     void* dx, bvq_stream_t stream) {
+  int rc = group_check(d, "bvq_group_shifted_bwd", true);
+  if (rc) return rc;
+  if (!g || !x || !stat || !dx) {
+    set_error("bvq_group_shifted_bwd: null pointer");
+    return BVQ_ERR_INVALID;
+  }
+  if (!aligned16(g) || !aligned16(x) || !aligned16(dx)) {
+    set_error("bvq_group_shifted_bwd: g, x and dx must lie on 16-byte boundaries");
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  GroupShiftedArgs a = group_shifted_args(d, min_val, use_min, thr_div);
+  a.x = x;
+  a.g = g;
+  a.y = dx;
+  a.stat = const_cast<void*>(stat);
+  a.gscale = gscale;
+  a.gzp = gzp;
+  const bool nt = a.chunks * 48 >= nt_threshold_bytes();  // g and x read, dx written
+  rc = with_group_variant(d, nt, [&](auto t, auto l, auto ntc) {
+    group_shifted_bwd_kernel<typename decltype(t)::type, l, ntc>
+        <<<group_grid(a.chunks, kShiftedBwdDepth), kBlock, 0, (hipStream_t)stream>>>(a);
+  });
+  return rc ? rc : check_launch("bvq_group_shifted_bwd");
+}

@@ -27,6 +27,7 @@ __all__ = ['Int8WeightPerChannelFloat', 'Int4WeightPerChannelFloat', 'Int8Weight
            'Int8WeightPerTensorFloat',
            'Int8ActPerTensorFloat', 'Uint8ActPerTensorFloat', 'Int8ActPerChannelFloat',
            'ShiftedUint8WeightPerTensorFloat', 'ShiftedUint8WeightPerChannelFloat', 'ShiftedUint8ActPerTensorFloat',
+           'ShiftedUint8WeightPerGroupFloat', 'ShiftedUint4WeightPerGroupFloat',
            'Int8WeightPerTensorFixedPoint', 'Int8WeightPerChannelFixedPoint', 'Int8ActPerTensorFixedPoint',
            'Int8ActPerTensorFloatMinMaxInit', 'Uint8ActPerTensorFloatMaxInit',
            'Uint8ActPerTensorFixedPoint', 'Uint8ActPerTensorFixedPointMaxInit', 'Int8Bias', 'Int16Bias', 'Int24Bias',
@@ -62,8 +63,8 @@ def Int4WeightPerChannelFloat(weights) -> RescalingIntQuant:
     return Int8WeightPerChannelFloat(weights, bit_width=4)
 
 
-def _group_weight_modules(weights, group_size: int, bit_width: int) -> tuple:
-    """the constructor arguments of GroupwiseRescalingIntQuant for one tracked weight, its shape checked here"""
+def _group_tracked_weight(weights, group_size: int) -> tuple:
+    """(the one tracked weight as a list, group size, scaling shape) of a group-wise weight quantizer, checked"""
     tracked = _params(weights)
     if len(tracked) != 1:
         raise ValueError('a group-wise weight quantizer tracks exactly one weight, got a list of %d' % len(tracked))
@@ -72,7 +73,12 @@ def _group_weight_modules(weights, group_size: int, bit_width: int) -> tuple:
     if w.dim() < 2 or group_size < 1 or (w.numel() // max(w.shape[0], 1)) % group_size != 0:
         raise ValueError('a weight of shape %s has no whole groups of %d elements per output channel'
                          % (tuple(w.shape), group_size))
-    shape = (w.numel() // group_size, 1)
+    return tracked, group_size, (w.numel() // group_size, 1)
+
+
+def _group_weight_modules(weights, group_size: int, bit_width: int) -> tuple:
+    """the constructor arguments of GroupwiseRescalingIntQuant for one tracked weight, its shape checked here"""
+    tracked, group_size, shape = _group_tracked_weight(weights, group_size)
     return (
         IntQuant(narrow_range=True, signed=True, float_to_int_impl=RoundSte(), tensor_clamp_impl=TensorClampSte()),
         StatsFromParameterScaling(AbsMax(1), OverSubChannelBlockView(group_size), 1, tracked, FloatRestrictValue(),
@@ -306,6 +312,39 @@ def ShiftedUint8WeightPerTensorFloat(weights, bit_width: int = 8) -> RescalingIn
 def ShiftedUint8WeightPerChannelFloat(weights, bit_width: int = 8) -> RescalingIntQuant:
     """B/quant/shifted_scaled_int.py:55-70"""
     return _shifted_weight_quant(weights, True, bit_width)
+
+
+def ShiftedUint8WeightPerGroupFloat(weights: Union[torch.nn.Parameter, Sequence[torch.nn.Parameter]],
+                                    group_size: int = 128, bit_width: int = 8) -> GroupwiseRescalingIntQuant:
+    """ShiftedUint8WeightPerChannelFloat with one scale and one integer zero-point per `group_size` consecutive input
+    weights of each output channel (ShiftedUint8WeightPerGroupFloat of later Brevitas releases, the unsigned format of
+    AWQ / GPTQ style checkpoints; not in this reference snapshot): the per-channel graph on the weight regrouped as
+    [out * K / group_size, group_size], K = Cin * kh * kw in memory order.  Per group
+        scale = max(|max - min|, 1e-10) / (2^b - 1),  zero_point = clamp(round(-min(min, 0) / scale), 0, 2^b - 1),
+        y = (clamp(round(w / scale + zero_point), 0, 2^b - 1) - zero_point) * scale.
+    y has the weight's shape; scale and zero_point are (out, K / group_size, 1), the zero-point integer-valued in the
+    weight's dtype; both statistics are back-propagated through.  In a layer:
+    weight_quant=functools.partial(ShiftedUint4WeightPerGroupFloat, group_size=64).  One tracked weight only.
+
+    The range is the reference's max - min: a group of positive values only gets zero-point 0 and clips its upper part,
+    one of negative values only gets 2^b - 1 and clips likewise, a constant non-zero group gets the lower bound of the
+    scale.  y and the gradients stay finite in all of them."""
+    tracked, group_size, shape = _group_tracked_weight(weights, group_size)
+    int_quant = IntQuant(narrow_range=False, signed=False, float_to_int_impl=RoundSte(),
+                         tensor_clamp_impl=TensorClampSte())
+    return GroupwiseRescalingIntQuant(
+        int_quant,
+        StatsFromParameterScaling(AbsMinMax(1), OverSubChannelBlockView(group_size), 1, tracked, FloatRestrictValue(),
+                                  shape, affine_rescaling=False, scaling_min_val=SCALING_MIN_VAL),
+        IntScaling(signed=False, narrow_range=False),
+        StatsFromParameterZeroPoint(int_quant, True, OverSubChannelBlockView(group_size), 1, NegativeMinOrZero(1), shape,
+                                    tracked),
+        BitWidthConst(bit_width), group_size)
+
+
+def ShiftedUint4WeightPerGroupFloat(weights, group_size: int = 128) -> GroupwiseRescalingIntQuant:
+    """ShiftedUint8WeightPerGroupFloat with bit_width = 4: the usual asymmetric weight-only format of LLM-sized layers"""
+    return ShiftedUint8WeightPerGroupFloat(weights, group_size=group_size, bit_width=4)
 
 
 def ShiftedUint8ActPerTensorFloat(collect_stats_steps: int = 300, bit_width: int = 8) -> RescalingIntQuant:

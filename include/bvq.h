@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 3
+#define BVQ_ABI_VERSION 4
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -740,6 +740,36 @@ int bvq_group_mse_fwd(const bvq_quant_desc* desc, const void* x, const float* ra
 int bvq_group_mse_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* stat, const void* idx,
                       const void* gscale, const float* ratios, int n_ratios, double min_val, int use_min,
                       double thr_div, void* dx, bvq_stream_t stream);
+
+/* ---- asymmetric group-wise weights: one scale and one integer zero-point per group ------------------------------------
+ * The unsigned weight-only format of AWQ / GPTQ style checkpoints (ShiftedUint8WeightPerGroupFloat of later Brevitas
+ * releases).  The descriptor is that of the group-wise section with zp_per_channel = 1 and zp_dtype = x_dtype; T is x's
+ * dtype.  The results are those of the per-channel asymmetric graph (AbsMinMax scale, NegativeMinOrZero zero-point
+ * quantized through IntQuant.to_int) on the tensor regrouped as [groups, group_size], every operation rounding to T:
+ *     mx = max x, mn = min x                          (a NaN anywhere in the group is both)
+ *     scale = T(clamp_min(|T(mx - mn)|, min_val) / thr_div)
+ *     m0 = mn <= 0 ? mn : 0;  zp = clamp(round_half_even(T(T(-m0 / scale) + 0)), qmin, qmax)
+ *     q = clamp(round_half_even(T(T(x / scale) + zp)), qmin, qmax);  y = T(T(q - zp) * scale)
+ *   bvq_group_shifted_fwd: y like x; scale, zp: [groups] in T; stat: [2 * groups] in T, the maxima then the minima (the
+ *     layout of BVQ_STAT_MINMAX).
+ *   bvq_group_shifted_bwd: the autograd of that graph.  dx = the quantizer's input gradient; the group's scale and
+ *     zero-point gradients are float32 sums rounded to T, joined by gscale / gzp (nullable, [groups] in T: gradients
+ *     arriving through the returned scale / zero-point); the zero-point's travels through its own clamp (masked where it
+ *     clipped unless clamp_ste), the rounding (straight-through) and -m0 / scale to the scale and, where mn <= 0, to mn;
+ *     the scale's through / thr_div, the straight-through clamp_min and |mx - mn| (zero gradient at 0) to mx and mn.  The
+ *     gradient of mx is added to the first element of the group equal to mx, that of mn to the first equal to mn (-0
+ *     equals +0; a NaN statistic is equal to nothing).  stat: the forward's output; scale and zero-point are derived from
+ *     it again, same bits.
+ * One launch each way, no workspace, no atomics.  Only the order in which a group's float32 gradient terms are added
+ * differs from the per-channel kernels (the two deposited elements can move by a rounding).  Covered: what the
+ * group-wise entries cover; anything else returns BVQ_ERR_UNSUPPORTED with a bvq_last_error() text, found before
+ * anything touches the device; bvq_group_shifted_supported answers 1 / 0 for a descriptor and x. */
+int bvq_group_shifted_supported(const bvq_quant_desc* desc, const void* x);
+int bvq_group_shifted_fwd(const bvq_quant_desc* desc, const void* x, double min_val, int use_min, double thr_div,
+                          void* y, void* scale, void* zp, void* stat, bvq_stream_t stream);
+int bvq_group_shifted_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* stat,
+                          const void* gscale, const void* gzp, double min_val, int use_min, double thr_div, void* dx,
+                          bvq_stream_t stream);
 
 /* ---- MX block-scaled quantizers: groups sharing one power-of-two scale, minifloat or MXINT8 elements -----------------
  * The OCP Microscaling formats the gfx950 matrix units take natively, as quantize-dequantize for training (no
