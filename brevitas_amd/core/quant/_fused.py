@@ -514,6 +514,22 @@ def group_quant_call(x: Tensor, group_size: int, int_threshold: float, qmin: flo
     return desc, _as_dtype_value(int_threshold, x.dtype)
 
 
+def _group_grads(x: Tensor, gy, side, side_dtype=None, align_side=False):
+    """The backward prelude of the Functions on the group walk: gy and the gradients `side` that arrived through the
+    per-group outputs, any of them None -> (gy, side) as the kernels take them, or None when nothing arrived.  gy: x's
+    dtype, contiguous, on a 16-byte boundary, zeros when only a per-group output was used downstream; side: flat,
+    contiguous, `side_dtype` (x's unless named), None kept, on a 16-byte boundary when `align_side`."""
+    if gy is None and all(s is None for s in side):
+        return None
+    gy = torch.zeros_like(x) if gy is None else gy.to(x.dtype).contiguous()
+    side = [None if s is None else s.to(side_dtype or x.dtype).reshape(-1).contiguous() for s in side]
+    if align_side:
+        side = [s.clone() if s is not None and s.data_ptr() % 16 != 0 else s for s in side]
+    if gy.data_ptr() % 16 != 0:
+        gy = gy.clone()
+    return gy, side
+
+
 class GroupStatsFakeQuantFn(Function):
     """Group-wise weights: AbsMax per group of `group_size` consecutive elements -> clamp_min(min_val) -> / int_threshold
     -> IntQuant with a zero zero-point, x -> (y like x, scale [groups, 1]).  One launch each way (csrc/bvq_group_quant.hip):
@@ -532,16 +548,10 @@ class GroupStatsFakeQuantFn(Function):
     @staticmethod
     def backward(ctx, gy, gscale):
         x, scale, stat = ctx.saved_tensors
-        if gy is None:  # only `scale` was used downstream
-            if gscale is None:
-                return (None,) * 7
-            gy = torch.zeros_like(x)
-        else:
-            gy = gy.to(x.dtype).contiguous()
-        if gscale is not None:
-            gscale = gscale.to(x.dtype).reshape(-1).contiguous()
-        if gy.data_ptr() % 16 != 0:
-            gy = gy.clone()
+        grads = _group_grads(x, gy, [gscale])
+        if grads is None:
+            return (None,) * 7
+        gy, (gscale,) = grads
         dx = nat.group_quant_bwd(ctx.desc, gy, x, scale, stat, gscale, ctx.min_val, ctx.thr_div)
         return (dx,) + (None,) * 6
 
@@ -575,18 +585,10 @@ class GroupShiftedFakeQuantFn(Function):
     @staticmethod
     def backward(ctx, gy, gscale, gzp):
         x, stat = ctx.saved_tensors
-        if gy is None:  # only `scale` / `zero_point` were used downstream
-            if gscale is None and gzp is None:
-                return (None,) * 7
-            gy = torch.zeros_like(x)
-        else:
-            gy = gy.to(x.dtype).contiguous()
-        if gscale is not None:
-            gscale = gscale.to(x.dtype).reshape(-1).contiguous()
-        if gzp is not None:
-            gzp = gzp.to(x.dtype).reshape(-1).contiguous()
-        if gy.data_ptr() % 16 != 0:
-            gy = gy.clone()
+        grads = _group_grads(x, gy, [gscale, gzp])
+        if grads is None:
+            return (None,) * 7
+        gy, (gscale, gzp) = grads
         dx = nat.group_shifted_bwd(ctx.desc, gy, x, stat, gscale, gzp, ctx.min_val, ctx.thr_div)
         return (dx,) + (None,) * 6
 
@@ -611,16 +613,10 @@ class GroupMSEFakeQuantFn(Function):
     @staticmethod
     def backward(ctx, gy, gscale, _gidx):
         x, stat, idx = ctx.saved_tensors
-        if gy is None:  # only `scale` was used downstream
-            if gscale is None:
-                return (None,) * 8
-            gy = torch.zeros_like(x)
-        else:
-            gy = gy.to(x.dtype).contiguous()
-        if gscale is not None:
-            gscale = gscale.to(x.dtype).reshape(-1).contiguous()
-        if gy.data_ptr() % 16 != 0:
-            gy = gy.clone()
+        grads = _group_grads(x, gy, [gscale])
+        if grads is None:
+            return (None,) * 8
+        gy, (gscale,) = grads
         dx = nat.group_mse_bwd(ctx.desc, gy, x, stat, idx, gscale, ctx.table, ctx.min_val, ctx.thr_div)
         return (dx,) + (None,) * 7
 
@@ -641,18 +637,10 @@ class MXQuantFn(Function):
     @staticmethod
     def backward(ctx, gy, gscale):
         x, = ctx.saved_tensors
-        if gy is None:  # only `scale` was used downstream
-            if gscale is None:
-                return (None,) * 5
-            gy = torch.zeros_like(x)
-        else:
-            gy = gy.to(x.dtype).contiguous()
-        if gscale is not None:
-            gscale = gscale.to(torch.float32).reshape(-1).contiguous()
-            if gscale.data_ptr() % 16 != 0:
-                gscale = gscale.clone()
-        if gy.data_ptr() % 16 != 0:
-            gy = gy.clone()
+        grads = _group_grads(x, gy, [gscale], torch.float32, align_side=True)   # as bvq_mx_quant_bwd wants its gscale
+        if grads is None:
+            return (None,) * 5
+        gy, (gscale,) = grads
         return (nat.mx_quant_bwd(gy, x, gscale, *ctx.args),) + (None,) * 4
 
 

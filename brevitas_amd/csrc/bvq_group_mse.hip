@@ -18,22 +18,12 @@
 
 namespace bvq {
 
-#ifndef BVQ_GROUP_MSE_FWD_DEPTH
-#define BVQ_GROUP_MSE_FWD_DEPTH 4  // wave loads of x in flight per wave
-#endif
-#ifndef BVQ_GROUP_MSE_BWD_DEPTH
-#define BVQ_GROUP_MSE_BWD_DEPTH 2  // wave loads of x and of g in flight per wave
-#endif
-constexpr int kGroupMseFwdDepth = BVQ_GROUP_MSE_FWD_DEPTH;
-constexpr int kGroupMseBwdDepth = BVQ_GROUP_MSE_BWD_DEPTH;
 constexpr int kMseMaxRatios = 64;
 
-struct GroupMseArgs {
-  GroupArgs g;
+struct GroupMseArgs : GroupArgs {
   void* idx;  // [groups] uint8: fwd out, bwd in
   int32_t n;  // candidates, 1..kMseMaxRatios
   float ratio[kMseMaxRatios];
-  int64_t chunks;  // = g.chunks (GroupWindow reads it here)
 };
 
 // one byte per group through the buffer descriptor (a vector store; dropped at kBufSkip and past the extent)
@@ -66,116 +56,65 @@ __device__ __forceinline__ float group_err_chunk(const vec_t<T, elem<T>::vec>& x
   return acc.x + acc.y;
 }
 
-template <typename T, int L, bool NT>
-__global__ __launch_bounds__(kBlock) void group_mse_fwd_kernel(GroupMseArgs m) {
-  constexpr int VEC = elem<T>::vec, kD = kGroupMseFwdDepth;
-  const GroupArgs& a = m.g;
-  GroupWindow<T, L, kD> w;
-  if (!w.init(m)) return;
-  const int lane = threadIdx.x & 63;
-  const buf_t bx = w.elems(a.x), by = w.elems(a.y), bs = w.groups(a.scale), bt = w.groups(a.stat);
-  const buf_t bi = w.template groups<uint8_t>(m.idx);
-  const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
-  const bool use_min = a.use_min != 0;
-  const int n = m.n;
-  vec_t<T, VEC> xv[kD];
-#pragma unroll
-  for (int j = 0; j < kD; ++j) xv[j] = buf_load<T, VEC, NT>(bx, (uint32_t)(j * kWave + lane) * 16u);
-#pragma unroll
-  for (int j = 0; j < kD; ++j) {
-    if ((uint32_t)(j * kWave) >= w.nch) break;  // wave-uniform: a load no lane has is not worked on
-    const float stat = key_value<T>(seg_max_u32<L>(chunk_key<T>(xv[j])));
+// the clip-search quantizer on the frame of bvq_group_walk.h
+template <typename T, int L>
+struct MseQuant {
+  using Args = GroupMseArgs;
+  using Vec = vec_t<T, elem<T>::vec>;
+  struct Side {
+    T stat, gscale;
+    uint32_t k;
+  };
+  const Args& a;
+  const buf_t bs, bt, bgs, bi;
+  const float qmin, qmax;
+  template <typename W>
+  __device__ __forceinline__ MseQuant(const Args& a, const W& w)
+      : a(a), bs(w.groups(a.scale)), bt(w.groups(a.stat)), bgs(w.groups_or_zeros(a.gscale, a.x)),
+        bi(w.template groups<uint8_t>(a.idx)), qmin(rnd<T>(a.qmin)), qmax(rnd<T>(a.qmax)) {}
+
+  __device__ __forceinline__ Vec fwd(const Vec& xv, const GroupPlace& p) const {
+    const bool use_min = a.use_min != 0;
+    const int n = a.n;
+    const float stat = key_value<T>(seg_max_u32<L>(chunk_key<T>(xv)));
     // the search: first candidate with an error strictly below every earlier one.  A NaN error (a NaN or Inf group)
     // is below nothing and nothing is below it: such a group keeps candidate 0.
     float e_best = 0.f, s_best = 0.f;
     uint32_t k_best = 0;
-    for (int i = 0; i < n; ++i) {  // wave-uniform count; m.ratio[i] is a scalar read
-      const float s = group_scale<T>(mse_threshold<T>(stat, m.ratio[i]), use_min, a.min_val, a.thr_div);
-      float e;
-      if constexpr (sizeof(T) == 2) {
-        if (wave_fast_div<T>(s))  // either division gives the same bits where both apply
-          e = group_err_chunk<T>(xv[j], fast_div<T>(s), s, qmin, qmax);
-        else
-          e = group_err_chunk<T>(xv[j], DivExact{s}, s, qmin, qmax);
-      } else {
-        e = group_err_chunk<T>(xv[j], DivExact{s}, s, qmin, qmax);
-      }
-      e = seg_sum<L>(e);
+    for (int i = 0; i < n; ++i) {  // wave-uniform count; a.ratio[i] is a scalar read
+      const float s = group_scale<T>(mse_threshold<T>(stat, a.ratio[i]), use_min, a.min_val, a.thr_div);
+      const float e = seg_sum<L>(
+          with_group_div<T>(s, [&](const auto& div) { return group_err_chunk<T>(xv, div, s, qmin, qmax); }));
       const bool better = i == 0 || e < e_best;
       e_best = better ? e : e_best;
       s_best = better ? s : s_best;
       k_best = better ? (uint32_t)i : k_best;
     }
-    // one lane per segment writes the three small outputs (vector stores; dropped for the groups past the end)
-    const bool head = (lane & (L - 1)) == 0;
-    const uint32_t gi = (uint32_t)(j * (kWave / L) + lane / L);
-    const uint32_t goff = head ? gi * (uint32_t)sizeof(T) : kBufSkip;
-    vec_t<T, 1> sv, tv;
-    sv.v[0] = from_f<T>(s_best);
-    tv.v[0] = from_f<T>(stat);  // exact: stat is a value of T
-    buf_store<T, 1>(bs, goff, sv);
-    buf_store<T, 1>(bt, goff, tv);
-    buf_store_u8(bi, head ? gi : kBufSkip, k_best);
-    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
-    if constexpr (sizeof(T) == 2) {
-      if (wave_fast_div<T>(s_best)) {
-        group_fwd_chunk<T, NT>(xv[j], by, off, fast_div<T>(s_best), s_best, qmin, qmax);
-        continue;
-      }
-    }
-    group_fwd_chunk<T, NT>(xv[j], by, off, DivExact{s_best}, s_best, qmin, qmax);
+    store_group(bs, p, from_f<T>(s_best));
+    store_group(bt, p, from_f<T>(stat));  // exact: stat is a value of T
+    buf_store_u8(bi, p.head_at(1), k_best);
+    return with_group_div<T>(s_best, [&](const auto& div) { return group_fwd_chunk<T>(xv, div, s_best, qmin, qmax); });
   }
-}
 
-// group_quant_bwd_kernel with the scale derived from the chosen candidate's threshold and the statistic's gradient
-// scaled by its ratio (group_bwd_chunk<.., kRatio = true>)
-template <typename T, int L, bool NT>
-__global__ __launch_bounds__(kBlock) void group_mse_bwd_kernel(GroupMseArgs m) {
-  constexpr int VEC = elem<T>::vec, kD = kGroupMseBwdDepth;
-  const GroupArgs& a = m.g;
-  GroupWindow<T, L, kD> w;
-  if (!w.init(m)) return;
-  const int lane = threadIdx.x & 63;
-  const buf_t bx = w.elems(a.x), bg = w.elems(a.g), bd = w.elems(a.y), bt = w.groups(a.stat);
-  const buf_t bgs = w.groups(a.gscale ? a.gscale : a.stat);
-  const buf_t bi = w.template groups<uint8_t>(m.idx);
-  const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
-  const int n = m.n;
-  vec_t<T, VEC> xv[kD], gv[kD];
-  vec_t<T, 1> tv[kD], gsv[kD];
-  uint32_t kv[kD];
-#pragma unroll
-  for (int j = 0; j < kD; ++j) {
-    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
-    const uint32_t gi = (uint32_t)(j * (kWave / L) + lane / L);  // one address per segment
-    xv[j] = buf_load<T, VEC, NT>(bx, off);
-    gv[j] = buf_load<T, VEC, NT>(bg, off);
-    tv[j] = buf_load<T, 1>(bt, gi * (uint32_t)sizeof(T));
-    gsv[j] = buf_load<T, 1>(bgs, gi * (uint32_t)sizeof(T));
-    kv[j] = buf_load_u8(bi, gi);
+  __device__ __forceinline__ Side side(const GroupPlace& p) const {
+    return {load_group<T>(bt, p), load_group<T>(bgs, p), buf_load_u8(bi, p.at(1))};
   }
-#pragma unroll
-  for (int j = 0; j < kD; ++j) {
-    if ((uint32_t)(j * kWave) >= w.nch) break;  // wave-uniform
-    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
-    const float stat = to_f<T>(tv[j].v[0]);
+  // PlainQuant::bwd with the scale derived from the chosen candidate's threshold and the statistic's gradient scaled
+  // by its ratio (group_bwd_chunk<.., kRatio = true>)
+  __device__ __forceinline__ Vec bwd(const Vec& xv, const Vec& gv, const Side& sd, const GroupPlace& p) const {
+    const int n = a.n;
+    const float stat = to_f<T>(sd.stat), gsc = to_f<T>(sd.gscale);
     // the lane's ratio: a uniform walk over the table, one conditional move per candidate (an index the forward did
     // not write selects nothing and leaves ratio 0, which is 1)
-    float ratio = m.ratio[0];
-    for (int i = 1; i < n; ++i) ratio = kv[j] == (uint32_t)i ? m.ratio[i] : ratio;
+    float ratio = a.ratio[0];
+    for (int i = 1; i < n; ++i) ratio = sd.k == (uint32_t)i ? a.ratio[i] : ratio;
     // the forward's scale from the saved statistic and index: the same arithmetic, the saved bits
     const float s = group_scale<T>(mse_threshold<T>(stat, ratio), a.use_min != 0, a.min_val, a.thr_div);
-    const float gsc = to_f<T>(gsv[j].v[0]);
-    if constexpr (sizeof(T) == 2) {
-      if (wave_fast_div<T>(s)) {
-        group_bwd_chunk<T, L, NT, true>(a, xv[j], gv[j], bd, off, lane, fast_div<T>(s), s, stat, gsc, qmin, qmax,
-                                        ratio);
-        continue;
-      }
-    }
-    group_bwd_chunk<T, L, NT, true>(a, xv[j], gv[j], bd, off, lane, DivExact{s}, s, stat, gsc, qmin, qmax, ratio);
+    return with_group_div<T>(s, [&](const auto& div) {
+      return group_bwd_chunk<T, L, true>(a, xv, gv, p.sub, div, s, stat, gsc, qmin, qmax, ratio);
+    });
   }
-}
+};
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -203,7 +142,6 @@ static int mse_fill(GroupMseArgs& m, const float* ratios, int n_ratios, const ch
     return BVQ_ERR_UNSUPPORTED;
   }
   m.n = n_ratios;
-  m.chunks = m.g.chunks;
   return BVQ_OK;
 }
 
@@ -220,60 +158,40 @@ extern "C" int bvq_group_mse_supported(const bvq_quant_desc* d, const void* x, i
 extern "C" int bvq_group_mse_fwd(const bvq_quant_desc* d, const void* x, const float* ratios, int n_ratios,
                                  double min_val, int use_min, double thr_div, void* y, void* scale, void* stat,
                                  void* idx, bvq_stream_t stream) {
-  int rc = group_check(d, "bvq_group_mse_fwd");
-  if (rc) return rc;
-  if (!x || !ratios || !y || !scale || !stat || !idx) {
-    set_error("bvq_group_mse_fwd: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  if ((rc = mse_count_check(n_ratios, "bvq_group_mse_fwd"))) return rc;
-  if (!aligned16(x) || !aligned16(y)) {
-    set_error("bvq_group_mse_fwd: x and y must lie on 16-byte boundaries");
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  GroupMseArgs m = {};
-  m.g = group_args(d, min_val, use_min, thr_div);
-  if ((rc = mse_fill(m, ratios, n_ratios, "bvq_group_mse_fwd"))) return rc;
-  m.g.x = x;
-  m.g.y = y;
-  m.g.scale = scale;
-  m.g.stat = stat;
+  const char* what = "bvq_group_mse_fwd";
+  int rc = group_required(what, group_check(d, what), {x, ratios, y, scale, stat, idx});
+  if (!rc) rc = mse_count_check(n_ratios, what);
+  if ((rc = group_aligned(what, rc, {x, y}, "x and y"))) return rc;
+  GroupMseArgs m = group_args<GroupMseArgs>(d, min_val, use_min, thr_div);
+  if ((rc = mse_fill(m, ratios, n_ratios, what))) return rc;
+  m.x = x;
+  m.y = y;
+  m.scale = scale;
+  m.stat = stat;
   m.idx = idx;
-  const bool nt = m.chunks * 32 >= nt_threshold_bytes();  // x read + y written
-  rc = with_group_variant(d, nt, [&](auto t, auto l, auto ntc) {
-    group_mse_fwd_kernel<typename decltype(t)::type, l, ntc>
-        <<<group_grid(m.chunks, kGroupMseFwdDepth), kBlock, 0, (hipStream_t)stream>>>(m);
+  // x read + y written
+  return group_launch(what, d->x_dtype, d->inner, m.chunks, 32, kGroupFwdDepth, [&](auto t, auto l, auto nt, unsigned grid) {
+    group_fwd_kernel<MseQuant, typename decltype(t)::type, l, nt><<<grid, kBlock, 0, (hipStream_t)stream>>>(m);
   });
-  return rc ? rc : check_launch("bvq_group_mse_fwd");
 }
 
 extern "C" int bvq_group_mse_bwd(const bvq_quant_desc* d, const void* g, const void* x, const void* stat,
                                  const void* idx, const void* gscale, const float* ratios, int n_ratios,
                                  double min_val, int use_min, double thr_div, void* dx, bvq_stream_t stream) {
-  int rc = group_check(d, "bvq_group_mse_bwd");
-  if (rc) return rc;
-  if (!g || !x || !stat || !idx || !ratios || !dx) {
-    set_error("bvq_group_mse_bwd: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  if ((rc = mse_count_check(n_ratios, "bvq_group_mse_bwd"))) return rc;
-  if (!aligned16(g) || !aligned16(x) || !aligned16(dx)) {
-    set_error("bvq_group_mse_bwd: g, x and dx must lie on 16-byte boundaries");
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  GroupMseArgs m = {};
-  m.g = group_args(d, min_val, use_min, thr_div);
-  if ((rc = mse_fill(m, ratios, n_ratios, "bvq_group_mse_bwd"))) return rc;
-  m.g.x = x;
-  m.g.g = g;
-  m.g.y = dx;
-  m.g.stat = const_cast<void*>(stat);
-  m.g.gscale = gscale;
+  const char* what = "bvq_group_mse_bwd";
+  int rc = group_required(what, group_check(d, what), {g, x, stat, idx, ratios, dx});
+  if (!rc) rc = mse_count_check(n_ratios, what);
+  if ((rc = group_aligned(what, rc, {g, x, dx}, "g, x and dx"))) return rc;
+  GroupMseArgs m = group_args<GroupMseArgs>(d, min_val, use_min, thr_div);
+  if ((rc = mse_fill(m, ratios, n_ratios, what))) return rc;
+  m.x = x;
+  m.g = g;
+  m.y = dx;
+  m.stat = const_cast<void*>(stat);
+  m.gscale = gscale;
   m.idx = const_cast<void*>(idx);
-  const bool nt = m.chunks * 48 >= nt_threshold_bytes();  // g and x read, dx written
-  rc = with_group_variant(d, nt, [&](auto t, auto l, auto ntc) {
-    group_mse_bwd_kernel<typename decltype(t)::type, l, ntc>
-        <<<group_grid(m.chunks, kGroupMseBwdDepth), kBlock, 0, (hipStream_t)stream>>>(m);
+  // g and x read, dx written
+  return group_launch(what, d->x_dtype, d->inner, m.chunks, 48, kGroupBwdDepth, [&](auto t, auto l, auto nt, unsigned grid) {
+    group_bwd_kernel<MseQuant, typename decltype(t)::type, l, nt><<<grid, kBlock, 0, (hipStream_t)stream>>>(m);
   });
-  return rc ? rc : check_launch("bvq_group_mse_bwd");
 }

@@ -1,7 +1,8 @@
-// bvq_group_quant.h -- what the kernels on the sub-wave group walk that quantize to integers share: the group-wise
-// quantizer with the abs-max scale (bvq_group_quant.hip) and the one that searches a clipped threshold per group
-// (bvq_group_mse.hip).  The argument struct, statistic -> scale, the forward chain of a chunk, the backward of a chunk
-// with its scale-gradient sum and arg-max deposit, and the host-side coverage check.
+// bvq_group_quant.h -- what the quantizers on the sub-wave group walk that quantize to integers share: the group-wise
+// quantizer with the abs-max scale (bvq_group_quant.hip), the one that searches a clipped threshold per group
+// (bvq_group_mse.hip) and the asymmetric one (bvq_group_shifted.hip).  The argument struct, statistic -> scale, the
+// choice of the division, the forward chain of a chunk, the backward of a chunk with its scale-gradient sum and arg-max
+// deposit, and the host-side coverage check.
 #pragma once
 
 #include "bvq_fakequant_bwd.h"
@@ -10,14 +11,10 @@
 
 namespace bvq {
 
-struct GroupArgs {
-  const void* x;
-  const void* g;       // bwd
-  void* y;             // fwd: y, bwd: dx
+struct GroupArgs : WalkArgs {
   void* scale;         // fwd: [groups] out
   void* stat;          // fwd: [groups] out, bwd: in
   const void* gscale;  // bwd, nullable: gradient arriving through the returned scale, [groups]
-  int64_t chunks;      // 16-byte chunks of the tensor = groups * L
   float qmin, qmax, min_val, thr_div;
   int32_t use_min, clamp_ste;
 };
@@ -46,9 +43,9 @@ __device__ __forceinline__ f2 group_fwd_pair(f2 xf, const Div& div, float s, flo
   return sizeof(T) == 2 ? q * s : rnd2<T>(q - 0.f) * s;
 }
 
-template <typename T, bool NT, bool kZp = false, typename Div>
-__device__ __forceinline__ void group_fwd_chunk(const vec_t<T, elem<T>::vec>& xv, buf_t by, uint32_t off,
-                                                const Div& div, float s, float qmin, float qmax, float zp = 0.f) {
+template <typename T, bool kZp = false, typename Div>
+__device__ __forceinline__ vec_t<T, elem<T>::vec> group_fwd_chunk(const vec_t<T, elem<T>::vec>& xv, const Div& div,
+                                                                  float s, float qmin, float qmax, float zp = 0.f) {
   constexpr int VEC = elem<T>::vec;
   vec_t<T, VEC> yv;
 #pragma unroll
@@ -56,7 +53,7 @@ __device__ __forceinline__ void group_fwd_chunk(const vec_t<T, elem<T>::vec>& xv
     const f2 r = group_fwd_pair<T, kZp>(widen2<T>(xv.v[k], xv.v[k + 1]), div, s, qmin, qmax, zp);
     pack2<T>(r, yv.v[k], yv.v[k + 1]);
   }
-  buf_store<T, VEC, NT>(by, off, yv);  // dropped past the tensor's end
+  return yv;
 }
 
 // every lane's scale suits the reciprocal form of its dtype (bvq_fakequant.h): decided per wave load, and the two
@@ -79,17 +76,26 @@ __device__ __forceinline__ FastDiv<T> fast_div(float s) {
   else
     return DivF16R{s, 1.0f / s};
 }
+// f(div) with the division by s that the wave takes for this load
+template <typename T, typename F>
+__device__ __forceinline__ auto with_group_div(float s, F&& f) {
+  if constexpr (sizeof(T) == 2) {
+    if (wave_fast_div<T>(s)) return f(fast_div<T>(s));
+  }
+  return f(DivExact{s});
+}
 
 // One chunk of the backward: dx and the two rounded scale-gradient terms per element exactly as the per-channel
 // backward of the stats-scaled graph computes them (bwd_elem2, kBwdDs), the group's sum, the statistic's gradient
 // with the rounding points of bwd_stats_finish_kernel, and its deposit on the first element attaining the statistic.
 // kRatio: the scale came from the threshold stat * ratio rounded to T (bvq_group_mse.hip), so the threshold's gradient
 // is multiplied by `ratio` and rounded once more on its way to the statistic; the element match still uses `stat`.
-template <typename T, int L, bool NT, bool kRatio = false, typename Div>
-__device__ __forceinline__ void group_bwd_chunk(const GroupArgs& a, const vec_t<T, elem<T>::vec>& xv,
-                                                const vec_t<T, elem<T>::vec>& gv, buf_t bd, uint32_t off, int lane,
-                                                const Div& div, float s, float stat, float gsc, float qmin,
-                                                float qmax, float ratio = 1.f) {
+// sub: the lane within its segment (GroupPlace).
+template <typename T, int L, bool kRatio = false, typename Div>
+__device__ __forceinline__ vec_t<T, elem<T>::vec> group_bwd_chunk(const GroupArgs& a, const vec_t<T, elem<T>::vec>& xv,
+                                                                  const vec_t<T, elem<T>::vec>& gv, uint32_t sub,
+                                                                  const Div& div, float s, float stat, float gsc,
+                                                                  float qmin, float qmax, float ratio = 1.f) {
   constexpr int VEC = elem<T>::vec;
   constexpr bool kZp0 = sizeof(T) == 2, kSame16 = sizeof(T) == 2;
   const bool clamp_ste = a.clamp_ste != 0;
@@ -111,7 +117,7 @@ __device__ __forceinline__ void group_bwd_chunk(const GroupArgs& a, const vec_t<
   if constexpr (kRatio) dstat = rnd<T>(dstat * ratio);
   // first element of the group whose |x| is the statistic: segment-wide minimum over lane * VEC + index
   const uint32_t skey = abs_bits<T>(from_f<T>(stat));
-  const uint32_t e0 = (uint32_t)(lane & (L - 1)) * VEC;
+  const uint32_t e0 = sub * VEC;
   uint32_t first = ~0u;
 #pragma unroll
   for (int k = VEC - 1; k >= 0; --k) first = abs_bits<T>(xv.v[k]) == skey ? e0 + k : first;
@@ -122,7 +128,7 @@ __device__ __forceinline__ void group_bwd_chunk(const GroupArgs& a, const vec_t<
     const float dep = to_f<T>(dv.v[k]) + deposit<T, BVQ_MATCH_ABS>(dstat, xv.v[k]);
     dv.v[k] = first == e0 + k ? from_f<T>(dep) : dv.v[k];
   }
-  buf_store<T, VEC, NT>(bd, off, dv);
+  return dv;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -171,8 +177,10 @@ static int group_check(const bvq_quant_desc* d, const char* what, bool shifted =
   return BVQ_OK;
 }
 
-static GroupArgs group_args(const bvq_quant_desc* d, double min_val, int use_min, double thr_div) {
-  GroupArgs a = {};
+// Args: GroupArgs or what a quantizer extends it to; everything the descriptor and the scalars do not give is zero
+template <typename Args = GroupArgs>
+static Args group_args(const bvq_quant_desc* d, double min_val, int use_min, double thr_div) {
+  Args a = {};
   a.chunks = d->channels * (d->inner * dtype_size(d->x_dtype) / 16);
   a.qmin = d->qmin;
   a.qmax = d->qmax;
@@ -181,12 +189,6 @@ static GroupArgs group_args(const bvq_quant_desc* d, double min_val, int use_min
   a.use_min = use_min;
   a.clamp_ste = d->clamp_ste;
   return a;
-}
-
-// f(type_tag<T>, int_c<L>, std::bool_constant<NT>) for the lanes per group of d's dtype and group size
-template <typename F>
-static int with_group_variant(const bvq_quant_desc* d, bool nt, F&& f) {
-  return with_group_variant(d->x_dtype, d->inner, nt, f);
 }
 
 }  // namespace bvq

@@ -19,15 +19,6 @@
 
 namespace bvq {
 
-#ifndef BVQ_GROUP_SHIFTED_FWD_DEPTH
-#define BVQ_GROUP_SHIFTED_FWD_DEPTH 4  // wave loads of x in flight per wave
-#endif
-#ifndef BVQ_GROUP_SHIFTED_BWD_DEPTH
-#define BVQ_GROUP_SHIFTED_BWD_DEPTH 2  // wave loads of x and of g in flight per wave
-#endif
-constexpr int kShiftedFwdDepth = BVQ_GROUP_SHIFTED_FWD_DEPTH;
-constexpr int kShiftedBwdDepth = BVQ_GROUP_SHIFTED_BWD_DEPTH;
-
 // GroupArgs with `stat` holding [2 * groups] values, the maxima then the minima (as BVQ_STAT_MINMAX)
 struct GroupShiftedArgs : GroupArgs {
   void* zp;         // fwd: [groups] out
@@ -123,49 +114,6 @@ __device__ __forceinline__ ShiftedGroup shifted_group(float mx, float mn, const 
   return p;
 }
 
-template <typename T, int L, bool NT>
-__global__ __launch_bounds__(kBlock) void group_shifted_fwd_kernel(GroupShiftedArgs a) {
-  constexpr int VEC = elem<T>::vec, kD = kShiftedFwdDepth;
-  GroupWindow<T, L, kD> w;
-  if (!w.init(a)) return;
-  const int lane = threadIdx.x & 63;
-  const T* statp = reinterpret_cast<const T*>(a.stat);
-  const buf_t bx = w.elems(a.x), by = w.elems(a.y), bs = w.groups(a.scale), bz = w.groups(a.zp);
-  const buf_t btx = w.groups(statp), btn = w.groups(statp + a.chunks / L);
-  const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
-  vec_t<T, VEC> xv[kD];
-#pragma unroll
-  for (int j = 0; j < kD; ++j) xv[j] = buf_load<T, VEC, NT>(bx, (uint32_t)(j * kWave + lane) * 16u);
-#pragma unroll
-  for (int j = 0; j < kD; ++j) {
-    if ((uint32_t)(j * kWave) >= w.nch) break;  // wave-uniform: a load no lane has is not worked on
-    uint32_t kmax, kmin;
-    chunk_minmax_keys<T>(xv[j], kmax, kmin);
-    float mx, mn;
-    shifted_stats<T>(seg_max_u32<L>(kmax), seg_min_u32<L>(kmin), mx, mn);
-    const ShiftedGroup p = shifted_group<T>(mx, mn, a, qmin, qmax);
-    // one lane per segment writes the four small outputs (vector stores; dropped for the groups past the end)
-    const uint32_t goff = (lane & (L - 1)) == 0 ? (uint32_t)(j * (kWave / L) + lane / L) * (uint32_t)sizeof(T) : kBufSkip;
-    vec_t<T, 1> sv, zv, txv, tnv;
-    sv.v[0] = from_f<T>(p.s);
-    zv.v[0] = from_f<T>(p.zp);  // exact: an integer of the code range
-    txv.v[0] = from_f<T>(mx);   // exact: values of T
-    tnv.v[0] = from_f<T>(mn);
-    buf_store<T, 1>(bs, goff, sv);
-    buf_store<T, 1>(bz, goff, zv);
-    buf_store<T, 1>(btx, goff, txv);
-    buf_store<T, 1>(btn, goff, tnv);
-    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
-    if constexpr (sizeof(T) == 2) {
-      if (wave_fast_div<T>(p.s)) {
-        group_fwd_chunk<T, NT, true>(xv[j], by, off, fast_div<T>(p.s), p.s, qmin, qmax, p.zp);
-        continue;
-      }
-    }
-    group_fwd_chunk<T, NT, true>(xv[j], by, off, DivExact{p.s}, p.s, qmin, qmax, p.zp);
-  }
-}
-
 // One chunk of the backward: dx and the rounded gradient terms of scale and zero-point per element exactly as the
 // per-channel backward computes them (bwd_elem2, kBwdDsDzp), the group's two sums, then the autograd of the scale-shaped
 // torch ops of the graph, each rounding to T:
@@ -175,11 +123,11 @@ __global__ __launch_bounds__(kBlock) void group_shifted_fwd_kernel(GroupShiftedA
 // and the deposits in the order the per-channel route adds its dense gradients to dx: the zero-point statistic's first
 // (on the first element equal to mn), then the scale statistic's (max and min, added to each other first where one
 // element is both).  Every element of dx has been through "+ 0" there, which turns a -0 into +0.
-template <typename T, int L, bool NT, typename Div>
-__device__ __forceinline__ void group_shifted_bwd_chunk(const GroupShiftedArgs& a, const vec_t<T, elem<T>::vec>& xv,
-                                                        const vec_t<T, elem<T>::vec>& gv, buf_t bd, uint32_t off,
-                                                        int lane, const Div& div, const ShiftedGroup& p, float mx,
-                                                        float mn, float gsc, float gzp, float qmin, float qmax) {
+// sub: the lane within its segment (GroupPlace).
+template <typename T, int L, typename Div>
+__device__ __forceinline__ vec_t<T, elem<T>::vec> group_shifted_bwd_chunk(
+    const GroupShiftedArgs& a, const vec_t<T, elem<T>::vec>& xv, const vec_t<T, elem<T>::vec>& gv, uint32_t sub,
+    const Div& div, const ShiftedGroup& p, float mx, float mn, float gsc, float gzp, float qmin, float qmax) {
   constexpr int VEC = elem<T>::vec;
   const bool clamp_ste = a.clamp_ste != 0;
   f2 ds2 = splat2(0.f), dz2 = splat2(0.f), unused = splat2(0.f);
@@ -210,7 +158,7 @@ __device__ __forceinline__ void group_shifted_bwd_chunk(const GroupShiftedArgs& 
   const float dmn_z = mn <= 0.f ? -dn : 0.f;
   // first element of the group equal to each statistic: segment-wide minimum over lane * VEC + index (a NaN statistic
   // is equal to nothing)
-  const uint32_t e0 = (uint32_t)(lane & (L - 1)) * VEC;
+  const uint32_t e0 = sub * VEC;
   uint32_t fmx = ~0u, fmn = ~0u;
 #pragma unroll
   for (int k = VEC - 1; k >= 0; --k) {
@@ -229,57 +177,53 @@ __device__ __forceinline__ void group_shifted_bwd_chunk(const GroupShiftedArgs& 
     dep = is_mn ? rnd<T>(dep - dd) : dep;
     dv.v[k] = (is_mx || is_mn) ? from_f<T>(val + dep) : dv.v[k];
   }
-  buf_store<T, VEC, NT>(bd, off, dv);
+  return dv;
 }
 
-template <typename T, int L, bool NT>
-__global__ __launch_bounds__(kBlock) void group_shifted_bwd_kernel(GroupShiftedArgs a) {
-  constexpr int VEC = elem<T>::vec, kD = kShiftedBwdDepth;
-  GroupWindow<T, L, kD> w;
-  if (!w.init(a)) return;
-  const int lane = threadIdx.x & 63;
-  const T* statp = reinterpret_cast<const T*>(a.stat);
-  const buf_t bx = w.elems(a.x), bg = w.elems(a.g), bd = w.elems(a.y);
-  const buf_t btx = w.groups(statp), btn = w.groups(statp + a.chunks / L);
-  const buf_t bgs = w.groups(a.gscale ? a.gscale : a.stat), bgz = w.groups(a.gzp ? a.gzp : a.stat);
-  const float qmin = rnd<T>(a.qmin), qmax = rnd<T>(a.qmax);
-  vec_t<T, VEC> xv[kD], gv[kD];
-  vec_t<T, 1> txv[kD], tnv[kD], gsv[kD], gzv[kD];
-#pragma unroll
-  for (int j = 0; j < kD; ++j) {
-    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
-    const uint32_t goff = (uint32_t)(j * (kWave / L) + lane / L) * (uint32_t)sizeof(T);  // one address per segment
-    xv[j] = buf_load<T, VEC, NT>(bx, off);
-    gv[j] = buf_load<T, VEC, NT>(bg, off);
-    txv[j] = buf_load<T, 1>(btx, goff);
-    tnv[j] = buf_load<T, 1>(btn, goff);
-    gsv[j] = buf_load<T, 1>(bgs, goff);
-    gzv[j] = buf_load<T, 1>(bgz, goff);
+// the asymmetric quantizer on the frame of bvq_group_walk.h
+template <typename T, int L>
+struct ShiftedQuant {
+  using Args = GroupShiftedArgs;
+  using Vec = vec_t<T, elem<T>::vec>;
+  struct Side {
+    T mx, mn, gscale, gzp;
+  };
+  const Args& a;
+  const buf_t bs, bz, btx, btn, bgs, bgz;
+  const float qmin, qmax;
+  template <typename W>
+  __device__ __forceinline__ ShiftedQuant(const Args& a, const W& w)
+      : a(a), bs(w.groups(a.scale)), bz(w.groups(a.zp)), btx(w.groups(a.stat)),
+        btn(w.groups(reinterpret_cast<const T*>(a.stat) + a.chunks / L)), bgs(w.groups_or_zeros(a.gscale, a.x)),
+        bgz(w.groups_or_zeros(a.gzp, a.x)), qmin(rnd<T>(a.qmin)), qmax(rnd<T>(a.qmax)) {}
+
+  __device__ __forceinline__ Vec fwd(const Vec& xv, const GroupPlace& p) const {
+    uint32_t kmax, kmin;
+    chunk_minmax_keys<T>(xv, kmax, kmin);
+    float mx, mn;
+    shifted_stats<T>(seg_max_u32<L>(kmax), seg_min_u32<L>(kmin), mx, mn);
+    const ShiftedGroup sg = shifted_group<T>(mx, mn, a, qmin, qmax);
+    store_group(bs, p, from_f<T>(sg.s));
+    store_group(bz, p, from_f<T>(sg.zp));  // exact: an integer of the code range
+    store_group(btx, p, from_f<T>(mx));    // exact: values of T
+    store_group(btn, p, from_f<T>(mn));
+    return with_group_div<T>(sg.s, [&](const auto& div) {
+      return group_fwd_chunk<T, true>(xv, div, sg.s, qmin, qmax, sg.zp);
+    });
   }
-#pragma unroll
-  for (int j = 0; j < kD; ++j) {
-    if ((uint32_t)(j * kWave) >= w.nch) break;  // wave-uniform
-    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
-    const float mx = to_f<T>(txv[j].v[0]), mn = to_f<T>(tnv[j].v[0]);
+
+  __device__ __forceinline__ Side side(const GroupPlace& p) const {
+    return {load_group<T>(btx, p), load_group<T>(btn, p), load_group<T>(bgs, p), load_group<T>(bgz, p)};
+  }
+  __device__ __forceinline__ Vec bwd(const Vec& xv, const Vec& gv, const Side& sd, const GroupPlace& p) const {
+    const float mx = to_f<T>(sd.mx), mn = to_f<T>(sd.mn), gsc = to_f<T>(sd.gscale), gzp = to_f<T>(sd.gzp);
     // the forward's scale and zero-point from the saved statistics: the same arithmetic, the saved bits
-    const ShiftedGroup p = shifted_group<T>(mx, mn, a, qmin, qmax);
-    const float gsc = to_f<T>(gsv[j].v[0]), gzp = to_f<T>(gzv[j].v[0]);
-    if constexpr (sizeof(T) == 2) {
-      if (wave_fast_div<T>(p.s)) {
-        group_shifted_bwd_chunk<T, L, NT>(a, xv[j], gv[j], bd, off, lane, fast_div<T>(p.s), p, mx, mn, gsc, gzp, qmin,
-                                          qmax);
-        continue;
-      }
-    }
-    group_shifted_bwd_chunk<T, L, NT>(a, xv[j], gv[j], bd, off, lane, DivExact{p.s}, p, mx, mn, gsc, gzp, qmin, qmax);
+    const ShiftedGroup sg = shifted_group<T>(mx, mn, a, qmin, qmax);
+    return with_group_div<T>(sg.s, [&](const auto& div) {
+      return group_shifted_bwd_chunk<T, L>(a, xv, gv, p.sub, div, sg, mx, mn, gsc, gzp, qmin, qmax);
+    });
   }
-}
-
-static GroupShiftedArgs group_shifted_args(const bvq_quant_desc* d, double min_val, int use_min, double thr_div) {
-  GroupShiftedArgs a = {};
-  static_cast<GroupArgs&>(a) = group_args(d, min_val, use_min, thr_div);
-  return a;
-}
+};
 
 }  // namespace bvq
 
@@ -292,54 +236,36 @@ extern "C" int bvq_group_shifted_supported(const bvq_quant_desc* d, const void* 
 
 extern "C" int bvq_group_shifted_fwd(const bvq_quant_desc* d, const void* x, double min_val, int use_min,
                                      double thr_div, void* y, void* scale, void* zp, void* stat, bvq_stream_t stream) {
-  int rc = group_check(d, "bvq_group_shifted_fwd", true);
-  if (rc) return rc;
-  if (!x || !y || !scale || !zp || !stat) {
-    set_error("bvq_group_shifted_fwd: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  if (!aligned16(x) || !aligned16(y)) {
-    set_error("bvq_group_shifted_fwd: x and y must lie on 16-byte boundaries");
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  GroupShiftedArgs a = group_shifted_args(d, min_val, use_min, thr_div);
+  const char* what = "bvq_group_shifted_fwd";
+  int rc = group_required(what, group_check(d, what, true), {x, y, scale, zp, stat});
+  if ((rc = group_aligned(what, rc, {x, y}, "x and y"))) return rc;
+  GroupShiftedArgs a = group_args<GroupShiftedArgs>(d, min_val, use_min, thr_div);
   a.x = x;
   a.y = y;
   a.scale = scale;
   a.zp = zp;
   a.stat = stat;
-  const bool nt = a.chunks * 32 >= nt_threshold_bytes();  // x read + y written
-  rc = with_group_variant(d, nt, [&](auto t, auto l, auto ntc) {
-    group_shifted_fwd_kernel<typename decltype(t)::type, l, ntc>
-        <<<group_grid(a.chunks, kShiftedFwdDepth), kBlock, 0, (hipStream_t)stream>>>(a);
+  // x read + y written
+  return group_launch(what, d->x_dtype, d->inner, a.chunks, 32, kGroupFwdDepth, [&](auto t, auto l, auto nt, unsigned grid) {
+    group_fwd_kernel<ShiftedQuant, typename decltype(t)::type, l, nt><<<grid, kBlock, 0, (hipStream_t)stream>>>(a);
   });
-  return rc ? rc : check_launch("bvq_group_shifted_fwd");
 }
 
 extern "C" int bvq_group_shifted_bwd(const bvq_quant_desc* d, const void* g, const void* x, const void* stat,
                                      const void* gscale, const void* gzp, double min_val, int use_min, double thr_div,
                                      void* dx, bvq_stream_t stream) {
-  int rc = group_check(d, "bvq_group_shifted_bwd", true);
-  if (rc) return rc;
-  if (!g || !x || !stat || !dx) {
-    set_error("bvq_group_shifted_bwd: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  if (!aligned16(g) || !aligned16(x) || !aligned16(dx)) {
-    set_error("bvq_group_shifted_bwd: g, x and dx must lie on 16-byte boundaries");
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  GroupShiftedArgs a = group_shifted_args(d, min_val, use_min, thr_div);
+  const char* what = "bvq_group_shifted_bwd";
+  int rc = group_required(what, group_check(d, what, true), {g, x, stat, dx});
+  if ((rc = group_aligned(what, rc, {g, x, dx}, "g, x and dx"))) return rc;
+  GroupShiftedArgs a = group_args<GroupShiftedArgs>(d, min_val, use_min, thr_div);
   a.x = x;
   a.g = g;
   a.y = dx;
   a.stat = const_cast<void*>(stat);
   a.gscale = gscale;
   a.gzp = gzp;
-  const bool nt = a.chunks * 48 >= nt_threshold_bytes();  // g and x read, dx written
-  rc = with_group_variant(d, nt, [&](auto t, auto l, auto ntc) {
-    group_shifted_bwd_kernel<typename decltype(t)::type, l, ntc>
-        <<<group_grid(a.chunks, kShiftedBwdDepth), kBlock, 0, (hipStream_t)stream>>>(a);
+  // g and x read, dx written
+  return group_launch(what, d->x_dtype, d->inner, a.chunks, 48, kGroupBwdDepth, [&](auto t, auto l, auto nt, unsigned grid) {
+    group_bwd_kernel<ShiftedQuant, typename decltype(t)::type, l, nt><<<grid, kBlock, 0, (hipStream_t)stream>>>(a);
   });
-  return rc ? rc : check_launch("bvq_group_shifted_bwd");
 }

@@ -17,14 +17,6 @@
 
 namespace bvq {
 
-#ifndef BVQ_MX_FWD_DEPTH
-#define BVQ_MX_FWD_DEPTH 4  // wave loads of x in flight per wave
-#endif
-#ifndef BVQ_MX_BWD_DEPTH
-#define BVQ_MX_BWD_DEPTH 2  // wave loads of x and of g in flight per wave
-#endif
-constexpr int kMxFwdDepth = BVQ_MX_FWD_DEPTH;
-constexpr int kMxBwdDepth = BVQ_MX_BWD_DEPTH;
 constexpr int kMxEMin = -126, kMxEMax = 127;  // the scale stays a normal float32
 
 // r = p rounded to a multiple of 2^max(floor(log2 |p|) - mbits, qe_min); MXINT8 has mbits so large that the quantum
@@ -34,13 +26,9 @@ struct MxFormat {
   int32_t emax, mbits, qe_min;
 };
 
-struct MxArgs {
-  const void* x;
-  const void* g;       // bwd
-  void* y;             // fwd: y, bwd: dx
-  float* scale;        // fwd: [groups] out
-  const float* gscale; // bwd, nullable: gradient arriving through the returned scale, [groups]
-  int64_t chunks;      // 16-byte chunks of the tensor = groups * L
+struct MxArgs : WalkArgs {
+  float* scale;         // fwd: [groups] out
+  const float* gscale;  // bwd, nullable: gradient arriving through the returned scale, [groups]
   MxFormat f;
   int32_t ceil_rule, clamp_ste;
 };
@@ -94,86 +82,63 @@ __device__ __forceinline__ MxElem mx_elem(float x, const MxGroup& gr, const MxFo
   return r;
 }
 
-template <typename T, int L, bool NT>
-__global__ __launch_bounds__(kBlock) void mx_quant_fwd_kernel(MxArgs a) {
-  constexpr int VEC = elem<T>::vec, kD = kMxFwdDepth;
-  GroupWindow<T, L, kD> w;
-  if (!w.init(a)) return;
-  const int lane = threadIdx.x & 63;
-  const buf_t bx = w.elems(a.x), by = w.elems(a.y), bs = w.template groups<float>(a.scale);
-  const MxFormat f = a.f;
-  const bool ceil_rule = a.ceil_rule != 0;
-  vec_t<T, VEC> xv[kD];
-#pragma unroll
-  for (int j = 0; j < kD; ++j) xv[j] = buf_load<T, VEC, NT>(bx, (uint32_t)(j * kWave + lane) * 16u);
-#pragma unroll
-  for (int j = 0; j < kD; ++j) {
-    if ((uint32_t)(j * kWave) >= w.nch) break;  // wave-uniform: a load no lane has is not worked on
-    const MxGroup gr = mx_group(key_value<T>(seg_max_u32<L>(chunk_key<T>(xv[j]))), f, ceil_rule);
-    // one lane per segment writes the scale (a vector store; dropped for the groups past the end)
-    const uint32_t goff = (lane & (L - 1)) == 0 ? (uint32_t)(j * (kWave / L) + lane / L) * 4u : kBufSkip;
-    vec_t<float, 1> sv;
-    sv.v[0] = gr.finite ? ldexpf(1.0f, gr.e) : __builtin_nanf("");
-    buf_store<float, 1>(bs, goff, sv);
-    vec_t<T, VEC> yv;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) yv.v[k] = from_f<T>(ldexpf(mx_elem(to_f<T>(xv[j].v[k]), gr, f).q, gr.e));
-    buf_store<T, VEC, NT>(by, (uint32_t)(j * kWave + lane) * 16u, yv);  // dropped past the tensor's end
-  }
-}
+// the MX quantizer on the frame of bvq_group_walk.h
+template <typename T, int L>
+struct MxQuant {
+  using Args = MxArgs;
+  using Vec = vec_t<T, elem<T>::vec>;
+  static constexpr int VEC = elem<T>::vec;
+  struct Side {
+    float gscale;
+  };
+  const buf_t bs, bgs;
+  const MxFormat f;
+  const bool ceil_rule, clamp_ste;
+  template <typename W>
+  __device__ __forceinline__ MxQuant(const Args& a, const W& w)
+      : bs(w.template groups<float>(a.scale)), bgs(w.template groups_or_zeros<float>(a.gscale, a.x)), f(a.f),
+        ceil_rule(a.ceil_rule != 0), clamp_ste(a.clamp_ste != 0) {}
 
-template <typename T, int L, bool NT>
-__global__ __launch_bounds__(kBlock) void mx_quant_bwd_kernel(MxArgs a) {
-  constexpr int VEC = elem<T>::vec, kD = kMxBwdDepth;
-  GroupWindow<T, L, kD> w;
-  if (!w.init(a)) return;
-  const int lane = threadIdx.x & 63;
-  const buf_t bx = w.elems(a.x), bg = w.elems(a.g), bd = w.elems(a.y);
-  // no gradient through the scale: a descriptor of no bytes, whose loads return zeros without a memory access
-  const buf_t bgs = a.gscale ? w.template groups<float>(a.gscale) : make_buf(reinterpret_cast<const float*>(a.x), 0u);
-  const MxFormat f = a.f;
-  const bool ceil_rule = a.ceil_rule != 0, clamp_ste = a.clamp_ste != 0;
-  vec_t<T, VEC> xv[kD], gv[kD];
-  vec_t<float, 1> gsv[kD];
+  __device__ __forceinline__ Vec fwd(const Vec& xv, const GroupPlace& p) const {
+    const MxGroup gr = mx_group(key_value<T>(seg_max_u32<L>(chunk_key<T>(xv))), f, ceil_rule);
+    store_group(bs, p, gr.finite ? ldexpf(1.0f, gr.e) : __builtin_nanf(""));
+    Vec yv;
 #pragma unroll
-  for (int j = 0; j < kD; ++j) {
-    const uint32_t off = (uint32_t)(j * kWave + lane) * 16u;
-    xv[j] = buf_load<T, VEC, NT>(bx, off);
-    gv[j] = buf_load<T, VEC, NT>(bg, off);
-    gsv[j] = buf_load<float, 1>(bgs, (uint32_t)(j * (kWave / L) + lane / L) * 4u);  // one address per segment
+    for (int k = 0; k < VEC; ++k) yv.v[k] = from_f<T>(ldexpf(mx_elem(to_f<T>(xv.v[k]), gr, f).q, gr.e));
+    return yv;
   }
-#pragma unroll
-  for (int j = 0; j < kD; ++j) {
-    if ((uint32_t)(j * kWave) >= w.nch) break;  // wave-uniform
-    const uint32_t key = seg_max_u32<L>(chunk_key<T>(xv[j]));
+
+  __device__ __forceinline__ Side side(const GroupPlace& p) const { return {load_group<float>(bgs, p)}; }
+  __device__ __forceinline__ Vec bwd(const Vec& xv, const Vec& gv, const Side& sd, const GroupPlace& p) const {
+    const uint32_t key = seg_max_u32<L>(chunk_key<T>(xv));
     const float amax = key_value<T>(key);
     const MxGroup gr = mx_group(amax, f, ceil_rule);
     float acc = 0.f;
-    vec_t<T, VEC> dv;
+    Vec dv;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-      const MxElem e = mx_elem(to_f<T>(xv[j].v[k]), gr, f);
+      const MxElem e = mx_elem(to_f<T>(xv.v[k]), gr, f);
       const bool pass = e.inside || clamp_ste;
-      acc += to_f<T>(gv[j].v[k]) * (e.q - (pass ? e.p : 0.f));  // q - p is exact; the product is rounded once
-      dv.v[k] = pass ? gv[j].v[k] : from_f<T>(0.f);
+      acc += to_f<T>(gv.v[k]) * (e.q - (pass ? e.p : 0.f));  // q - p is exact; the product is rounded once
+      dv.v[k] = pass ? gv.v[k] : from_f<T>(0.f);
     }
     const float s = seg_sum<L>(acc);
     // d scale / d a = scale / a: the floor (or ceil) of the exponent is straight-through
-    const float da = gr.no_da ? 0.f : (gsv[j].v[0] + s) * (ldexpf(1.0f, gr.e) / amax);
+    const float da = gr.no_da ? 0.f : (sd.gscale + s) * (ldexpf(1.0f, gr.e) / amax);
     // first element of the group whose |x| is the abs-max: segment-wide minimum over lane * VEC + index
-    const uint32_t e0 = (uint32_t)(lane & (L - 1)) * VEC;
+    const uint32_t e0 = p.sub * VEC;
     uint32_t first = ~0u;
 #pragma unroll
-    for (int k = VEC - 1; k >= 0; --k) first = abs_bits<T>(xv[j].v[k]) == key ? e0 + k : first;
+    for (int k = VEC - 1; k >= 0; --k) first = abs_bits<T>(xv.v[k]) == key ? e0 + k : first;
     first = gr.no_da ? ~0u : seg_min_u32<L>(first);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-      const float dep = to_f<T>(dv.v[k]) + (to_f<T>(xv[j].v[k]) < 0.f ? -da : da);
+      const float dep = to_f<T>(dv.v[k]) + (to_f<T>(xv.v[k]) < 0.f ? -da : da);
       dv.v[k] = first == e0 + k ? from_f<T>(dep) : dv.v[k];
     }
-    buf_store<T, VEC, NT>(bd, (uint32_t)(j * kWave + lane) * 16u, dv);
+    return dv;
   }
-}
+};
 
 // ------------------------------------------------------------------------------------------------
 // the wire format (include/bvq.h, "MX wire format"): packed element codes and E8M0 scale bytes
@@ -192,12 +157,9 @@ struct MxCode {
   int32_t special;   // 0 none, 1 E4M3 (S.1111.111 is NaN), 2 E5M2 (exponent field 31 is Inf / NaN), 3 MXINT8
 };
 
-struct MxPackArgs {
-  const void* x;       // encode
-  void* y;             // decode
+struct MxPackArgs : WalkArgs {  // x: encode, y: decode
   void* codes;
-  void* scale;         // E8M0 bytes, [groups]
-  int64_t chunks;      // 16-byte chunks of x / y = groups * L
+  void* scale;  // E8M0 bytes, [groups]
   MxFormat f;
   MxCode c;
   int32_t ceil_rule, lanes_log2;
@@ -290,7 +252,7 @@ __device__ __forceinline__ void store_scale_dword(buf_t bs, uint32_t off, uint32
 
 template <typename T, int L, bool NT, int BITS>
 __global__ __launch_bounds__(kBlock) void mx_encode_kernel(MxPackArgs a) {
-  constexpr int VEC = elem<T>::vec, kD = kMxFwdDepth, W = VEC * BITS, GL = kWave / L;  // GL groups per load
+  constexpr int VEC = elem<T>::vec, kD = kGroupFwdDepth, W = VEC * BITS, GL = kWave / L;  // GL groups per load
   GroupWindow<T, L, kD> w;
   if (!w.init(a)) return;
   const int lane = threadIdx.x & 63;
@@ -363,7 +325,7 @@ __device__ __forceinline__ uint64_t stream_bits(const vec_t<uint32_t, 4>& r, int
 // argument: there is no segmented reduction here
 template <typename T, bool NT, int BITS>
 __global__ __launch_bounds__(kBlock) void mx_decode_kernel(MxPackArgs a) {
-  constexpr int VEC = elem<T>::vec, kD = kMxFwdDepth, W = VEC * BITS;
+  constexpr int VEC = elem<T>::vec, kD = kGroupFwdDepth, W = VEC * BITS;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t c0 = ((int64_t)blockIdx.x * kWavesPerBlock + wave) * (kD * kWave);
   if (c0 >= a.chunks) return;
@@ -479,52 +441,34 @@ extern "C" int bvq_mx_quant_supported(int dtype, int64_t groups, int group_size,
 
 extern "C" int bvq_mx_quant_fwd(int dtype, int64_t groups, int group_size, int format, int scale_rule, const void* x,
                                 void* y, void* scale, bvq_stream_t stream) {
-  int rc = mx_check(dtype, groups, group_size, format, scale_rule, "bvq_mx_quant_fwd");
-  if (rc) return rc;
-  if (!x || !y || !scale) {
-    set_error("bvq_mx_quant_fwd: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  if (!aligned16(x) || !aligned16(y) || !aligned16(scale)) {
-    set_error("bvq_mx_quant_fwd: x, y and scale must lie on 16-byte boundaries");
-    return BVQ_ERR_UNSUPPORTED;
-  }
+  const char* what = "bvq_mx_quant_fwd";
+  int rc = group_required(what, mx_check(dtype, groups, group_size, format, scale_rule, what), {x, y, scale});
+  if ((rc = group_aligned(what, rc, {x, y, scale}, "x, y and scale"))) return rc;
   MxArgs a = mx_args(dtype, groups, group_size, format, scale_rule);
   a.x = x;
   a.y = y;
   a.scale = static_cast<float*>(scale);
-  const bool nt = a.chunks * 32 >= nt_threshold_bytes();  // x read + y written
-  rc = with_group_variant(dtype, group_size, nt, [&](auto t, auto l, auto ntc) {
-    mx_quant_fwd_kernel<typename decltype(t)::type, l, ntc>
-        <<<group_grid(a.chunks, kMxFwdDepth), kBlock, 0, (hipStream_t)stream>>>(a);
+  // x read + y written
+  return group_launch(what, dtype, group_size, a.chunks, 32, kGroupFwdDepth, [&](auto t, auto l, auto nt, unsigned grid) {
+    group_fwd_kernel<MxQuant, typename decltype(t)::type, l, nt><<<grid, kBlock, 0, (hipStream_t)stream>>>(a);
   });
-  return rc ? rc : check_launch("bvq_mx_quant_fwd");
 }
 
 extern "C" int bvq_mx_quant_bwd(int dtype, int64_t groups, int group_size, int format, int scale_rule, int clamp_ste,
                                 const void* g, const void* x, const void* gscale, void* dx, bvq_stream_t stream) {
-  int rc = mx_check(dtype, groups, group_size, format, scale_rule, "bvq_mx_quant_bwd");
-  if (rc) return rc;
-  if (!g || !x || !dx) {
-    set_error("bvq_mx_quant_bwd: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  if (!aligned16(g) || !aligned16(x) || !aligned16(dx) || !aligned16(gscale)) {
-    set_error("bvq_mx_quant_bwd: g, x, gscale and dx must lie on 16-byte boundaries");
-    return BVQ_ERR_UNSUPPORTED;
-  }
+  const char* what = "bvq_mx_quant_bwd";
+  int rc = group_required(what, mx_check(dtype, groups, group_size, format, scale_rule, what), {g, x, dx});
+  if ((rc = group_aligned(what, rc, {g, x, dx, gscale}, "g, x, gscale and dx"))) return rc;
   MxArgs a = mx_args(dtype, groups, group_size, format, scale_rule);
   a.x = x;
   a.g = g;
   a.y = dx;
   a.gscale = static_cast<const float*>(gscale);
   a.clamp_ste = clamp_ste != 0;
-  const bool nt = a.chunks * 48 >= nt_threshold_bytes();  // g and x read, dx written
-  rc = with_group_variant(dtype, group_size, nt, [&](auto t, auto l, auto ntc) {
-    mx_quant_bwd_kernel<typename decltype(t)::type, l, ntc>
-        <<<group_grid(a.chunks, kMxBwdDepth), kBlock, 0, (hipStream_t)stream>>>(a);
+  // g and x read, dx written
+  return group_launch(what, dtype, group_size, a.chunks, 48, kGroupBwdDepth, [&](auto t, auto l, auto nt, unsigned grid) {
+    group_bwd_kernel<MxQuant, typename decltype(t)::type, l, nt><<<grid, kBlock, 0, (hipStream_t)stream>>>(a);
   });
-  return rc ? rc : check_launch("bvq_mx_quant_bwd");
 }
 
 extern "C" int bvq_mx_encode_supported(int dtype, int64_t groups, int group_size, int format, const void* x) {
@@ -534,54 +478,34 @@ extern "C" int bvq_mx_encode_supported(int dtype, int64_t groups, int group_size
 
 extern "C" int bvq_mx_encode(int dtype, int64_t groups, int group_size, int format, int scale_rule, const void* x,
                              void* codes, void* scale_e8m0, bvq_stream_t stream) {
-  int rc = mx_check(dtype, groups, group_size, format, scale_rule, "bvq_mx_encode");
-  if (rc) return rc;
-  if (!x || !codes || !scale_e8m0) {
-    set_error("bvq_mx_encode: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  if (!aligned16(x) || !aligned16(codes) || !aligned16(scale_e8m0)) {
-    set_error("bvq_mx_encode: x, codes and scale_e8m0 must lie on 16-byte boundaries");
-    return BVQ_ERR_UNSUPPORTED;
-  }
+  const char* what = "bvq_mx_encode";
+  int rc = group_required(what, mx_check(dtype, groups, group_size, format, scale_rule, what), {x, codes, scale_e8m0});
+  if ((rc = group_aligned(what, rc, {x, codes, scale_e8m0}, "x, codes and scale_e8m0"))) return rc;
   MxPackArgs a = mx_pack_args(dtype, groups, group_size, format, scale_rule);
   a.x = x;
   a.codes = codes;
   a.scale = scale_e8m0;
-  const bool nt = a.chunks * 32 >= nt_threshold_bytes();  // the policy of the forward, on the same x
-  rc = with_group_variant(dtype, group_size, nt, [&](auto t, auto l, auto ntc) {
+  // the policy of the forward, on the same x
+  return group_launch(what, dtype, group_size, a.chunks, 32, kGroupFwdDepth, [&](auto t, auto l, auto nt, unsigned grid) {
     return with_code_bits(format, [&](auto b) {
-      mx_encode_kernel<typename decltype(t)::type, l, ntc, b>
-          <<<group_grid(a.chunks, kMxFwdDepth), kBlock, 0, (hipStream_t)stream>>>(a);
+      mx_encode_kernel<typename decltype(t)::type, l, nt, b><<<grid, kBlock, 0, (hipStream_t)stream>>>(a);
     });
   });
-  return rc ? rc : check_launch("bvq_mx_encode");
 }
 
 extern "C" int bvq_mx_decode(int dtype, int64_t groups, int group_size, int format, const void* codes,
                              const void* scale_e8m0, void* y, bvq_stream_t stream) {
-  int rc = mx_check(dtype, groups, group_size, format, BVQ_MX_FLOOR, "bvq_mx_decode");
-  if (rc) return rc;
-  if (!codes || !scale_e8m0 || !y) {
-    set_error("bvq_mx_decode: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  if (!aligned16(codes) || !aligned16(scale_e8m0) || !aligned16(y)) {
-    set_error("bvq_mx_decode: codes, scale_e8m0 and y must lie on 16-byte boundaries");
-    return BVQ_ERR_UNSUPPORTED;
-  }
+  const char* what = "bvq_mx_decode";
+  int rc = group_required(what, mx_check(dtype, groups, group_size, format, BVQ_MX_FLOOR, what), {codes, scale_e8m0, y});
+  if ((rc = group_aligned(what, rc, {codes, scale_e8m0, y}, "codes, scale_e8m0 and y"))) return rc;
   MxPackArgs a = mx_pack_args(dtype, groups, group_size, format, BVQ_MX_FLOOR);
   a.y = y;
   a.codes = const_cast<void*>(codes);
   a.scale = const_cast<void*>(scale_e8m0);
-  const bool nt = a.chunks * 32 >= nt_threshold_bytes();
-  rc = with_dtype(dtype, [&](auto t) {
-    return with_bool(nt, [&](auto ntc) {
-      return with_code_bits(format, [&](auto b) {
-        mx_decode_kernel<typename decltype(t)::type, ntc, b>
-            <<<group_grid(a.chunks, kMxFwdDepth), kBlock, 0, (hipStream_t)stream>>>(a);
-      });
+  // the kernel takes the lanes per group from its arguments: one instantiation serves every L
+  return group_launch(what, dtype, group_size, a.chunks, 32, kGroupFwdDepth, [&](auto t, auto, auto nt, unsigned grid) {
+    return with_code_bits(format, [&](auto b) {
+      mx_decode_kernel<typename decltype(t)::type, nt, b><<<grid, kBlock, 0, (hipStream_t)stream>>>(a);
     });
   });
-  return rc ? rc : check_launch("bvq_mx_decode");
 }

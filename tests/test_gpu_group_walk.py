@@ -2,12 +2,14 @@
 load, window and workgroup boundary of each L = g * sizeof(T) / 16; every NT = true instantiation through the forced-NT
 build of the library (brevitas_amd/libbvq_nt0.so, made by __graft_entry__.build()); and the backward branches of the
 two autograd Functions that no other test reaches on a device.  The six entry points are called through their
-brevitas_amd._native wrappers: group_quant_fwd / bwd, mx_quant_fwd / bwd, mx_encode, mx_decode.
+brevitas_amd._native wrappers: group_quant_fwd / bwd, mx_quant_fwd / bwd, mx_encode, mx_decode; the asymmetric kernels
+(group_shifted_fwd / bwd) through their quantizer module.
 
 No bar of its own.  MX: y and scale bit for bit against the numpy oracle, dx by assert_dx of test_mx_quant_host.py; codes
 and scale bytes byte for byte against the numpy encoder of test_mx_pack_host.py, the decoder against the device forward.
 Group-wise integer: y and scale bit for bit against the CPU oracle and the per-channel route on the regrouped weight, dw
-by assert_dw of test_gpu_group_quant.py with its derived deposit_ulps.
+by assert_dw of test_gpu_group_quant.py with its derived deposit_ulps.  Asymmetric: y, scale and zp bit for bit against
+the per-channel route on the regrouped weight, dw by compare of test_gpu_group_shifted.py.
 """
 import functools
 
@@ -16,9 +18,10 @@ import torch
 
 import golden_util as G
 import test_gpu_group_quant as GQ
+import test_gpu_group_shifted as GS
 import test_mx_pack_host as P
 import test_mx_quant_host as H
-from test_group_walk_host import NT_BYTES, edge_counts, nt0_path
+from test_group_walk_host import FWD_DEPTH, LANES, NT_BYTES, WAVES, edge_counts, lanes_per_group, nt0_path
 from test_gpu_mx_quant import untie
 from test_mx_quant_host import DT
 
@@ -80,7 +83,8 @@ def launches(monkeypatch):
                 calls['grad_ptrs'].append((a[1].data_ptr(), None if a[5] is None else a[5].data_ptr()))
             return real(*a, **k)
         monkeypatch.setattr(n, name, counted)
-    for name in ('group_quant_fwd', 'group_quant_bwd', 'mx_quant_fwd', 'mx_quant_bwd', 'mx_encode', 'mx_decode'):
+    for name in ('group_quant_fwd', 'group_quant_bwd', 'mx_quant_fwd', 'mx_quant_bwd', 'mx_encode', 'mx_decode',
+                 'group_shifted_fwd', 'group_shifted_bwd'):
         count(name)
     return calls
 
@@ -198,6 +202,39 @@ def check_group(out, ref, w, grad, g, bits, ste, dn):
     return GQ.assert_dw(dw, dw_r, w, grad, g, bits, dn)
 
 
+# ---- asymmetric group-wise integer: inputs, the device steps with their bar --------------------------------------------
+
+SHIFTED_BITS = 4      # the format's own width (unsigned 4-bit codes with a zero-point per group)
+
+
+@functools.lru_cache(None)
+def shifted_inputs(dn, g, groups):
+    """(w [groups, g], grad, gscale, gzp) on the CPU: the first groups of the weight of test_gpu_group_shifted.py, whose
+    groups 0 .. 9 are planted -- those of them that exist"""
+    w, grad, gscale, gzp = GS.make_weight((max(groups, 10), g), g, dn)
+    return tuple(t[:groups].contiguous() for t in (w, grad, gscale, gzp))
+
+
+def shifted_steps(dn, g, groups, ste):
+    """-> (device inputs, (y, scale, zp, dw) of the one-kernel route, the same of the per-channel route).
+    A single group's per-channel reference is its row of the first two groups' step: the device route quantizes a
+    weight of ONE channel with whole-tensor statistics, whose tied extrema share their gradient evenly (torch.max()),
+    and the planted group 0 is all ties.  Measured on an MI355X, float32, g = 16, group 0 alone: the one-kernel route
+    and the CPU put -2409982720 on element 0 and leave the others, the one-channel device route puts -150623920
+    (a sixteenth) on each of the 16.  Channels are independent, so a row of the two-group step is the reference."""
+    dev = tuple(t.to(DEV) for t in shifted_inputs(dn, g, groups))
+    wd, gd, gsd, gzd = dev
+    rw, rg, rgs, rgz = dev if groups > 1 else (t.to(DEV) for t in shifted_inputs(dn, g, 2))
+    ref = tuple(t[:groups] for t in GS.per_channel_step(rw, g, SHIFTED_BITS, ste, rg, rgs, rgz))
+    return dev, GS.grouped_step(wd, g, SHIFTED_BITS, ste, gd, gsd, gzd), ref
+
+
+def check_shifted(out, ref, dev, dn, g):
+    """the bar of test_gpu_group_shifted.py on the device inputs `dev` -> the worst deposit difference in ulps"""
+    wd, gd, gsd, gzd = dev
+    return GS.compare(out, ref, wd, gd, g, SHIFTED_BITS, dn, gsd, gzd)
+
+
 # ---- a: one group below, on and above every boundary ----------------------------------------------------------------
 
 @dtypes
@@ -247,6 +284,22 @@ def test_group_quant_at_the_edges(dn, g, bits):
             except AssertionError as e:
                 raise AssertionError('%d groups, ste=%d: %s' % (groups, ste, e)) from e
     print('GROUP_WALK_EDGE_INT_DEPOSIT_ULPS %s g=%d bits=%d worst=%.3f' % (dn, g, bits, worst))
+
+
+@dtypes
+@edge_sizes
+def test_group_shifted_at_the_edges(dn, g, launches):
+    worst, steps = 0.0, 0
+    for groups in edge_counts(dn, g):
+        for ste in (True, False):
+            try:
+                dev, out, ref = shifted_steps(dn, g, groups, ste)
+                worst = max(worst, check_shifted(out, ref, dev, dn, g))
+            except AssertionError as e:
+                raise AssertionError('%d groups, ste=%d: %s' % (groups, ste, e)) from e
+            steps += 1
+    assert launches['group_shifted_fwd'] == launches['group_shifted_bwd'] == steps
+    print('GROUP_WALK_EDGE_SHIFTED_DEPOSIT_ULPS %s g=%d worst=%.3f' % (dn, g, worst))
 
 
 # ---- c: every NT = true instantiation -------------------------------------------------------------------------------
@@ -311,6 +364,28 @@ def test_group_quant_nt(dn, g, bits, use_nt0):
             assert bits_equal(a, b), '%s of the NT kernel differs from the default library (ste=%d)' % (what, ste)
         worst = max(worst, check_group(out, ref, w, grad, g, bits, ste, dn))
     print('GROUP_WALK_NT_INT_DEPOSIT_ULPS %s g=%d bits=%d worst=%.3f' % (dn, g, bits, worst))
+
+
+@dtypes
+@pytest.mark.parametrize('g', [16, 256])
+def test_group_shifted_nt(dn, g, use_nt0, launches):
+    """one workgroup's forward window, one group less and one group more"""
+    window = LANES // lanes_per_group(dn, g) * FWD_DEPTH * WAVES
+    assert nat().lib.bvq_nt_threshold_bytes() == NT_BYTES
+    cases = [(groups, ste) for groups in (window - 1, window + 1) for ste in (True, False)]
+    # the reference route runs on the default library: the per-channel kernels' NT variants are not the subject
+    plain = [shifted_steps(dn, g, groups, ste) for groups, ste in cases]
+    use_nt0()
+    worst = 0.0
+    for (groups, ste), (dev, want, ref) in zip(cases, plain):
+        wd, gd, gsd, gzd = dev
+        out = GS.grouped_step(wd, g, SHIFTED_BITS, ste, gd, gsd, gzd)
+        for a, b, what in zip(out, want, ('y', 'scale', 'zp', 'dw')):
+            assert bits_equal(a, b), '%s of the NT kernel differs from the default library (%d groups, ste=%d)' \
+                % (what, groups, ste)
+        worst = max(worst, check_shifted(out, ref, dev, dn, g))
+    assert launches['group_shifted_fwd'] == launches['group_shifted_bwd'] == 2 * len(cases)
+    print('GROUP_WALK_NT_SHIFTED_DEPOSIT_ULPS %s g=%d worst=%.3f' % (dn, g, worst))
 
 
 # ---- d: backward branches of the autograd Functions -----------------------------------------------------------------

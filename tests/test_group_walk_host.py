@@ -42,18 +42,18 @@ def test_edge_counts_sit_on_the_boundaries():
 
 
 def test_geometry_constants_are_those_of_the_sources():
+    """one pair of depths, in the walk's header, and no file of the four families defines a depth of its own"""
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'brevitas_amd', 'csrc')
 
-    def define(name, *files):
-        for f in files:
-            m = re.search(r'#define %s (\d+)' % name, open(os.path.join(csrc, f)).read())
-            assert m, (name, f)
-            yield int(m.group(1))
-    assert set(define('BVQ_MX_FWD_DEPTH', 'bvq_mx_quant.hip')) | set(define('BVQ_GROUP_FWD_DEPTH', 'bvq_group_quant.hip')) \
-        == {FWD_DEPTH}
-    assert set(define('BVQ_MX_BWD_DEPTH', 'bvq_mx_quant.hip')) | set(define('BVQ_GROUP_BWD_DEPTH', 'bvq_group_quant.hip')) \
-        == {BWD_DEPTH}
+    def source(f):
+        with open(os.path.join(csrc, f)) as fh:
+            return fh.read()
+    depths = dict(re.findall(r'#define (BVQ_\w+_DEPTH) (\d+)', source('bvq_group_walk.h')))
+    assert depths == {'BVQ_GROUP_FWD_DEPTH': str(FWD_DEPTH), 'BVQ_GROUP_BWD_DEPTH': str(BWD_DEPTH)}
+    for f in ('bvq_group_quant.hip', 'bvq_group_mse.hip', 'bvq_group_shifted.hip', 'bvq_mx_quant.hip',
+              'bvq_group_quant.h'):
+        assert not re.search(r'#\s*define\s+\w*DEPTH', source(f)), f
 
 
 def test_the_forced_nt_variant_keeps_its_threshold_next_to_a_global_libbvq():
