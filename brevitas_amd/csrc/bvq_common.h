@@ -571,9 +571,10 @@ struct ChunkCursor {
 };
 
 // The same walk with a loop for the row carry: the form the read-only kernels (statistics, select, tie
-// scan) keep -- measured on MI355X they stream 5-10 % faster with it (their loads are predicated, and a
-// single-row unit, the common case, advances with one add), while the quantizer kernels, which issue
-// their loads unconditionally, are faster with the branch-free ChunkCursor above.
+// scan: walk_unit, bvq_unit_walk.h) keep -- measured on MI355X they stream 5-10 % faster with it (their
+// loads are predicated, and a single-row unit, the common case, advances with one add), while the
+// quantizer kernels, which issue their loads unconditionally, are faster with the branch-free
+// ChunkCursor above.
 struct ChunkWalker {
   int32_t row;    // row inside the unit
   int32_t chunk;  // chunk inside the row

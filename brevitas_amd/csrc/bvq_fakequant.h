@@ -1,11 +1,13 @@
 // bvq_fakequant.h -- what the quantizer translation units share: the kernel argument blocks, the division forms,
-// the column-mapped lane state, and the host-side helpers of the entry points (validation, layout -> arguments).
+// the column-mapped lane state (placed by cols_locate, bvq_unit_walk.h), and the host-side helpers of the entry points
+// (validation, layout -> arguments).
 // Included by bvq_fakequant_fwd.hip (forward kernels + entry points), bvq_fakequant_bwd.hip (backward entry points,
 // column-mapped and finishing kernels) and, through bvq_fakequant_bwd.h, by the three translation units that
 // instantiate the row-mapped backward kernel per dtype family (bvq_fakequant_bwd_{bf16,f16,f32}.hip).
 #pragma once
 
 #include "bvq_quant_math.h"
+#include "bvq_unit_walk.h"
 #include "bvq_ties.h"
 #include "bvq_sums.h"
 
@@ -254,31 +256,15 @@ struct ColsQuantArgs {
 
 // what a lane needs to know about its VEC columns, loaded once per unit
 template <typename T, int V = elem<T>::vec>
-struct ColsLane {
+struct ColsLane : ColsPlace {  // where the lane stands (bvq_unit_walk.h): row0, row_end, blk0, chunk, sub, active
   static constexpr int VEC = V;
-  int64_t row0, row_end;
-  int64_t blk0;  // first row of the unit's row block (wave-uniform)
-  int32_t chunk, sub;
-  bool active;
   int32_t ch[VEC];
   f2 s2[VEC / 2], z2[VEC / 2];
   bool fast, zp0;  // wave-uniform: every column's scale suits the bf16 reciprocal / every zero-point is +0
 
-  // team: the unit is the WORKGROUP's -- its waves take the block's rows in turn (wave w: rows w, w + 4, ... of each
-  // lane group), so that the workgroup walks one contiguous window of memory, and combine their partials on chip
+  // team: the unit is the WORKGROUP's (cols_locate) -- its waves combine their partials on chip
   __device__ __forceinline__ bool init(const ColsQuantArgs& a, bool team = false) {
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    const int64_t unit = team ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * kWavesPerBlock + wave;
-    if (unit >= a.p.units) return false;
-    const int64_t rblk = unit / a.p.strips;
-    const int32_t strip = (int32_t)(unit - rblk * a.p.strips);
-    sub = lane / a.p.lpr;
-    chunk = strip * kWave + (lane - sub * a.p.lpr);
-    active = sub < a.p.rpp && chunk < a.p.cps;
-    blk0 = rblk * a.p.rb;
-    row0 = blk0 + (team ? (int64_t)wave * a.p.rpp : 0) + sub;
-    row_end = (rblk + 1) * a.p.rb < a.p.rows ? (rblk + 1) * a.p.rb : a.p.rows;
+    if (!cols_locate(a.p, team, *this)) return false;
     bool ok_fast = true, ok_zp0 = true;
     float sv[VEC], zv[VEC];
 #pragma unroll

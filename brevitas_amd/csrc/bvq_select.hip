@@ -8,13 +8,14 @@
 // Values are mapped to order-preserving unsigned keys (16 bits for bf16/f16, 32 for f32; every NaN
 // sorts last, as torch.kthvalue orders them) and the k-th key is found digit by digit from the top:
 // each pass streams x once, histograms one 11-bit digit of the keys that match the prefix found so
-// far (LDS, one private 2048-bin histogram per wave, flushed with global atomics), and a tiny
-// kernel picks the bin that holds the k-th element.  16-bit types need 2 passes (11 + 5 bits), f32
-// 3 (11 + 11 + 10); after the first pass almost no key matches the prefix, so later passes are pure
-// streaming reads.  Algorithmic bytes per element: passes * sizeof(x).  The result is exact.
+// far (the row-mapped walk of bvq_unit_walk.h; LDS, one private 2048-bin histogram per wave, flushed
+// with global atomics), and a tiny kernel picks the bin that holds the k-th element.  16-bit types need
+// 2 passes (11 + 5 bits), f32 3 (11 + 11 + 10); after the first pass almost no key matches the prefix,
+// so later passes are pure streaming reads.  Algorithmic bytes per element: passes * sizeof(x).  The result is exact.
 // One-channel (per-tensor) calls of bvq_kth_value take a wider first digit instead -- 15 bits, all 32768 bins in
 // the LDS of one 1024-thread workgroup per CU -- and need one read (|x| of a 16-bit type) or two: see below.
 #include "bvq_common.h"
+#include "bvq_unit_walk.h"
 #include "bvq_ties.h"
 
 namespace bvq {
@@ -89,40 +90,21 @@ __global__ __launch_bounds__(kBlock) void kth_hist_kernel(SelArgs a) {
   __syncthreads();  // every wave reaches this (the unit check comes after)
   const Unit u = locate_unit(a.t);
   if (!u.valid) return;
-  const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + u.base;
   const uint32_t want = a.first_pass ? 0u : a.prefix[u.channel];
   const int hi_shift = a.shift + a.bits;  // bits above this pass's digit
   const uint32_t mask = (1u << a.bits) - 1u;
-  ChunkWalker cur;
-  cur.init(u, VEC, lane);
-  const int64_t total = (int64_t)u.nrows * cur.cpr;
-  for (int64_t done = 0; done < total; done += (int64_t)kWave * kSelUnroll) {
-    vec_t<T, VEC> xv[kSelUnroll];
-    bool ok[kSelUnroll];
-#pragma unroll
-    for (int j = 0; j < kSelUnroll; ++j) {
-      ok[j] = cur.valid();
-      if (ok[j]) xv[j] = load_vec<T, VEC, NT>(xp + cur.offset(u.row_stride, VEC));
-      cur.next();
-    }
-#pragma unroll
-    for (int j = 0; j < kSelUnroll; ++j) {
-      if (ok[j]) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-          const uint32_t key = sel_key<T, ABS>(xv[j].v[k]);
-          const bool match = a.first_pass || (hi_shift >= 32 ? true : (key >> hi_shift) == want);
-          if (match) atomicAdd(&h[(key >> a.shift) & mask], 1u);
-        }
-      }
-    }
-  }
-  const int64_t i = (int64_t)cur.cpr * VEC + lane;
-  if (u.nrows == 1 && i < u.len) {
-    const uint32_t key = sel_key<T, ABS>(xp[i]);
+  auto count = [&](T v) {
+    const uint32_t key = sel_key<T, ABS>(v);
     const bool match = a.first_pass || (hi_shift >= 32 ? true : (key >> hi_shift) == want);
     if (match) atomicAdd(&h[(key >> a.shift) & mask], 1u);
-  }
+  };
+  walk_unit<T, VEC, NT, kSelUnroll>(
+      u, reinterpret_cast<const T*>(a.x) + u.base, a.t.row_len, lane,
+      [&](const vec_t<T, VEC>& xv, int64_t, int64_t) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) count(xv.v[k]);
+      },
+      [&](T v, int64_t, int64_t) { count(v); });
   // flush the non-empty bins of this wave's histogram
   uint32_t* gh = a.hist + (int64_t)u.channel * kBins;
   for (int b = lane; b < kBins; b += kWave) {

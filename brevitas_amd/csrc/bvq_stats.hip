@@ -8,10 +8,16 @@
 // abs-max works on the raw bit patterns: for |x| the IEEE order equals the unsigned-integer order
 // of (bits & ~sign), and every NaN pattern is larger than +inf, so an unsigned max IS
 // torch.max(torch.abs(x)) including its NaN propagation.  The result is exact (a max never rounds).
+//
+// The streaming kernels sit on the two walks of bvq_unit_walk.h: each is its state, a per-element function (shared by
+// the row-mapped and the column-mapped kernel of a statistic) and its write-out.  The one-launch abs-max keeps its own
+// software-pipelined loop (onepass_unit_max) and takes only its ragged ends from the walk; so do minmax_kernel and
+// tie_scan_kernel, which measured slower on walk_unit's main loop (profiles/stat_walk.md).
 #include <math.h>
 #include <string.h>
 
 #include "bvq_common.h"
+#include "bvq_unit_walk.h"
 #include "bvq_act.h"
 #include "bvq_ties.h"
 #include "bvq_sums.h"
@@ -19,7 +25,8 @@
 
 namespace bvq {
 
-constexpr int kStatUnroll = 8;
+constexpr int kStatUnroll = 8;  // row-mapped statistic kernels: 16-byte loads in flight per lane
+constexpr int kColsStatUnroll = 4;  // column-mapped ones: rows in flight per lane
 
 struct StatArgs {
   Tiling t;
@@ -29,106 +36,47 @@ struct StatArgs {
   float* pivot;      // moments: [channels] the value the sums are shifted by (written by the kernel)
 };
 
-// ACT: the activation of bvq_act.h applied to x first (0: none; RELU is the ReLU)
-template <typename T, int ACT>
-__device__ __forceinline__ uint32_t act_abs_bits(T v) {
-  return abs_bits<T>(from_f<T>(act_rnd<T, ACT>(to_f<T>(v))));
-}
+struct ColsStatArgs {
+  ColsPlan p;
+  const void* x;
+  uint32_t* part;  // [prows][L]
+};
 
-template <typename T, int VEC, bool NT, bool RELU, int ACT = 0>
-__global__ __launch_bounds__(kBlock) void absmax_kernel(StatArgs a) {
-  const Unit u = locate_unit(a.t);
-  if (!u.valid) return;
-  const int lane = threadIdx.x & 63;
-  const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + u.base;
-  uint32_t m = 0;
-  ChunkWalker cur;
-  cur.init(u, VEC, lane);
-  const int64_t total = (int64_t)u.nrows * cur.cpr;
-  for (int64_t done = 0; done < total; done += (int64_t)kWave * kStatUnroll) {
-    vec_t<T, VEC> xv[kStatUnroll];
-    bool ok[kStatUnroll];
-#pragma unroll
-    for (int j = 0; j < kStatUnroll; ++j) {
-      ok[j] = cur.valid();
-      if (ok[j]) xv[j] = load_vec<T, VEC, NT>(xp + cur.offset(u.row_stride, VEC));
-      cur.next();
-    }
-#pragma unroll
-    for (int j = 0; j < kStatUnroll; ++j) {
-      if (ok[j]) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-          const uint32_t b = ACT != 0 ? act_abs_bits<T, ACT>(xv[j].v[k]) : pre_abs_bits<T, RELU>(xv[j].v[k]);
-          m = b > m ? b : m;
-        }
-      }
-    }
-  }
-  // ragged ends: the (< VEC) elements after the last full chunk of every row of the unit
-  const int32_t tail = (int32_t)(u.len - (int64_t)cur.cpr * VEC);
-  for (int32_t e = lane; e < u.nrows * tail; e += kWave) {
-    const int32_t r = e / tail, k = e - r * tail;
-    const T xe = xp[(int64_t)r * u.row_stride + (int64_t)cur.cpr * VEC + k];
-    const uint32_t b = ACT != 0 ? act_abs_bits<T, ACT>(xe) : pre_abs_bits<T, RELU>(xe);
-    m = b > m ? b : m;
-  }
-  m = wave_max_u32(m);
-  if (lane == 0) a.part_a[u.id] = m;
-}
+// ---- per-element arithmetic of the statistics, one function for both mappings ------------------------------------
+// A row-mapped kernel keeps one state per lane and ends with a wave reduction; a column-mapped one keeps one state per
+// column of its chunk and writes them as partial row (row block * rpp + sub row) of the [partial rows][L] array that
+// the finishing kernel reduces.
 
-template <typename T, int VEC, bool NT, bool RELU, int ACT = 0>
-__global__ __launch_bounds__(kBlock) void minmax_kernel(StatArgs a) {
-  const Unit u = locate_unit(a.t);
-  if (!u.valid) return;
-  const int lane = threadIdx.x & 63;
-  const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + u.base;
-  float mx = -__builtin_inff(), mn = __builtin_inff();
-  uint32_t nan = 0;
-  ChunkWalker cur;
-  cur.init(u, VEC, lane);
-  const int64_t total = (int64_t)u.nrows * cur.cpr;
-  for (int64_t done = 0; done < total; done += (int64_t)kWave * kStatUnroll) {
-    vec_t<T, VEC> xv[kStatUnroll];
-    bool ok[kStatUnroll];
-#pragma unroll
-    for (int j = 0; j < kStatUnroll; ++j) {
-      ok[j] = cur.valid();
-      if (ok[j]) xv[j] = load_vec<T, VEC, NT>(xp + cur.offset(u.row_stride, VEC));
-      cur.next();
-    }
-#pragma unroll
-    for (int j = 0; j < kStatUnroll; ++j) {
-      if (ok[j]) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-          float f = RELU ? relu_f(to_f<T>(xv[j].v[k])) : to_f<T>(xv[j].v[k]);
-          if constexpr (ACT != 0) f = act_rnd<T, ACT>(f);
-          nan |= (f != f) ? 1u : 0u;
-          mx = fmaxf(mx, f);
-          mn = fminf(mn, f);
-        }
-      }
-    }
+// the value a statistic is taken of: PRE (bvq_pre_op) applied to v -- none, torch.relu, or an activation of bvq_act.h
+// rounded to T
+template <typename T, int PRE>
+__device__ __forceinline__ float pre_value(T v) {
+  if constexpr (PRE == BVQ_PRE_NONE) {
+    return to_f<T>(v);
+  } else if constexpr (PRE == BVQ_PRE_RELU) {
+    return relu_f(to_f<T>(v));
+  } else {
+    return act_rnd<T, PRE>(to_f<T>(v));
   }
-  const int32_t tail = (int32_t)(u.len - (int64_t)cur.cpr * VEC);  // ragged ends of every row
-  for (int32_t e = lane; e < u.nrows * tail; e += kWave) {
-    const int32_t r = e / tail, k = e - r * tail;
-    const T xe = xp[(int64_t)r * u.row_stride + (int64_t)cur.cpr * VEC + k];
-    float f = RELU ? relu_f(to_f<T>(xe)) : to_f<T>(xe);
-    if constexpr (ACT != 0) f = act_rnd<T, ACT>(f);
-    nan |= (f != f) ? 1u : 0u;
-    mx = fmaxf(mx, f);
-    mn = fminf(mn, f);
+}
+// |pre_value| as the abs_bits<> key
+template <typename T, int PRE>
+__device__ __forceinline__ uint32_t pre_key(T v) {
+  if constexpr (PRE == BVQ_PRE_NONE || PRE == BVQ_PRE_RELU) {
+    return pre_abs_bits<T, PRE == BVQ_PRE_RELU>(v);
+  } else {
+    return abs_bits<T>(from_f<T>(pre_value<T, PRE>(v)));
   }
-  mx = wave_max(mx);
-  mn = wave_min(mn);
-  nan = wave_or_u32(nan);
-  if (lane == 0) {
-    // torch.max / torch.min propagate NaN
-    a.part_a[u.id] = nan ? 0x7fc00000u : __builtin_bit_cast(uint32_t, mx);
-    a.part_b[u.id] = nan ? 0x7fc00000u : __builtin_bit_cast(uint32_t, mn);
-  }
+}
+constexpr int pre_of(bool relu) { return relu ? BVQ_PRE_RELU : BVQ_PRE_NONE; }
+
+__device__ __forceinline__ void absmax_take(uint32_t key, uint32_t& m) { m = key > m ? key : m; }
+
+// min / max of f; a NaN sets `bit` of the flag word (torch.max / torch.min propagate NaN, fmaxf / fminf drop it)
+__device__ __forceinline__ void minmax_take(float f, float& mx, float& mn, uint32_t& nan, uint32_t bit) {
+  nan |= (f != f) ? bit : 0u;
+  mx = fmaxf(mx, f);
+  mn = fminf(mn, f);
 }
 
 // ---- first and second moment of |x| (AbsAve, MeanSigmaStd, B/core/stats/stats_op.py:186-262) -------
@@ -142,15 +90,50 @@ __device__ __forceinline__ float moments_pivot(const void* x, int64_t first) {
   const float p = fabsf(to_f<T>(reinterpret_cast<const T*>(x)[first]));
   return p <= 3.4028234663852886e38f ? p : 0.f;  // inf / NaN: no shift
 }
+template <typename T>
+__device__ __forceinline__ void moments_take(T v, float p, float& s1, float& s2) {
+  const float d = fabsf(to_f<T>(v)) - p;
+  s1 += d;
+  s2 += d * d;
+}
 
-template <typename T, int VEC, bool NT>
-__global__ __launch_bounds__(kBlock) void absmoments_kernel(StatArgs a) {
+// sgn(x) * (a + b * |x|): the backward of any statistic that is a function of the mean and the variance of |x|
+// (sgn(0) = 0, torch.abs's subgradient; NaN in, NaN out)
+template <typename T>
+__device__ __forceinline__ T abs_affine(T v, float a, float b) {
+  const float xf = to_f<T>(v);
+  const float m = a + b * fabsf(xf);
+  return from_f<T>(xf > 0.f ? m : (xf < 0.f ? -m : (xf == 0.f ? 0.f : xf)));
+}
+
+// ---- row-mapped kernels (walk_unit, bvq_unit_walk.h) ---------------------------------------------------------------
+template <typename T, int VEC, bool NT, int PRE>
+__global__ __launch_bounds__(kBlock) void absmax_kernel(StatArgs a) {
   const Unit u = locate_unit(a.t);
   if (!u.valid) return;
   const int lane = threadIdx.x & 63;
+  uint32_t m = 0;
+  walk_unit<T, VEC, NT, kStatUnroll>(
+      u, reinterpret_cast<const T*>(a.x) + u.base, a.t.row_len, lane,
+      [&](const vec_t<T, VEC>& xv, int64_t, int64_t) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) absmax_take(pre_key<T, PRE>(xv.v[k]), m);
+      },
+      [&](T v, int64_t, int64_t) { absmax_take(pre_key<T, PRE>(v), m); });
+  m = wave_max_u32(m);
+  if (lane == 0) a.part_a[u.id] = m;
+}
+
+template <typename T, int VEC, bool NT, int PRE>
+__global__ __launch_bounds__(kBlock) void minmax_kernel(StatArgs a) {
+  const Unit u = locate_unit(a.t);
+  if (!u.valid) return;
+  const int lane = threadIdx.x & 63;
+  float mx = -__builtin_inff(), mn = __builtin_inff();
+  uint32_t nan = 0;
+  // (its own main loop, the walk's written out: on walk_unit the per-tensor 16-bit min/max streamed 0.5 - 0.7 % slower
+  //  than the parent, outside the parent's own spread, profiles/stat_walk.md; the ragged end is the walk's)
   const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + u.base;
-  const float p = moments_pivot<T>(a.x, (int64_t)u.channel * a.t.row_len);
-  float s1 = 0.f, s2 = 0.f;
   ChunkWalker cur;
   cur.init(u, VEC, lane);
   const int64_t total = (int64_t)u.nrows * cur.cpr;
@@ -167,20 +150,35 @@ __global__ __launch_bounds__(kBlock) void absmoments_kernel(StatArgs a) {
     for (int j = 0; j < kStatUnroll; ++j) {
       if (ok[j]) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-          const float d = fabsf(to_f<T>(xv[j].v[k])) - p;
-          s1 += d;
-          s2 += d * d;
-        }
+        for (int k = 0; k < VEC; ++k) minmax_take(pre_value<T, PRE>(xv[j].v[k]), mx, mn, nan, 1u);
       }
     }
   }
-  const int64_t i = (int64_t)cur.cpr * VEC + lane;
-  if (u.nrows == 1 && i < u.len) {
-    const float d = fabsf(to_f<T>(xp[i])) - p;
-    s1 += d;
-    s2 += d * d;
+  walk_unit_tail<VEC>(u, a.t.row_len, lane,
+                      [&](int64_t off, int64_t) { minmax_take(pre_value<T, PRE>(xp[off]), mx, mn, nan, 1u); });
+  mx = wave_max(mx);
+  mn = wave_min(mn);
+  nan = wave_or_u32(nan);
+  if (lane == 0) {
+    a.part_a[u.id] = nan ? 0x7fc00000u : __builtin_bit_cast(uint32_t, mx);
+    a.part_b[u.id] = nan ? 0x7fc00000u : __builtin_bit_cast(uint32_t, mn);
   }
+}
+
+template <typename T, int VEC, bool NT>
+__global__ __launch_bounds__(kBlock) void absmoments_kernel(StatArgs a) {
+  const Unit u = locate_unit(a.t);
+  if (!u.valid) return;
+  const int lane = threadIdx.x & 63;
+  const float p = moments_pivot<T>(a.x, (int64_t)u.channel * a.t.row_len);
+  float s1 = 0.f, s2 = 0.f;
+  walk_unit<T, VEC, NT, kStatUnroll>(
+      u, reinterpret_cast<const T*>(a.x) + u.base, a.t.row_len, lane,
+      [&](const vec_t<T, VEC>& xv, int64_t, int64_t) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) moments_take<T>(xv.v[k], p, s1, s2);
+      },
+      [&](T v, int64_t, int64_t) { moments_take<T>(v, p, s1, s2); });
   s1 = wave_sum(s1);
   s2 = wave_sum(s2);
   if (lane == 0) {
@@ -190,39 +188,24 @@ __global__ __launch_bounds__(kBlock) void absmoments_kernel(StatArgs a) {
   }
 }
 
-// dx = sgn(x) * (a[c] + b[c] * |x|): the backward of any statistic that is a function of the mean and the
-// variance of |x| (sgn(0) = 0, torch.abs's subgradient)
+// dx = abs_affine(x, a[c], b[c])
 template <typename T, int VEC>
 __global__ __launch_bounds__(kBlock) void abs_affine_bwd_kernel(Tiling t, const void* x, const float* ca,
                                                                 const float* cb, void* dx) {
   const Unit u = locate_unit(t);
   if (!u.valid) return;
   const int lane = threadIdx.x & 63;
-  const T* __restrict__ xp = reinterpret_cast<const T*>(x) + u.base;
   T* __restrict__ dp = reinterpret_cast<T*>(dx) + u.base;
   const float a = ca[u.channel], b = cb[u.channel];
-  auto f = [a, b](T v) -> T {
-    const float xf = to_f<T>(v);
-    const float m = a + b * fabsf(xf);
-    return from_f<T>(xf > 0.f ? m : (xf < 0.f ? -m : (xf == 0.f ? 0.f : xf)));  // NaN in, NaN out
-  };
-  ChunkWalker cur;
-  cur.init(u, VEC, lane);
-  const int64_t total = (int64_t)u.nrows * cur.cpr;
-  for (int64_t done = 0; done < total; done += kWave) {
-    if (cur.valid()) {
-      const int64_t off = cur.offset(u.row_stride, VEC);
-      const vec_t<T, VEC> xv = load_vec<T, VEC>(xp + off);
-      vec_t<T, VEC> dv;
+  walk_unit<T, VEC, false, 1>(
+      u, reinterpret_cast<const T*>(x) + u.base, t.row_len, lane,
+      [&](const vec_t<T, VEC>& xv, int64_t off, int64_t) {
+        vec_t<T, VEC> dv;
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) dv.v[k] = f(xv.v[k]);
-      store_vec<T, VEC>(dp + off, dv);
-    }
-    cur.next();
-  }
-  if (u.nrows == 1 && lane == 0) {
-    for (int64_t e = (int64_t)cur.cpr * VEC; e < u.len; ++e) dp[e] = f(xp[e]);
-  }
+        for (int k = 0; k < VEC; ++k) dv.v[k] = abs_affine<T>(xv.v[k], a, b);
+        store_vec<T, VEC>(dp + off, dv);
+      },
+      [&](T v, int64_t off, int64_t) { dp[off] = abs_affine<T>(v, a, b); });
 }
 
 // the same for channel-last layouts (short `inner`): the tensor is rows of L = channels * inner elements; a thread owns
@@ -247,74 +230,32 @@ __global__ __launch_bounds__(kBlock) void abs_affine_bwd_cols_kernel(const void*
     const vec_t<T, VEC> xv = load_vec<T, VEC>(xp + r * L);
     vec_t<T, VEC> dv;
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      const float xf = to_f<T>(xv.v[k]);
-      const float m = a[k] + b[k] * fabsf(xf);
-      dv.v[k] = from_f<T>(xf > 0.f ? m : (xf < 0.f ? -m : (xf == 0.f ? 0.f : xf)));  // NaN in, NaN out
-    }
+    for (int k = 0; k < VEC; ++k) dv.v[k] = abs_affine<T>(xv.v[k], a[k], b[k]);
     store_vec<T, VEC>(dp + r * L, dv);
   }
 }
 
-// ---- column-mapped abs-max (ColsPlan in bvq_common.h) -------------------------------------------------
-// a lane keeps one running maximum per column of its chunk and writes them as partial row
-// (row block * rpp + sub row) of the [partial rows][L] array the finishing kernel reduces
-struct ColsStatArgs {
-  ColsPlan p;
-  const void* x;
-  uint32_t* part;  // [prows][L]
-};
-
+// ---- column-mapped kernels (cols_locate / walk_cols, bvq_unit_walk.h) ------------------------------------------------
 template <typename T, bool NT, bool RELU>
 __global__ __launch_bounds__(kBlock) void absmax_cols_kernel(ColsStatArgs a) {
   constexpr int VEC = elem<T>::vec;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63;
-  const int64_t unit = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (unit >= a.p.units) return;
-  const int64_t rblk = unit / a.p.strips;
-  const int32_t strip = (int32_t)(unit - rblk * a.p.strips);
-  const int32_t sub = lane / a.p.lpr;                       // which of the rpp rows of a pass
-  const int32_t chunk = strip * kWave + (lane - sub * a.p.lpr);  // column chunk of this lane
-  const bool active = sub < a.p.rpp && chunk < a.p.cps;
-  const int64_t row0 = rblk * a.p.rb + sub;
-  const int64_t row_end = (rblk + 1) * a.p.rb < a.p.rows ? (rblk + 1) * a.p.rb : a.p.rows;
-  const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + (int64_t)chunk * VEC;
+  ColsPlace c;
+  if (!cols_locate(a.p, false, c) || !c.active) return;
   uint32_t m[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) m[k] = 0;
-  if (active) {
-    constexpr int kU = 4;
-    for (int64_t r = row0; r < row_end; r += (int64_t)kU * a.p.rpp) {
-      vec_t<T, VEC> xv[kU];
-      bool ok[kU];
+  const T* x = reinterpret_cast<const T*>(a.x);
+  walk_cols<T, VEC, NT, kColsStatUnroll>(a.p, c, x, [&](const vec_t<T, VEC>& xv, int64_t) {
 #pragma unroll
-      for (int j = 0; j < kU; ++j) {
-        const int64_t rr = r + (int64_t)j * a.p.rpp;
-        ok[j] = rr < row_end;
-        xv[j] = load_vec<T, VEC, NT>(xp + (ok[j] ? rr : row0) * a.p.L);
-      }
+    for (int k = 0; k < VEC; ++k) absmax_take(pre_key<T, pre_of(RELU)>(xv.v[k]), m[k]);
+  });
+  uint32_t* out = a.part + (c.rblk * a.p.rpp + c.sub) * a.p.L + (int64_t)c.chunk * VEC;
 #pragma unroll
-      for (int j = 0; j < kU; ++j) {
-        if (ok[j]) {
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) {
-            const uint32_t b = pre_abs_bits<T, RELU>(xv[j].v[k]);
-            m[k] = b > m[k] ? b : m[k];
-          }
-        }
-      }
-    }
-    uint32_t* out = a.part + (rblk * a.p.rpp + sub) * a.p.L + (int64_t)chunk * VEC;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) out[k] = m[k];
-  }
+  for (int k = 0; k < VEC; ++k) out[k] = m[k];
 }
 
-// ---- column-mapped moments (AbsAve / MeanSigmaStd on channel-last layouts) ---------------------------------------
-// the same decomposition: a lane keeps sum(|x| - p) and sum((|x| - p)^2) per column of its chunk (p: the pivot of the
-// column's channel, moments_pivot above) and writes them as its partial row of two [partial rows][L] float arrays;
-// the fold of the scale-gradient sums (double accumulation, rows in order) and channel_sum_kernel finish them.
+// moments: the fold of the scale-gradient sums (double accumulation, rows in order) and channel_sum_kernel finish the
+// two [partial rows][L] float arrays
 struct ColsMomentArgs {
   ColsPlan p;
   const void* x;
@@ -327,51 +268,23 @@ struct ColsMomentArgs {
 template <typename T, bool NT>
 __global__ __launch_bounds__(kBlock) void absmoments_cols_kernel(ColsMomentArgs a) {
   constexpr int VEC = elem<T>::vec;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63;
-  const int64_t unit = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (unit >= a.p.units) return;
-  const int64_t rblk = unit / a.p.strips;
-  const int32_t strip = (int32_t)(unit - rblk * a.p.strips);
-  const int32_t sub = lane / a.p.lpr;
-  const int32_t chunk = strip * kWave + (lane - sub * a.p.lpr);
-  const bool active = sub < a.p.rpp && chunk < a.p.cps;
-  if (!active) return;
-  const int64_t row0 = rblk * a.p.rb + sub;
-  const int64_t row_end = (rblk + 1) * a.p.rb < a.p.rows ? (rblk + 1) * a.p.rb : a.p.rows;
-  const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + (int64_t)chunk * VEC;
+  ColsPlace c;
+  if (!cols_locate(a.p, false, c) || !c.active) return;
   float pv[VEC], s1[VEC], s2[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) {
-    const int64_t col = (int64_t)chunk * VEC + k;
-    const int64_t c = col / a.inner;
-    pv[k] = moments_pivot<T>(a.x, c * a.inner);  // |x| of the channel's first element (row 0)
+    const int64_t col = (int64_t)c.chunk * VEC + k;
+    const int64_t ch = col / a.inner;
+    pv[k] = moments_pivot<T>(a.x, ch * a.inner);  // |x| of the channel's first element (row 0)
     s1[k] = s2[k] = 0.f;
-    if (rblk == 0 && sub == 0 && col == c * a.inner) a.pivot[c] = pv[k];
+    if (c.rblk == 0 && c.sub == 0 && col == ch * a.inner) a.pivot[ch] = pv[k];
   }
-  constexpr int kU = 4;
-  for (int64_t r = row0; r < row_end; r += (int64_t)kU * a.p.rpp) {
-    vec_t<T, VEC> xv[kU];
-    bool ok[kU];
+  const T* x = reinterpret_cast<const T*>(a.x);
+  walk_cols<T, VEC, NT, kColsStatUnroll>(a.p, c, x, [&](const vec_t<T, VEC>& xv, int64_t) {
 #pragma unroll
-    for (int j = 0; j < kU; ++j) {
-      const int64_t rr = r + (int64_t)j * a.p.rpp;
-      ok[j] = rr < row_end;
-      xv[j] = load_vec<T, VEC, NT>(xp + (ok[j] ? rr : row0) * a.p.L);
-    }
-#pragma unroll
-    for (int j = 0; j < kU; ++j) {
-      if (ok[j]) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-          const float d = fabsf(to_f<T>(xv[j].v[k])) - pv[k];
-          s1[k] += d;
-          s2[k] += d * d;
-        }
-      }
-    }
-  }
-  const int64_t base = (rblk * a.p.rpp + sub) * a.p.L + (int64_t)chunk * VEC;
+    for (int k = 0; k < VEC; ++k) moments_take<T>(xv.v[k], pv[k], s1[k], s2[k]);
+  });
+  const int64_t base = (c.rblk * a.p.rpp + c.sub) * a.p.L + (int64_t)c.chunk * VEC;
 #pragma unroll
   for (int k = 0; k < VEC; ++k) {
     a.part1[base + k] = s1[k];
@@ -379,7 +292,7 @@ __global__ __launch_bounds__(kBlock) void absmoments_cols_kernel(ColsMomentArgs 
   }
 }
 
-// min/max over the same mapping.  Partials are order-preserving unsigned keys so that the abs-max fold
+// min/max.  Partials are order-preserving unsigned keys so that the abs-max fold
 // (an unsigned max) serves both: columns [0, L) hold key(max), columns [L, 2L) hold key(-min); a NaN
 // anywhere in a column turns both of its keys into 0xffffffff (torch.max / torch.min propagate NaN).
 __device__ __forceinline__ uint32_t order_key(float f) {
@@ -394,18 +307,8 @@ __device__ __forceinline__ float order_key_value(uint32_t k) {
 template <typename T, bool NT, bool RELU>
 __global__ __launch_bounds__(kBlock) void minmax_cols_kernel(ColsStatArgs a) {
   constexpr int VEC = elem<T>::vec;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63;
-  const int64_t unit = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (unit >= a.p.units) return;
-  const int64_t rblk = unit / a.p.strips;
-  const int32_t strip = (int32_t)(unit - rblk * a.p.strips);
-  const int32_t sub = lane / a.p.lpr;
-  const int32_t chunk = strip * kWave + (lane - sub * a.p.lpr);
-  const bool active = sub < a.p.rpp && chunk < a.p.cps;
-  const int64_t row0 = rblk * a.p.rb + sub;
-  const int64_t row_end = (rblk + 1) * a.p.rb < a.p.rows ? (rblk + 1) * a.p.rb : a.p.rows;
-  const T* __restrict__ xp = reinterpret_cast<const T*>(a.x) + (int64_t)chunk * VEC;
+  ColsPlace c;
+  if (!cols_locate(a.p, false, c) || !c.active) return;
   float mx[VEC], mn[VEC];
   uint32_t nan = 0;  // bit k: column k saw a NaN
 #pragma unroll
@@ -413,37 +316,17 @@ __global__ __launch_bounds__(kBlock) void minmax_cols_kernel(ColsStatArgs a) {
     mx[k] = -__builtin_inff();
     mn[k] = __builtin_inff();
   }
-  if (active) {
-    constexpr int kU = 4;
-    for (int64_t r = row0; r < row_end; r += (int64_t)kU * a.p.rpp) {
-      vec_t<T, VEC> xv[kU];
-      bool ok[kU];
+  const T* x = reinterpret_cast<const T*>(a.x);
+  walk_cols<T, VEC, NT, kColsStatUnroll>(a.p, c, x, [&](const vec_t<T, VEC>& xv, int64_t) {
 #pragma unroll
-      for (int j = 0; j < kU; ++j) {
-        const int64_t rr = r + (int64_t)j * a.p.rpp;
-        ok[j] = rr < row_end;
-        xv[j] = load_vec<T, VEC, NT>(xp + (ok[j] ? rr : row0) * a.p.L);
-      }
+    for (int k = 0; k < VEC; ++k) minmax_take(pre_value<T, pre_of(RELU)>(xv.v[k]), mx[k], mn[k], nan, 1u << k);
+  });
+  uint32_t* out = a.part + (c.rblk * a.p.rpp + c.sub) * (2 * a.p.L) + (int64_t)c.chunk * VEC;
 #pragma unroll
-      for (int j = 0; j < kU; ++j) {
-        if (ok[j]) {
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) {
-            const float f = RELU ? relu_f(to_f<T>(xv[j].v[k])) : to_f<T>(xv[j].v[k]);
-            nan |= (f != f) ? (1u << k) : 0u;
-            mx[k] = fmaxf(mx[k], f);
-            mn[k] = fminf(mn[k], f);
-          }
-        }
-      }
-    }
-    uint32_t* out = a.part + (rblk * a.p.rpp + sub) * (2 * a.p.L) + (int64_t)chunk * VEC;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      const bool bad = (nan >> k) & 1u;
-      out[k] = bad ? 0xffffffffu : order_key(mx[k]);
-      out[a.p.L + k] = bad ? 0xffffffffu : order_key(-mn[k]);
-    }
+  for (int k = 0; k < VEC; ++k) {
+    const bool bad = (nan >> k) & 1u;
+    out[k] = bad ? 0xffffffffu : order_key(mx[k]);
+    out[a.p.L + k] = bad ? 0xffffffffu : order_key(-mn[k]);
   }
 }
 
@@ -680,13 +563,8 @@ __device__ __forceinline__ uint32_t onepass_unit_max(const StatArgs& a, const Un
     const uint32_t m16 = m2.x > m2.y ? m2.x : m2.y;
     m = elem<T>::id == BVQ_BF16 ? (m16 << 16) : m16;  // the abs_bits<> key space
   }
-  // ragged ends: the (< VEC) elements after the last full chunk of every row of the unit
-  const int32_t tail = (int32_t)(u.len - (int64_t)cur.cpr * VEC);
-  for (int32_t e = lane; e < u.nrows * tail; e += kWave) {
-    const int32_t tr = e / tail, k = e - tr * tail;
-    const uint32_t b = pre_abs_bits<T, RELU>(xp[(int64_t)tr * u.row_stride + (int64_t)cur.cpr * VEC + k]);
-    m = b > m ? b : m;
-  }
+  walk_unit_tail<VEC>(u, a.t.row_len, lane,
+                      [&](int64_t off, int64_t) { absmax_take(pre_abs_bits<T, RELU>(xp[off]), m); });
   return m;
 }
 
@@ -814,6 +692,8 @@ __global__ __launch_bounds__(kBlock) void tie_scan_kernel(Tiling t, const void* 
   T* __restrict__ dp = reinterpret_cast<T*>(dx) + u.base;
   const T sv = reinterpret_cast<const T*>(stat)[u.channel];
   const bool per_channel = t.channels > 1 || first_only;  // record the first position only
+  // (its own load-use-advance loop: on walk_unit, which advances the walker between the load and the body, the scan
+  //  streamed 0.7 - 1.9 % slower on the 16-bit full-size shapes, profiles/stat_walk.md; the ragged end is the walk's)
   ChunkWalker cur;
   cur.init(u, VEC, lane);
   const int64_t total = (int64_t)u.nrows * cur.cpr;
@@ -833,13 +713,10 @@ __global__ __launch_bounds__(kBlock) void tie_scan_kernel(Tiling t, const void* 
     }
     cur.next();
   }
-  // ragged end (single-row units only): lane 0 walks the (< VEC) leftover elements
-  if (u.nrows == 1 && lane == 0) {
-    for (int64_t e = (int64_t)cur.cpr * VEC; e < u.len; ++e) {
-      if (WRITE_ZERO) dp[e] = zero_like<T, MATCH>(xp[e]);
-      if (is_tie<T, MATCH>(xp[e], sv)) record_tie(info, per_channel, u.channel, (unsigned long long)(u.pos0 + e));
-    }
-  }
+  walk_unit_tail<VEC>(u, t.row_len, lane, [&](int64_t off, int64_t pos) {
+    if (WRITE_ZERO) dp[off] = zero_like<T, MATCH>(xp[off]);
+    if (is_tie<T, MATCH>(xp[off], sv)) record_tie(info, per_channel, u.channel, (unsigned long long)(u.pos0 + pos));
+  });
 }
 
 // the same scan on channel-last layouts (ColsPlan units: a lane owns the VEC columns of its chunk for a block of rows):
@@ -850,27 +727,20 @@ template <typename T, int MATCH, bool WRITE_ZERO>
 __global__ __launch_bounds__(kBlock) void tie_scan_cols_kernel(ColsPlan p, const void* x, const void* stat,
                                                                unsigned long long* info, void* dx, int64_t inner) {
   constexpr int VEC = elem<T>::vec;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63;
-  const int64_t unit = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (unit >= p.units) return;
-  const int64_t rblk = unit / p.strips;
-  const int32_t strip = (int32_t)(unit - rblk * p.strips);
-  const int32_t sub = lane / p.lpr;
-  const int32_t chunk = strip * kWave + (lane - sub * p.lpr);
-  if (!(sub < p.rpp && chunk < p.cps)) return;
-  const int64_t row0 = rblk * p.rb + sub;
-  const int64_t row_end = (rblk + 1) * p.rb < p.rows ? (rblk + 1) * p.rb : p.rows;
-  const T* __restrict__ xp = reinterpret_cast<const T*>(x) + (int64_t)chunk * VEC;
-  T* __restrict__ dp = reinterpret_cast<T*>(dx) + (int64_t)chunk * VEC;
+  ColsPlace c;
+  if (!cols_locate(p, false, c) || !c.active) return;
+  const T* __restrict__ xp = reinterpret_cast<const T*>(x) + (int64_t)c.chunk * VEC;
+  T* __restrict__ dp = reinterpret_cast<T*>(dx) + (int64_t)c.chunk * VEC;
   T sv[VEC];
   int64_t first[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) {
-    sv[k] = reinterpret_cast<const T*>(stat)[((int64_t)chunk * VEC + k) / inner];
+    sv[k] = reinterpret_cast<const T*>(stat)[((int64_t)c.chunk * VEC + k) / inner];
     first[k] = -1;
   }
-  for (int64_t r = row0; r < row_end; r += p.rpp) {
+  // (one load in flight, its own loop: through walk_cols the 16-bit instantiations take 4 to 15 more registers and
+  //  fall an occupancy step, profiles/stat_walk.md)
+  for (int64_t r = c.row0; r < c.row_end; r += p.rpp) {
     const vec_t<T, VEC> xv = load_vec<T, VEC>(xp + r * p.L);
     vec_t<T, VEC> zv;
 #pragma unroll
@@ -883,7 +753,7 @@ __global__ __launch_bounds__(kBlock) void tie_scan_cols_kernel(ColsPlan p, const
 #pragma unroll
   for (int k = 0; k < VEC; ++k) {
     if (first[k] >= 0) {
-      const int64_t col = (int64_t)chunk * VEC + k;
+      const int64_t col = (int64_t)c.chunk * VEC + k;
       record_tie(info, true, (int32_t)(col / inner), (unsigned long long)(first[k] * inner + col % inner));
     }
   }
@@ -1142,27 +1012,15 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
         absmax_onepass_kernel<T, elem<T>::vec, ntc, relu><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a, r, no_ep);
       });
     });
-  } else if (act) {
-    rc = with_dtype(dtype, [&](auto t) {
-      using T = typename decltype(t)::type;
-      return with_value<BVQ_PRE_SIGMOID, BVQ_PRE_TANH>(pre_op, [&](auto ac) {
-        return with_read_variant<elem<T>::vec>(vec, nt, [&](auto v, auto ntc) {
-          if (kind == BVQ_STAT_ABSMAX)
-            absmax_kernel<T, v, ntc, false, ac><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
-          else
-            minmax_kernel<T, v, ntc, false, ac><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
-        });
-      });
-    });
   } else {
     rc = with_dtype(dtype, [&](auto t) {
       using T = typename decltype(t)::type;
-      return with_bool(pre_op == BVQ_PRE_RELU, [&](auto relu) {
+      return with_value<BVQ_PRE_NONE, BVQ_PRE_RELU, BVQ_PRE_SIGMOID, BVQ_PRE_TANH>(pre_op, [&](auto pre) {
         return with_read_variant<elem<T>::vec>(vec, nt, [&](auto v, auto ntc) {
           if (kind == BVQ_STAT_ABSMAX)
-            absmax_kernel<T, v, ntc, relu><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+            absmax_kernel<T, v, ntc, pre><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
           else
-            minmax_kernel<T, v, ntc, relu><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
+            minmax_kernel<T, v, ntc, pre><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
         });
       });
     });

@@ -9,9 +9,12 @@
 // write of dx, with the gradients of the scales riding on the same reads as per-unit partial sums (fixed-order
 // double combine, bvq_sums.h).  Every intermediate is rounded to the compute dtype CT exactly where the
 // reference's op chain rounds it (bvq_quant_math.h), so y and dx are the reference's bits.
+// variant_kernel keeps its own main loop (two input tensors and a store per chunk) and takes the ragged ends of its
+// rows from walk_unit_tail (bvq_unit_walk.h).
 #include "bvq_quant_math.h"
 #include "bvq_sums.h"
 #include "bvq_ties.h"
+#include "bvq_unit_walk.h"
 
 namespace bvq {
 
@@ -206,16 +209,12 @@ __global__ __launch_bounds__(kBlock) void variant_kernel(VarArgs a) {
       }
     }
   }
-  // ragged ends: the (< VEC) elements after the last full chunk of every row of the unit
-  const int32_t tail = (int32_t)(u.len - (int64_t)cur.cpr * VEC);
-  for (int32_t e = lane; e < u.nrows * tail; e += kWave) {
-    const int32_t tr = e / tail, tk = e - tr * tail;
-    const int64_t i = (int64_t)tr * u.row_stride + (int64_t)cur.cpr * VEC + tk;
+  walk_unit_tail<VEC>(u, a.t.row_len, lane, [&](int64_t i, int64_t) {
     if constexpr (BWD)
       op[i] = from_f<OT>(var_bwd<CT>(kind, to_f<XT>(xp[i]), to_f<CT>(gp[i]), k, da, db));
     else
       op[i] = from_f<OT>(var_fwd<CT>(kind, to_f<XT>(xp[i]), k));
-  }
+  });
   if constexpr (BWD) {
     if (a.part_a) {
       da = wave_sum(da);
