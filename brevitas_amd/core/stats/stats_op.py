@@ -58,6 +58,13 @@ def _as_rows(x: Tensor, dim: Optional[int]):
     return xc, 1, xc.shape[0], xc.shape[1], out_shape
 
 
+def _first_flag(dim, ch) -> int:
+    """nat.MATCH_FIRST for a statistic reduced along a dim whose kept axis has ONE entry: torch.max(x, dim)[0] puts the
+    gradient on the first attaining element whatever the channel count, and the native layer tells the two rules
+    apart by channels > 1 alone (include/bvq.h, bvq_match_kind).  With more channels the flag changes nothing."""
+    return nat.MATCH_FIRST if dim is not None and ch == 1 else 0
+
+
 def _sharded_stat_bwd(match, flat, stat, gstat, outer, ch, inner, group, first_only):
     """backward of a max / min / k-th-value statistic of a batch-sharded tensor: the (summed) gradient goes
     where the single-device run on the concatenated batch puts it -- the lowest rank holding the first
@@ -91,10 +98,12 @@ class _AbsMaxFn(Function):
         x, stat = ctx.saved_tensors
         outer, ch, inner, dim = ctx.layout
         xc, _, _, _, _ = _as_rows(x, dim)
+        first = _first_flag(dim, ch)
         if ctx.group is not None:
-            dx = _sharded_stat_bwd(nat.MATCH_ABS, xc.reshape(-1), stat, gstat, outer, ch, inner, ctx.group, False)
+            dx = _sharded_stat_bwd(nat.MATCH_ABS, xc.reshape(-1), stat, gstat, outer, ch, inner, ctx.group,
+                                   bool(first))
         else:
-            dx = nat.stat_bwd(nat.MATCH_ABS, xc.reshape(-1), stat, gstat.reshape(-1), outer, ch, inner)
+            dx = nat.stat_bwd(nat.MATCH_ABS | first, xc.reshape(-1), stat, gstat.reshape(-1), outer, ch, inner)
         return _unrows(dx, x, dim), None, None
 
 
@@ -123,12 +132,14 @@ class _MinMaxFn(Function):
         outer, ch, inner, dim = ctx.layout
         xc, _, _, _, _ = _as_rows(x, dim)
         flat = xc.reshape(-1)
+        first = _first_flag(dim, ch)
         if ctx.group is not None:
-            dx = _sharded_stat_bwd(nat.MATCH_VALUE, flat, mx, gmax, outer, ch, inner, ctx.group, False)
-            dx = dx + _sharded_stat_bwd(nat.MATCH_VALUE, flat, mn, gmin, outer, ch, inner, ctx.group, False)
+            dx = _sharded_stat_bwd(nat.MATCH_VALUE, flat, mx, gmax, outer, ch, inner, ctx.group, bool(first))
+            dx = dx + _sharded_stat_bwd(nat.MATCH_VALUE, flat, mn, gmin, outer, ch, inner, ctx.group, bool(first))
         else:
-            dx = nat.stat_bwd(nat.MATCH_VALUE, flat, mx, gmax.reshape(-1), outer, ch, inner)
-            dx = nat.stat_bwd(nat.MATCH_VALUE, flat, mn, gmin.reshape(-1), outer, ch, inner, dx=dx)
+            kind = nat.MATCH_VALUE | first
+            dx = nat.stat_bwd(kind, flat, mx, gmax.reshape(-1), outer, ch, inner)
+            dx = nat.stat_bwd(kind, flat, mn, gmin.reshape(-1), outer, ch, inner, dx=dx)
         return _unrows(dx, x, dim), None, None
 
 

@@ -128,6 +128,42 @@ def test_sharded_named_act_quantizers_equal_unsharded(nccl_world1, name, dtype):
             assert bool(((a - b).abs() <= 2.0 ** -6 * (a.abs() + b.abs() + 1e-3)).all())
 
 
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32, torch.float16], ids=['bf16', 'f32', 'f16'])
+def test_sharded_one_channel_statistics_along_a_dim_deposit_on_the_first_tie(nccl_world1, dtype):
+    """AbsMax(1) and AbsMinMax(1) of a one-channel tensor whose extrema are tied, batch-sharded: the unsharded module's
+    result and torch's own graph, bit for bit -- a statistic reduced along a dim puts its gradient on the first tie
+    whatever the channel count"""
+    from brevitas_amd.core.stats import AbsMax, AbsMinMax
+    view = torch.int32 if dtype == torch.float32 else torch.int16
+    graphs = ((AbsMax, lambda t: torch.max(torch.abs(t), dim=1)[0]),
+              (AbsMinMax, lambda t: torch.abs(torch.max(t, dim=1)[0] - torch.min(t, dim=1)[0])))
+    g = torch.tensor([1.5], device=DEV, dtype=dtype)
+    for k in (40, 4099):
+        gen = torch.Generator().manual_seed(31)
+        x = torch.rand(1, k, generator=gen) * 4 - 2
+        x[0, [7, k - 7]] = -5.0     # the minimum twice, and the first tie of max |x|
+        x[0, [20, k - 5]] = 5.0     # the maximum twice
+        x = x.to(dtype).to(DEV)
+        for cls, graph in graphs:
+            outs = []
+            for group in (None, nccl_world1):
+                mod = cls(1)
+                if group is not None:
+                    mod.bvq_shard_group = group
+                xi = x.clone().requires_grad_(True)
+                out = mod(xi)
+                out.backward(g)
+                outs.append((out.detach(), xi.grad))
+            xi = x.clone().requires_grad_(True)
+            out = graph(xi)
+            out.backward(g)
+            for got_out, got_dx in outs:
+                assert torch.equal(got_out.view(view), out.detach().view(view)), (cls.__name__, k)
+                assert torch.equal(got_dx.view(view), xi.grad.view(view)), (cls.__name__, k)
+            if cls is AbsMax:
+                assert int((xi.grad != 0).sum()) == 1 and float(xi.grad[0, 7]) == -1.5
+
+
 @pytest.mark.parametrize('per_channel', [True, False], ids=['per_channel', 'per_tensor'])
 def test_shard_pack_unpack_kernels_for_three_ranks(per_channel):
     """bvq_shard_pack / bvq_shard_unpack with the messages of three simulated ranks (no collective needed) against

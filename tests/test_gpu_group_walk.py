@@ -216,16 +216,13 @@ def shifted_inputs(dn, g, groups):
 
 
 def shifted_steps(dn, g, groups, ste):
-    """-> (device inputs, (y, scale, zp, dw) of the one-kernel route, the same of the per-channel route).
-    A single group's per-channel reference is its row of the first two groups' step: the device route quantizes a
-    weight of ONE channel with whole-tensor statistics, whose tied extrema share their gradient evenly (torch.max()),
-    and the planted group 0 is all ties.  Measured on an MI355X, float32, g = 16, group 0 alone: the one-kernel route
-    and the CPU put -2409982720 on element 0 and leave the others, the one-channel device route puts -150623920
-    (a sixteenth) on each of the 16.  Channels are independent, so a row of the two-group step is the reference."""
+    """-> (device inputs, (y, scale, zp, dw) of the one-kernel route, the same of the per-channel route on the regrouped
+    weight).  A single group is a weight of ONE channel there, the planted group 0 all ties: its statistics are reduced
+    along a dim, so the per-channel route too puts the gradient of a tied extremum on the first tie (torch.max(x, dim)),
+    whatever the channel count (tests/test_gpu_tie_routes.py)."""
     dev = tuple(t.to(DEV) for t in shifted_inputs(dn, g, groups))
     wd, gd, gsd, gzd = dev
-    rw, rg, rgs, rgz = dev if groups > 1 else (t.to(DEV) for t in shifted_inputs(dn, g, 2))
-    ref = tuple(t[:groups] for t in GS.per_channel_step(rw, g, SHIFTED_BITS, ste, rg, rgs, rgz))
+    ref = GS.per_channel_step(wd, g, SHIFTED_BITS, ste, gd, gsd, gzd)
     return dev, GS.grouped_step(wd, g, SHIFTED_BITS, ste, gd, gsd, gzd), ref
 
 
