@@ -739,28 +739,26 @@ def absmax_scale(x, outer, channels, inner, min_val, int_threshold, scale_dtype,
     return stat, scale
 
 
-def kth_value(x, k, outer, channels, inner, abs_key):
-    """exact k-th smallest (1-indexed) of |x| or x per channel of x[outer, channels, inner] -> [channels]"""
+def _kth(entry, bracket, x, ks, outer, channels, inner, abs_key):
+    """ranks ks of |x| or x per channel of x[outer, channels, inner] -> [len(ks), channels]"""
     dev = require_device(x)
     assert x.is_contiguous() and x.numel() == outer * channels * inner
     dt = dtype_code(x.dtype)
-    out = torch.empty(channels, dtype=x.dtype, device=dev)
+    out = torch.empty(len(ks), channels, dtype=x.dtype, device=dev)
     ws, wsb = _workspace(dev, 'bvq_kth_workspace_bytes', dt, outer, channels, inner)
-    _launch(dev, 'bvq_kth_value', 'bvq_kth_value', int(abs_key), dt, ptr(x), outer, channels, inner, int(k), ptr(out),
-            ptr(ws), wsb)
+    _launch(dev, entry, bracket, int(abs_key), dt, ptr(x), outer, channels, inner, *map(int, ks), ptr(out), ptr(ws),
+            wsb)
     return out
+
+
+def kth_value(x, k, outer, channels, inner, abs_key):
+    """exact k-th smallest (1-indexed) of |x| or x per channel of x[outer, channels, inner] -> [channels]"""
+    return _kth('bvq_kth_value', 'bvq_kth_value', x, (k,), outer, channels, inner, abs_key)[0]
 
 
 def kth_pair(x, k_first, k_second, outer, channels, inner, abs_key):
     """two ranks of the same tensor, one histogram read where the per-tensor route applies -> [2, channels]"""
-    dev = require_device(x)
-    assert x.is_contiguous() and x.numel() == outer * channels * inner
-    dt = dtype_code(x.dtype)
-    out = torch.empty(2, channels, dtype=x.dtype, device=dev)
-    ws, wsb = _workspace(dev, 'bvq_kth_workspace_bytes', dt, outer, channels, inner)
-    _launch(dev, 'bvq_kth_pair', None, int(abs_key), dt, ptr(x), outer, channels, inner, int(k_first), int(k_second),
-            ptr(out), ptr(ws), wsb)
-    return out
+    return _kth('bvq_kth_pair', None, x, (k_first, k_second), outer, channels, inner, abs_key)
 
 
 KTH_EXPLICIT, KTH_HIGH, KTH_LOW = 0, 1, 2
@@ -860,81 +858,92 @@ def abs_affine_bwd(x, a, b, outer, channels, inner):
     return dx
 
 
-class KthSelectSteps:
+class _KthSteps:
+    """A select in steps on one shard: begin / hist(p) / pick(p) / finish over the entries `prefix`_begin .. _finish of
+    include/bvq.h.  A route gives the prefix, the leading arguments of its entries and where the counters of a pass
+    lie; `passes`, `per_channel` (elements per channel on THIS shard) and the workspace come from its constructor."""
+
+    def __init__(self, x, abs_key, rule, q, k, channels):
+        self.dev = require_device(x)
+        assert x.is_contiguous()
+        self.x, self.abs_key, self.channels = x, int(abs_key), channels
+        self.rule, self.q, self.k = int(rule), float(q), int(k)
+        self.dt = dtype_code(x.dtype)
+
+    def _step(self, step, *args):
+        _launch(self.dev, '%s_%s' % (self.prefix, step), None, *args, ptr(self.ws), self.wsb)
+
+    def begin(self):
+        self._step('begin', *self._begin_args())
+
+    def hist(self, p):
+        """histogram this shard's elements for pass p -> the counters to be summed over the shards (int32 view of the
+        unsigned counters: a two's-complement sum over the shards is their unsigned sum)"""
+        self._step('hist', self.abs_key, self.dt, ptr(self.x) if self.x.numel() else None, *self._shape, p)
+        off, words = self._counters(p)
+        return self.ws[off:off + 4 * words].view(torch.int32)
+
+    def pick(self, p):
+        self._step('pick', *self._pick_args(p))
+
+    def finish(self):
+        out = torch.empty(self.channels, dtype=self.x.dtype, device=self.dev)
+        self._step('finish', *self._lead, ptr(out))
+        return out
+
+
+class KthSelectSteps(_KthSteps):
     """bvq_kth_value in steps (include/bvq.h) for a batch-sharded tensor: between hist(p) and pick(p)
     the caller sums the returned counters over the shards (brevitas_amd.distributed.sharded_kth_value).
     rule / q: the rank is derived on the device from the global element count (KTH_HIGH / KTH_LOW), or
     KTH_EXPLICIT with k."""
+    prefix = 'bvq_kth'
 
     def __init__(self, x, outer, channels, inner, abs_key, rule, q, k=0):
-        self.dev = require_device(x)
-        assert x.is_contiguous() and x.numel() == outer * channels * inner
-        self.x, self.layout, self.abs_key = x, (outer, channels, inner), int(abs_key)
-        self.rule, self.q, self.k = int(rule), float(q), int(k)
-        self.per_channel = outer * inner if channels > 1 else x.numel()  # elements per channel on THIS shard
-        self.dt = dtype_code(x.dtype)
+        super().__init__(x, abs_key, rule, q, k, channels)
+        assert x.numel() == outer * channels * inner
+        self.layout = self._shape = (outer, channels, inner)
+        self.per_channel = outer * inner if channels > 1 else x.numel()
         self.passes = int(lib.bvq_kth_passes(self.dt))
+        self._lead = (self.abs_key, self.dt, channels)
         self.ws, self.wsb = _workspace(self.dev, 'bvq_kth_workspace_bytes', self.dt, outer, channels, inner)
 
-    def begin(self):
-        _launch(self.dev, 'bvq_kth_begin', None, self.dt, self.layout[1], self.rule, self.k, self.q, ptr(self.ws),
-                self.wsb)
+    def _begin_args(self):
+        return self.dt, self.channels, self.rule, self.k, self.q
 
-    def hist(self, p):
-        """histogram this shard's elements for pass p -> the [channels * 2048] counters (int32 view of the
-        unsigned counters: a two's-complement sum over the shards is their unsigned sum)"""
-        outer, channels, inner = self.layout
-        _launch(self.dev, 'bvq_kth_hist', None, self.abs_key, self.dt, ptr(self.x), outer, channels, inner, p,
-                ptr(self.ws), self.wsb)
-        off = int(lib.bvq_kth_hist_offset(self.dt, channels, p))
-        return self.ws[off:off + 4 * channels * _KBINS].view(torch.int32)
+    def _pick_args(self, p):
+        return self.dt, self.channels, p, self.rule, self.q
 
-    def pick(self, p):
-        _launch(self.dev, 'bvq_kth_pick', None, self.dt, self.layout[1], p, self.rule, self.q, ptr(self.ws), self.wsb)
-
-    def finish(self):
-        out = torch.empty(self.layout[1], dtype=self.x.dtype, device=self.dev)
-        _launch(self.dev, 'bvq_kth_finish', None, self.abs_key, self.dt, self.layout[1], ptr(out), ptr(self.ws),
-                self.wsb)
-        return out
+    def _counters(self, p):
+        return int(lib.bvq_kth_hist_offset(self.dt, self.channels, p)), self.channels * _KBINS
 
 
-class KthWideSteps:
+class KthWideSteps(_KthSteps):
     """the sharded selection of a whole-tensor statistic with the 15-bit first digit (include/bvq.h, bvq_kthw_*):
     same interface as KthSelectSteps -- begin / hist(p) / pick(p) / finish, `passes`, `per_channel` -- for
     brevitas_amd.distributed.sharded_kth_value; one pass for |x| of a 16-bit type, two otherwise"""
+    prefix = 'bvq_kthw'
 
     def __init__(self, x, abs_key, rule, q, k=0):
-        self.dev = require_device(x)
-        assert x.is_contiguous()
-        self.x, self.abs_key = x.reshape(-1), int(abs_key)
-        self.rule, self.q, self.k = int(rule), float(q), int(k)
+        super().__init__(x.reshape(-1), abs_key, rule, q, k, 1)
+        self._shape = (x.numel(),)
         self.per_channel = x.numel()
-        self.dt = dtype_code(x.dtype)
         self.passes = int(lib.bvq_kthw_plan(self.abs_key, self.dt, -1, None, None))
         if self.passes < 1:
             raise BvqError('bvq_kthw_plan: bad arguments')
+        self._lead = (self.abs_key, self.dt)
         self.ws, self.wsb = _workspace(self.dev, 'bvq_kth_workspace_bytes', self.dt, 1, 1, max(x.numel(), 1))
 
-    def begin(self):
-        _launch(self.dev, 'bvq_kthw_begin', None, self.abs_key, self.dt, ptr(self.ws), self.wsb)
+    def _begin_args(self):
+        return self._lead
 
-    def hist(self, p):
-        """-> the counters of pass p to be summed over the shards (int32 view of the unsigned counters)"""
-        _launch(self.dev, 'bvq_kthw_hist', None, self.abs_key, self.dt, ptr(self.x) if self.x.numel() else None,
-                self.x.numel(), p, ptr(self.ws), self.wsb)
+    def _pick_args(self, p):
+        return self.abs_key, self.dt, p, self.rule, self.k, self.q
+
+    def _counters(self, p):
         off, words = ctypes.c_int64(0), ctypes.c_int64(0)
         lib.bvq_kthw_plan(self.abs_key, self.dt, p, ctypes.byref(off), ctypes.byref(words))
-        return self.ws[off.value:off.value + 4 * words.value].view(torch.int32)
-
-    def pick(self, p):
-        _launch(self.dev, 'bvq_kthw_pick', None, self.abs_key, self.dt, p, self.rule, self.k, self.q, ptr(self.ws),
-                self.wsb)
-
-    def finish(self):
-        out = torch.empty(1, dtype=self.x.dtype, device=self.dev)
-        _launch(self.dev, 'bvq_kthw_finish', None, self.abs_key, self.dt, ptr(out), ptr(self.ws), self.wsb)
-        return out
+        return off.value, words.value
 
 
 def running_stats_update(running, stat, momentum, first_batch):

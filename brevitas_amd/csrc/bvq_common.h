@@ -304,6 +304,16 @@ int default_piece_chunks();
 int pick_vec(int max_vec, int64_t rows, int64_t row_len, const void* const* ptrs, const int* elsizes,
              int nptr, bool ragged_ok = false);
 
+// x[outer, channels, inner] as the rows a Tiling is made of: per tensor (channels == 1) ONE row holds everything.
+// vec: the full 16-byte width when every row of each buffer in ptrs (elements of dtype, null entries skipped, at most 2)
+// allows it (pick_vec), else 1 -- nothing in between.
+struct RowView {
+  int64_t outer, row_len;
+  int vec;
+};
+RowView row_view(int dtype, int64_t outer, int64_t channels, int64_t inner, const void* const* ptrs = nullptr,
+                 int nptr = 0, bool ragged_ok = false);
+
 Tiling make_tiling(int64_t outer, int32_t channels, int64_t row_len, int vec, int64_t unit_cap = 0,
                    bool few_rows = false);
 // fewer rows per unit until every unit's byte extent (first to last element, elsize bytes each) stays below

@@ -120,6 +120,17 @@ int pick_vec(int max_vec, int64_t rows, int64_t row_len, const void* const* ptrs
   return vec;
 }
 
+RowView row_view(int dtype, int64_t outer, int64_t channels, int64_t inner, const void* const* ptrs, int nptr,
+                 bool ragged_ok) {
+  RowView r;
+  r.outer = channels > 1 ? outer : 1;
+  r.row_len = channels > 1 ? inner : outer * inner;
+  const int full = 16 / dtype_size(dtype);
+  const int els[2] = {dtype_size(dtype), dtype_size(dtype)};
+  r.vec = pick_vec(full, r.outer * channels, r.row_len, ptrs, els, nptr < 2 ? nptr : 2, ragged_ok) == full ? full : 1;
+  return r;
+}
+
 // noinline, and bvq_nt_threshold_bytes below calls it through its address: the entry reports the definition that the
 // calls from the other objects bind to, not a constant folded into this object
 __attribute__((noinline)) int64_t nt_threshold_bytes() { return kNtBytes; }

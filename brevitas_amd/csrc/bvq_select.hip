@@ -113,8 +113,6 @@ __global__ __launch_bounds__(kBlock) void kth_hist_kernel(SelArgs a) {
   }
 }
 
-// one workgroup per channel: find the bin that holds the k-th (1-indexed) matching key, append its
-// digit to the prefix and make k relative to that bin
 // rank rule of the percentile statistics (B/core/stats/stats_op.py:56,84,114-116), evaluated on the
 // device from the number of elements the first histogram counted -- for a tensor sharded over several
 // devices that is the GLOBAL count once the histograms have been summed, with no host round trip.
@@ -128,38 +126,48 @@ __device__ __forceinline__ int64_t rank_from_rule(int rule, double q, int64_t n)
   return k;
 }
 
-__global__ __launch_bounds__(kBlock) void kth_pick_kernel(const uint32_t* __restrict__ hist,
-                                                          uint32_t* __restrict__ prefix,
-                                                          int64_t* __restrict__ krem, int32_t bits,
-                                                          int32_t rule, double q) {
-  __shared__ int64_t part[kBlock];
+// One workgroup of kB threads per channel c = blockIdx.x: the bin of the channel's histogram hist[c][0, nbins) that
+// holds the k-th (1-indexed) counted key; sel[c] <- sel[c] << bits | bin (first: sel[c] counts as 0, whatever it
+// holds), krem[c] <- rank inside that bin.  kNBins: the bin count where it is fixed (the digit passes), 0: nbins.
+// The rank k: from the rule and the histogram's total -- the GLOBAL element count once the shards' histograms have
+// been summed -- when a rule is given (a first pick), else k_arg when that is > 0, else krem[c] (a later pick, or a
+// first one whose rank bvq_kth_begin stored).
+template <int kB, int kNBins>
+__global__ __launch_bounds__(kB) void kth_pick_kernel(const uint32_t* __restrict__ hist, int32_t nbins, int32_t bits,
+                                                      int32_t first, int64_t k_arg, uint32_t* __restrict__ sel,
+                                                      int64_t* __restrict__ krem, int32_t rule, double q) {
+  __shared__ int64_t part[kB];
+  __shared__ int64_t before_me[kB];
+  __shared__ int64_t k_sh;
+  __shared__ uint32_t prev_sh;
   const int c = blockIdx.x;
-  const uint32_t* h = hist + (int64_t)c * kBins;
-  constexpr int kPer = kBins / kBlock;  // consecutive bins per thread
+  const int nb = kNBins ? kNBins : nbins;
+  const uint32_t* h = hist + (int64_t)c * nb;
+  static_assert(kNBins % kB == 0, "a fixed bin count is a whole number of bins per thread");
+  const int per = (nb + kB - 1) / kB;  // consecutive bins per thread (a constant trip count where kNBins is given)
+  const int lo = threadIdx.x * per, hi = kNBins || lo + per < nb ? lo + per : nb;
   int64_t mine = 0;
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) mine += h[threadIdx.x * kPer + j];
+  for (int b = lo; b < hi; ++b) mine += h[b];
   part[threadIdx.x] = mine;
   __syncthreads();
-  // exclusive prefix over the 256 partial sums (serial on one thread: 256 adds)
-  __shared__ int64_t before_me[kBlock];
-  __shared__ int64_t k_sh;
+  // exclusive prefix over the partial sums (serial on one thread: kB adds)
   if (threadIdx.x == 0) {
     int64_t run = 0;
-    for (int t = 0; t < kBlock; ++t) {
+    for (int t = 0; t < kB; ++t) {
       before_me[t] = run;
       run += part[t];
     }
-    k_sh = rule != BVQ_KTH_EXPLICIT ? rank_from_rule(rule, q, run) : krem[c];
+    k_sh = rule != BVQ_KTH_EXPLICIT ? rank_from_rule(rule, q, run) : (k_arg > 0 ? k_arg : krem[c]);
+    prev_sh = first ? 0u : sel[c];
   }
-  __syncthreads();
+  __syncthreads();  // krem / sel have been read before the owner overwrites them
   const int64_t k = k_sh;
   int64_t run = before_me[threadIdx.x];
   if (k > run && k <= run + mine) {  // exactly one thread owns the k-th element
-    for (int j = 0; j < kPer; ++j) {
-      const int64_t cnt = h[threadIdx.x * kPer + j];
+    for (int b = lo; b < hi; ++b) {
+      const int64_t cnt = h[b];
       if (k <= run + cnt) {
-        prefix[c] = (prefix[c] << bits) | (uint32_t)(threadIdx.x * kPer + j);
+        sel[c] = (prev_sh << bits) | (uint32_t)b;
         krem[c] = k - run;
         break;
       }
@@ -204,43 +212,21 @@ __global__ void kth_init_kernel(uint32_t* prefix, int64_t* krem, int64_t k, int3
 constexpr int kBins15 = 1 << 15;
 constexpr int kBlock15 = 1024;
 constexpr int kLowBitsMax = 17;
+constexpr int64_t kLowStride = (int64_t)1 << kLowBitsMax;  // counters of one rank's second read
 
 __global__ void kth_zero_kernel(uint32_t* p, int32_t n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 0;
 }
 
-// head: elements in front of x (x - head .. x) that precede the first 16-byte boundary of the caller's buffer
+// first read, on walk_flat (x, n, head: see there): each workgroup counts in LDS and flushes its non-empty bins
 template <typename T, bool ABS, bool NT>
 __global__ __launch_bounds__(kBlock15) void kth_hist15_kernel(const T* __restrict__ x, int64_t n, int32_t shift,
-                                                             uint32_t* __restrict__ hist, int32_t head = 0) {
-  constexpr int VEC = elem<T>::vec;
+                                                             uint32_t* __restrict__ hist, int32_t head) {
   __shared__ uint32_t h[kBins15];
   for (int b = threadIdx.x; b < kBins15; b += kBlock15) h[b] = 0;
   __syncthreads();
-  if (blockIdx.x == 0 && (int32_t)threadIdx.x < head)
-    atomicAdd(&h[sel_key<T, ABS>(x[(int64_t)threadIdx.x - head]) >> shift], 1u);
-  const int64_t chunks = n / VEC;
-  const int64_t stride = (int64_t)gridDim.x * kBlock15;
-  for (int64_t c = (int64_t)blockIdx.x * kBlock15 + threadIdx.x; c < chunks; c += stride * kSelUnroll) {
-    vec_t<T, VEC> xv[kSelUnroll];
-    bool ok[kSelUnroll];
-#pragma unroll
-    for (int j = 0; j < kSelUnroll; ++j) {
-      const int64_t cj = c + (int64_t)j * stride;
-      ok[j] = cj < chunks;
-      if (ok[j]) xv[j] = load_vec<T, VEC, NT>(x + cj * VEC);
-    }
-#pragma unroll
-    for (int j = 0; j < kSelUnroll; ++j) {
-      if (ok[j]) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) atomicAdd(&h[sel_key<T, ABS>(xv[j].v[k]) >> shift], 1u);
-      }
-    }
-  }
-  if (blockIdx.x == 0 && chunks * VEC + threadIdx.x < n)  // the < VEC elements after the last chunk
-    atomicAdd(&h[sel_key<T, ABS>(x[chunks * VEC + threadIdx.x]) >> shift], 1u);
+  walk_flat<T, kBlock15, NT, kSelUnroll>(x, n, head, [&](T v) { atomicAdd(&h[sel_key<T, ABS>(v) >> shift], 1u); });
   __syncthreads();
   for (int b = threadIdx.x; b < kBins15; b += kBlock15) {
     const uint32_t c = h[b];
@@ -269,101 +255,30 @@ __device__ __forceinline__ void low_count(uint32_t key, uint32_t want, int32_t s
 template <typename T, bool ABS, bool NT, bool SMALL>
 __global__ __launch_bounds__(kBlock) void kth_low_kernel(const T* __restrict__ x, int64_t n, int32_t shift,
                                                         const uint32_t* __restrict__ sel, uint32_t* __restrict__ gh,
-                                                        int32_t nk, int32_t head = 0) {
+                                                        int32_t nk, int32_t head) {
   // nk (1 or 2) ranks are served by the same read: rank i has its own chosen bin sel[i] and its own counters
-  constexpr int VEC = elem<T>::vec;
   __shared__ uint32_t lh[SMALL ? 2 * kBins : 1];
   if constexpr (SMALL) {
     for (int b = threadIdx.x; b < 2 * kBins; b += kBlock) lh[b] = 0;
     __syncthreads();
   }
   uint32_t* ghist = SMALL ? lh : gh;
-  const int64_t hstride = SMALL ? kBins : ((int64_t)1 << kLowBitsMax);
+  const int64_t hstride = SMALL ? kBins : kLowStride;
   const uint32_t want = sel[0], want2 = nk > 1 ? sel[1] : 0u;
   const uint32_t lowmask = (1u << shift) - 1u;
-  const int64_t chunks = n / VEC;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x; c < chunks; c += stride * kSelUnroll) {
-    vec_t<T, VEC> xv[kSelUnroll];
-    bool ok[kSelUnroll];
-#pragma unroll
-    for (int j = 0; j < kSelUnroll; ++j) {
-      const int64_t cj = c + (int64_t)j * stride;
-      ok[j] = cj < chunks;
-      if (ok[j]) xv[j] = load_vec<T, VEC, NT>(x + cj * VEC);
-    }
-#pragma unroll
-    for (int j = 0; j < kSelUnroll; ++j) {
-      if (ok[j]) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-          const uint32_t key = sel_key<T, ABS>(xv[j].v[k]);
-          low_count(key, want, shift, lowmask, ghist);
-          if (nk > 1) low_count(key, want2, shift, lowmask, ghist + hstride);
-        }
-      }
-    }
-  }
-  if (blockIdx.x == 0 && chunks * VEC + threadIdx.x < n) {
-    const uint32_t key = sel_key<T, ABS>(x[chunks * VEC + threadIdx.x]);
+  // (head, chunks and tail reach low_count from separate branches of the walk: its ballots see whole waves)
+  walk_flat<T, kBlock, NT, kSelUnroll>(x, n, head, [&](T v) {
+    const uint32_t key = sel_key<T, ABS>(v);
     low_count(key, want, shift, lowmask, ghist);
     if (nk > 1) low_count(key, want2, shift, lowmask, ghist + hstride);
-  }
-  if (blockIdx.x == 0 && (int32_t)threadIdx.x < head) {  // (a separate branch: low_count's ballots see whole waves)
-    const uint32_t key = sel_key<T, ABS>(x[(int64_t)threadIdx.x - head]);
-    low_count(key, want, shift, lowmask, ghist);
-    if (nk > 1) low_count(key, want2, shift, lowmask, ghist + hstride);
-  }
+  });
   if constexpr (SMALL) {
     __syncthreads();
     for (int i = 0; i < nk; ++i)
       for (int b = threadIdx.x; b < (1 << shift); b += kBlock) {
         const uint32_t c = lh[i * kBins + b];
-        if (c) atomicAdd(&gh[(int64_t)i * ((int64_t)1 << kLowBitsMax) + b], c);
+        if (c) atomicAdd(&gh[i * kLowStride + b], c);
       }
-  }
-}
-
-// one workgroup: the bin of hist[0, nbins) that holds the k-th (1-indexed) element; sel[0] <- sel[0] << bits | bin
-// (sel[0] starts at 0), krem[0] <- rank inside that bin.  first: k comes as an argument, else from krem[0].
-// rule / q (first pick only): the rank from the total count of the histogram -- the GLOBAL element count once the
-// shards' histograms have been summed -- instead of k_arg
-__global__ __launch_bounds__(kBlock15) void kth_pick_wide_kernel(const uint32_t* __restrict__ hist, int32_t nbins,
-                                                                int32_t bits, int32_t first, int64_t k_arg,
-                                                                uint32_t* __restrict__ sel, int64_t* __restrict__ krem,
-                                                                int32_t rule = BVQ_KTH_EXPLICIT, double q = 0.0) {
-  __shared__ int64_t part[kBlock15];
-  __shared__ int64_t before_me[kBlock15];
-  __shared__ int64_t total;
-  const int per = (nbins + kBlock15 - 1) / kBlock15;
-  const int lo = threadIdx.x * per, hi = lo + per < nbins ? lo + per : nbins;
-  int64_t mine = 0;
-  for (int b = lo; b < hi; ++b) mine += hist[b];
-  part[threadIdx.x] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t run = 0;
-    for (int t = 0; t < kBlock15; ++t) {
-      before_me[t] = run;
-      run += part[t];
-    }
-    total = run;
-  }
-  __syncthreads();
-  const int64_t k = first ? (rule != BVQ_KTH_EXPLICIT ? rank_from_rule(rule, q, total) : k_arg) : krem[0];
-  const uint32_t prev = first ? 0u : sel[0];
-  __syncthreads();  // everyone has read krem / sel before the owner overwrites them
-  int64_t run = before_me[threadIdx.x];
-  if (k > run && k <= run + mine) {
-    for (int b = lo; b < hi; ++b) {
-      const int64_t cnt = hist[b];
-      if (k <= run + cnt) {
-        sel[0] = (prev << bits) | (uint32_t)b;
-        krem[0] = k - run;
-        break;
-      }
-      run += cnt;
-    }
   }
 }
 
@@ -439,14 +354,34 @@ static int64_t sel_steps_bytes(int dtype, int64_t channels) {
          channels * (int64_t)(sizeof(uint32_t) + sizeof(int64_t)) + 256;
 }
 
-// (+ the per-tensor route of bvq_kth_value behind the stepwise layout: 32768 + 2^17 counters, key, rank)
-static int64_t sel_wide_bytes() {
-  return ((int64_t)kBins15 + 2 * ((int64_t)1 << kLowBitsMax)) * (int64_t)sizeof(uint32_t) + 64;
+// The per-tensor ("wide") route's state, behind the stepwise layout of a one-channel workspace.  This function alone
+// knows where its parts lie: the one-shot route, the bvq_kthw_* steps, bvq_kthw_plan's offsets and the workspace size
+// all take them from here (workspace = nullptr: the pointers are offsets from the workspace base).
+struct WideWs {
+  uint32_t* hist;  // [32768]
+  uint32_t* low;   // [2][kLowStride]
+  int64_t* krem;   // [2]
+  uint32_t* sel;   // [2]
+  int64_t bytes;   // of a workspace that holds all of it
+};
+static WideWs wide_ws(int dtype, const void* workspace) {
+  const uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
+  uintptr_t p = base + (uintptr_t)((sel_steps_bytes(dtype, 1) + 255) / 256 * 256);
+  WideWs w;
+  w.hist = reinterpret_cast<uint32_t*>(p);
+  p += kBins15 * sizeof(uint32_t);
+  w.low = reinterpret_cast<uint32_t*>(p);
+  p += 2 * kLowStride * sizeof(uint32_t);
+  w.krem = reinterpret_cast<int64_t*>(p);
+  p += 2 * sizeof(int64_t);
+  w.sel = reinterpret_cast<uint32_t*>(p);
+  p += 2 * sizeof(uint32_t);
+  w.bytes = (int64_t)((p - base + 63) / 64 * 64);
+  return w;
 }
 
 static int64_t sel_workspace_bytes(int dtype, int64_t channels) {
-  const int64_t base = (sel_steps_bytes(dtype, channels) + 255) / 256 * 256;
-  return base + (channels == 1 ? sel_wide_bytes() : 0);
+  return channels == 1 ? wide_ws(dtype, nullptr).bytes : (sel_steps_bytes(dtype, channels) + 255) / 256 * 256;
 }
 
 static SelWorkspace sel_workspace(int dtype, int64_t channels, void* workspace) {
@@ -469,9 +404,10 @@ static void pass_bits(int dtype, int pass, int& bits, int& shift) {
   }
 }
 
+// the workspace of every step, per channel or wide (channels = 1)
 static int sel_check(const char* who, int dtype, int64_t channels, const void* workspace,
                      int64_t workspace_bytes) {
-  if (dtype < BVQ_F32 || dtype > BVQ_F16 || channels < 1) {
+  if (bad_dtype(dtype) || channels < 1) {
     set_error("%s: bad argument", who);
     return BVQ_ERR_INVALID;
   }
@@ -483,12 +419,32 @@ static int sel_check(const char* who, int dtype, int64_t channels, const void* w
   return BVQ_OK;
 }
 
+static bool bad_rule(int rule) { return rule < BVQ_KTH_EXPLICIT || rule > BVQ_KTH_LOW; }
+// a first pick's rank: an explicit k >= 1, or a percentile for the rule
+static bool bad_rank(int rule, int64_t k, double q) {
+  return bad_rule(rule) || (rule == BVQ_KTH_EXPLICIT ? k < 1 : !(q >= 0.0 && q <= 100.0));
+}
+
+// (a kernel, not hipMemsetAsync: every step of the select is then an ordinary launch under graph capture)
+static void launch_zero(uint32_t* p, int64_t words, hipStream_t st) {
+  kth_zero_kernel<<<dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st>>>(p, (int32_t)words);
+}
+
+static int launch_store(int abs_key, int dtype, const uint32_t* keys, void* out, int64_t n, unsigned grid, unsigned block,
+                        hipStream_t st) {
+  return with_dtype(dtype, [&](auto t) {
+    return with_bool(abs_key, [&](auto abs) {
+      kth_store_kernel<typename decltype(t)::type, abs><<<grid, block, 0, st>>>(keys, out, (int32_t)n);
+    });
+  });
+}
+
 // (the transposed copy of a channel-last tensor sits behind the select's own state; sized whether or not x will turn out
 //  16-byte aligned)
 static int64_t sel_scratch_offset(int dtype, int64_t channels) { return (sel_workspace_bytes(dtype, channels) + 255) / 256 * 256; }
 
 extern "C" int64_t bvq_kth_workspace_bytes(int dtype, int64_t outer, int64_t channels, int64_t inner) {
-  if (dtype < BVQ_F32 || dtype > BVQ_F16 || outer < 0 || channels < 1 || inner < 0) {
+  if (bad_dtype(dtype) || outer < 0 || channels < 1 || inner < 0) {
     set_error("bvq_kth_workspace_bytes: bad argument");
     return -1;
   }
@@ -497,12 +453,10 @@ extern "C" int64_t bvq_kth_workspace_bytes(int dtype, int64_t outer, int64_t cha
   return sel_workspace_bytes(dtype, channels);
 }
 
-extern "C" int bvq_kth_passes(int dtype) {
-  return (dtype < BVQ_F32 || dtype > BVQ_F16) ? -1 : passes_for(dtype);
-}
+extern "C" int bvq_kth_passes(int dtype) { return bad_dtype(dtype) ? -1 : passes_for(dtype); }
 
 extern "C" int64_t bvq_kth_hist_offset(int dtype, int64_t channels, int pass) {
-  if (dtype < BVQ_F32 || dtype > BVQ_F16 || channels < 1 || pass < 0 || pass >= passes_for(dtype)) return -1;
+  if (bad_dtype(dtype) || channels < 1 || pass < 0 || pass >= passes_for(dtype)) return -1;
   return (int64_t)pass * channels * kBins * (int64_t)sizeof(uint32_t);
 }
 
@@ -510,15 +464,13 @@ extern "C" int bvq_kth_begin(int dtype, int64_t channels, int rule, int64_t k, d
                              int64_t workspace_bytes, bvq_stream_t stream) {
   int rc = sel_check("bvq_kth_begin", dtype, channels, workspace, workspace_bytes);
   if (rc) return rc;
-  if (rule < BVQ_KTH_EXPLICIT || rule > BVQ_KTH_LOW || (rule == BVQ_KTH_EXPLICIT && k < 1) ||
-      (rule != BVQ_KTH_EXPLICIT && !(q >= 0.0 && q <= 100.0))) {
+  if (bad_rank(rule, k, q)) {
     set_error("bvq_kth_begin: bad rank (rule %d, k %lld, q %g)", rule, (long long)k, q);
     return BVQ_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
   const SelWorkspace w = sel_workspace(dtype, channels, workspace);
-  // (a kernel, not hipMemsetAsync: every step of the select is then an ordinary launch under graph capture)
-  kth_zero_kernel<<<dim3((unsigned)((w.hist_words + 255) / 256)), dim3(256), 0, st>>>(w.hist, (int32_t)w.hist_words);
+  launch_zero(w.hist, w.hist_words, st);
   kth_init_kernel<<<dim3((unsigned)((channels + 255) / 256)), dim3(256), 0, st>>>(
       w.prefix, w.krem, rule == BVQ_KTH_EXPLICIT ? k : 0, (int32_t)channels);
   return check_launch("bvq_kth_begin");
@@ -575,16 +527,12 @@ extern "C" int bvq_kth_hist(int abs_key, int dtype, const void* x, int64_t outer
     inner = outer * inner;
     outer = 1;
   }
-  const int64_t t_outer = channels > 1 ? outer : 1;
-  const int64_t row_len = channels > 1 ? inner : outer * inner;
-  const int full = 16 / dtype_size(dtype);
   const void* ptrs[1] = {x};
-  const int els[1] = {dtype_size(dtype)};
-  int vec = pick_vec(full, t_outer * channels, row_len, ptrs, els, 1);
-  vec = vec == full ? full : 1;
+  const RowView r = row_view(dtype, outer, channels, inner, ptrs, 1);
+  const int vec = r.vec;
   SelArgs a;
   // every wave flushes a 2048-bin histogram: keep the waves few and their pieces long
-  a.t = make_tiling(t_outer, (int32_t)channels, row_len, vec, kSelUnitCap);
+  a.t = make_tiling(r.outer, (int32_t)channels, r.row_len, vec, kSelUnitCap);
   a.x = x;
   a.prefix = w.prefix;
   a.hist = w.hist + (int64_t)pass * channels * kBins;
@@ -609,16 +557,18 @@ extern "C" int bvq_kth_pick(int dtype, int64_t channels, int pass, int rule, dou
                             int64_t workspace_bytes, bvq_stream_t stream) {
   int rc = sel_check("bvq_kth_pick", dtype, channels, workspace, workspace_bytes);
   if (rc) return rc;
-  if (pass < 0 || pass >= passes_for(dtype) || rule < BVQ_KTH_EXPLICIT || rule > BVQ_KTH_LOW) {
+  if (pass < 0 || pass >= passes_for(dtype) || bad_rule(rule)) {
     set_error("bvq_kth_pick: bad argument");
     return BVQ_ERR_INVALID;
   }
   const SelWorkspace w = sel_workspace(dtype, channels, workspace);
   int bits, shift;
   pass_bits(dtype, pass, bits, shift);
-  // the rank rule applies once, to the count of the first pass; later passes continue from krem
-  kth_pick_kernel<<<dim3((unsigned)channels), dim3(kBlock), 0, (hipStream_t)stream>>>(
-      w.hist + (int64_t)pass * channels * kBins, w.prefix, w.krem, bits, pass == 0 ? rule : BVQ_KTH_EXPLICIT, q);
+  // the rank rule applies once, to the count of the first pass; otherwise the rank is the one bvq_kth_begin stored or
+  // the last pick left
+  kth_pick_kernel<kBlock, kBins><<<dim3((unsigned)channels), dim3(kBlock), 0, (hipStream_t)stream>>>(
+      w.hist + (int64_t)pass * channels * kBins, kBins, bits, pass == 0, 0, w.prefix, w.krem,
+      pass == 0 ? rule : BVQ_KTH_EXPLICIT, q);
   return check_launch("bvq_kth_pick");
 }
 
@@ -630,19 +580,15 @@ extern "C" int bvq_kth_finish(int abs_key, int dtype, int64_t channels, void* ou
     set_error("bvq_kth_finish: null pointer");
     return BVQ_ERR_INVALID;
   }
-  hipStream_t st = (hipStream_t)stream;
   const SelWorkspace w = sel_workspace(dtype, channels, workspace);
-  const unsigned nb = (unsigned)((channels + 255) / 256);
-  rc = with_dtype(dtype, [&](auto t) {
-    return with_bool(abs_key, [&](auto abs) {
-      kth_store_kernel<typename decltype(t)::type, abs><<<nb, 256, 0, st>>>(w.prefix, out, (int32_t)channels);
-    });
-  });
+  rc = launch_store(abs_key, dtype, w.prefix, out, channels, (unsigned)((channels + 255) / 256), 256, (hipStream_t)stream);
   return rc ? rc : check_launch("bvq_kth_finish");
 }
 
-// per-tensor route (see kth_hist15_kernel): nk = 1 or 2 ranks from ONE histogram read (+ one read for the low bits
-// of both); out[nk]
+// ---- the per-tensor route (see kth_hist15_kernel), as steps -----------------------------------------------------
+// zero, histogram of pass p, pick of pass p for rank i, store: bvq_kth_value / bvq_kth_pair run them in order for nk = 1
+// or 2 ranks (ONE histogram read, + one read for the low bits of both); each bvq_kthw_* entry (include/bvq.h: the same
+// route for a batch-sharded tensor) is one of them.  The steps launch; their callers check the launch and choose the grid.
 #ifndef BVQ_KTH_WIDE
 #define BVQ_KTH_WIDE 1  // 0: the digit passes for every layout
 #endif
@@ -651,105 +597,89 @@ static bool wide_select_applies(int64_t channels, int64_t n, const void* x) {
   return kKthWide && channels == 1 && n >= ((int64_t)1 << 22) && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
 }
 
-static int wide_select(int abs_key, int dtype, const void* x, int64_t n, const int64_t* ks, int nk, void* out,
-                       void* workspace, int64_t workspace_bytes, bvq_stream_t stream) {
-  if (workspace_bytes < sel_workspace_bytes(dtype, 1)) {
-    set_error("bvq_kth_value: workspace too small");
-    return BVQ_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  char* base = reinterpret_cast<char*>(workspace) + (sel_steps_bytes(dtype, 1) + 255) / 256 * 256;
-  uint32_t* hist = reinterpret_cast<uint32_t*>(base);  // [32768]
-  uint32_t* low = hist + kBins15;                      // [2][1 << 17]
-  const int64_t lstride = (int64_t)1 << kLowBitsMax;
-  int64_t* krem = reinterpret_cast<int64_t*>(low + 2 * lstride);  // [2]
-  uint32_t* sel = reinterpret_cast<uint32_t*>(krem + 2);          // [2]
-  const int key_bits = (dtype == BVQ_F32 ? 32 : 16) - (abs_key ? 1 : 0);
-  const int shift = key_bits - 15;  // 0, 1, 16 or 17 low bits left for the second read
-  const int32_t words = kBins15 + (shift ? (int32_t)(2 * lstride) : 0);
-  kth_zero_kernel<<<dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st>>>(hist, words);
-  const bool nt = n * (int64_t)dtype_size(dtype) >= nt_threshold_bytes();
-  // one workgroup per CU is all the LDS allows; 256 of them cover the chip
-  const int rc = with_dtype(dtype, [&](auto t) {
+// low bits left for the second read: 0 (|x| of a 16-bit type: one pass), 1, 16 or 17
+static int wide_shift(int abs_key, int dtype) { return (dtype == BVQ_F32 ? 32 : 16) - (abs_key ? 1 : 0) - 15; }
+static int wide_passes(int abs_key, int dtype) { return wide_shift(abs_key, dtype) ? 2 : 1; }
+// the second read's SMALL form (kth_low_kernel)
+static bool wide_low_small(int shift) { return shift <= kDigitBits; }
+static int wide_block(int pass) { return pass == 0 ? kBlock15 : kBlock; }
+// The grid of pass p that covers the chip.  First read: one workgroup per CU is all the LDS allows, 256 of them.
+static unsigned wide_full_grid(int pass, int shift) { return pass == 0 ? 256 : wide_low_small(shift) ? 1024 : 2048; }
+
+// x: 16-byte aligned, n elements behind it and `head` in front of it
+static int wide_hist(int abs_key, int dtype, const void* x, int64_t n, int32_t head, int pass, int nk, unsigned grid,
+                     const WideWs& w, hipStream_t st) {
+  const int shift = wide_shift(abs_key, dtype);
+  const bool nt = (n + head) * (int64_t)dtype_size(dtype) >= nt_threshold_bytes();
+  return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
     return with_bool(abs_key, [&](auto abs) {
       const T* xp = reinterpret_cast<const T*>(x);
-      with_bool(nt, [&](auto ntc) { kth_hist15_kernel<T, abs, ntc><<<256, kBlock15, 0, st>>>(xp, n, shift, hist); });
-      for (int i = 0; i < nk; ++i)
-        kth_pick_wide_kernel<<<1, kBlock15, 0, st>>>(hist, kBins15, 15, 1, ks[i], sel + i, krem + i);
-      if (shift) {
-        if (shift <= kDigitBits)
-          kth_low_kernel<T, abs, false, true><<<1024, kBlock, 0, st>>>(xp, n, shift, sel, low, nk);
-        else
-          with_bool(nt, [&](auto ntc) {
-            kth_low_kernel<T, abs, ntc, false><<<2048, kBlock, 0, st>>>(xp, n, shift, sel, low, nk);
-          });
-        for (int i = 0; i < nk; ++i)
-          kth_pick_wide_kernel<<<1, kBlock15, 0, st>>>(low + i * lstride, 1 << shift, shift, 0, 0, sel + i, krem + i);
-      }
-      kth_store_kernel<T, abs><<<1, 64, 0, st>>>(sel, out, nk);
+      if (pass == 0)
+        with_bool(nt, [&](auto ntc) { kth_hist15_kernel<T, abs, ntc><<<grid, kBlock15, 0, st>>>(xp, n, shift, w.hist, head); });
+      else if (wide_low_small(shift))
+        kth_low_kernel<T, abs, false, true><<<grid, kBlock, 0, st>>>(xp, n, shift, w.sel, w.low, nk, head);
+      else
+        with_bool(nt, [&](auto ntc) {
+          kth_low_kernel<T, abs, ntc, false><<<grid, kBlock, 0, st>>>(xp, n, shift, w.sel, w.low, nk, head);
+        });
     });
   });
+}
+
+// rank i of pass p; rule / k / q: the first pick's rank (bad_rank), ignored by the second
+static void wide_pick(int abs_key, int dtype, int pass, int i, int rule, int64_t k, double q, const WideWs& w,
+                      hipStream_t st) {
+  const int shift = wide_shift(abs_key, dtype);
+  if (pass == 0)
+    kth_pick_kernel<kBlock15, 0><<<1, kBlock15, 0, st>>>(w.hist, kBins15, 15, 1, k, w.sel + i, w.krem + i, rule, q);
+  else
+    kth_pick_kernel<kBlock15, 0><<<1, kBlock15, 0, st>>>(w.low + i * kLowStride, 1 << shift, shift, 0, 0, w.sel + i,
+                                                         w.krem + i, BVQ_KTH_EXPLICIT, 0.0);
+}
+
+static int wide_store(int abs_key, int dtype, void* out, int nk, const WideWs& w, hipStream_t st) {
+  return launch_store(abs_key, dtype, w.sel, out, nk, 1, 64, st);
+}
+
+// the steps in order, for a tensor in one piece; out[nk]
+static int wide_select(int abs_key, int dtype, const void* x, int64_t n, const int64_t* ks, int nk, void* out,
+                       void* workspace, hipStream_t st) {
+  const WideWs w = wide_ws(dtype, workspace);
+  const int shift = wide_shift(abs_key, dtype);
+  launch_zero(w.hist, kBins15 + (shift ? 2 * kLowStride : 0), st);
+  int rc = BVQ_OK;
+  for (int p = 0; !rc && p < wide_passes(abs_key, dtype); ++p) {
+    rc = wide_hist(abs_key, dtype, x, n, 0, p, nk, wide_full_grid(p, shift), w, st);
+    for (int i = 0; !rc && i < nk; ++i) wide_pick(abs_key, dtype, p, i, BVQ_KTH_EXPLICIT, ks[i], 0.0, w, st);
+  }
+  if (!rc) rc = wide_store(abs_key, dtype, out, nk, w, st);
   return rc ? rc : check_launch("bvq_kth_value/wide");
 }
 
-// ---- the per-tensor route in steps, for a batch-sharded tensor (include/bvq.h, bvq_kthw_*) --------------------
-struct WideWs {
-  uint32_t* hist;  // [32768]
-  uint32_t* low;   // [2][1 << 17]
-  int64_t* krem;   // [2]
-  uint32_t* sel;   // [2]
-};
-static WideWs wide_ws(int dtype, void* workspace) {
-  WideWs w;
-  char* base = reinterpret_cast<char*>(workspace) + (sel_steps_bytes(dtype, 1) + 255) / 256 * 256;
-  w.hist = reinterpret_cast<uint32_t*>(base);
-  w.low = w.hist + kBins15;
-  w.krem = reinterpret_cast<int64_t*>(w.low + 2 * ((int64_t)1 << kLowBitsMax));
-  w.sel = reinterpret_cast<uint32_t*>(w.krem + 2);
-  return w;
-}
-static int wide_shift(int abs_key, int dtype) { return (dtype == BVQ_F32 ? 32 : 16) - (abs_key ? 1 : 0) - 15; }
-
-static int kthw_check(const char* who, int dtype, const void* workspace, int64_t workspace_bytes) {
-  if (dtype < BVQ_F32 || dtype > BVQ_F16) {
-    set_error("%s: bad dtype", who);
-    return BVQ_ERR_INVALID;
-  }
-  if (!workspace || workspace_bytes < sel_workspace_bytes(dtype, 1)) {
-    set_error("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)sel_workspace_bytes(dtype, 1));
-    return BVQ_ERR_WORKSPACE;
-  }
-  return BVQ_OK;
-}
-
 extern "C" int bvq_kthw_plan(int abs_key, int dtype, int pass, int64_t* hist_offset_bytes, int64_t* hist_words) {
-  if (dtype < BVQ_F32 || dtype > BVQ_F16) return -1;
-  const int shift = wide_shift(abs_key, dtype);
-  const int passes = shift ? 2 : 1;
+  if (bad_dtype(dtype)) return -1;
+  const int passes = wide_passes(abs_key, dtype);
   if (pass < 0 || pass >= passes) return passes;  // (a query for the pass count alone)
-  const int64_t base = (sel_steps_bytes(dtype, 1) + 255) / 256 * 256;
-  if (hist_offset_bytes) *hist_offset_bytes = base + (pass ? (int64_t)kBins15 * (int64_t)sizeof(uint32_t) : 0);
-  if (hist_words) *hist_words = pass ? ((int64_t)1 << shift) : kBins15;
+  const WideWs w = wide_ws(dtype, nullptr);       // (offsets from the workspace base)
+  if (hist_offset_bytes) *hist_offset_bytes = (int64_t)reinterpret_cast<uintptr_t>(pass ? w.low : w.hist);
+  if (hist_words) *hist_words = pass ? (int64_t)1 << wide_shift(abs_key, dtype) : (int64_t)(w.low - w.hist);
   return passes;
 }
 
 extern "C" int bvq_kthw_begin(int abs_key, int dtype, void* workspace, int64_t workspace_bytes, bvq_stream_t stream) {
-  int rc = kthw_check("bvq_kthw_begin", dtype, workspace, workspace_bytes);
+  int rc = sel_check("bvq_kthw_begin", dtype, 1, workspace, workspace_bytes);
   if (rc) return rc;
-  const WideWs w = wide_ws(dtype, workspace);
   const int shift = wide_shift(abs_key, dtype);
-  const int32_t words = kBins15 + (shift ? (int32_t)((int64_t)1 << shift) : 0);
-  kth_zero_kernel<<<dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(w.hist, words);
+  launch_zero(wide_ws(dtype, workspace).hist, kBins15 + (shift ? (int64_t)1 << shift : 0), (hipStream_t)stream);
   return check_launch("bvq_kthw_begin");
 }
 
 extern "C" int bvq_kthw_hist(int abs_key, int dtype, const void* x, int64_t n, int pass, void* workspace,
                              int64_t workspace_bytes, bvq_stream_t stream) {
-  int rc = kthw_check("bvq_kthw_hist", dtype, workspace, workspace_bytes);
+  int rc = sel_check("bvq_kthw_hist", dtype, 1, workspace, workspace_bytes);
   if (rc) return rc;
-  const int shift = wide_shift(abs_key, dtype);
-  if (n < 0 || pass < 0 || pass >= (shift ? 2 : 1)) {
+  if (n < 0 || pass < 0 || pass >= wide_passes(abs_key, dtype)) {
     set_error("bvq_kthw_hist: bad argument");
     return BVQ_ERR_INVALID;
   }
@@ -762,140 +692,96 @@ extern "C" int bvq_kthw_hist(int abs_key, int dtype, const void* x, int64_t n, i
     set_error("bvq_kthw_hist: null pointer");
     return BVQ_ERR_INVALID;
   }
-  hipStream_t st = (hipStream_t)stream;
-  const WideWs w = wide_ws(dtype, workspace);
   // the kernels take 16-byte chunks from an aligned address: the elements in front of it are counted one by one
   const int es = dtype_size(dtype);
   int64_t head = (int64_t)(((16 - (reinterpret_cast<uintptr_t>(x) & 15)) & 15) / (uintptr_t)es);
   if (head > n) head = n;
-  const char* xa = reinterpret_cast<const char*>(x) + head * es;
-  const int64_t na = n - head;
-  const bool nt = n * (int64_t)es >= nt_threshold_bytes();
-  // few elements: few workgroups (each one flushes its own 32768-bin histogram)
-  const int64_t chunks = na / (16 / es);
-  unsigned g15 = (unsigned)((chunks + kBlock15 * kSelUnroll - 1) / (kBlock15 * kSelUnroll));
-  g15 = g15 < 1 ? 1 : (g15 > 256 ? 256 : g15);
-  unsigned glow = (unsigned)((chunks + kBlock * kSelUnroll - 1) / (kBlock * kSelUnroll));
-  glow = glow < 1 ? 1 : (glow > 2048 ? 2048 : glow);
-  rc = with_dtype(dtype, [&](auto t) {
-    using T = typename decltype(t)::type;
-    return with_bool(abs_key, [&](auto abs) {
-      const T* xp = reinterpret_cast<const T*>(xa);
-      if (pass == 0)
-        with_bool(nt, [&](auto ntc) {
-          kth_hist15_kernel<T, abs, ntc><<<g15, kBlock15, 0, st>>>(xp, na, shift, w.hist, (int32_t)head);
-        });
-      else if (shift <= kDigitBits)
-        kth_low_kernel<T, abs, false, true><<<glow > 1024 ? 1024 : glow, kBlock, 0, st>>>(xp, na, shift, w.sel, w.low, 1,
-                                                                                          (int32_t)head);
-      else
-        with_bool(nt, [&](auto ntc) {
-          kth_low_kernel<T, abs, ntc, false><<<glow, kBlock, 0, st>>>(xp, na, shift, w.sel, w.low, 1, (int32_t)head);
-        });
-    });
-  });
+  // few elements: few workgroups (each one flushes its own histogram), at most the grid that covers the chip
+  const int64_t chunks = (n - head) / (16 / es), per_group = (int64_t)wide_block(pass) * kSelUnroll;
+  const int64_t full = wide_full_grid(pass, wide_shift(abs_key, dtype));
+  int64_t grid = (chunks + per_group - 1) / per_group;
+  grid = grid < 1 ? 1 : (grid > full ? full : grid);
+  rc = wide_hist(abs_key, dtype, reinterpret_cast<const char*>(x) + head * es, n - head, (int32_t)head, pass, 1,
+                 (unsigned)grid, wide_ws(dtype, workspace), (hipStream_t)stream);
   return rc ? rc : check_launch("bvq_kthw_hist");
 }
 
 extern "C" int bvq_kthw_pick(int abs_key, int dtype, int pass, int rule, int64_t k, double q, void* workspace,
                              int64_t workspace_bytes, bvq_stream_t stream) {
-  int rc = kthw_check("bvq_kthw_pick", dtype, workspace, workspace_bytes);
+  int rc = sel_check("bvq_kthw_pick", dtype, 1, workspace, workspace_bytes);
   if (rc) return rc;
-  const int shift = wide_shift(abs_key, dtype);
-  if (pass < 0 || pass >= (shift ? 2 : 1) || rule < BVQ_KTH_EXPLICIT || rule > BVQ_KTH_LOW ||
-      (pass == 0 && rule == BVQ_KTH_EXPLICIT && k < 1) || (pass == 0 && rule != BVQ_KTH_EXPLICIT && !(q >= 0.0 && q <= 100.0))) {
+  if (pass < 0 || pass >= wide_passes(abs_key, dtype) || (pass == 0 ? bad_rank(rule, k, q) : bad_rule(rule))) {
     set_error("bvq_kthw_pick: bad argument");
     return BVQ_ERR_INVALID;
   }
-  const WideWs w = wide_ws(dtype, workspace);
-  if (pass == 0)
-    kth_pick_wide_kernel<<<dim3(1), dim3(kBlock15), 0, (hipStream_t)stream>>>(w.hist, kBins15, 15, 1, k, w.sel, w.krem,
-                                                                             rule, q);
-  else
-    kth_pick_wide_kernel<<<dim3(1), dim3(kBlock15), 0, (hipStream_t)stream>>>(w.low, 1 << shift, shift, 0, 0, w.sel,
-                                                                             w.krem);
+  wide_pick(abs_key, dtype, pass, 0, rule, k, q, wide_ws(dtype, workspace), (hipStream_t)stream);
   return check_launch("bvq_kthw_pick");
 }
 
 extern "C" int bvq_kthw_finish(int abs_key, int dtype, void* out, void* workspace, int64_t workspace_bytes,
                                bvq_stream_t stream) {
-  int rc = kthw_check("bvq_kthw_finish", dtype, workspace, workspace_bytes);
+  int rc = sel_check("bvq_kthw_finish", dtype, 1, workspace, workspace_bytes);
   if (rc) return rc;
   if (!out) {
     set_error("bvq_kthw_finish: null pointer");
     return BVQ_ERR_INVALID;
   }
-  hipStream_t st = (hipStream_t)stream;
-  const WideWs w = wide_ws(dtype, workspace);
-  rc = with_dtype(dtype, [&](auto t) {
-    return with_bool(abs_key, [&](auto abs) {
-      kth_store_kernel<typename decltype(t)::type, abs><<<1, 64, 0, st>>>(w.sel, out, 1);
-    });
-  });
+  rc = wide_store(abs_key, dtype, out, 1, wide_ws(dtype, workspace), (hipStream_t)stream);
   return rc ? rc : check_launch("bvq_kthw_finish");
+}
+
+// bvq_kth_value (nk = 1) and bvq_kth_pair (nk = 2): ranks ks[nk] -> out[nk][channels]; who: the entry the error text names
+static int kth_select(const char* who, int abs_key, int dtype, const void* x, int64_t outer, int64_t channels,
+                      int64_t inner, const int64_t* ks, int nk, void* out, void* workspace, int64_t workspace_bytes,
+                      bvq_stream_t stream) {
+  if (bad_dtype(dtype) || outer < 0 || channels < 1 || inner < 0) {
+    set_error("%s: bad argument", who);
+    return BVQ_ERR_INVALID;
+  }
+  const int64_t per_channel = outer * inner;
+  if (per_channel > kSelMaxCount) {
+    set_error("%s: %lld elements per channel; the digit counters are 32-bit (limit 2^32 - 1)", who,
+              (long long)per_channel);
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  for (int i = 0; i < nk; ++i)
+    if (ks[i] < 1 || ks[i] > per_channel) {  // torch.kthvalue: "selected index k out of range"
+      set_error("%s: k = %lld out of range [1, %lld]", who, (long long)ks[i], (long long)per_channel);
+      return BVQ_ERR_INVALID;
+    }
+  if (!x || !out || !workspace) {
+    set_error("%s: null pointer", who);
+    return BVQ_ERR_INVALID;
+  }
+  if (wide_select_applies(channels, per_channel, x)) {
+    const int rc = sel_check(who, dtype, 1, workspace, workspace_bytes);
+    return rc ? rc : wide_select(abs_key, dtype, x, per_channel, ks, nk, out, workspace, (hipStream_t)stream);
+  }
+  int rc = BVQ_OK;
+  for (int i = 0; !rc && i < nk; ++i) {  // the digit passes, once per rank
+    rc = bvq_kth_begin(dtype, channels, BVQ_KTH_EXPLICIT, ks[i], 0.0, workspace, workspace_bytes, stream);
+    for (int p = 0; !rc && p < passes_for(dtype); ++p) {
+      rc = bvq_kth_hist(abs_key, dtype, x, outer, channels, inner, p, workspace, workspace_bytes, stream);
+      if (!rc) rc = bvq_kth_pick(dtype, channels, p, BVQ_KTH_EXPLICIT, 0.0, workspace, workspace_bytes, stream);
+    }
+    if (!rc)
+      rc = bvq_kth_finish(abs_key, dtype, channels, reinterpret_cast<char*>(out) + i * channels * (int64_t)dtype_size(dtype),
+                          workspace, workspace_bytes, stream);
+  }
+  return rc;
 }
 
 extern "C" int bvq_kth_value(int abs_key, int dtype, const void* x, int64_t outer, int64_t channels,
                              int64_t inner, int64_t k, void* out, void* workspace,
                              int64_t workspace_bytes, bvq_stream_t stream) {
-  if (dtype < BVQ_F32 || dtype > BVQ_F16 || outer < 0 || channels < 1 || inner < 0) {
-    set_error("bvq_kth_value: bad argument");
-    return BVQ_ERR_INVALID;
-  }
-  const int64_t per_channel = outer * inner;
-  if (per_channel > kSelMaxCount) {
-    set_error("bvq_kth_value: %lld elements per channel; the digit counters are 32-bit (limit 2^32 - 1)",
-              (long long)per_channel);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (k < 1 || k > per_channel) {  // torch.kthvalue: "selected index k out of range"
-    set_error("bvq_kth_value: k = %lld out of range [1, %lld]", (long long)k, (long long)per_channel);
-    return BVQ_ERR_INVALID;
-  }
-  if (!x || !out || !workspace) {
-    set_error("bvq_kth_value: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  if (wide_select_applies(channels, per_channel, x))
-    return wide_select(abs_key, dtype, x, per_channel, &k, 1, out, workspace, workspace_bytes, stream);
-  int rc = bvq_kth_begin(dtype, channels, BVQ_KTH_EXPLICIT, k, 0.0, workspace, workspace_bytes, stream);
-  for (int p = 0; !rc && p < passes_for(dtype); ++p) {
-    rc = bvq_kth_hist(abs_key, dtype, x, outer, channels, inner, p, workspace, workspace_bytes, stream);
-    if (!rc) rc = bvq_kth_pick(dtype, channels, p, BVQ_KTH_EXPLICIT, 0.0, workspace, workspace_bytes, stream);
-  }
-  if (!rc) rc = bvq_kth_finish(abs_key, dtype, channels, out, workspace, workspace_bytes, stream);
-  return rc;
+  return kth_select("bvq_kth_value", abs_key, dtype, x, outer, channels, inner, &k, 1, out, workspace, workspace_bytes,
+                    stream);
 }
 
 extern "C" int bvq_kth_pair(int abs_key, int dtype, const void* x, int64_t outer, int64_t channels, int64_t inner,
                             int64_t k_first, int64_t k_second, void* out, void* workspace, int64_t workspace_bytes,
                             bvq_stream_t stream) {
-  if (dtype < BVQ_F32 || dtype > BVQ_F16 || outer < 0 || channels < 1 || inner < 0) {
-    set_error("bvq_kth_pair: bad argument");
-    return BVQ_ERR_INVALID;
-  }
-  const int64_t per_channel = outer * inner;
-  if (per_channel > kSelMaxCount) {
-    set_error("bvq_kth_pair: %lld elements per channel; the digit counters are 32-bit (limit 2^32 - 1)",
-              (long long)per_channel);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (k_first < 1 || k_first > per_channel || k_second < 1 || k_second > per_channel) {
-    set_error("bvq_kth_pair: rank out of range [1, %lld]", (long long)per_channel);
-    return BVQ_ERR_INVALID;
-  }
-  if (!x || !out || !workspace) {
-    set_error("bvq_kth_pair: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  if (wide_select_applies(channels, per_channel, x)) {
-    const int64_t ks[2] = {k_first, k_second};
-    return wide_select(abs_key, dtype, x, per_channel, ks, 2, out, workspace, workspace_bytes, stream);
-  }
-  int rc = bvq_kth_value(abs_key, dtype, x, outer, channels, inner, k_first, out, workspace, workspace_bytes, stream);
-  if (!rc)
-    rc = bvq_kth_value(abs_key, dtype, x, outer, channels, inner, k_second,
-                       reinterpret_cast<char*>(out) + channels * (int64_t)dtype_size(dtype), workspace, workspace_bytes,
-                       stream);
-  return rc;
+  const int64_t ks[2] = {k_first, k_second};
+  return kth_select("bvq_kth_pair", abs_key, dtype, x, outer, channels, inner, ks, 2, out, workspace, workspace_bytes,
+                    stream);
 }

@@ -9,8 +9,8 @@
 // of (bits & ~sign), and every NaN pattern is larger than +inf, so an unsigned max IS
 // torch.max(torch.abs(x)) including its NaN propagation.  The result is exact (a max never rounds).
 //
-// The streaming kernels sit on the two walks of bvq_unit_walk.h: each is its state, a per-element function (shared by
-// the row-mapped and the column-mapped kernel of a statistic) and its write-out.  The one-launch abs-max keeps its own
+// The streaming kernels sit on the walks of bvq_unit_walk.h: each is its state, a per-element function (shared by
+// the row-mapped and the column-mapped kernel of a statistic) and its write-out; histc_kernel takes the flat walk.  The one-launch abs-max keeps its own
 // software-pipelined loop (onepass_unit_max) and takes only its ragged ends from the walk; so do minmax_kernel and
 // tie_scan_kernel, which measured slower on walk_unit's main loop (profiles/stat_walk.md).
 #include <math.h>
@@ -842,22 +842,16 @@ __global__ __launch_bounds__(kBlock) void tie_apply_full_kernel(const void* x, c
 // ------------------------------------------------------------------------------------------------
 static Tiling stat_tiling(int dtype, const void* x, const void* dx, int64_t outer, int64_t channels,
                           int64_t inner, int& vec, bool ragged_ok = false) {
-  // per-tensor: one row holding everything
-  const int64_t t_outer = channels > 1 ? outer : 1;
-  const int64_t row_len = channels > 1 ? inner : outer * inner;
-  const int full = 16 / dtype_size(dtype);
   const void* ptrs[2] = {x, dx};
-  const int els[2] = {dtype_size(dtype), dtype_size(dtype)};
-  vec = pick_vec(full, t_outer * channels, row_len, ptrs, els, 2, ragged_ok);
-  vec = vec == full ? full : 1;
-  return make_tiling(t_outer, (int32_t)channels, row_len, vec);
+  const RowView r = row_view(dtype, outer, channels, inner, ptrs, 2, ragged_ok);
+  vec = r.vec;
+  return make_tiling(r.outer, (int32_t)channels, r.row_len, vec);
 }
 
 static int64_t worst_units(int dtype, int64_t outer, int64_t channels, int64_t inner) {
-  const int64_t t_outer = channels > 1 ? outer : 1;
-  const int64_t row_len = channels > 1 ? inner : outer * inner;
-  const int64_t a = make_tiling(t_outer, (int32_t)channels, row_len, 16 / dtype_size(dtype)).units;
-  const int64_t b = make_tiling(t_outer, (int32_t)channels, row_len, 1).units;
+  const RowView r = row_view(dtype, outer, channels, inner);
+  const int64_t a = make_tiling(r.outer, (int32_t)channels, r.row_len, 16 / dtype_size(dtype)).units;
+  const int64_t b = make_tiling(r.outer, (int32_t)channels, r.row_len, 1).units;
   return a > b ? a : b;
 }
 
@@ -1544,23 +1538,14 @@ __global__ __launch_bounds__(kBlock) void histc_kernel(const T* __restrict__ x, 
   __syncthreads();
   const float hi = to_f<T>(*reinterpret_cast<const T*>(absmax)), lo = -hi;
   const float width = hi - lo;
-  constexpr int VEC = elem<T>::vec;
-  const int64_t nvec = n / VEC;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  auto count = [&](float v) {
+  walk_flat<T, kBlock, false, 1>(x, n, 0, [&](T xv) {
+    const float v = to_f<T>(xv);
     if (v >= lo && v <= hi) {
       int b = (int)((v - lo) * (float)bins / width);
       if (b == bins) b -= 1;
       if (b >= 0 && b < bins) atomicAdd(&sh[b], 1);  // (width == 0: NaN bin index, nothing counted by the guard)
     }
-  };
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nvec; i += stride) {
-    const vec_t<T, VEC> xv = load_vec<T, VEC>(x + i * VEC);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) count(to_f<T>(xv.v[k]));
-  }
-  const int64_t t = nvec * VEC + (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (t < n) count(to_f<T>(x[t]));
+  });
   __syncthreads();
   for (int i = threadIdx.x; i < bins; i += kBlock)
     if (sh[i]) atomicAdd(&out[i], sh[i]);

@@ -1,11 +1,13 @@
-// bvq_unit_walk.h -- the two walks of the read-mostly kernels (statistics, select, tie scan, abs-affine backward):
-// how a wave gets from its unit to the vectors and elements it owns.  A kernel on a walk is its state, a body per
-// vector or element, and its write-out; nothing here knows a statistic.
+// bvq_unit_walk.h -- the three walks of the read-mostly kernels (statistics, select, tie scan, abs-affine backward):
+// how a wave gets from its unit, or a workgroup from its place in the grid, to the vectors and elements it owns.  A
+// kernel on a walk is its state, a body per vector or element, and its write-out; nothing here knows a statistic.
 //
 //   row-mapped    (Tiling / Unit, bvq_common.h): walk_unit -- ChunkWalker over the full chunks of the unit's rows, kU
 //                 predicated loads in flight before the first use, then walk_unit_tail over the ragged ends.
 //   column-mapped (ColsPlan, bvq_common.h): cols_locate places a lane (ColsPlace), walk_cols takes it down its rows
 //                 with kU loads in flight.
+//   flat          (a pointer and a count): walk_flat -- the grid's workgroups stride over the 16-byte chunks of a
+//                 buffer with kU predicated loads in flight; workgroup 0 takes the elements around the chunks.
 #pragma once
 
 #include "bvq_common.h"
@@ -124,6 +126,40 @@ __device__ __forceinline__ void walk_cols(const ColsPlan& p, const ColsPlace& c,
       if (ok[j]) body(xv[j], r + (int64_t)j * p.rpp);
     }
   }
+}
+
+// ---- flat -----------------------------------------------------------------------------------------------------------
+// The whole grid over [x - head, x + n), x on a 16-byte boundary, workgroups of kB threads: a workgroup-strided run
+// over the full 16-byte chunks of [x, x + n) with kU predicated loads (cache policy NT) issued before the first is
+// used, then workgroup 0 alone over the (< VEC) elements after the last chunk and the `head` (< VEC) elements in front
+// of x -- what lies before the first 16-byte boundary of a caller's buffer.  each(v) per element; it sees every element
+// exactly once, in no particular order (the kernels on this walk count).
+// Chunks, tail and head are three separate branches: a body that votes across its wave (low_count, bvq_select.hip)
+// must meet, in one ballot, only lanes that came through the same branch.
+template <typename T, int kB, bool NT, int kU, typename E>
+__device__ __forceinline__ void walk_flat(const T* __restrict__ x, int64_t n, int32_t head, E&& each) {
+  constexpr int VEC = elem<T>::vec;
+  const int64_t chunks = n / VEC;
+  const int64_t stride = (int64_t)gridDim.x * kB;
+  for (int64_t c = (int64_t)blockIdx.x * kB + threadIdx.x; c < chunks; c += stride * kU) {
+    vec_t<T, VEC> xv[kU];
+    bool ok[kU];
+#pragma unroll
+    for (int j = 0; j < kU; ++j) {
+      const int64_t cj = c + (int64_t)j * stride;
+      ok[j] = cj < chunks;
+      if (ok[j]) xv[j] = load_vec<T, VEC, NT>(x + cj * VEC);
+    }
+#pragma unroll
+    for (int j = 0; j < kU; ++j) {
+      if (ok[j]) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) each(xv[j].v[k]);
+      }
+    }
+  }
+  if (blockIdx.x == 0 && chunks * VEC + threadIdx.x < n) each(x[chunks * VEC + threadIdx.x]);
+  if (blockIdx.x == 0 && (int32_t)threadIdx.x < head) each(x[(int64_t)threadIdx.x - head]);
 }
 
 }  // namespace bvq
