@@ -33,7 +33,7 @@ CLUSTER_AUTO, CLUSTER_WALK, CLUSTER_ONESHOT = range(3)
 MX_E4M3, MX_E5M2, MX_E3M2, MX_E2M3, MX_E2M1, MX_INT8 = range(6)
 MX_FLOOR, MX_CEIL = 0, 1
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -161,6 +161,8 @@ _SIG = {
     'bvq_group_shifted_supported': (_i32, [_qd, _vp]),
     'bvq_group_shifted_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
     'bvq_group_shifted_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
+    'bvq_gptq_block_supported': (_i32, [_qd, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    'bvq_gptq_block': (_i32, [_qd, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
     'bvq_mx_quant_supported': (_i32, [_i32, _i64, _i32, _i32, _vp]),
     'bvq_mx_quant_fwd': (_i32, [_i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'bvq_mx_quant_bwd': (_i32, [_i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -588,6 +590,32 @@ def group_shifted_bwd(desc, g, x, stat, gscale, gzp, min_val, thr_div):
     _launch(dev, 'bvq_group_shifted_bwd', 'bvq_group_shifted_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(stat),
             ptr(gscale), ptr(gzp), *_scale_args(min_val, thr_div), ptr(dx))
     return dx
+
+
+GPTQ_BLOCK = 128  # columns of one bvq_gptq_block launch
+
+
+def gptq_block_supported(desc, wf, u, q, col0, block_cols, computed):
+    """the GPTQ column-loop kernel covers this descriptor (that of the group-wise entries for the weight [rows, cols]
+    regrouped by the group size), block and tensors"""
+    rows, cols = wf.shape
+    return bool(lib.bvq_gptq_block_supported(ctypes.byref(desc), rows, cols, int(col0), int(block_cols), int(computed),
+                                             ptr(wf), ptr(u), ptr(q)))
+
+
+def gptq_block(desc, wf, u, col0, block_cols, computed, min_val, thr_div, q, scale, zp):
+    """the GPTQ column loop of the block [col0, col0 + block_cols) in ONE launch (include/bvq.h, "GPTQ"): reads wf
+    (float32 [rows, cols]) and u (float32 [cols, cols]), writes the block's columns of q (like wf, in the quantizer's
+    dtype) and, computed, the block's entries of scale / zp ([rows, cols / group size]; given, they are read; zp None for
+    a symmetric quantizer) -> err float32 [rows, block_cols]"""
+    dev = require_device(wf, u, q, scale, zp)
+    assert wf.dtype == torch.float32 and u.dtype == torch.float32 and wf.is_contiguous() and u.is_contiguous()
+    assert q.is_contiguous() and q.shape == wf.shape and scale.is_contiguous() and (zp is None or zp.is_contiguous())
+    rows, cols = wf.shape
+    err = torch.empty(rows, block_cols, dtype=torch.float32, device=dev)
+    _launch(dev, 'bvq_gptq_block', 'bvq_gptq_block', ctypes.byref(desc), ptr(wf), ptr(u), rows, cols, int(col0),
+            int(block_cols), int(computed), *_scale_args(min_val, thr_div), ptr(q), ptr(err), ptr(scale), ptr(zp))
+    return err
 
 
 def mx_quant_supported(x, group_size, fmt):

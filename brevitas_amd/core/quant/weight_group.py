@@ -138,6 +138,8 @@ class WeightQuantGroup:
         if getattr(q, 'bvq_collect_only', False) or (mem.layer is not None and
                                                      getattr(mem.layer, 'bvq_disable_weight_quant', False)):
             return None, 'calibrating'
+        if mem.layer is not None and mem.layer._buffers.get('frozen_weight_scale') is not None:
+            return None, 'frozen weight (graph/gptq.py: freeze_weight_quant)'
         bw = q.msb_clamp_bit_width_impl()
         tmpl = q._stats_template(bw)
         if tmpl is None:

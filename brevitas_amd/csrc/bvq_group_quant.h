@@ -69,12 +69,17 @@ __device__ __forceinline__ bool wave_fast_div(float s) {
 }
 template <typename T>
 using FastDiv = std::conditional_t<elem<T>::id == BVQ_BF16, DivBf16, DivF16R>;
+// r: 1.0f / s, for a caller that keeps it across several uses of one scale (bvq_gptq.hip)
+template <typename T>
+__device__ __forceinline__ FastDiv<T> fast_div(float s, float r) {
+  if constexpr (elem<T>::id == BVQ_BF16)
+    return DivBf16{r};
+  else
+    return DivF16R{s, r};
+}
 template <typename T>
 __device__ __forceinline__ FastDiv<T> fast_div(float s) {
-  if constexpr (elem<T>::id == BVQ_BF16)
-    return DivBf16{1.0f / s};
-  else
-    return DivF16R{s, 1.0f / s};
+  return fast_div<T>(s, 1.0f / s);
 }
 // f(div) with the division by s that the wave takes for this load
 template <typename T, typename F>

@@ -1,3 +1,5 @@
 from .calibrate import DisableEnableQuantization, calibration_mode, finalize_collect_stats
+from .gptq import GPTQResult, freeze_weight_quant, gptq_mode, gptq_quantize_weight, unfreeze_weight_quant
 
-__all__ = ['calibration_mode', 'finalize_collect_stats', 'DisableEnableQuantization']
+__all__ = ['calibration_mode', 'finalize_collect_stats', 'DisableEnableQuantization', 'gptq_mode',
+           'gptq_quantize_weight', 'GPTQResult', 'freeze_weight_quant', 'unfreeze_weight_quant']

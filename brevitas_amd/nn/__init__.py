@@ -61,6 +61,11 @@ class _QuantWeightMixin:
         """-> (dequantized weight, scale, zero_point, bit_width); identity if no weight quantizer"""
         if self.weight_quant is None or getattr(self, 'bvq_disable_weight_quant', False):  # calibration
             return self.weight, None, None, None
+        if self._buffers.get('frozen_weight_scale') is not None:
+            # frozen (graph/gptq.py: freeze_weight_quant): the weight holds dequantized codes whose scales the
+            # quantizer would not reproduce
+            return (self.weight, self.frozen_weight_scale, self.frozen_weight_zero_point,
+                    self.weight_quant.msb_clamp_bit_width_impl())
         return self.weight_quant(self.weight)
 
     def packed_weight(self):

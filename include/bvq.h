@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 4
+#define BVQ_ABI_VERSION 5
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -770,6 +770,41 @@ int bvq_group_shifted_fwd(const bvq_quant_desc* desc, const void* x, double min_
 int bvq_group_shifted_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* stat,
                           const void* gscale, const void* gzp, double min_val, int use_min, double thr_div, void* dx,
                           bvq_stream_t stream);
+
+/* ---- GPTQ: the column loop of one block of up to 128 input columns -----------------------------------------------------
+ * GPTQ (Frantar et al. 2022; `gptq_mode` of later Brevitas releases, no reference counterpart) quantizes a weight one
+ * input column at a time and pushes each column's error onto the columns not yet quantized.  Definition, which the
+ * composed route of brevitas_amd/graph/gptq.py and this kernel compute with the same bits:
+ *   W  [R, K] of dtype T (a conv weight flattened to K = in * kh * kw), Wf its float32 working copy,
+ *   U  [K, K] float32, the upper Cholesky factor of the damped inverse Hessian of the layer's inputs,
+ *   blocks of B = 128 columns (the last may be shorter), group size g dividing K.
+ * For each block [c0, c1), for i = c0 .. c1 - 1, for every row r:
+ *   group start  if i % g == 0 and the parameters are computed in the loop: scale, zp of (r, i / g) are what
+ *                bvq_group_quant_fwd (symmetric) or bvq_group_shifted_fwd (asymmetric) computes for the group
+ *                T(Wf[r, i : i + g]) as it stands, partly updated; same min_val, thr_div and rounding points
+ *   quantize     q = the value of T those entries store for the element T(Wf[r, i]) at that scale, zp; Q[r, i] = q
+ *   error        e = (Wf[r, i] - float32(q)) / U[i, i], float32, IEEE division; E[r, i - c0] = e
+ *   update       for j = i + 1 .. c1 - 1: Wf[r, j] = Wf[r, j] - e * U[i, j], the product rounded to float32, then the
+ *                difference rounded (no fused multiply-add)
+ * and after each block Wf[:, c1:] -= E @ U[c0:c1, c1:] as one float32 matrix product, which is the caller's.
+ * bvq_gptq_block runs that loop for ONE block in one launch: one wave per row, the block's columns in registers (two
+ * per lane), a group start as a segmented butterfly; no workspace, no atomics.  It reads the block's columns of wf
+ * ([rows, cols] float32) and the [block_cols, block_cols] triangle of u ([cols, cols] float32) and writes the block's
+ * columns of q ([rows, cols] of T) and err ([rows, block_cols] float32).  desc: outer 1, channels = rows * cols / g,
+ * inner = g, scale_per_channel, x_dtype = ct_dtype = scale_dtype; zp_per_channel = 1 with zp_dtype = x_dtype for an
+ * asymmetric quantizer, whose zp is then required.  scale, zp: [rows, cols / g] of T;
+ *   computed = 1: the block's entries are WRITTEN; g is 16, 32, 64 or 128 and divides col0 and block_cols;
+ *   computed = 0: they are READ (computed once from the original weight by the caller); any g dividing cols.
+ * min_val / use_min / thr_div as in bvq_group_quant_fwd (read when computed = 1).
+ * Checked before anything touches the device, with a bvq_last_error() text: null pointers (BVQ_ERR_INVALID), wf, u, q or
+ * err off a 16-byte boundary and a group size the loop cannot compute (BVQ_ERR_UNSUPPORTED), block_cols outside
+ * 1 .. 128, columns outside the weight and a col0 that is no multiple of g where computed (BVQ_ERR_INVALID).
+ * bvq_gptq_block_supported answers 1 / 0. */
+int bvq_gptq_block_supported(const bvq_quant_desc* desc, int64_t rows, int64_t cols, int64_t col0, int block_cols,
+                             int computed, const void* wf, const void* u, const void* q);
+int bvq_gptq_block(const bvq_quant_desc* desc, const float* wf, const float* u, int64_t rows, int64_t cols,
+                   int64_t col0, int block_cols, int computed, double min_val, int use_min, double thr_div, void* q,
+                   float* err, void* scale, void* zp, bvq_stream_t stream);
 
 /* ---- MX block-scaled quantizers: groups sharing one power-of-two scale, minifloat or MXINT8 elements -----------------
  * The OCP Microscaling formats the gfx950 matrix units take natively, as quantize-dequantize for training (no
