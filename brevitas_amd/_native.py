@@ -32,8 +32,9 @@ CLUSTER_AUTO, CLUSTER_WALK, CLUSTER_ONESHOT = range(3)
 # bvq_mx_format, bvq_mx_scale_rule
 MX_E4M3, MX_E5M2, MX_E3M2, MX_E2M3, MX_E2M1, MX_INT8 = range(6)
 MX_FLOOR, MX_CEIL = 0, 1
+LR_HARD_SIGMOID, LR_SIGMOID = 0, 1  # bvq_learned_round_impl
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -163,6 +164,9 @@ _SIG = {
     'bvq_group_shifted_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
     'bvq_gptq_block_supported': (_i32, [_qd, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     'bvq_gptq_block': (_i32, [_qd, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_learned_round_supported': (_i32, [_qd, _vp, _vp, _vp]),
+    'bvq_learned_round_fwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _i32, _vp, _vp]),
+    'bvq_learned_round_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp]),
     'bvq_mx_quant_supported': (_i32, [_i32, _i64, _i32, _i32, _vp]),
     'bvq_mx_quant_fwd': (_i32, [_i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'bvq_mx_quant_bwd': (_i32, [_i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -616,6 +620,33 @@ def gptq_block(desc, wf, u, col0, block_cols, computed, min_val, thr_div, q, sca
     _launch(dev, 'bvq_gptq_block', 'bvq_gptq_block', ctypes.byref(desc), ptr(wf), ptr(u), rows, cols, int(col0),
             int(block_cols), int(computed), *_scale_args(min_val, thr_div), ptr(q), ptr(err), ptr(scale), ptr(zp))
     return err
+
+
+def learned_round_supported(desc, x, value):
+    """the learned-round kernels cover this descriptor (that of fakequant_fwd) and these tensors"""
+    return bool(lib.bvq_learned_round_supported(ctypes.byref(desc), ptr(x), ptr(value), None))
+
+
+def learned_round_fwd(desc, x, value, scale, zp, impl, consts, hard):
+    """IntQuant with floor(t) + h(value) in ONE launch (include/bvq.h, "Learned rounding") -> y like x; hard: h is 0 or 1
+    (eval mode); consts: (c0, c1) of the impl"""
+    dev = require_device(x, value, scale, zp)
+    assert x.is_contiguous() and value.is_contiguous() and value.dtype == x.dtype and value.numel() == x.numel()
+    y = torch.empty_like(x)
+    _launch(dev, 'bvq_learned_round_fwd', 'bvq_learned_round_fwd', ctypes.byref(desc), ptr(x), ptr(value), ptr(scale),
+            ptr(zp), int(impl), float(consts[0]), float(consts[1]), int(bool(hard)), ptr(y))
+    return y
+
+
+def learned_round_bwd(desc, g, x, value, scale, zp, impl, consts, want_dx):
+    """backward of learned_round_fwd (soft h) in ONE launch -> (dvalue like value, dx like x or None)"""
+    dev = require_device(g, x, value, scale, zp)
+    assert g.is_contiguous() and x.is_contiguous() and value.is_contiguous() and g.dtype == x.dtype == value.dtype
+    dvalue = torch.empty_like(value)
+    dx = torch.empty_like(x) if want_dx else None
+    _launch(dev, 'bvq_learned_round_bwd', 'bvq_learned_round_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(value),
+            ptr(scale), ptr(zp), int(impl), float(consts[0]), float(consts[1]), ptr(dvalue), ptr(dx))
+    return dvalue, dx
 
 
 def mx_quant_supported(x, group_size, fmt):

@@ -278,6 +278,36 @@ class LearnedScaleFakeQuantFn(Function):
         return dx, dvalue.view(value.shape), None, None, None, None, None, None, None, None, None
 
 
+class LearnedRoundFakeQuantFn(Function):
+    """IntQuant whose float_to_int_impl is a LearnedRoundSte (core/function_wrapper/learned_round.py): x, value -> y, one
+    launch each way (csrc/bvq_learned_round.hip).  Returns dvalue, and dx when x asks for it; scale, zero-point and bit
+    width get no gradient here -- the caller has checked that none wants one, and what the kernels cover
+    (IntQuant._learned_round_args).  hard: eval mode, h(value) is 0 or 1 and nothing is differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, value, scale, zp, p, qmin, qmax, clamp_ste, kind, consts, hard):
+        sc = scale.detach().reshape(-1).contiguous()
+        zc = zp.detach().reshape(-1).contiguous()
+        desc = make_desc(p, x, sc, zc, qmin, qmax, nat.FLOOR, clamp_ste, nat.OUT_DEQUANT)
+        y = nat.learned_round_fwd(desc, x, value, sc, zc, kind, consts, hard)
+        if hard:
+            ctx.mark_non_differentiable(y)
+        else:
+            ctx.desc, ctx.kind, ctx.consts = desc, kind, consts
+            ctx.save_for_backward(x, value, sc, zc)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, value, sc, zc = ctx.saved_tensors
+        gy = gy.to(x.dtype).contiguous()
+        if gy.data_ptr() % 16 != 0:
+            gy = gy.clone()
+        dvalue, dx = nat.learned_round_bwd(ctx.desc, gy, x, value, sc, zc, ctx.kind, ctx.consts,
+                                           ctx.needs_input_grad[0])
+        return (dx, dvalue.view(value.shape) if ctx.needs_input_grad[1] else None) + (None,) * 9
+
+
 class VariantFn(Function):
     """BinaryQuant / ClampedBinaryQuant / TernaryQuant / DecoupledIntQuant / TruncIntQuant on their fused kernels
     (include/bvq.h, bvq_variant_fwd / bvq_variant_bwd): one read + one write forward, two reads + one write backward,

@@ -14,7 +14,7 @@ from torch.nn import Module
 
 import brevitas_amd.config as config
 from brevitas_amd import _native as nat
-from brevitas_amd.core.function_wrapper import RoundSte, TensorClamp
+from brevitas_amd.core.function_wrapper import LearnedRoundSte, RoundSte, TensorClamp
 from brevitas_amd.core.quant import _fused
 from brevitas_amd.core.quant.delay import DelayWrapper, _NoDelay
 from brevitas_amd.function.ops import int_range_host, max_int, min_int
@@ -77,6 +77,42 @@ class IntQuant(torch.nn.Module):
             return None
         qmin, qmax = int_range_host(self.signed, self.narrow_range, bw)
         return p, qmin, qmax, round_mode, clamp_ste
+
+    def _learned_round_args(self, scale: Tensor, zero_point: Tensor, bit_width: Tensor, x: Tensor):
+        """(value, plan, qmin, qmax, clamp_ste, impl kind, impl constants, hard) if float_to_int_impl is a LearnedRoundSte
+        and the learned-round kernels cover this call ("Learned rounding"), else None: the op-by-op chain
+        runs, with the same bits"""
+        if not config.FUSED_PATHS or type(self) is not IntQuant or \
+                not isinstance(self.delay_wrapper.delay_impl, _NoDelay):
+            return None
+        lr = self.float_to_int_impl
+        if not isinstance(lr, LearnedRoundSte):
+            return None
+        found = lr.bvq_learned_round()
+        clamp_ste = getattr(self.tensor_clamp_impl, 'bvq_clamp_ste', None)
+        bw = getattr(bit_width, 'bvq_host_value', None)
+        if found is None or clamp_ste is None or bw is None:
+            return None
+        kind, consts, value = found
+        if x.dtype == torch.float16 and not lr.learned_round_impl.bvq_f16_ok():
+            return None  # torch's float16 kernels are not one function of their inputs there (DESIGN.md §9)
+        grad = torch.is_grad_enabled()
+        if grad and (scale.requires_grad or zero_point.requires_grad or bit_width.requires_grad):
+            return None  # the kernels return dx and dvalue only
+        hard = not lr.training
+        if hard and grad and (x.requires_grad or value.requires_grad):
+            return None  # a gradient through the hard offsets: autograd's business
+        p = _fused.plan(x, scale, zero_point)
+        if p is None or p.nhwc or p.ct != x.dtype or not x.is_contiguous():
+            return None
+        if not value.is_cuda or value.device != x.device or value.dtype != x.dtype or value.numel() != x.numel() or \
+                not value.is_contiguous():
+            return None
+        qmin, qmax = int_range_host(self.signed, self.narrow_range, bw)
+        desc = _fused.make_desc(p, x, scale, zero_point, qmin, qmax, nat.FLOOR, clamp_ste, nat.OUT_DEQUANT)
+        if not nat.learned_round_supported(desc, x, value):
+            return None
+        return value, p, qmin, qmax, clamp_ste, kind, consts, hard
 
     # ---- reference surface ----------------------------------------------------------------------------
 
@@ -154,6 +190,9 @@ class IntQuant(torch.nn.Module):
                         ) -> Tensor:
         """forward(scale, zero_point, bit_width, pre_op(x)) with the activation `pre_op`
         (include/bvq.h, bvq_pre_op) folded into the quantizer kernel when that kernel applies"""
+        lr = self._learned_round_args(scale, zero_point, bit_width, x) if pre_op == nat.PRE_NONE else None
+        if lr is not None:
+            return _fused.LearnedRoundFakeQuantFn.apply(x, lr[0], scale, zero_point, *lr[1:])
         fa = self._fused_args(scale, zero_point, bit_width, x)
         if pre_op in _fused.ACT_PRE_OPS and (fa is None or bit_width.requires_grad or zero_point.requires_grad
                                              or not _fused.act_fusable(x, fa[0], pre_op)):

@@ -30,6 +30,7 @@ from typing import List, NamedTuple, Optional, Tuple
 import torch
 
 from brevitas_amd import _native as nat
+from brevitas_amd.core.function_wrapper.learned_round import LearnedRoundSte
 from brevitas_amd.core.quant import _fused
 from brevitas_amd.core.quant import int as _int
 from brevitas_amd.core.quant.int import GroupwiseRescalingIntQuant, RescalingIntQuant
@@ -140,6 +141,8 @@ class WeightQuantGroup:
             return None, 'calibrating'
         if mem.layer is not None and mem.layer._buffers.get('frozen_weight_scale') is not None:
             return None, 'frozen weight (graph/gptq.py: freeze_weight_quant)'
+        if isinstance(getattr(q.int_quant, 'float_to_int_impl', None), LearnedRoundSte):
+            return None, 'learned rounding (graph/learned_round.py: learned_round_mode): the layer quantizes it on its own'
         bw = q.msb_clamp_bit_width_impl()
         tmpl = q._stats_template(bw)
         if tmpl is None:

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 5
+#define BVQ_ABI_VERSION 6
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -805,6 +805,44 @@ int bvq_gptq_block_supported(const bvq_quant_desc* desc, int64_t rows, int64_t c
 int bvq_gptq_block(const bvq_quant_desc* desc, const float* wf, const float* u, int64_t rows, int64_t cols,
                    int64_t col0, int block_cols, int computed, double min_val, int use_min, double thr_div, void* q,
                    float* err, void* scale, void* zp, bvq_stream_t stream);
+
+/* ---- Learned rounding: IntQuant with floor(t) + h(value), one trainable offset per element ------------------------------
+ * AdaRound (Nagel et al. 2020; LearnedRoundSte of later Brevitas releases, no reference counterpart): the weights are
+ * frozen and `value`, shaped like x, is trained.  desc is the descriptor of bvq_fakequant_fwd for x [outer, channels,
+ * inner]; T = x_dtype = ct_dtype is also value's dtype; scale and zero-point have one element or `channels` elements
+ * each, in scale_dtype / zp_dtype, and scalar_mode, qmin / qmax and clamp_ste mean what they mean there.  Every line is
+ * one torch op of the composed route (brevitas_amd/core/function_wrapper/learned_round.py inside IntQuant), rounded to
+ * T where torch's device kernel rounds it; c0f = float(c0), c1f = float(c1):
+ *   h, BVQ_LR_HARD_SIGMOID (c0 = zeta - gamma, c1 = gamma; Python-float operands enter in float32 opmath):
+ *     sg = sigmoid(value) ; m = sg * c0f ; pre = m + c1f ; p = clamp(pre, 0, 1)          hard: p > 0.5
+ *   h, BVQ_LR_SIGMOID (c0 = temperature, c1 unused; a division by a host scalar is a multiplication by 1.0f / c0f):
+ *     u = value * (1.0f / c0f) ; sg = sigmoid(u) ; p = sg                                hard: value > 0
+ *   forward:  t = x / scale ; t = t + zp ; f = floor(t) ; r = f + p (hard: + 0 or 1)
+ *             c = where(r > qmax, qmax, r), then where(c < qmin, qmin, c) (a NaN passes) ; y = (c - zp) * scale
+ *   backward, given g = dL/dy in T (soft h only):
+ *             dc = g * scale ; dr = dc where clamp_ste or not (r > qmax or r < qmin), else 0
+ *             dx = dr / scale                                                            (dx nullable: not computed)
+ *             hard sigmoid: dp = dr where 0 <= pre <= 1 else 0 ; dp = dp * c0f ; dvalue = sigmoid_backward(dp, sg)
+ *             sigmoid:      dvalue = sigmoid_backward(dr, sg) * (1.0f / c0f)
+ *   with sigmoid and sigmoid_backward as torch's device kernels compute them (brevitas_amd/csrc/bvq_act.h).  The
+ *   products with a host scalar (* c0f, * (1.0f / c0f)) round the float32 product to T.  torch's float16 kernel does so
+ *   in its vectorised body only (its tail path rounds the exact product once and returns +0 for a -0 product), so the
+ *   Python routing takes these entries for float16 only where the two cannot differ ("Learned rounding").
+ *   Gradients of scale and zero-point are not computed.
+ * One launch each way: a flat stream of 16-byte lane accesses, no workspace, no atomics, no LDS.  forward reads x and
+ * value and writes y; backward reads g, x and value and writes dvalue, and dx when it is given.
+ * Covered: float32 / bfloat16 / float16; BVQ_PRE_NONE; BVQ_OUT_DEQUANT; a one-element scale and zero-point on any
+ * shape whose bytes are a multiple of 16, or per-channel operands with outer = 1 and inner * sizeof(T) a multiple of 16
+ * (a weight [R, K], or the regrouped [R * G, g]); fewer than 2^31 16-byte chunks and 2^30 channels; x, value, y, g, dvalue and dx on
+ * 16-byte boundaries.  Anything else returns BVQ_ERR_UNSUPPORTED with a bvq_last_error() text, found before anything
+ * touches the device; bvq_learned_round_supported answers 1 / 0 for a descriptor and the forward's tensors. */
+typedef enum bvq_learned_round_impl { BVQ_LR_HARD_SIGMOID = 0, BVQ_LR_SIGMOID = 1 } bvq_learned_round_impl;
+int bvq_learned_round_supported(const bvq_quant_desc* desc, const void* x, const void* value, const void* y);
+int bvq_learned_round_fwd(const bvq_quant_desc* desc, const void* x, const void* value, const void* scale,
+                          const void* zp, int impl, double c0, double c1, int hard, void* y, bvq_stream_t stream);
+int bvq_learned_round_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* value,
+                          const void* scale, const void* zp, int impl, double c0, double c1, void* dvalue, void* dx,
+                          bvq_stream_t stream);
 
 /* ---- MX block-scaled quantizers: groups sharing one power-of-two scale, minifloat or MXINT8 elements -----------------
  * The OCP Microscaling formats the gfx950 matrix units take natively, as quantize-dequantize for training (no
