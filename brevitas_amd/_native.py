@@ -7,6 +7,7 @@ PyTorch is used here as plumbing only: device memory (torch.empty), the current 
 device guard.  Signatures carry raw pointers and sizes.
 """
 import ctypes
+import operator
 import os
 
 import torch
@@ -47,6 +48,22 @@ class QuantDesc(ctypes.Structure):
         ('zp_per_channel', ctypes.c_int32), ('qmin', ctypes.c_float), ('qmax', ctypes.c_float),
         ('round_mode', ctypes.c_int32), ('scalar_mode', ctypes.c_int32), ('clamp_ste', ctypes.c_int32),
         ('out_kind', ctypes.c_int32), ('pre_op', ctypes.c_int32), ('codes_dtype', ctypes.c_int32)]
+
+    # the integer fields as the C++ autograd node takes and hands back a descriptor (csrc/bvq_autograd.cpp, desc_ints /
+    # desc_from: `dv`, in this order; qmin and qmax travel apart, as doubles)
+    DV_FIELDS = ('outer', 'channels', 'inner', 'x_dtype', 'ct_dtype', 'scale_dtype', 'zp_dtype', 'scale_per_channel',
+                 'zp_per_channel', 'round_mode', 'scalar_mode', 'clamp_ste', 'out_kind', 'pre_op', 'codes_dtype')
+
+    def to_dv(self):
+        return _DV_OF(self)
+
+    @classmethod
+    def from_dv(cls, dv, qmin, qmax):
+        """inverse of to_dv; entries of dv behind the descriptor's 15 are the node's own"""
+        return cls(qmin=qmin, qmax=qmax, **dict(zip(cls.DV_FIELDS, dv)))
+
+
+_DV_OF = operator.attrgetter(*QuantDesc.DV_FIELDS)
 
 
 class VariantDesc(ctypes.Structure):
@@ -178,7 +195,7 @@ _SIG = {
 
 EXPORTS = ('bvq_abi_version', 'bvq_last_error') + tuple(_SIG)
 
-_TORCH_DTYPES = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
+TORCH_DTYPES = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
 
 def _load(path=None, strict=True):
@@ -469,7 +486,7 @@ def stat_bwd(match, x, stat, gstat, outer, channels, inner, dx=None):
 def fakequant_fwd(desc, x, scale, zp, want_codes=False, want_y=True):
     """-> y, (y, codes) or codes alone; codes have the element type of desc.codes_dtype"""
     dev = require_device(x, scale, zp)
-    y = torch.empty(x.shape, dtype=_TORCH_DTYPES[desc.ct_dtype], device=dev) if want_y else None
+    y = torch.empty(x.shape, dtype=TORCH_DTYPES[desc.ct_dtype], device=dev) if want_y else None
     codes = torch.empty(x.shape, dtype=_CODES_TORCH[desc.codes_dtype], device=dev) if want_codes else None
     _launch(dev, 'bvq_fakequant_fwd', 'bvq_fakequant_fwd', ctypes.byref(desc), ptr(x), ptr(scale), ptr(zp), ptr(y),
             ptr(codes))
@@ -745,19 +762,27 @@ def absmax_fakequant_cluster(desc, x, min_val, int_threshold, scale_dtype, runni
     return stat, scale, y
 
 
+def _absmax_list_args(xs, outers, channels, inners):
+    """the leading arguments bvq_absmax_list_supported and bvq_absmax_scale_list share"""
+    n = len(xs)
+    return (dtype_code(xs[0].dtype), n, (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs]),
+            (ctypes.c_int64 * n)(*outers), channels, (ctypes.c_int64 * n)(*inners))
+
+
+def absmax_list_supported(xs, outers, channels, inners) -> bool:
+    """the list kernel covers these tensors (absmax_scale_list returns None only for want of an arrival buffer)"""
+    return bool(lib.bvq_absmax_list_supported(*_absmax_list_args(xs, outers, channels, inners)))
+
+
 def absmax_scale_list(xs, outers, channels, inners, min_val, int_threshold, scale_dtype):
     """abs-max statistic of a LIST of contiguous tensors [outers[i], channels, inners[i]] (the concatenation the
     reference builds is never materialised) and the scale derived from it, ONE launch:
     -> (stat [channels], scale [channels]), or None when the list is not covered / no arrival buffer"""
     dev = require_device(*xs)
-    n = len(xs)
-    dt = dtype_code(xs[0].dtype)
     for x, o, i in zip(xs, outers, inners):
         assert x.is_contiguous() and x.dtype == xs[0].dtype and x.numel() == o * channels * i
-    ptrs = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
-    oa = (ctypes.c_int64 * n)(*outers)
-    ia = (ctypes.c_int64 * n)(*inners)
-    if not lib.bvq_absmax_list_supported(dt, n, ptrs, oa, channels, ia):
+    args = _absmax_list_args(xs, outers, channels, inners)
+    if not lib.bvq_absmax_list_supported(*args):
         return None
     with _DeviceGuard(dev) as st:
         arrive = ws = None
@@ -769,7 +794,7 @@ def absmax_scale_list(xs, outers, channels, inners, min_val, int_threshold, scal
             ws = torch.empty(1 << 14, dtype=torch.uint8, device=dev)
         stat = torch.empty(channels, dtype=xs[0].dtype, device=dev)
         scale = torch.empty(channels, dtype=scale_dtype, device=dev)
-        _call('bvq_absmax_scale_list', None, dt, n, ptrs, oa, channels, ia, ptr(stat),
+        _call('bvq_absmax_scale_list', None, *args, ptr(stat),
               *_scale_args(min_val, int_threshold), dtype_code(scale_dtype), ptr(scale), ptr(arrive),
               arrive.numel() if arrive is not None else 0, ptr(ws), ws.numel() if ws is not None else 0, st)
     return stat, scale
@@ -1083,7 +1108,7 @@ def fakequant_bwd_stats(desc, g, x, scale, zp, stat, scale_dtype, int_threshold,
 def variant_fwd(desc, x, scale, pre_scale=None, zp=None, pre_zp=None):
     """forward of the sign / decoupled / truncating quantizers (include/bvq.h, bvq_variant_fwd) -> y in desc.ct_dtype"""
     dev = require_device(x, scale, pre_scale, zp, pre_zp)
-    y = torch.empty(x.shape, dtype=_TORCH_DTYPES[desc.ct_dtype], device=dev)
+    y = torch.empty(x.shape, dtype=TORCH_DTYPES[desc.ct_dtype], device=dev)
     _launch(dev, 'bvq_variant_fwd', None, ctypes.byref(desc), ptr(x), ptr(scale), ptr(pre_scale), ptr(zp), ptr(pre_zp),
             ptr(y))
     return y
@@ -1108,7 +1133,7 @@ def fakequant_fwd_bounds(desc, x, scale, zp, bounds):
     """bvq_fakequant_fwd with the integer range [qmin, qmax] read from the device (float32 [2]) -> y"""
     dev = require_device(x, scale, zp, bounds)
     assert bounds.dtype == torch.float32 and bounds.numel() == 2 and bounds.is_contiguous()
-    y = torch.empty(x.shape, dtype=_TORCH_DTYPES[desc.ct_dtype], device=dev)
+    y = torch.empty(x.shape, dtype=TORCH_DTYPES[desc.ct_dtype], device=dev)
     _launch(dev, 'bvq_fakequant_fwd_bounds', None, ctypes.byref(desc), ptr(x), ptr(scale), ptr(zp), ptr(bounds), ptr(y))
     return y
 

@@ -10,6 +10,7 @@ every intermediate is rounded to it, the output has it, and the gradient w.r.t. 
 x's dtype.  Layouts the kernels do not cover make `plan()` return None and the caller falls back
 to the op-by-op composition (same results, more passes).
 """
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -37,6 +38,13 @@ def is_nhwc(x: Tensor, channel_dim) -> bool:
     column-mapped kernels take as it lies (no NCHW copy and back)"""
     return channel_dim == 1 and x.dim() == 4 and not x.is_contiguous() \
         and x.is_contiguous(memory_format=torch.channels_last)
+
+
+def split_at_channel(x: Tensor, cd: int):
+    """x as [outer, channels, inner] around its dim `cd` -> (outer, channels, inner, nhwc); nhwc: see Plan.nhwc"""
+    if is_nhwc(x, cd):
+        return x.numel() // x.shape[1], x.shape[1], 1, True
+    return math.prod(x.shape[:cd]), x.shape[cd], math.prod(x.shape[cd + 1:]), False
 
 
 def _channel_dim(x: Tensor, t: Tensor):
@@ -72,15 +80,8 @@ def plan(x: Tensor, scale: Tensor, zp: Tensor) -> Optional[Plan]:
     cd = sd if sd is not None else zd
     if cd is None:
         return Plan(1, 1, x.numel(), False, False, ct)
-    if is_nhwc(x, cd):
-        return Plan(x.numel() // x.shape[1], x.shape[1], 1, sd is not None, zd is not None, ct, True)
-    outer = 1
-    for s in x.shape[:cd]:
-        outer *= s
-    inner = 1
-    for s in x.shape[cd + 1:]:
-        inner *= s
-    return Plan(outer, x.shape[cd], inner, sd is not None, zd is not None, ct)
+    outer, channels, inner, nhwc = split_at_channel(x, cd)
+    return Plan(outer, channels, inner, sd is not None, zd is not None, ct, nhwc)
 
 
 _ACT_OPS = {nat.PRE_RELU: torch.relu, nat.PRE_SIGMOID: torch.sigmoid, nat.PRE_TANH: torch.tanh}
@@ -114,9 +115,25 @@ def scalar_mode():
 
 def make_desc(p: Plan, x: Tensor, scale: Tensor, zp: Tensor, qmin, qmax, round_mode, clamp_ste, out_kind,
               pre_op=nat.PRE_NONE):
-    return nat.QuantDesc(p.outer, p.channels, p.inner, nat.dtype_code(x.dtype), nat.dtype_code(p.ct),
-                         nat.dtype_code(scale.dtype), nat.dtype_code(zp.dtype), int(p.scale_pc), int(p.zp_pc),
-                         qmin, qmax, round_mode, scalar_mode(), int(clamp_ste), out_kind, pre_op)
+    """the descriptor of a Plan: dtypes from the operands, the compute dtype from the plan"""
+    return nat.QuantDesc(outer=p.outer, channels=p.channels, inner=p.inner, x_dtype=nat.dtype_code(x.dtype),
+                         ct_dtype=nat.dtype_code(p.ct), scale_dtype=nat.dtype_code(scale.dtype),
+                         zp_dtype=nat.dtype_code(zp.dtype), scale_per_channel=int(p.scale_pc),
+                         zp_per_channel=int(p.zp_pc), qmin=qmin, qmax=qmax, round_mode=round_mode,
+                         scalar_mode=scalar_mode(), clamp_ste=int(clamp_ste), out_kind=out_kind, pre_op=pre_op)
+
+
+def channel_desc(outer, channels, inner, dtype, qmin, qmax, round_mode, clamp_ste, scale_dtype=None,
+                 zp_dtype=torch.float32, scale_pc=True, zp_pc=False, pre_op=nat.PRE_NONE):
+    """the descriptor of the statistic-scaled kernels: x of `dtype` as [outer, channels, inner], computed and dequantized
+    in that dtype, one scale per channel (or group) in `scale_dtype` (x's unless named), a zero zero-point (0-dim
+    float32) unless zp_dtype / zp_pc say one per channel"""
+    code = nat.dtype_code(dtype)
+    return nat.QuantDesc(outer=outer, channels=channels, inner=inner, x_dtype=code, ct_dtype=code,
+                         scale_dtype=code if scale_dtype is None else nat.dtype_code(scale_dtype),
+                         zp_dtype=nat.dtype_code(zp_dtype), scale_per_channel=int(scale_pc), zp_per_channel=int(zp_pc),
+                         qmin=qmin, qmax=qmax, round_mode=round_mode, scalar_mode=scalar_mode(),
+                         clamp_ste=int(clamp_ste), out_kind=nat.OUT_DEQUANT, pre_op=pre_op)
 
 
 def _reduce_like(sums: Tensor, like: Tensor) -> Tensor:
@@ -156,21 +173,33 @@ def _restore(t: Tensor, back) -> Tensor:
     return t if back is None else t.permute(back)
 
 
+def _quantize(p: Plan, xc: Tensor, back, scale: Tensor, zp: Tensor, qmin, qmax, round_mode, clamp_ste, out_kind, pre_op):
+    """the quantizer kernel on xc = _memory_order(x)[0] -> (descriptor, y in x's logical layout)"""
+    sc = scale.reshape(-1).contiguous()
+    zc = zp.reshape(-1).contiguous()
+    desc = make_desc(p, xc, sc, zc, qmin, qmax, round_mode, clamp_ste, out_kind, pre_op)
+    return desc, _restore(nat.fakequant_fwd(desc, xc, sc, zc), back)
+
+
+def _incoming(gy: Optional[Tensor], desc, xc: Tensor, back) -> Tensor:
+    """y's gradient as the backward kernels take it: in the compute dtype and the forward's element order; zeros when
+    none arrived (only `scale` was used downstream)"""
+    ct = nat.TORCH_DTYPES[desc.ct_dtype]
+    if gy is None:
+        return torch.zeros(xc.shape, dtype=ct, device=xc.device)
+    return _like_memory_order(gy.to(ct), back)
+
+
 class FakeQuantFn(Function):
     """IntQuant.forward / IntQuant.to_int on the fused kernel (B/core/quant/int_base.py:63-97)"""
 
     @staticmethod
     def forward(ctx, x, scale, zp, p, qmin, qmax, round_mode, clamp_ste, out_kind, pre_op=nat.PRE_NONE):
         xc, back = _memory_order(x, p.channels, p.nhwc)
-        sc = scale.reshape(-1).contiguous()
-        zc = zp.reshape(-1).contiguous()
-        desc = make_desc(p, xc, sc, zc, qmin, qmax, round_mode, clamp_ste, out_kind, pre_op)
-        y = nat.fakequant_fwd(desc, xc, sc, zc)
+        desc, y = _quantize(p, xc, back, scale, zp, qmin, qmax, round_mode, clamp_ste, out_kind, pre_op)
         ctx.desc = desc
         ctx.back = back
         ctx.save_for_backward(xc, scale, zp)
-        if back is not None:
-            y = y.permute(back)
         if out_kind == nat.OUT_INT:
             ctx.mark_non_differentiable(y)
         return y
@@ -180,8 +209,7 @@ class FakeQuantFn(Function):
         xc, scale, zp = ctx.saved_tensors
         desc = ctx.desc
         need_ds, need_dz = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        ct = {nat.F32: torch.float32, nat.BF16: torch.bfloat16, nat.F16: torch.float16}[desc.ct_dtype]
-        gy = _like_memory_order(gy.to(ct), ctx.back)
+        gy = _incoming(gy, desc, xc, ctx.back)
         dx, ds, dz = nat.fakequant_bwd(desc, gy, xc, scale.reshape(-1).contiguous(), zp.reshape(-1).contiguous(),
                                        need_ds, need_dz)
         if ctx.back is not None:
@@ -213,8 +241,7 @@ class FakeQuantBoundsFn(Function):
     def backward(ctx, gy):
         xc, scale, zp, bounds, qmin_t, qmax_t = ctx.saved_tensors
         desc = ctx.desc
-        ct = {nat.F32: torch.float32, nat.BF16: torch.bfloat16, nat.F16: torch.float16}[desc.ct_dtype]
-        gy = _like_memory_order(gy.to(ct), ctx.back)
+        gy = _incoming(gy, desc, xc, ctx.back)
         need_db = (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]) and not desc.clamp_ste
         dx, ds, db = nat.fakequant_bwd_bounds(desc, gy, xc, scale.reshape(-1).contiguous(), zp.reshape(-1).contiguous(),
                                               bounds, need_db)
@@ -223,7 +250,7 @@ class FakeQuantBoundsFn(Function):
         dmin = dmax = None
         if need_db:
             # the reference sums where()'s masked gradient in the clamp's dtype, then casts to the bound's
-            sums = db.sum(dim=1).to(ct)
+            sums = db.sum(dim=1).to(gy.dtype)
             dmin = sums[0].to(qmin_t.dtype).reshape(qmin_t.shape) if ctx.needs_input_grad[3] else None
             dmax = sums[1].to(qmax_t.dtype).reshape(qmax_t.shape) if ctx.needs_input_grad[4] else None
         return dx, ds, None, dmin, dmax, None, None, None, None
@@ -246,12 +273,9 @@ class LearnedScaleFakeQuantFn(Function):
         xc, back = _memory_order(x, p.channels, p.nhwc)
         sc = nat.learned_scale(value, min_val, thr_div, scale_dtype)
         zp = _zero_zero_point(x.device)
-        desc = make_desc(p, xc, sc, zp.reshape(-1), qmin, qmax, round_mode, clamp_ste, nat.OUT_DEQUANT, pre_op)
-        y = nat.fakequant_fwd(desc, xc, sc, zp.reshape(-1))
+        desc, y = _quantize(p, xc, back, sc, zp, qmin, qmax, round_mode, clamp_ste, nat.OUT_DEQUANT, pre_op)
         ctx.desc, ctx.back, ctx.args = desc, back, (min_val, thr_div)
         ctx.save_for_backward(xc, sc, zp, value)
-        if back is not None:
-            y = y.permute(back)
         return y, sc.view(value.shape)
 
     @staticmethod
@@ -259,7 +283,6 @@ class LearnedScaleFakeQuantFn(Function):
         xc, sc, zp, value = ctx.saved_tensors
         desc = ctx.desc
         min_val, thr_div = ctx.args
-        ct = {nat.F32: torch.float32, nat.BF16: torch.bfloat16, nat.F16: torch.float16}[desc.ct_dtype]
         if gy is None:  # only `scale` was used downstream: its own small autograd chain, no tensor pass
             if gscale is None:
                 return (None,) * 11
@@ -268,7 +291,7 @@ class LearnedScaleFakeQuantFn(Function):
                 v = torch.clamp_min(v, min_val)
             sign = torch.ge(v, 0.0).to(v.dtype) - torch.lt(v, 0.0).to(v.dtype)
             return None, (sign * (gscale.reshape(value.shape) / thr_div).to(v.dtype)), *(None,) * 9
-        gy = _like_memory_order(gy.to(ct), ctx.back)
+        gy = _incoming(gy, desc, xc, ctx.back)
         gs = gscale.reshape(-1).contiguous().to(sc.dtype) if gscale is not None else None
         dx, _, dvalue = nat.fakequant_bwd_learned(desc, gy, xc, sc, zp.reshape(-1), value, min_val, thr_div, gs)
         if not ctx.needs_input_grad[0]:
@@ -336,9 +359,8 @@ class VariantFn(Function):
     def backward(ctx, gy):
         xc, sc, ps, zc, pz = ctx.saved_tensors
         desc = ctx.desc
-        ct = {nat.F32: torch.float32, nat.BF16: torch.bfloat16, nat.F16: torch.float16}[desc.ct_dtype]
         need_ds, need_dp = ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ps is not None
-        dx, ds, dp = nat.variant_bwd(desc, gy.to(ct).contiguous(), xc, sc, ps, zc, pz, need_ds, need_dp)
+        dx, ds, dp = nat.variant_bwd(desc, _incoming(gy, desc, xc, None), xc, sc, ps, zc, pz, need_ds, need_dp)
         sshape, sdt, pre = ctx.shapes
         ds = ds.reshape(sshape).to(sdt) if need_ds else None
         dp = dp.reshape(pre[0]).to(pre[1]) if need_dp else None
@@ -410,43 +432,56 @@ def _as_dtype_value(v: float, dtype: torch.dtype) -> float:
     return r
 
 
+class ScaleRule(NamedTuple):
+    scale_dtype: torch.dtype  # of scale = stat / int_threshold
+    thr_div: float            # the value that division divides by
+    quot_dtype: torch.dtype   # of the backward's dscale / int_threshold
+    thr_bwd: float            # the value that one divides by
+
+
+def scale_rule(dtype: torch.dtype, scaling_shape, int_threshold: float, thr_dtype: torch.dtype = torch.float32,
+               thr_as_stored: bool = False) -> ScaleRule:
+    """torch's type promotion in `t / int_threshold`, t of `dtype` and shaped `scaling_shape` (forward: the statistic,
+    which has x's dtype; backward: the scale's gradient, which has the scale's), int_threshold the 0-dim tensor of
+    `thr_dtype` whose host value is given.  A dimensioned t keeps its dtype and the threshold is converted to it; a
+    0-dim t promotes with the threshold's dtype.  The 0-dim case divides by the host value as it is on the
+    statistic-scaled routes, and by that value as `thr_dtype` holds it where `thr_as_stored` (the learned-scale route,
+    whose int_threshold has the bit width's dtype): equal unless the threshold is not representable in thr_dtype
+    (32767 next to a bfloat16 bit width), so each route keeps its own."""
+    if len(scaling_shape) > 0:
+        thr = _as_dtype_value(int_threshold, dtype)
+        return ScaleRule(dtype, thr, dtype, thr)
+    scale_dtype = torch.promote_types(dtype, thr_dtype)
+    thr = _as_dtype_value(int_threshold, thr_dtype) if thr_as_stored else int_threshold
+    return ScaleRule(scale_dtype, thr, torch.promote_types(scale_dtype, thr_dtype), thr)
+
+
+def _running_buffer(runtime, channels: int) -> Optional[Tensor]:
+    """the running-statistic buffer of a _RuntimeStats when the kernels can fold the statistic into it (a plain
+    [channels] device tensor), else None; None for no runtime"""
+    if runtime is None:
+        return None
+    buf = runtime.running_stats
+    return buf if buf.is_cuda and buf.is_contiguous() and buf.numel() == channels and buf.dtype in _FLOATS else None
+
+
 def stats_scale(flat: Tensor, int_threshold: Tensor, sp, group, pre_op, running=None):
     """AbsMax statistic of the [outer, channels, inner] tensor `flat` and the scale derived from it:
     -> (stat [channels] in x's dtype, scale shaped sp.scaling_shape).  group: the tensor is one batch shard.
     running: (buffer, momentum, first_batch) of a _RuntimeStats to fold the statistic into in the same launch
     (sharded: the statistic -> scale launch behind the all-reduce)."""
+    rule = scale_rule(flat.dtype, sp.scaling_shape, sp.int_threshold, int_threshold.dtype)
+    fold = {} if running is None else dict(zip(('running', 'momentum', 'first_batch'), running))
     if group is None:
-        # statistic -> clamp_min -> / int_threshold in the reduction's own finishing launch.
-        # torch's promotion: a dimensioned threshold keeps its dtype (the 0-dim float32
-        # int_threshold is converted to it), a 0-dim one is promoted with float32.
-        if len(sp.scaling_shape) > 0:
-            scale_dtype, thr_div = flat.dtype, _as_dtype_value(sp.int_threshold, flat.dtype)
-        else:
-            scale_dtype = torch.promote_types(flat.dtype, int_threshold.dtype)
-            thr_div = sp.int_threshold
-        if running is not None:
-            buf, momentum, first = running
-            stat, scale = nat.absmax_scale(flat, sp.outer, sp.channels, sp.inner, sp.min_val, thr_div, scale_dtype,
-                                           pre_op, running=buf, momentum=momentum, first_batch=first)
-        else:
-            stat, scale = nat.absmax_scale(flat, sp.outer, sp.channels, sp.inner, sp.min_val, thr_div, scale_dtype,
-                                           pre_op)
-        return stat, scale.view(sp.scaling_shape)
-    # batch-sharded tensor: the statistic of the whole batch is the max over the shards
-    from brevitas_amd.distributed import sync_stat_max
-    stat32 = sync_stat_max(nat.stats(nat.STAT_ABSMAX, flat, sp.outer, sp.channels, sp.inner, out_f32=True,
-                                     pre_op=pre_op), group)
-    # statistic -> clamp_min -> / int_threshold with the promotion rules of the unsharded route, one launch
-    if len(sp.scaling_shape) > 0:
-        scale_dtype, thr_div = flat.dtype, _as_dtype_value(sp.int_threshold, flat.dtype)
+        # statistic -> clamp_min -> / int_threshold in the reduction's own finishing launch
+        stat, scale = nat.absmax_scale(flat, sp.outer, sp.channels, sp.inner, sp.min_val, rule.thr_div,
+                                       rule.scale_dtype, pre_op, **fold)
     else:
-        scale_dtype = torch.promote_types(flat.dtype, int_threshold.dtype)
-        thr_div = sp.int_threshold
-    if running is not None:
-        buf, momentum, first = running
-        stat, scale = nat.scale_from_stat(stat32, flat.dtype, sp.min_val, thr_div, scale_dtype, buf, momentum, first)
-    else:
-        stat, scale = nat.scale_from_stat(stat32, flat.dtype, sp.min_val, thr_div, scale_dtype)
+        # batch-sharded tensor: the statistic of the whole batch is the max over the shards, then the same in one launch
+        from brevitas_amd.distributed import sync_stat_max
+        stat32 = sync_stat_max(nat.stats(nat.STAT_ABSMAX, flat, sp.outer, sp.channels, sp.inner, out_f32=True,
+                                         pre_op=pre_op), group)
+        stat, scale = nat.scale_from_stat(stat32, flat.dtype, sp.min_val, rule.thr_div, rule.scale_dtype, **fold)
     return stat, scale.view(sp.scaling_shape)
 
 
@@ -466,64 +501,46 @@ class StatsFakeQuantFn(Function):
         ctx.pre_op = pre_op
         xc, back = _memory_order(x, sp.channels, sp.nhwc)
         ctx.back = back
-        flat = xc.reshape(-1)
         zp = _zero_zero_point(x.device)
+        # _RuntimeStats' running average rides on the launch that finishes the statistic when its buffer is a plain
+        # [channels] device tensor (the module is told through `bvq_running_folded`)
+        running = _running_buffer(runtime, sp.channels)
         fused = None
         if group is None and config.FUSED_PATHS and x.dtype in _FLOATS:
             # one launch: the channel stays in registers between the reduction and the quantization
             # (x is read once).  Covers channels that fit a team's registers; None otherwise.
-            if len(sp.scaling_shape) > 0:
-                scale_dtype, thr_div = x.dtype, _as_dtype_value(sp.int_threshold, x.dtype)
-            else:
-                scale_dtype = torch.promote_types(x.dtype, int_threshold.dtype)
-                thr_div = sp.int_threshold
-            code = nat.dtype_code(x.dtype)
-            desc = nat.QuantDesc(sp.outer, sp.channels, sp.inner, code, code, nat.dtype_code(scale_dtype),
-                                 nat.dtype_code(zp.dtype), int(sp.channels > 1), 0, qmin, qmax, round_mode,
-                                 scalar_mode(), int(clamp_ste), nat.OUT_DEQUANT, pre_op)
-            fused = nat.stats_fakequant_fwd(desc, xc, sp.min_val, thr_div, scale_dtype)
-            if fused is None and len(sp.scaling_shape) > 0 and sp.channels > 1:
-                # a channel larger than one workgroup: held by a cluster of workgroups, x still read once; the running
-                # statistic rides on the same launch
-                running = None
-                if runtime is not None:
-                    buf = runtime.running_stats
-                    if buf.is_cuda and buf.is_contiguous() and buf.numel() == sp.channels and buf.dtype in _FLOATS:
-                        running = buf
-                if runtime is None or running is not None:
-                    fused = nat.absmax_fakequant_cluster(
-                        desc, xc, sp.min_val, thr_div, scale_dtype, running,
-                        runtime.momentum if running is not None else 0.0,
-                        runtime.first_batch if running is not None else False)
-                    if fused is not None and running is not None:
-                        runtime.bvq_running_folded = True
+            rule = scale_rule(x.dtype, sp.scaling_shape, sp.int_threshold, int_threshold.dtype)
+            desc = channel_desc(sp.outer, sp.channels, sp.inner, x.dtype, qmin, qmax, round_mode, clamp_ste,
+                                scale_dtype=rule.scale_dtype, scale_pc=sp.channels > 1, pre_op=pre_op)
+            fused = nat.stats_fakequant_fwd(desc, xc, sp.min_val, rule.thr_div, rule.scale_dtype)
+            if fused is None and len(sp.scaling_shape) > 0 and sp.channels > 1 and \
+                    (runtime is None or running is not None):
+                # a channel larger than one workgroup: held by a cluster of workgroups, x still read once
+                fused = nat.absmax_fakequant_cluster(
+                    desc, xc, sp.min_val, rule.thr_div, rule.scale_dtype, running,
+                    runtime.momentum if running is not None else 0.0,
+                    runtime.first_batch if running is not None else False)
+                if fused is not None and running is not None:
+                    runtime.bvq_running_folded = True
         if fused is not None:
             stat, scale, y = fused
             scale = scale.view(sp.scaling_shape)
+            y = _restore(y, back)
         else:
-            # _RuntimeStats' running average rides on the statistic's finishing launch when its buffer is a plain
-            # [channels] device tensor (the module is told through `bvq_running_folded`)
-            running = None
-            if runtime is not None:
-                buf = runtime.running_stats
-                if buf.is_cuda and buf.is_contiguous() and buf.numel() == sp.channels and buf.dtype in _FLOATS:
-                    running = (buf, runtime.momentum, runtime.first_batch)
-                    runtime.bvq_running_folded = True
-            stat, scale = stats_scale(flat, int_threshold, sp, group, pre_op, running)
+            if running is not None:
+                running = (running, runtime.momentum, runtime.first_batch)
+                runtime.bvq_running_folded = True
+            stat, scale = stats_scale(xc.reshape(-1), int_threshold, sp, group, pre_op, running)
             p = Plan(sp.outer, sp.channels, sp.inner, sp.channels > 1, False, torch.result_type(x, scale), sp.nhwc)
             if not (p.ct == x.dtype or p.ct == torch.float32):
                 raise nat.BvqError('StatsFakeQuantFn: unsupported operand layout (caller must pre-check)')
-            sc = scale.reshape(-1).contiguous()
-            desc = make_desc(p, xc, sc, zp.reshape(-1), qmin, qmax, round_mode, clamp_ste, nat.OUT_DEQUANT, pre_op)
-            y = nat.fakequant_fwd(desc, xc, sc, zp.reshape(-1))
+            desc, y = _quantize(p, xc, back, scale, zp, qmin, qmax, round_mode, clamp_ste, nat.OUT_DEQUANT, pre_op)
         ctx.desc = desc
         ctx.sp = sp
         ctx.group = group
         ctx.save_for_backward(xc, scale, zp, stat, int_threshold)
         stat_out = stat.view(sp.scaling_shape)
         ctx.mark_non_differentiable(stat_out)
-        if back is not None:
-            y = y.permute(back)
         return y, scale, stat_out
 
     @staticmethod
@@ -537,11 +554,9 @@ class StatsFakeQuantFn(Function):
 def group_quant_call(x: Tensor, group_size: int, int_threshold: float, qmin: float, qmax: float, clamp_ste):
     """-> (descriptor, threshold divisor) that nat.group_quant_fwd / group_quant_bwd take for x in groups of `group_size`
     (GroupStatsFakeQuantFn, and the tests that launch the kernels through those wrappers)"""
-    code = nat.dtype_code(x.dtype)
-    desc = nat.QuantDesc(1, x.numel() // group_size, group_size, code, code, code, nat.F32, 1, 0, qmin, qmax,
-                         nat.ROUND, scalar_mode(), int(clamp_ste), nat.OUT_DEQUANT, nat.PRE_NONE)
-    # a dimensioned threshold keeps its dtype: the 0-dim float32 int_threshold is converted to it
-    return desc, _as_dtype_value(int_threshold, x.dtype)
+    groups = x.numel() // group_size
+    desc = channel_desc(1, groups, group_size, x.dtype, qmin, qmax, nat.ROUND, clamp_ste)
+    return desc, scale_rule(x.dtype, (groups, 1), int_threshold).thr_div
 
 
 def _group_grads(x: Tensor, gy, side, side_dtype=None, align_side=False):
@@ -589,10 +604,9 @@ class GroupStatsFakeQuantFn(Function):
 def group_shifted_call(x: Tensor, group_size: int, int_threshold: float, qmin: float, qmax: float, clamp_ste):
     """group_quant_call for the asymmetric kernels (nat.group_shifted_fwd / group_shifted_bwd): one zero-point per
     group, in x's dtype"""
-    code = nat.dtype_code(x.dtype)
-    desc = nat.QuantDesc(1, x.numel() // group_size, group_size, code, code, code, code, 1, 1, qmin, qmax,
-                         nat.ROUND, scalar_mode(), int(clamp_ste), nat.OUT_DEQUANT, nat.PRE_NONE)
-    return desc, _as_dtype_value(int_threshold, x.dtype)
+    groups = x.numel() // group_size
+    desc = channel_desc(1, groups, group_size, x.dtype, qmin, qmax, nat.ROUND, clamp_ste, zp_dtype=x.dtype, zp_pc=True)
+    return desc, scale_rule(x.dtype, (groups, 1), int_threshold).thr_div
 
 
 class GroupShiftedFakeQuantFn(Function):
@@ -701,15 +715,11 @@ class StatsGraphFakeQuantFn(Function):
         p = plan(xc if back is None else x, scale, zp)
         if p is None or p.zp_pc or p.nhwc != sp.nhwc:
             raise nat.BvqError('StatsGraphFakeQuantFn: operand layout not covered by the quantizer kernels')
-        sc = scale.reshape(-1).contiguous()
-        desc = make_desc(p, xc, sc, zp.reshape(-1), qmin, qmax, round_mode, clamp_ste, nat.OUT_DEQUANT, pre_op)
-        y = nat.fakequant_fwd(desc, xc, sc, zp.reshape(-1))
+        desc, y = _quantize(p, xc, back, scale, zp, qmin, qmax, round_mode, clamp_ste, nat.OUT_DEQUANT, pre_op)
         ctx.desc, ctx.sp, ctx.back, ctx.pre_op = desc, sp, back, pre_op
         ctx.graph = (s_leaf, scale_g, params)
         ctx.save_for_backward(xc, scale, zp, stat)
         ctx.mark_non_differentiable(stat)
-        if back is not None:
-            y = y.permute(back)
         return y, scale, stat
 
     @staticmethod
@@ -718,13 +728,9 @@ class StatsGraphFakeQuantFn(Function):
         desc, sp = ctx.desc, ctx.sp
         s_leaf, scale_g, params = ctx.graph
         none = (None,) * 9
-        ct = {nat.F32: torch.float32, nat.BF16: torch.bfloat16, nat.F16: torch.float16}[desc.ct_dtype]
         if gy is None and gscale is None:
             return none + (None,) * len(params)
-        if gy is None:
-            gy = torch.zeros(xc.shape, dtype=ct, device=xc.device)
-        else:
-            gy = _like_memory_order(gy.to(ct), ctx.back)
+        gy = _incoming(gy, desc, xc, ctx.back)
         stat_x = stat.reshape(-1).to(xc.dtype).contiguous()
         dx, ds, _, ties = nat.fakequant_bwd(desc, gy, xc, scale.reshape(-1).contiguous(), zp.reshape(-1), True, False,
                                             tie_stat=stat_x)
@@ -747,17 +753,13 @@ def _list_views(params, sp):
 
 def list_stats_supported(params, sp) -> bool:
     """the one-launch statistic over a parameter list applies (nat.absmax_scale_list would not return None)"""
-    import ctypes
     if not config.FUSED_PATHS or params[0].dtype not in _FLOATS or sp.outer != 1 or sp.nhwc:
         return False
     flats, outers, inners = _list_views(params, sp)
-    n = len(flats)
     st = nat.stream_ptr(flats[0].device)
     if sp.channels > 1 and nat.arrival_buffer(flats[0].device, st, max(2 * sp.channels, 18)) is None:
         return False
-    return bool(nat.lib.bvq_absmax_list_supported(
-        nat.dtype_code(flats[0].dtype), n, (ctypes.c_void_p * n)(*[f.data_ptr() for f in flats]),
-        (ctypes.c_int64 * n)(*outers), sp.channels, (ctypes.c_int64 * n)(*inners)))
+    return nat.absmax_list_supported(flats, outers, sp.channels, inners)
 
 
 class ListStatsFakeQuantFn(Function):
@@ -779,12 +781,8 @@ class ListStatsFakeQuantFn(Function):
     def forward(ctx, x, int_threshold, sp, qmin, qmax, round_mode, clamp_ste, index, *params):
         ctx.set_materialize_grads(False)
         flats, outers, inners = _list_views(params, sp)
-        if len(sp.scaling_shape) > 0:
-            scale_dtype, thr_div = x.dtype, _as_dtype_value(sp.int_threshold, x.dtype)
-        else:
-            scale_dtype = torch.promote_types(x.dtype, int_threshold.dtype)
-            thr_div = sp.int_threshold
-        out = nat.absmax_scale_list(flats, outers, sp.channels, inners, sp.min_val, thr_div, scale_dtype)
+        rule = scale_rule(x.dtype, sp.scaling_shape, sp.int_threshold, int_threshold.dtype)
+        out = nat.absmax_scale_list(flats, outers, sp.channels, inners, sp.min_val, rule.thr_div, rule.scale_dtype)
         if out is None:
             raise nat.BvqError('ListStatsFakeQuantFn: list not covered (caller must pre-check list_stats_supported)')
         stat, scale = out
@@ -794,9 +792,7 @@ class ListStatsFakeQuantFn(Function):
         p = Plan(sp.outer, sp.channels, sp.inner, sp.channels > 1, False, torch.result_type(x, scale), False)
         if not (p.ct == x.dtype or p.ct == torch.float32):
             raise nat.BvqError('ListStatsFakeQuantFn: unsupported operand layout')
-        sc = scale.reshape(-1).contiguous()
-        desc = make_desc(p, xc, sc, zp.reshape(-1), qmin, qmax, round_mode, clamp_ste, nat.OUT_DEQUANT, nat.PRE_NONE)
-        y = nat.fakequant_fwd(desc, xc, sc, zp.reshape(-1))
+        desc, y = _quantize(p, xc, None, scale, zp, qmin, qmax, round_mode, clamp_ste, nat.OUT_DEQUANT, nat.PRE_NONE)
         ctx.desc, ctx.sp, ctx.index, ctx.inners = desc, sp, index, inners
         ctx.save_for_backward(scale, zp, stat, int_threshold, *params)
         stat_out = stat.view(sp.scaling_shape)
@@ -812,8 +808,7 @@ class ListStatsFakeQuantFn(Function):
         if gy is None and gscale is None:
             return none + (None,) * len(params)
         x = params[index].detach()
-        ct = {nat.F32: torch.float32, nat.BF16: torch.bfloat16, nat.F16: torch.float16}[desc.ct_dtype]
-        gy = torch.zeros(x.shape, dtype=ct, device=x.device) if gy is None else gy.to(ct).contiguous()
+        gy = _incoming(gy, desc, x, None)
         stat_x = stat.reshape(-1).to(x.dtype).contiguous()
         dx, ds, _, own = nat.fakequant_bwd(desc, gy, x, scale.reshape(-1).contiguous(), zp.reshape(-1), True, False,
                                            tie_stat=stat_x)
@@ -853,20 +848,17 @@ class ListStatsFakeQuantFn(Function):
 def stats_backward(xc, scale, zp, stat, int_threshold, desc, sp, group, pre_op, back, gy, gscale):
     """backward of StatsFakeQuantFn (also the fallback of the C++ node, brevitas_amd/csrc/bvq_autograd.cpp) -> dx or None;
     sp: anything with outer / channels / inner / int_threshold"""
-    ct = {nat.F32: torch.float32, nat.BF16: torch.bfloat16, nat.F16: torch.float16}[desc.ct_dtype]
-    if gy is None:  # only `scale` was used downstream
-        if gscale is None:
-            return None
-        gy = torch.zeros(xc.shape, dtype=ct, device=xc.device)
-    else:
-        gy = _like_memory_order(gy.to(ct), back)
+    if gy is None and gscale is None:
+        return None
+    gy = _incoming(gy, desc, xc, back)
+    # dscale / int_threshold: the forward's division, on the scale's gradient
+    rule = scale_rule(scale.dtype, scale.shape, sp.int_threshold, int_threshold.dtype)
     if group is None and gscale is None and sp.channels > 1 and scale.numel() == sp.channels:
         # per-channel scale, nothing else feeding the scale's gradient: two launches in all -- the backward
         # kernel (dx, per-unit dscale sums and arg-max positions) and one finishing kernel that sums,
         # converts dscale into the statistic's gradient and deposits it (None: layout not covered)
-        thr_div = _as_dtype_value(sp.int_threshold, scale.dtype)
         dx = nat.fakequant_bwd_stats(desc, gy, xc, scale.reshape(-1).contiguous(), zp.reshape(-1), stat,
-                                     scale.dtype, thr_div, scale.dtype)
+                                     scale.dtype, rule.thr_bwd, rule.quot_dtype)
         if dx is not None:
             return _restore(dx, back)
     if group is not None and gscale is None and sp.channels > 1 and scale.numel() == sp.channels:
@@ -883,9 +875,8 @@ def stats_backward(xc, scale, zp, stat, int_threshold, desc, sp, group, pre_op, 
                 dist.all_gather_into_tensor(gathered, msg, group=group)
             else:
                 gathered = msg
-            thr_div = _as_dtype_value(sp.int_threshold, scale.dtype)
             nat.shard_unpack_deposit(xc.reshape(-1), dx.reshape(-1), gathered, world, sp.channels, rank, pos, sp.inner,
-                                     scale.dtype, thr_div, scale.dtype, pre_op)
+                                     scale.dtype, rule.thr_bwd, rule.quot_dtype, pre_op)
             return _restore(dx, back)
     # one pass: dx, the scale-gradient sums and the positions attaining the statistic
     dx, ds, _, ties = nat.fakequant_bwd(desc, gy, xc, scale.reshape(-1).contiguous(), zp.reshape(-1), True,
@@ -893,10 +884,7 @@ def stats_backward(xc, scale, zp, stat, int_threshold, desc, sp, group, pre_op, 
     total_ties = None
     if group is None and gscale is None and ds.numel() == scale.numel():
         # dscale -> dstat -> deposit in one launch (same rounding points as the ops below)
-        dimensioned = scale.dim() > 0
-        quot_dtype = scale.dtype if dimensioned else torch.promote_types(scale.dtype, int_threshold.dtype)
-        thr_div = _as_dtype_value(sp.int_threshold, scale.dtype) if dimensioned else sp.int_threshold
-        nat.stat_tie_apply_dscale(xc.reshape(-1), stat, ds, scale.dtype, thr_div, quot_dtype, ties,
+        nat.stat_tie_apply_dscale(xc.reshape(-1), stat, ds, scale.dtype, rule.thr_bwd, rule.quot_dtype, ties,
                                   dx.reshape(-1), sp.outer, sp.channels, sp.inner, pre_op=pre_op)
         return _restore(dx, back)
     if group is not None:
@@ -934,10 +922,9 @@ class _SpLike(NamedTuple):
 def _fast_backward_fallback(xc, scale, zp, stat, int_threshold, dv, qr, shape, gy, gscale, group=None):
     """what the C++ nodes cannot do themselves (a gradient arriving through `scale`, an unaligned or strided gradient,
     a batch-sharded whole-tensor statistic)"""
-    desc = nat.QuantDesc(dv[0], dv[1], dv[2], dv[3], dv[4], dv[5], dv[6], dv[7], dv[8], qr[0], qr[1], dv[9], dv[10],
-                         dv[11], dv[12], dv[13], dv[14])
-    sp = _SpLike(dv[0], dv[1], dv[2], qr[3])
-    return stats_backward(xc, scale.view(shape), zp, stat, int_threshold, desc, sp, group, dv[13], None, gy, gscale)
+    desc = nat.QuantDesc.from_dv(dv, qr[0], qr[1])
+    sp = _SpLike(desc.outer, desc.channels, desc.inner, qr[3])  # qr: qmin, qmax, thr_bwd, the threshold's host value
+    return stats_backward(xc, scale.view(shape), zp, stat, int_threshold, desc, sp, group, desc.pre_op, None, gy, gscale)
 
 
 def _fast_module():
@@ -959,33 +946,44 @@ def _fast_module():
     return _FAST
 
 
-def fast_stats_fakequant(x, int_threshold, sp, qmin, qmax, round_mode, clamp_ste, pre_op):
-    """StatsFakeQuantFn through the C++ node -> (y, scale, stat), or None: not a case it covers (per-tensor scale,
-    channels_last / strided input, layouts outside the one-launch forward, no extension built, timers active)"""
+def _fast_gate(x, sp):
+    """the C++ node's module when it can take x (a dense device tensor in NCHW order, no timers bracketing the calls,
+    the current device), else None"""
     mod = _fast_module()
-    if not mod or not x.is_cuda or sp.nhwc or sp.channels <= 1 or not x.is_contiguous() or x.dtype not in _FLOATS \
-            or not config.FUSED_PATHS:
+    if not mod or not x.is_cuda or sp.nhwc or not x.is_contiguous() or x.dtype not in _FLOATS or not config.FUSED_PATHS:
         return None
     timer = nat._timer
     if timer is not None and getattr(timer, 'enabled', True):
         return None  # bench.py is bracketing the C-ABI calls of this step with HIP events: keep them visible
     if x.device.index is not None and x.device.index != torch.cuda.current_device():
         return None  # the node launches on the current device: the Python route switches devices around its calls
-    if len(sp.scaling_shape) > 0:
-        scale_dtype, thr_div = x.dtype, _as_dtype_value(sp.int_threshold, x.dtype)
-    else:
-        scale_dtype = torch.promote_types(x.dtype, int_threshold.dtype)
-        thr_div = sp.int_threshold
-    code, sdt = nat.dtype_code(x.dtype), nat.dtype_code(scale_dtype)
-    zp = _zero_zero_point(x.device)
-    dv = (sp.outer, sp.channels, sp.inner, code, code, sdt, nat.dtype_code(zp.dtype), 1, 0, round_mode, scalar_mode(),
-          int(clamp_ste), nat.OUT_DEQUANT, pre_op, 0)
-    thr_bwd = _as_dtype_value(sp.int_threshold, scale_dtype)
+    return mod
+
+
+def _node_dv(sp, dtype, scale_dtype, round_mode, clamp_ste, pre_op):
+    """channel_desc(sp.outer, sp.channels, sp.inner, dtype, ..., scale_dtype=scale_dtype, scale_pc=sp.channels > 1,
+    pre_op=pre_op).to_dv(), written out: the node builds its own bvq_quant_desc from these integers, and a ctypes
+    struct made only to be read back costs 2 of the ~48 us a weight step spends on the host (tools/host_cost.py).
+    tests/test_fused_host_rules.py holds the two equal."""
+    code = nat.dtype_code(dtype)
+    return (sp.outer, sp.channels, sp.inner, code, code, nat.dtype_code(scale_dtype), nat.F32, int(sp.channels > 1), 0,
+            round_mode, scalar_mode(), int(clamp_ste), nat.OUT_DEQUANT, pre_op, 0)
+
+
+def fast_stats_fakequant(x, int_threshold, sp, qmin, qmax, round_mode, clamp_ste, pre_op):
+    """StatsFakeQuantFn through the C++ node -> (y, scale, stat), or None: not a case it covers (per-tensor scale,
+    channels_last / strided input, layouts outside the one-launch forward, no extension built, timers active)"""
+    mod = _fast_gate(x, sp)
+    if mod is None or sp.channels <= 1:
+        return None
+    # (more than one channel: the scaling shape is dimensioned, and the rule's backward pair is the node's)
+    rule = scale_rule(x.dtype, sp.scaling_shape, sp.int_threshold, int_threshold.dtype)
+    dv = _node_dv(sp, x.dtype, rule.scale_dtype, round_mode, clamp_ste, pre_op)
     st = nat.stream_ptr(x.device)
     arrive = nat.arrival_buffer(x.device, st, sp.channels) if nat.ONEPASS_BWD else None
-    return mod.stats_fakequant(x, zp, int_threshold, arrive, dv, float(qmin), float(qmax), float(sp.min_val or 0.0),
-                               bool(sp.min_val), float(thr_div), float(thr_bwd), float(sp.int_threshold), sdt,
-                               list(sp.scaling_shape), st)
+    return mod.stats_fakequant(x, _zero_zero_point(x.device), int_threshold, arrive, dv, float(qmin), float(qmax),
+                               float(sp.min_val or 0.0), bool(sp.min_val), float(rule.thr_div), float(rule.thr_bwd),
+                               float(sp.int_threshold), dv[5], list(sp.scaling_shape), st)
 
 
 def fast_act_stats_fakequant(x, int_threshold, sp, qmin, qmax, round_mode, clamp_ste, pre_op, group, runtime):
@@ -993,46 +991,28 @@ def fast_act_stats_fakequant(x, int_threshold, sp, qmin, qmax, round_mode, clamp
     optionally batch-sharded with its two collectives) through the C++ node -> (y, scale, stat) with
     `runtime.bvq_running_folded` set, or None: not a case it covers (channels_last / strided / unaligned input, a running
     buffer that is not a plain [channels] device tensor, no extension built, timers active)."""
-    mod = _fast_module()
-    if not mod or not hasattr(mod, 'act_stats_fakequant') or not x.is_cuda or sp.nhwc or not x.is_contiguous() \
-            or x.dtype not in _FLOATS or not config.FUSED_PATHS or x.numel() == 0:
-        return None
-    timer = nat._timer
-    if timer is not None and getattr(timer, 'enabled', True):
-        return None  # bench.py is bracketing the C-ABI calls of this step with HIP events: keep them visible
-    if x.device.index is not None and x.device.index != torch.cuda.current_device():
+    mod = _fast_gate(x, sp)
+    if mod is None or not hasattr(mod, 'act_stats_fakequant') or x.numel() == 0:
         return None
     if group is not None and not config.CPP_AUTOGRAD_SHARDED:
         return None
-    running = None
-    momentum, first = 0.0, False
-    if runtime is not None:
-        buf = runtime.running_stats
-        if not (buf.is_cuda and buf.is_contiguous() and buf.numel() == sp.channels and buf.dtype in _FLOATS):
-            return None
-        running, momentum, first = buf, runtime.momentum, runtime.first_batch
-    if len(sp.scaling_shape) > 0:
-        scale_dtype, thr_div = x.dtype, _as_dtype_value(sp.int_threshold, x.dtype)
-        quot_dtype, thr_bwd = scale_dtype, _as_dtype_value(sp.int_threshold, scale_dtype)
-    else:
-        scale_dtype = torch.promote_types(x.dtype, int_threshold.dtype)
-        thr_div = sp.int_threshold
-        quot_dtype, thr_bwd = torch.promote_types(scale_dtype, int_threshold.dtype), sp.int_threshold
+    running = _running_buffer(runtime, sp.channels)
+    if runtime is not None and running is None:
+        return None
+    momentum, first = (runtime.momentum, runtime.first_batch) if runtime is not None else (0.0, False)
+    rule = scale_rule(x.dtype, sp.scaling_shape, sp.int_threshold, int_threshold.dtype)
     if sp.channels > 1 and len(sp.scaling_shape) == 0:
         return None
-    ct = torch.result_type(x, torch.empty(sp.scaling_shape, dtype=scale_dtype, device='meta'))
+    ct = torch.result_type(x, torch.empty(sp.scaling_shape, dtype=rule.scale_dtype, device='meta'))
     if ct != x.dtype:
         return None
-    code, sdt = nat.dtype_code(x.dtype), nat.dtype_code(scale_dtype)
-    zp = _zero_zero_point(x.device)
+    dv = _node_dv(sp, x.dtype, rule.scale_dtype, round_mode, clamp_ste, pre_op)
     st = nat.stream_ptr(x.device)
     arrive = nat.arrival_buffer(x.device, st, max(2 * sp.channels, 18))
-    dv = (sp.outer, sp.channels, sp.inner, code, code, sdt, nat.dtype_code(zp.dtype), int(sp.channels > 1), 0, round_mode,
-          scalar_mode(), int(clamp_ste), nat.OUT_DEQUANT, pre_op, 0)
-    out = mod.act_stats_fakequant(x, zp, int_threshold, running, arrive, dv, float(qmin), float(qmax),
-                                  float(sp.min_val or 0.0), bool(sp.min_val), float(thr_div), float(thr_bwd),
-                                  float(sp.int_threshold), sdt, nat.dtype_code(quot_dtype), list(sp.scaling_shape), st,
-                                  float(momentum), bool(first), group)
+    out = mod.act_stats_fakequant(x, _zero_zero_point(x.device), int_threshold, running, arrive, dv, float(qmin),
+                                  float(qmax), float(sp.min_val or 0.0), bool(sp.min_val), float(rule.thr_div),
+                                  float(rule.thr_bwd), float(sp.int_threshold), dv[5], nat.dtype_code(rule.quot_dtype),
+                                  list(sp.scaling_shape), st, float(momentum), bool(first), group)
     if out is not None and runtime is not None:
         runtime.bvq_running_folded = True
     return out

@@ -75,17 +75,27 @@ class RescalingIntQuant(torch.nn.Module):
         self.__dict__['_bvq_template'] = (key, tmpl)
         return tmpl
 
-    def _build_stats_template(self, bw):
-        if not config.FUSED_PATHS or bw is None:
-            return None
+    def _plain_int_quant(self, bw):
+        """(qmin, qmax, round_mode, clamp_ste, int_threshold) on the host if this is a plain IntQuant (no delay, a
+        rounding and a clamp the kernels know) with a zero zero-point, IntScaling and the host-known bit width `bw`;
+        else None"""
         iq = self.int_quant
-        if type(iq) is not IntQuant or not isinstance(iq.delay_wrapper.delay_impl, _NoDelay):
+        if bw is None or type(iq) is not IntQuant or not isinstance(iq.delay_wrapper.delay_impl, _NoDelay):
             return None
-        if getattr(iq.float_to_int_impl, 'bvq_round_mode', None) is None or \
-                getattr(iq.tensor_clamp_impl, 'bvq_clamp_ste', None) is None:
+        round_mode = getattr(iq.float_to_int_impl, 'bvq_round_mode', None)
+        clamp_ste = getattr(iq.tensor_clamp_impl, 'bvq_clamp_ste', None)
+        if round_mode is None or clamp_ste is None:
             return None
         if type(self.zero_point_impl) is not ZeroZeroPoint or type(self.int_scaling_impl) is not IntScaling:
             return None
+        qmin, qmax = int_range_host(iq.signed, iq.narrow_range, bw)
+        return qmin, qmax, round_mode, clamp_ste, self.int_scaling_impl.host_value(bw)
+
+    def _build_stats_template(self, bw):
+        plain = self._plain_int_quant(bw) if config.FUSED_PATHS else None
+        if plain is None:
+            return None
+        qmin, qmax, round_mode, clamp_ste, int_thr = plain
         sc = self.scaling_impl
         runtime, weight, shared = None, None, None
         if type(sc) is RuntimeStatsScaling:
@@ -121,12 +131,11 @@ class RescalingIntQuant(torch.nn.Module):
             per_channel = True
         else:
             return None
-        qmin, qmax = int_range_host(iq.signed, iq.narrow_range, bw)
         if shared is not None and (post is not None or len(shared) > 8):
             return None
         return dict(runtime=runtime, weight=weight, shared=shared, view=view, shape=shape, min_val=min_val, post=post,
-                    per_channel=per_channel, int_thr=self.int_scaling_impl.host_value(bw), qmin=qmin, qmax=qmax,
-                    round_mode=iq.float_to_int_impl.bvq_round_mode, clamp_ste=iq.tensor_clamp_impl.bvq_clamp_ste)
+                    per_channel=per_channel, int_thr=int_thr, qmin=qmin, qmax=qmax, round_mode=round_mode,
+                    clamp_ste=clamp_ste)
 
     def _stats_plan(self, x: Tensor, bit_width: Tensor):
         """(StatsPlan, template) if a recognised fused graph applies to this input, else None"""
@@ -162,16 +171,9 @@ class RescalingIntQuant(torch.nn.Module):
         padded = (1,) * (x.dim() - len(shape)) + shape
         if len(shape) > x.dim() or padded != want or x.shape[cd] == 1:
             return None
-        if _fused.is_nhwc(x, cd):  # dense channels_last activation: [N*H*W, C] in memory, column-mapped kernels
-            return _fused.StatsPlan(x.numel() // x.shape[1], x.shape[1], 1, shape, tmpl['min_val'], tmpl['int_thr'],
-                                    True), tmpl
-        outer = 1
-        for d in x.shape[:cd]:
-            outer *= d
-        inner = 1
-        for d in x.shape[cd + 1:]:
-            inner *= d
-        return _fused.StatsPlan(outer, x.shape[cd], inner, shape, tmpl['min_val'], tmpl['int_thr']), tmpl
+        # (a dense channels_last activation is [N*H*W, C] in memory: the column-mapped kernels)
+        outer, channels, inner, nhwc = _fused.split_at_channel(x, cd)
+        return _fused.StatsPlan(outer, channels, inner, shape, tmpl['min_val'], tmpl['int_thr'], nhwc), tmpl
 
     def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
         if _ACTIVE_GROUP is not None:  # inside `with WeightQuantGroup(...)`: the group may have quantized this weight
@@ -186,17 +188,11 @@ class RescalingIntQuant(torch.nn.Module):
         quantizer kernel covers the operands; else None"""
         if not config.FUSED_PATHS or not x.is_cuda:
             return None
-        bw = getattr(bit_width, 'bvq_host_value', None)
-        iq, sc = self.int_quant, self.scaling_impl
-        if bw is None or type(iq) is not IntQuant or not isinstance(iq.delay_wrapper.delay_impl, _NoDelay):
+        plain = self._plain_int_quant(getattr(bit_width, 'bvq_host_value', None))
+        if plain is None:
             return None
-        round_mode = getattr(iq.float_to_int_impl, 'bvq_round_mode', None)
-        clamp_ste = getattr(iq.tensor_clamp_impl, 'bvq_clamp_ste', None)
-        if round_mode is None or clamp_ste is None:
-            return None
-        if type(self.zero_point_impl) is not ZeroZeroPoint or type(self.int_scaling_impl) is not IntScaling:
-            return None
-        learned = getattr(sc, 'bvq_learned_scale', None)
+        qmin, qmax, round_mode, clamp_ste, int_thr = plain
+        learned = getattr(self.scaling_impl, 'bvq_learned_scale', None)
         found = learned() if learned is not None else None
         if found is None:
             return None
@@ -207,14 +203,9 @@ class RescalingIntQuant(torch.nn.Module):
         p = _fused.plan(x, value, zp)
         if p is None or p.zp_pc:
             return None
-        int_thr = self.int_scaling_impl.host_value(bw)
-        if value.dim() > 0:  # a dimensioned threshold keeps its dtype: the 0-dim int_threshold is converted to it
-            scale_dtype, thr_div = value.dtype, _fused._as_dtype_value(int_thr, value.dtype)
-        else:                # two 0-dim operands promote like tensors (int_threshold has the bit width's dtype)
-            scale_dtype = torch.promote_types(value.dtype, bit_width.dtype)
-            thr_div = _fused._as_dtype_value(int_thr, bit_width.dtype)
-        qmin, qmax = int_range_host(iq.signed, iq.narrow_range, bw)
-        return value, min_val, p, thr_div, scale_dtype, qmin, qmax, round_mode, clamp_ste
+        # int_threshold has the bit width's dtype: next to a 0-dim value the division sees it as that dtype holds it
+        rule = _fused.scale_rule(value.dtype, value.shape, int_thr, bit_width.dtype, thr_as_stored=True)
+        return value, min_val, p, rule.thr_div, rule.scale_dtype, qmin, qmax, round_mode, clamp_ste
 
     def _scale_ignores_input(self) -> bool:
         """True if scaling_impl(x) does not read x right now (learned / constant / frozen statistics)"""

@@ -62,7 +62,6 @@ class _WeightList:
         w0 = entries[0].weight
         self.scale_dtype = w0.dtype  # a dimensioned scale keeps the weight's dtype (_fused.stats_scale)
         self.round_mode = entries[0].tmpl['round_mode']
-        code = nat.dtype_code(w0.dtype)
         # chunks: one list call each way, at most WEIGHT_LIST_MAX weights whose channels fit one arrival buffer
         self.chunks, self.chunk_of = [], []
         lo, off = 0, 0
@@ -78,14 +77,13 @@ class _WeightList:
             it.inner = sp.inner
             it.min_val = float(sp.min_val or 0.0)
             it.use_min = int(bool(sp.min_val))
-            it.int_threshold = _fused._as_dtype_value(sp.int_threshold, w0.dtype)
+            it.int_threshold = _fused.scale_rule(w0.dtype, sp.scaling_shape, sp.int_threshold).thr_div
             it.qmin, it.qmax = t['qmin'], t['qmax']
             it.clamp_ste = int(t['clamp_ste'])
             self.offsets.append(off)
             off += sp.channels
-            self.descs.append(nat.QuantDesc(sp.outer, sp.channels, sp.inner, code, code, code, nat.F32, 1, 0, t['qmin'],
-                                            t['qmax'], t['round_mode'], _fused.scalar_mode(), int(t['clamp_ste']),
-                                            nat.OUT_DEQUANT, nat.PRE_NONE))
+            self.descs.append(_fused.channel_desc(sp.outer, sp.channels, sp.inner, w0.dtype, t['qmin'], t['qmax'],
+                                                  t['round_mode'], t['clamp_ste']))
             self.sps.append(_fused._SpLike(sp.outer, sp.channels, sp.inner, sp.int_threshold))
         self.chunks.append((lo, n))
 

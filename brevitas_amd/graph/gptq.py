@@ -214,6 +214,7 @@ def fused_block_args(plan: _Plan, rows: int, k: int, dtype: torch.dtype) -> Opti
     graph, the group size or the configuration is not what the kernel covers (tensors apart)"""
     if not config.FUSED_PATHS or dtype not in _fused._FLOATS:
         return None
+    groups = rows * (k // plan.group)
     min_val, thr_div = None, 1.0
     clamp_ste = getattr(plan.quant.int_quant.tensor_clamp_impl, 'bvq_clamp_ste', None)
     if clamp_ste is None:
@@ -223,11 +224,9 @@ def fused_block_args(plan: _Plan, rows: int, k: int, dtype: torch.dtype) -> Opti
         tmpl = plan.quant._group_template(plan.bit_width)
         if tmpl is None or plan.group not in _FUSED_GROUPS or tmpl['shifted'] != plan.shifted:
             return None
-        min_val, thr_div = tmpl['min_val'], _fused._as_dtype_value(tmpl['int_thr'], dtype)
-    code = nat.dtype_code(dtype)
-    desc = nat.QuantDesc(1, rows * (k // plan.group), plan.group, code, code, code, code if plan.shifted else nat.F32, 1,
-                         int(plan.shifted), plan.qmin, plan.qmax, nat.ROUND, _fused.scalar_mode(), int(bool(clamp_ste)),
-                         nat.OUT_DEQUANT, nat.PRE_NONE)
+        min_val, thr_div = tmpl['min_val'], _fused.scale_rule(dtype, (groups, 1), tmpl['int_thr']).thr_div
+    desc = _fused.channel_desc(1, groups, plan.group, dtype, plan.qmin, plan.qmax, nat.ROUND,
+                               bool(clamp_ste), zp_dtype=dtype if plan.shifted else torch.float32, zp_pc=plan.shifted)
     return _FusedArgs(desc, min_val, thr_div)
 
 
