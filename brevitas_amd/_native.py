@@ -35,7 +35,7 @@ MX_E4M3, MX_E5M2, MX_E3M2, MX_E2M3, MX_E2M1, MX_INT8 = range(6)
 MX_FLOOR, MX_CEIL = 0, 1
 LR_HARD_SIGMOID, LR_SIGMOID = 0, 1  # bvq_learned_round_impl
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -179,6 +179,10 @@ _SIG = {
     'bvq_group_shifted_supported': (_i32, [_qd, _vp]),
     'bvq_group_shifted_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
     'bvq_group_shifted_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
+    'bvq_row_shifted_max_row_bytes': (_i64, []),
+    'bvq_row_shifted_supported': (_i32, [_qd, _vp]),
+    'bvq_row_shifted_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_row_shifted_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
     'bvq_gptq_block_supported': (_i32, [_qd, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     'bvq_gptq_block': (_i32, [_qd, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
     'bvq_learned_round_supported': (_i32, [_qd, _vp, _vp, _vp]),
@@ -609,6 +613,45 @@ def group_shifted_bwd(desc, g, x, stat, gscale, gzp, min_val, thr_div):
     assert (gscale is None or gscale.is_contiguous()) and (gzp is None or gzp.is_contiguous())
     dx = torch.empty_like(x)
     _launch(dev, 'bvq_group_shifted_bwd', 'bvq_group_shifted_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(stat),
+            ptr(gscale), ptr(gzp), *_scale_args(min_val, thr_div), ptr(dx))
+    return dx
+
+
+def row_shifted_max_row_bytes():
+    """the longest row, in bytes, the asymmetric per-row kernels hold"""
+    return int(lib.bvq_row_shifted_max_row_bytes())
+
+
+def row_shifted_supported(desc, x):
+    """the asymmetric per-row kernels cover this descriptor (outer 1, channels = rows, inner = H, one scale and one
+    zero-point per row in x's dtype) and tensor"""
+    return bool(lib.bvq_row_shifted_supported(ctypes.byref(desc), ptr(x)))
+
+
+def row_shifted_fwd(desc, x, min_val, thr_div):
+    """max and min per row, scale, integer zero-point and quantize-dequantize in ONE launch -> (y like x, scale [rows],
+    zp [rows], stat [2 * rows]: the maxima then the minima), all in x's dtype"""
+    dev = require_device(x)
+    assert x.is_contiguous()
+    rows = int(desc.channels)
+    y = torch.empty_like(x)
+    scale = torch.empty(rows, dtype=x.dtype, device=dev)
+    zp = torch.empty(rows, dtype=x.dtype, device=dev)
+    stat = torch.empty(2 * rows, dtype=x.dtype, device=dev)
+    _launch(dev, 'bvq_row_shifted_fwd', 'bvq_row_shifted_fwd', ctypes.byref(desc), ptr(x),
+            *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(zp), ptr(stat))
+    return y, scale, zp, stat
+
+
+def row_shifted_bwd(desc, g, x, stat, gscale, gzp, min_val, thr_div):
+    """backward of row_shifted_fwd in ONE launch -> dx (the gradients of a row's maximum and minimum deposited on the
+    first element equal to each); gscale / gzp: None, or the gradient arriving through `scale` / `zp`, [rows] in x's
+    dtype"""
+    dev = require_device(g, x, stat, gscale, gzp)
+    assert g.is_contiguous() and x.is_contiguous() and stat.is_contiguous()
+    assert (gscale is None or gscale.is_contiguous()) and (gzp is None or gzp.is_contiguous())
+    dx = torch.empty_like(x)
+    _launch(dev, 'bvq_row_shifted_bwd', 'bvq_row_shifted_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(stat),
             ptr(gscale), ptr(gzp), *_scale_args(min_val, thr_div), ptr(dx))
     return dx
 

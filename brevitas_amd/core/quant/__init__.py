@@ -1,5 +1,6 @@
 from .binary import BinaryQuant, ClampedBinaryQuant
 from .delay import DelayWrapper
+from .dynamic import DynamicActIntQuant
 from .int import (DecoupledRescalingIntQuant, GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant,
                   PrescaledRestrictIntQuant, PrescaledRestrictIntQuantWithInputBitWidth, RescalingIntQuant,
                   TruncIntQuant)

@@ -637,6 +637,41 @@ class GroupShiftedFakeQuantFn(Function):
         return (dx,) + (None,) * 6
 
 
+def row_shifted_call(x: Tensor, int_threshold: float, qmin: float, qmax: float, clamp_ste):
+    """group_shifted_call for the asymmetric per-row kernels (nat.row_shifted_fwd / row_shifted_bwd): x as
+    [rows, H] = [numel / shape[-1], shape[-1]], one scale and one zero-point per row, in x's dtype"""
+    h = x.shape[-1]
+    rows = x.numel() // h
+    desc = channel_desc(1, rows, h, x.dtype, qmin, qmax, nat.ROUND, clamp_ste, zp_dtype=x.dtype, zp_pc=True)
+    return desc, scale_rule(x.dtype, (rows, 1), int_threshold).thr_div
+
+
+class RowShiftedFakeQuantFn(Function):
+    """Asymmetric per-row (per-token) dynamic activations: GroupShiftedFakeQuantFn with a row of x.shape[-1] elements in
+    the place of a group; x -> (y like x, scale [rows, 1], zero_point [rows, 1]).  One launch each way
+    (csrc/bvq_row_shifted.hip): a row stays in the registers of one wave or one workgroup.  The caller has checked what
+    the kernels cover (DynamicActIntQuant._route)."""
+
+    @staticmethod
+    def forward(ctx, x, min_val, int_threshold, qmin, qmax, clamp_ste):
+        ctx.set_materialize_grads(False)  # unused `scale` / `zero_point` outputs must not cost a zero-fill + add
+        desc, thr_div = row_shifted_call(x, int_threshold, qmin, qmax, clamp_ste)
+        y, scale, zp, stat = nat.row_shifted_fwd(desc, x, min_val, thr_div)
+        ctx.desc, ctx.min_val, ctx.thr_div = desc, min_val, thr_div
+        ctx.save_for_backward(x, stat)
+        return y, scale.view(-1, 1), zp.view(-1, 1)
+
+    @staticmethod
+    def backward(ctx, gy, gscale, gzp):
+        x, stat = ctx.saved_tensors
+        grads = _group_grads(x, gy, [gscale, gzp], align_side=True)
+        if grads is None:
+            return (None,) * 6
+        gy, (gscale, gzp) = grads
+        dx = nat.row_shifted_bwd(ctx.desc, gy, x, stat, gscale, gzp, ctx.min_val, ctx.thr_div)
+        return (dx,) + (None,) * 5
+
+
 class GroupMSEFakeQuantFn(Function):
     """Group-wise weights with a searched clipping threshold (GroupwiseMSEIntQuant): GroupStatsFakeQuantFn with, per
     group, the first of the candidate thresholds AbsMax * ratio_i that has the smallest squared quantization error,

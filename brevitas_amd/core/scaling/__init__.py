@@ -8,6 +8,7 @@ SCALING_STATS_REDUCE_DIM = 1  # per-channel statistics reduce along dim 1 of the
 
 IntScaling, PowerOfTwoIntScaling = int_scaling.IntScaling, int_scaling.PowerOfTwoIntScaling
 StatsFromParameterScaling, RuntimeStatsScaling = runtime.StatsFromParameterScaling, runtime.RuntimeStatsScaling
+RuntimeDynamicStatsScaling = runtime.RuntimeDynamicStatsScaling
 _StatsScaling = runtime._StatsScaling
 ConstScaling, ParameterScaling = standalone.ConstScaling, standalone.ParameterScaling
 ParameterFromRuntimeStatsScaling = standalone.ParameterFromRuntimeStatsScaling

@@ -7,7 +7,7 @@ from torch.nn import Module, Parameter
 from brevitas_amd.core._state import TolerantLoad
 from brevitas_amd.core.function_wrapper import Identity
 from brevitas_amd.core.restrict_val import _RestrictClampValue
-from brevitas_amd.core.stats import DEFAULT_MOMENTUM, _ParameterListStats, _RuntimeStats
+from brevitas_amd.core.stats import DEFAULT_MOMENTUM, _ParameterListStats, _RuntimeStats, _Stats
 from brevitas_amd.function.ops_ste import abs_binary_sign_grad
 
 
@@ -68,6 +68,24 @@ class StatsFromParameterScaling(torch.nn.Module):
 
     def forward(self, ignored: torch.Tensor) -> torch.Tensor:
         return self.stats_scaling_impl(self.parameter_list_stats())
+
+
+class RuntimeDynamicStatsScaling(torch.nn.Module):
+    """threshold from the statistic of the tensor passed to forward, in training and in eval alike
+    (RuntimeDynamicStatsScaling of later Brevitas releases): no running buffer, no parameter, nothing in the state dict;
+    the statistic is differentiated through, as in RuntimeStatsScaling's training branch.  `scaling_shape` is what the
+    statistic is viewed as and may hold one -1: () for one scale, (-1, 1) for one per row of the viewed input."""
+
+    def __init__(self, scaling_stats_impl: Module, scaling_stats_input_view_shape_impl: Module,
+                 restrict_scaling_impl: Module, scaling_shape: Tuple[int, ...] = (),
+                 scaling_min_val: Optional[float] = None) -> None:
+        super().__init__()
+        self.stats_input_view_shape_impl = scaling_stats_input_view_shape_impl
+        self.stats = _Stats(scaling_stats_impl, tuple(scaling_shape))
+        self.stats_scaling_impl = _StatsScaling(restrict_scaling_impl, tuple(scaling_shape), scaling_min_val, False)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.stats_scaling_impl(self.stats(self.stats_input_view_shape_impl(x)))
 
 
 class RuntimeStatsScaling(torch.nn.Module):

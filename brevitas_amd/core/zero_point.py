@@ -13,11 +13,12 @@ from torch import Tensor
 from torch.nn import Module, Parameter
 
 from brevitas_amd.core._state import CollectThenLearn, TolerantLoad
-from brevitas_amd.core.stats import DEFAULT_MOMENTUM, SCALAR_SHAPE, _ParameterListStats
+from brevitas_amd.core.stats import DEFAULT_MOMENTUM, SCALAR_SHAPE, _ParameterListStats, _Stats
 from brevitas_amd.core.utils import StatelessBuffer, inplace_tensor_add
 from brevitas_amd.function.ops_ste import abs_binary_sign_grad
 
-__all__ = ['ZeroZeroPoint', 'StatsFromParameterZeroPoint', 'ParameterFromRuntimeZeroPoint', 'ParameterZeroPoint']
+__all__ = ['ZeroZeroPoint', 'StatsFromParameterZeroPoint', 'RuntimeDynamicStatsZeroPoint',
+           'ParameterFromRuntimeZeroPoint', 'ParameterZeroPoint']
 
 
 class ZeroZeroPoint(torch.nn.Module):
@@ -61,6 +62,24 @@ class StatsFromParameterZeroPoint(torch.nn.Module):
 
     def forward(self, x: Tensor, scale: Tensor, bit_width: Tensor) -> torch.Tensor:
         stats = self.parameter_list_stats()
+        return self.scale_shift_zero_point(-stats, scale, bit_width)
+
+
+class RuntimeDynamicStatsZeroPoint(torch.nn.Module):
+    """zero-point from a statistic (e.g. NegativeMinOrZero) of the tensor passed to forward, in training and in eval
+    alike (RuntimeDynamicStatsZeroPoint of later Brevitas releases): StatsFromParameterZeroPoint with the current input
+    in the tracked weight's place.  No buffer, no parameter; the statistic is differentiated through.
+    `zero_point_shape` is what the statistic is viewed as and may hold one -1, like RuntimeDynamicStatsScaling's."""
+
+    def __init__(self, int_quant: Module, quantize_zero_point: bool, zero_point_stats_input_view_shape_impl: Module,
+                 zero_point_stats_impl: Module, zero_point_shape: Tuple[int, ...] = ()) -> None:
+        super().__init__()
+        self.stats_input_view_shape_impl = zero_point_stats_input_view_shape_impl
+        self.stats = _Stats(zero_point_stats_impl, tuple(zero_point_shape))
+        self.scale_shift_zero_point = _ScaleShiftZeroPoint(int_quant, quantize_zero_point)
+
+    def forward(self, x: Tensor, scale: Tensor, bit_width: Tensor) -> torch.Tensor:
+        stats = self.stats(self.stats_input_view_shape_impl(x))
         return self.scale_shift_zero_point(-stats, scale, bit_width)
 
 

@@ -141,7 +141,8 @@ __device__ __forceinline__ vec_t<T, elem<T>::vec> group_bwd_chunk(const GroupArg
 // ------------------------------------------------------------------------------------------------
 // what the kernels cover, apart from the pointers: BVQ_OK, or the error with its text
 // shifted: the asymmetric quantizer (bvq_group_shifted.hip), one zero-point per group in x's dtype
-static int group_check(const bvq_quant_desc* d, const char* what, bool shifted = false) {
+// any_size: every `inner` passes here (the per-row kernels of bvq_row_shifted.hip, which hold their own bound to it)
+static int group_check(const bvq_quant_desc* d, const char* what, bool shifted = false, bool any_size = false) {
   int rc = validate(d);
   if (rc) return rc;
   if (shifted && (d->outer != 1 || d->channels < 1 || !d->scale_per_channel || !d->zp_per_channel)) {
@@ -158,7 +159,7 @@ static int group_check(const bvq_quant_desc* d, const char* what, bool shifted =
     set_error("%s: x and zero-point dtype must agree (x=%d zp=%d)", what, d->x_dtype, d->zp_dtype);
     return BVQ_ERR_UNSUPPORTED;
   }
-  if (d->inner != 16 && d->inner != 32 && d->inner != 64 && d->inner != 128 && d->inner != 256) {
+  if (!any_size && d->inner != 16 && d->inner != 32 && d->inner != 64 && d->inner != 128 && d->inner != 256) {
     set_error("%s: group size %lld (16, 32, 64, 128 or 256)", what, (long long)d->inner);
     return BVQ_ERR_UNSUPPORTED;
   }

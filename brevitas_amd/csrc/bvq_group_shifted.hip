@@ -15,79 +15,27 @@
 //   backward  reads g and x, writes dx once    (+ 2 * bytes(x) / g for the statistics, + gscale / gzp when given)
 // Only the ORDER in which a group's float32 gradient terms are added differs from the per-channel kernels, which can
 // move the two deposited elements by a rounding.
-#include "bvq_group_shifted.h"  // the argument struct, the forward chain of a chunk, statistics -> scale and zero-point
+#include "bvq_group_shifted.h"  // the argument struct, statistics -> scale and zero-point, the steps of the backward
 
 namespace bvq {
 
-// GroupArgs with `stat` holding [2 * groups] values, the maxima then the minima (as BVQ_STAT_MINMAX)
-struct GroupShiftedArgs : GroupArgs {
-  void* zp;         // fwd: [groups] out
-  const void* gzp;  // bwd, nullable: gradient arriving through the returned zero-point, [groups]
-};
-
-// One chunk of the backward: dx and the rounded gradient terms of scale and zero-point per element exactly as the
-// per-channel backward computes them (bwd_elem2, kBwdDsDzp), the group's two sums, then the autograd of the scale-shaped
-// torch ops of the graph, each rounding to T:
-//   zero-point   dzp (+ gzp) -> its own clamp (masked where it clipped unless straight-through) -> round (STE) -> "+ 0"
-//                -> u = n / s: dn = dzp / s to n = -m0, -dzp * ((n / s) / s) to the scale -> m0 -> mn where mn <= 0
-//   scale        ds (+ gscale) + the zero-point's share -> / thr_div -> clamp_min (STE) -> |d|: * sgn(d) -> d = mx - mn
-// and the deposits in the order the per-channel route adds its dense gradients to dx: the zero-point statistic's first
-// (on the first element equal to mn), then the scale statistic's (max and min, added to each other first where one
-// element is both).  Every element of dx has been through "+ 0" there, which turns a -0 into +0.
-// sub: the lane within its segment (GroupPlace).
+// One chunk of the backward in the steps of bvq_group_shifted.h, a group's reductions being segmented butterflies
+// between them.  sub: the lane within its segment (GroupPlace).
 template <typename T, int L, typename Div>
 __device__ __forceinline__ vec_t<T, elem<T>::vec> group_shifted_bwd_chunk(
     const GroupShiftedArgs& a, const vec_t<T, elem<T>::vec>& xv, const vec_t<T, elem<T>::vec>& gv, uint32_t sub,
     const Div& div, const ShiftedGroup& p, float mx, float mn, float gsc, float gzp, float qmin, float qmax) {
   constexpr int VEC = elem<T>::vec;
-  const bool clamp_ste = a.clamp_ste != 0;
-  f2 ds2 = splat2(0.f), dz2 = splat2(0.f), unused = splat2(0.f);
-  vec_t<T, VEC> dv;
-#pragma unroll
-  for (int k = 0; k < VEC; k += 2) {
-    const f2 d = bwd_elem2<T, BVQ_ROUND, kBwdDsDzp, false, false, true>(
-        widen2<T>(xv.v[k], xv.v[k + 1]), widen2<T>(gv.v[k], gv.v[k + 1]), div, p.s, p.zp, qmin, qmax, clamp_ste,
-        BVQ_ROUND, ds2, dz2, unused);
-    pack2<T>(f2{plus_zero(d.x), plus_zero(d.y)}, dv.v[k], dv.v[k + 1]);  // (d is rounded to T: the conversion is exact)
-  }
+  f2 ds2 = splat2(0.f), dz2 = splat2(0.f);
+  vec_t<T, VEC> dv = shifted_bwd_elems<T>(a.clamp_ste != 0, xv, gv, div, p, qmin, qmax, ds2, dz2);
   const float ds = seg_sum<L>(ds2.x + ds2.y);
   const float dzs = seg_sum<L>(dz2.x + dz2.y);
-  // the zero-point's gradient on its way back through to_int
-  float dzp = rnd<T>(dzs);
-  if (a.gzp) dzp = rnd<T>(dzp + gzp);
-  const bool zhi = p.r > qmax;
-  const bool zlo = (zhi ? qmax : p.r) < qmin;
-  const float dzi = (clamp_ste || !(zhi || zlo)) ? dzp : 0.f;
-  const float dn = rnd<T>(dzi / p.s);
-  const float dsz = rnd<T>(-dzi * rnd<T>(p.u / p.s));
-  // the scale's gradient: the quantizer's, the one arriving through `scale`, the zero-point's share, in that order
-  float v = rnd<T>(ds);
-  if (a.gscale) v = rnd<T>(v + gsc);
-  v = rnd<T>(v + dsz);
-  const float dthr = rnd<T>(v / a.thr_div);
-  const float dd = rnd<T>(dthr * sgn_f(p.d));  // abs: zero at 0, a constant group deposits nothing through it
-  const float dmn_z = mn <= 0.f ? -dn : 0.f;
-  // first element of the group equal to each statistic: segment-wide minimum over lane * VEC + index (a NaN statistic
-  // is equal to nothing)
+  const ShiftedDeposit dep = shifted_bwd_chain<T>(a, p, mn, ds, dzs, gsc, gzp, qmin, qmax);
+  // first element of the group equal to each statistic: segment-wide minimum over lane * VEC + index
   const uint32_t e0 = sub * VEC;
   uint32_t fmx = ~0u, fmn = ~0u;
-#pragma unroll
-  for (int k = VEC - 1; k >= 0; --k) {
-    const float xf = to_f<T>(xv.v[k]);
-    fmx = xf == mx ? e0 + k : fmx;
-    fmn = xf == mn ? e0 + k : fmn;
-  }
-  fmx = seg_min_u32<L>(fmx);
-  fmn = seg_min_u32<L>(fmn);
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    const bool is_mx = fmx == e0 + k, is_mn = fmn == e0 + k;
-    float val = to_f<T>(dv.v[k]);
-    val = is_mn ? rnd<T>(val + dmn_z) : val;
-    float dep = is_mx ? dd : 0.f;
-    dep = is_mn ? rnd<T>(dep - dd) : dep;
-    dv.v[k] = (is_mx || is_mn) ? from_f<T>(val + dep) : dv.v[k];
-  }
+  shifted_first<T>(xv, e0, mx, mn, fmx, fmn);
+  shifted_deposit<T>(dv, e0, seg_min_u32<L>(fmx), seg_min_u32<L>(fmn), dep);
   return dv;
 }
 

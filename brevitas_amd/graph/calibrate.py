@@ -13,6 +13,7 @@ step moves 1x (abs-max) instead of 3x the activation through HBM.
 """
 import torch
 
+from brevitas_amd.core.quant.dynamic import DynamicActIntQuant
 from brevitas_amd.core.quant.int import RescalingIntQuant
 from brevitas_amd.core.quant.mx import MXQuant
 from brevitas_amd.proxy import FusedActivationQuantProxy
@@ -58,7 +59,8 @@ class DisableEnableQuantization:
     def disable_act_quantization(self, model, is_training):
         for q in _act_quantizers(model):
             q.train(is_training)
-            if isinstance(q, (RescalingIntQuant, MXQuant)):  # (an MX quantizer has nothing to collect)
+            # (an MX quantizer and a dynamic one have nothing to collect: the tensor passes them untouched)
+            if isinstance(q, (RescalingIntQuant, MXQuant, DynamicActIntQuant)):
                 q.bvq_collect_only = True
             else:
                 raise NotImplementedError('calibration of %s' % type(q).__name__)

@@ -37,6 +37,14 @@ class _QuantWeightMixin:
             # one scale per group of input weights: the accumulator the bias is added to has no single scale
             raise ValueError('a group-wise weight quantizer cannot be combined with an externally scaled bias quantizer '
                              '(Int8Bias ... Int32Bias); use a bias quantizer with internal scaling')
+        from brevitas_amd.core.quant.dynamic import DynamicActIntQuant
+        if isinstance(self.input_quant, DynamicActIntQuant) and self.input_quant.per_row and \
+                isinstance(self.bias_quant, PrescaledRestrictIntQuant):
+            # one input scale per row (or per group of a row): again no single scale of the accumulator
+            raise ValueError('a per-row or per-group dynamic input quantizer (Int8DynamicActPerRowFloat, '
+                             'ShiftedUint8DynamicActPerGroupFloat, ...) cannot be combined with an externally scaled bias '
+                             'quantizer (Int8Bias ... Int32Bias); use a per-tensor dynamic input quantizer or a bias '
+                             'quantizer with internal scaling')
 
     def _quant_all(self, x):
         """-> (x, w, bias) as the float op consumes them (B/nn/quant_layer.py:302-333)"""

@@ -13,14 +13,16 @@ import torch
 from brevitas_amd.core.bit_width import BitWidthConst
 from brevitas_amd.core.function_wrapper import (CeilSte, OverOutputChannelView, OverSubChannelBlockView, OverTensorView,
                                                 RoundSte, TensorClamp, TensorClampSte)
-from brevitas_amd.core.quant import (GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant, IntQuant, MXQuant,
-                                     PrescaledRestrictIntQuant, RescalingIntQuant)
+from brevitas_amd.core.quant import (DynamicActIntQuant, GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant, IntQuant,
+                                     MXQuant, PrescaledRestrictIntQuant, RescalingIntQuant)
 from brevitas_amd.core.restrict_val import FloatRestrictValue, PowerOfTwoRestrictValue
 from brevitas_amd.core.scaling import (IntScaling, ParameterFromRuntimeStatsScaling, ParameterScaling,
-                                       PowerOfTwoIntScaling, RuntimeStatsScaling, StatsFromParameterScaling)
+                                       PowerOfTwoIntScaling, RuntimeDynamicStatsScaling, RuntimeStatsScaling,
+                                       StatsFromParameterScaling)
 from brevitas_amd.core.stats import (AbsMax, AbsMinMax, AbsPercentile, NegativeMinOrZero, NegativePercentileOrZero,
                                      PercentileInterval)
-from brevitas_amd.core.zero_point import ParameterFromRuntimeZeroPoint, StatsFromParameterZeroPoint, ZeroZeroPoint
+from brevitas_amd.core.zero_point import (ParameterFromRuntimeZeroPoint, RuntimeDynamicStatsZeroPoint,
+                                          StatsFromParameterZeroPoint, ZeroZeroPoint)
 
 __all__ = ['Int8WeightPerChannelFloat', 'Int4WeightPerChannelFloat', 'Int8WeightPerGroupFloat',
            'Int4WeightPerGroupFloat', 'Int8WeightPerGroupFloatMSE', 'Int4WeightPerGroupFloatMSE',
@@ -34,7 +36,10 @@ __all__ = ['Int8WeightPerChannelFloat', 'Int4WeightPerChannelFloat', 'Int8Weight
            'Int32Bias', 'Int8BiasPerTensorFloatInternalScaling', 'Int8BiasPerTensorFixedPointInternalScaling',
            'MXFloat8e4m3Weight', 'MXFloat8e5m2Weight', 'MXFloat6e3m2Weight', 'MXFloat6e2m3Weight', 'MXFloat4e2m1Weight',
            'MXInt8Weight', 'MXFloat8e4m3Act', 'MXFloat8e5m2Act', 'MXFloat6e3m2Act', 'MXFloat6e2m3Act', 'MXFloat4e2m1Act',
-           'MXInt8Act']
+           'MXInt8Act',
+           'Int8DynamicActPerTensorFloat', 'Int8DynamicActPerRowFloat', 'Int8DynamicActPerGroupFloat',
+           'ShiftedUint8DynamicActPerTensorFloat', 'ShiftedUint8DynamicActPerRowFloat',
+           'ShiftedUint8DynamicActPerGroupFloat']
 
 SCALING_MIN_VAL = 1e-10  # B/quant/base.py:115-123, 169-182
 
@@ -361,6 +366,68 @@ def ShiftedUint8ActPerTensorFloat(collect_stats_steps: int = 300, bit_width: int
         ParameterFromRuntimeZeroPoint(collect_stats_steps, int_quant, True, NegativePercentileOrZero(0.001, None),
                                       (), OverTensorView(), 0.1),
         BitWidthConst(bit_width))
+
+
+# ---- dynamic activation quantizers: scale (and zero-point) from the tensor being quantized -----------------------------
+
+def _dynamic_act_quant(shifted: bool, granularity: str, bit_width: int, group_size: Optional[int] = None
+                       ) -> DynamicActIntQuant:
+    """The weight graph of the same granularity with the current input, viewed [rows, H], in the tracked weight's place
+    (core/quant/dynamic.py): plain clamp, full range, scaling_min_val 1e-10, float scales.  Stateless."""
+    if granularity == 'tensor':
+        view, dim, shape = OverTensorView, None, ()
+    elif granularity == 'row':
+        view, dim, shape = (lambda: OverOutputChannelView(None)), 1, (-1, 1)
+    else:
+        view, dim, shape = (lambda: OverSubChannelBlockView(int(group_size))), 1, (-1, 1)
+    int_quant = IntQuant(narrow_range=False, signed=not shifted, float_to_int_impl=RoundSte(),
+                         tensor_clamp_impl=TensorClamp())
+    scaling = RuntimeDynamicStatsScaling(AbsMinMax(dim) if shifted else AbsMax(dim), view(), FloatRestrictValue(), shape,
+                                         SCALING_MIN_VAL)
+    zero_point = RuntimeDynamicStatsZeroPoint(int_quant, True, view(), NegativeMinOrZero(dim), shape) if shifted \
+        else ZeroZeroPoint()
+    return DynamicActIntQuant(int_quant, scaling, IntScaling(signed=not shifted, narrow_range=False), zero_point,
+                              BitWidthConst(bit_width), granularity, group_size)
+
+
+def Int8DynamicActPerTensorFloat(bit_width: int = 8) -> DynamicActIntQuant:
+    """Int8DynamicActPerTensorFloat of later Brevitas releases: one scale, max |x| / 2^(b-1) of the current input, in
+    training and in eval; no buffer, no parameter.  The Int8WeightPerTensorFloat graph on the input with a plain clamp and
+    the full signed range.  scale is 0-dim (float32 for every input dtype, as a 0-dim statistic promotes)."""
+    return _dynamic_act_quant(False, 'tensor', bit_width)
+
+
+def Int8DynamicActPerRowFloat(bit_width: int = 8) -> DynamicActIntQuant:
+    """one scale per row of the last dimension (per token): the Int8WeightPerChannelFloat graph on x.reshape(rows, H);
+    scale is x.shape[:-1] + (1,) in x's dtype"""
+    return _dynamic_act_quant(False, 'row', bit_width)
+
+
+def Int8DynamicActPerGroupFloat(group_size: int = 32, bit_width: int = 8) -> DynamicActIntQuant:
+    """one scale per `group_size` consecutive elements of the last dimension: the Int8WeightPerGroupFloat graph on
+    x.reshape(rows, H); scale is x.shape[:-1] + (H / group_size, 1).  H must be a multiple of the group size."""
+    return _dynamic_act_quant(False, 'group', bit_width, group_size)
+
+
+def ShiftedUint8DynamicActPerTensorFloat(bit_width: int = 8) -> DynamicActIntQuant:
+    """asymmetric: unsigned codes, scale = max(|max - min|, 1e-10) / (2^b - 1) and an integer zero-point from the current
+    input; the ShiftedUint8WeightPerTensorFloat graph on the input with a plain clamp.  Runs as the composed route on the
+    device too."""
+    return _dynamic_act_quant(True, 'tensor', bit_width)
+
+
+def ShiftedUint8DynamicActPerRowFloat(bit_width: int = 8) -> DynamicActIntQuant:
+    """one scale and one integer zero-point per row of the last dimension (per token): the
+    ShiftedUint8WeightPerChannelFloat graph on x.reshape(rows, H); one kernel each way for rows of up to 32 KiB
+    (csrc/bvq_row_shifted.hip).  scale and zero_point are x.shape[:-1] + (1,) in x's dtype."""
+    return _dynamic_act_quant(True, 'row', bit_width)
+
+
+def ShiftedUint8DynamicActPerGroupFloat(group_size: int = 32, bit_width: int = 8) -> DynamicActIntQuant:
+    """one scale and one integer zero-point per `group_size` consecutive elements of the last dimension: the
+    ShiftedUint8WeightPerGroupFloat graph on x.reshape(rows, H); scale and zero_point are
+    x.shape[:-1] + (H / group_size, 1)"""
+    return _dynamic_act_quant(True, 'group', bit_width, group_size)
 
 
 # ---- fixed point: power-of-two scales (B/quant/fixed_point.py:23-73, PerTensorPoTScaling8bit B/quant/base.py:185-191)

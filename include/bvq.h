@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 6
+#define BVQ_ABI_VERSION 7
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -770,6 +770,46 @@ int bvq_group_shifted_fwd(const bvq_quant_desc* desc, const void* x, double min_
 int bvq_group_shifted_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* stat,
                           const void* gscale, const void* gzp, double min_val, int use_min, double thr_div, void* dx,
                           bvq_stream_t stream);
+
+/* ---- asymmetric per-row activations: one scale and one integer zero-point per row, from the row itself ----------------
+ * The per-token quantizer of the dynamic activation quantizers (ShiftedUint8DynamicActPerRowFloat).  x is [rows, H],
+ * contiguous; the descriptor has outer = 1, channels = rows, inner = H, x_dtype = ct_dtype = scale_dtype = zp_dtype = T,
+ * scale_per_channel = zp_per_channel = 1.  min_val / use_min / thr_div as in the group-wise section.  The arithmetic is
+ * that of the asymmetric group-wise entries above with "group" read as "row", every operation rounding to T:
+ *     mx = max x, mn = min x over the row            (a NaN anywhere in the row is both)
+ *     scale = T(clamp_min(|T(mx - mn)|, min_val) / thr_div)
+ *     m0 = mn <= 0 ? mn : 0;  zp = clamp(round_half_even(T(T(-m0 / scale) + 0)), qmin, qmax)
+ *     q = clamp(round_half_even(T(T(x / scale) + zp)), qmin, qmax);  y = T(T(q - zp) * scale)
+ *   bvq_row_shifted_fwd: y like x; scale, zp: [rows] in T; stat: [2 * rows] in T, the maxima then the minima.  A row
+ *     with a NaN has NaN scale, zp, stat and y; no other row sees it.
+ *   bvq_row_shifted_bwd: the autograd of that graph, as bvq_group_shifted_bwd states it: the row's scale and zero-point
+ *     gradients are float32 sums rounded to T, joined by gscale / gzp (nullable, [rows] in T); the gradient of mx is
+ *     added to the first element of the row equal to mx, that of mn to the first equal to mn -- first BY POSITION, the
+ *     lowest index in the row (-0 equals +0; a NaN statistic is equal to nothing) -- before dx is stored.  stat: the
+ *     forward's output; scale and zero-point are derived from it again, same bits.
+ * Geometry.  A row is C = H * sizeof(T) / 16 chunks of 16 bytes and is held in registers from its only load to its only
+ * store: by one wave for C <= 128 (four rows per 256-thread workgroup, two loads per lane), by one workgroup of four
+ * waves for C <= 512 (two loads per lane) and for C <= 2048 (eight).  Lane l of wave w holds chunks j * 64 W + 64 w + l
+ * (W waves per row, j the load).  The two ordered keys of the forward, and the two sums and two positions of the
+ * backward, cross a wave by xor butterflies and the row's waves through LDS with one barrier.
+ * Sum order.  Each of the two float32 sums of the backward adds: in a lane, the terms of its chunks in ascending j,
+ * inside a chunk in ascending element pairs, the two terms of an element to the two halves of a pair accumulator, then
+ * the halves; across the 64 lanes, the xor butterfly 32, 16, 8, 4, 2, 1; across the row's waves, ((w0 + w1) + w2) + w3.
+ * That order depends on H, T and the geometry above alone: the same inputs give the same bits on every run.  Only this
+ * ORDER differs from the per-channel kernels, which can move the two deposited elements by a rounding.
+ * ONE launch each way: no workspace, no atomics, no arrival words, nothing between workgroups.
+ * Covered: T float32, bfloat16 or float16; BVQ_ROUND; BVQ_PRE_NONE; BVQ_OUT_DEQUANT; both clamp modes; every tensor
+ * pointer on a 16-byte boundary; H * sizeof(T) any multiple of 16 from 16 up to bvq_row_shifted_max_row_bytes() (32768:
+ * 16384 16-bit or 8192 float32 elements); any rows >= 1.  Anything else returns BVQ_ERR_UNSUPPORTED with a
+ * bvq_last_error() text, found before anything touches the device; bvq_row_shifted_supported answers 1 / 0 for a
+ * descriptor and x. */
+int64_t bvq_row_shifted_max_row_bytes(void);
+int bvq_row_shifted_supported(const bvq_quant_desc* desc, const void* x);
+int bvq_row_shifted_fwd(const bvq_quant_desc* desc, const void* x, double min_val, int use_min, double thr_div,
+                        void* y, void* scale, void* zp, void* stat, bvq_stream_t stream);
+int bvq_row_shifted_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* stat,
+                        const void* gscale, const void* gzp, double min_val, int use_min, double thr_div, void* dx,
+                        bvq_stream_t stream);
 
 /* ---- GPTQ: the column loop of one block of up to 128 input columns -----------------------------------------------------
  * GPTQ (Frantar et al. 2022; `gptq_mode` of later Brevitas releases, no reference counterpart) quantizes a weight one
