@@ -34,8 +34,9 @@ CLUSTER_AUTO, CLUSTER_WALK, CLUSTER_ONESHOT = range(3)
 MX_E4M3, MX_E5M2, MX_E3M2, MX_E2M3, MX_E2M1, MX_INT8 = range(6)
 MX_FLOOR, MX_CEIL = 0, 1
 LR_HARD_SIGMOID, LR_SIGMOID = 0, 1  # bvq_learned_round_impl
+NORM_L1, NORM_L2 = 0, 1  # bvq_norm_kind
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -183,6 +184,9 @@ _SIG = {
     'bvq_row_shifted_supported': (_i32, [_qd, _vp]),
     'bvq_row_shifted_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
     'bvq_row_shifted_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
+    'bvq_weight_norm_supported': (_i32, [_qd, _i32, _dbl, _dbl, _vp]),
+    'bvq_weight_norm_fwd': (_i32, [_qd, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_weight_norm_bwd': (_i32, [_qd, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'bvq_gptq_block_supported': (_i32, [_qd, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     'bvq_gptq_block': (_i32, [_qd, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
     'bvq_learned_round_supported': (_i32, [_qd, _vp, _vp, _vp]),
@@ -654,6 +658,41 @@ def row_shifted_bwd(desc, g, x, stat, gscale, gzp, min_val, thr_div):
     _launch(dev, 'bvq_row_shifted_bwd', 'bvq_row_shifted_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(stat),
             ptr(gscale), ptr(gzp), *_scale_args(min_val, thr_div), ptr(dx))
     return dx
+
+
+def weight_norm_supported(desc, norm_kind, t_bound, norm_min, x):
+    """the weight-norm kernels cover this descriptor (outer 1, channels = rows, inner = K, float32 arithmetic and
+    scales, a narrow signed range, round-to-zero with NORM_L1 and half-even with NORM_L2), scalars and tensor"""
+    return bool(lib.bvq_weight_norm_supported(ctypes.byref(desc), int(norm_kind), float(t_bound), float(norm_min),
+                                              ptr(x)))
+
+
+def weight_norm_fwd(desc, norm_kind, t_bound, norm_min, x, scale, g):
+    """norm per row, pre-scale, quantize-dequantize in ONE launch -> (y like x, norm float32 [rows]); scale, g: float32
+    [rows]"""
+    dev = require_device(x, scale, g)
+    assert x.is_contiguous() and scale.is_contiguous() and g.is_contiguous()
+    assert scale.dtype == g.dtype == torch.float32 and scale.numel() == g.numel() == int(desc.channels)
+    y = torch.empty_like(x)
+    norm = torch.empty(int(desc.channels), dtype=torch.float32, device=dev)
+    _launch(dev, 'bvq_weight_norm_fwd', 'bvq_weight_norm_fwd', ctypes.byref(desc), int(norm_kind), float(t_bound),
+            float(norm_min), ptr(x), ptr(scale), ptr(g), ptr(y), ptr(norm))
+    return y, norm
+
+
+def weight_norm_bwd(desc, norm_kind, t_bound, norm_min, gy, x, scale, g, norm):
+    """backward of weight_norm_fwd in ONE launch -> (dx like x, dscale, dg: float32 [rows])"""
+    dev = require_device(gy, x, scale, g, norm)
+    assert gy.is_contiguous() and x.is_contiguous() and gy.dtype == x.dtype
+    assert scale.is_contiguous() and g.is_contiguous() and norm.is_contiguous()
+    assert scale.dtype == g.dtype == norm.dtype == torch.float32
+    assert scale.numel() == g.numel() == norm.numel() == int(desc.channels)
+    dx = torch.empty_like(x)
+    dscale = torch.empty(int(desc.channels), dtype=torch.float32, device=dev)
+    dg = torch.empty(int(desc.channels), dtype=torch.float32, device=dev)
+    _launch(dev, 'bvq_weight_norm_bwd', 'bvq_weight_norm_bwd', ctypes.byref(desc), int(norm_kind), float(t_bound),
+            float(norm_min), ptr(gy), ptr(x), ptr(scale), ptr(g), ptr(norm), ptr(dx), ptr(dscale), ptr(dg))
+    return dx, dscale, dg
 
 
 GPTQ_BLOCK = 128  # columns of one bvq_gptq_block launch

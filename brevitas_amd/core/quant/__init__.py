@@ -3,7 +3,7 @@ from .delay import DelayWrapper
 from .dynamic import DynamicActIntQuant
 from .int import (DecoupledRescalingIntQuant, GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant,
                   PrescaledRestrictIntQuant, PrescaledRestrictIntQuantWithInputBitWidth, RescalingIntQuant,
-                  TruncIntQuant)
+                  TruncIntQuant, WeightNormIntQuant)
 from .int_base import DecoupledIntQuant, IntQuant
 from .mx import MXPacked, MXQuant, mx_dequantize
 from .ternary import TernaryQuant

@@ -672,6 +672,55 @@ class RowShiftedFakeQuantFn(Function):
         return (dx,) + (None,) * 5
 
 
+def weight_norm_call(x: Tensor, qmax: float, round_mode: int, clamp_ste):
+    """-> the descriptor nat.weight_norm_fwd / weight_norm_bwd take for the weight x as [x.shape[0], K]: float32
+    arithmetic and scales whatever x's dtype, the narrow signed range [-qmax, qmax]"""
+    rows = x.shape[0]
+    desc = channel_desc(1, rows, x.numel() // rows, x.dtype, -qmax, qmax, round_mode, clamp_ste,
+                        scale_dtype=torch.float32)
+    desc.ct_dtype = nat.F32
+    return desc
+
+
+class WeightNormFakeQuantFn(Function):
+    """Weight-normalised weights (WeightNormIntQuant): per output channel n = norm(v), g' = min(g, T s), p = s n / g',
+    y = clamp(R(v / p)) s.  (x, value_s, value_g) -> (y like x, scale like value_s, n float32 [rows]) with the learned
+    parameters as they are stored: s = clamp_min(value_s, s_min) and g = clamp_min(value_g, g_min), both bounds positive,
+    are the forwards of ParameterScaling's restriction (the |.| of a positive number is the number), and its backward
+    -- a straight-through clamp, then the sign of a positive number -- is the identity, so dvalue_s = ds (+ what arrives
+    through the returned scale) and dvalue_g = dg.  One launch each way (csrc/bvq_weight_norm.hip) beside the two
+    clamps: a channel stays in the registers of one wave or one workgroup.  n is saved for the backward and is no
+    differentiable output.  The caller has checked what the kernels cover (WeightNormIntQuant._fused_call)."""
+
+    @staticmethod
+    def forward(ctx, x, value_s, value_g, s_min, g_min, desc, norm_kind, t_bound, norm_min):
+        ctx.set_materialize_grads(False)  # an unused `scale` output must not cost a zero-fill + add
+        scale = torch.clamp_min(value_s.detach(), s_min)
+        s = scale.reshape(-1).float()
+        g = torch.clamp_min(value_g.detach(), g_min).reshape(-1).float()
+        y, n = nat.weight_norm_fwd(desc, norm_kind, t_bound, norm_min, x, s, g)
+        ctx.desc, ctx.call = desc, (norm_kind, t_bound, norm_min)
+        ctx.like = (value_s.shape, value_s.dtype, value_g.shape, value_g.dtype)
+        ctx.save_for_backward(x, s, g, n)
+        ctx.mark_non_differentiable(n)
+        return y, scale, n
+
+    @staticmethod
+    def backward(ctx, gy, gscale, _gn):
+        x, s, g, n = ctx.saved_tensors
+        s_shape, s_dtype, g_shape, g_dtype = ctx.like
+        if gy is None:   # only the returned scale was used downstream
+            return (None, gscale, None) + (None,) * 6
+        gy = gy.to(x.dtype).contiguous()
+        if gy.data_ptr() % 16 != 0:
+            gy = gy.clone()
+        dx, dscale, dg = nat.weight_norm_bwd(ctx.desc, *ctx.call, gy, x, s, g, n)
+        dscale = dscale.reshape(s_shape).to(s_dtype)
+        if gscale is not None:
+            dscale = dscale + gscale
+        return (dx, dscale, dg.reshape(g_shape).to(g_dtype)) + (None,) * 6
+
+
 class GroupMSEFakeQuantFn(Function):
     """Group-wise weights with a searched clipping threshold (GroupwiseMSEIntQuant): GroupStatsFakeQuantFn with, per
     group, the first of the candidate thresholds AbsMax * ratio_i that has the smallest squared quantization error,

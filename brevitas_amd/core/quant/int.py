@@ -31,7 +31,8 @@ from brevitas_amd.core.scaling.runtime import RuntimeStatsScaling, StatsFromPara
 from brevitas_amd.core.scaling.standalone import ConstScaling, ParameterFromRuntimeStatsScaling, ParameterScaling
 from brevitas_amd.core.stats.stats_op import AbsMax, AbsMinMax, NegativeMinOrZero
 from brevitas_amd.core.zero_point import StatsFromParameterZeroPoint, ZeroZeroPoint
-from brevitas_amd.function.ops import int_range_host
+from brevitas_amd.function.ops import int_range_host, tensor_clamp
+from brevitas_amd.function.ops_ste import round_ste, round_to_zero_ste, tensor_clamp_ste
 
 
 # the WeightQuantGroup whose `with` block is running (brevitas_amd/core/quant/weight_group.py), or None
@@ -584,6 +585,154 @@ class GroupwiseMSEIntQuant(GroupwiseRescalingIntQuant):
         self.last_mse_index = idx.reshape(x.shape[0], -1)
         scale = scale.reshape(x.shape[0], -1, 1)
         return y.reshape(x.shape), scale, self.zero_point_impl(x, scale, bit_width), bit_width
+
+
+class WeightNormIntQuant(torch.nn.Module):
+    """Weight-normalised weight quantizer: per output channel c (dim 0), with v the channel's K weights, s the learned
+    scale (`scaling_impl`, a ParameterScaling) and g the learned norm parameter (`pre_scaling_impl`), all arithmetic in
+    float32 whatever the weight's dtype:
+
+        n   = norm(v) > 1e-10 ? norm(v) : 1e-10     norm = sum |v_i| ('l1')  or  sqrt(sum v_i^2) ('l2')
+        g'  = g <= T s ? g : T s                     T = pre_scaling_impl.upper_bound(), +inf without a bound
+        p   = (s n) / g'
+        q_i = clamp(R(v_i / p), -qmax, qmax)         R = round-to-zero ('l1') or round-half-even ('l2')
+        y_i = q_i s, rounded once to the weight's dtype
+
+    'l2' is the weight-norm quantizer, 'l1' with an AccumulatorAwareParameterPreScaling is A2Q: sum_i |q_i| <= T.
+    Returns the layers' (y, scale, zero_point, bit_width); scale is shaped (out, 1, ..., 1).  `pre_scale(weight)` gives p
+    and `int_weight(weight)` the integer codes.  State-dict keys: scaling_impl.value, pre_scaling_impl.value.
+
+    A contiguous 16-byte-aligned device weight whose channels are whole 16-byte chunks of at most 32 KiB runs as one
+    kernel each way (_fused.WeightNormFakeQuantFn, csrc/bvq_weight_norm.hip); CPU tensors and everything else take the
+    composed route: the same operations in the same order from torch ops and the STE functions, differentiated by
+    autograd.  DESIGN.md §9, "Weight-norm and accumulator-aware weights"."""
+
+    NORM_MIN = 1e-10
+
+    def __init__(self, scaling_impl: Module, pre_scaling_impl: Module, bit_width_impl: Module, norm: str = 'l2',
+                 clamp_ste: bool = True):
+        super().__init__()
+        if norm not in ('l1', 'l2'):
+            raise ValueError("norm must be 'l1' or 'l2', got %r" % (norm,))
+        self.scaling_impl = scaling_impl
+        self.pre_scaling_impl = pre_scaling_impl
+        self.zero_point_impl = ZeroZeroPoint()
+        self.msb_clamp_bit_width_impl = bit_width_impl
+        self.norm = norm
+        self.clamp_ste = bool(clamp_ste)
+
+    @property
+    def input_bit_width(self):
+        """what the accumulator bound assumes of the layer's input, or None without a bound"""
+        return getattr(self.pre_scaling_impl, 'input_bit_width', None)
+
+    @property
+    def input_signed(self):
+        return getattr(self.pre_scaling_impl, 'input_signed', None)
+
+    def _qmax(self, bit_width: Tensor) -> float:
+        bw = getattr(bit_width, 'bvq_host_value', None)
+        if bw is None:
+            raise NotImplementedError('WeightNormIntQuant needs a constant bit width (BitWidthConst)')
+        return int_range_host(True, True, bw)[1]
+
+    def _check(self, x: Tensor):
+        if x.dim() < 2 or x.shape[0] == 0 or x.numel() == 0 or x.dtype not in _fused._FLOATS + (torch.float64,):
+            raise ValueError('weight-norm quantizer: a floating-point weight of at least 2 dimensions, got %s %s'
+                             % (x.dtype, tuple(x.shape)))
+        rows = x.shape[0]
+        if self.scaling_impl.value.numel() != rows or self.pre_scaling_impl.value.numel() != rows:
+            raise ValueError('weight-norm quantizer: built for %d output channels, got a weight of shape %s'
+                             % (self.scaling_impl.value.numel(), tuple(x.shape)))
+
+    def _fused_call(self, x: Tensor, bit_width: Tensor):
+        """the arguments of _fused.WeightNormFakeQuantFn after x if the kernels cover this weight and both parameters
+        are stored as plain floats with a positive lower bound (what the factories build), else None; the descriptor is
+        kept until the weight, the bit width or the configuration changes"""
+        if not config.FUSED_PATHS or not x.is_cuda or x.dtype not in _fused._FLOATS or not x.is_contiguous():
+            return None
+        t_bound = self.pre_scaling_impl.upper_bound()
+        key = (x.data_ptr(), x.shape, x.dtype, x.device, getattr(bit_width, 'bvq_host_value', None), t_bound, self.norm,
+               self.clamp_ste, id(self.scaling_impl), id(self.pre_scaling_impl))
+        cached = self.__dict__.get('_bvq_call')
+        if cached is None or cached[0] != key:
+            cached = self.__dict__['_bvq_call'] = (key, self._build_fused_call(x, bit_width, t_bound))
+        call = cached[1]
+        if call is None:
+            return None
+        value_s, value_g = self.scaling_impl.value, self.pre_scaling_impl.value
+        if not (value_s.is_cuda and value_g.is_cuda and value_s.dtype in _fused._FLOATS
+                and value_g.dtype in _fused._FLOATS):
+            return None
+        return (value_s, value_g) + call
+
+    def _build_fused_call(self, x: Tensor, bit_width: Tensor, t_bound: float):
+        learned = [getattr(m, 'bvq_learned_scale', lambda: None)() for m in (self.scaling_impl, self.pre_scaling_impl)]
+        if any(found is None or found[1] is None or not found[1] > 0 for found in learned):
+            return None
+        kind = nat.NORM_L1 if self.norm == 'l1' else nat.NORM_L2
+        desc = _fused.weight_norm_call(x, self._qmax(bit_width), nat.ROUND_TO_ZERO if self.norm == 'l1' else nat.ROUND,
+                                       self.clamp_ste)
+        if not nat.weight_norm_supported(desc, kind, t_bound, self.NORM_MIN, x):
+            return None
+        return learned[0][1], learned[1][1], desc, kind, t_bound, self.NORM_MIN
+
+    def composed(self, x: Tensor, s: Tensor, g: Tensor, qmax: float):
+        """the composed route -> (y like x, n, p, q), n and p [rows, 1], q [rows, K], in float32 (float64 for a float64
+        weight): torch ops and the STE functions, in the order of the class docstring"""
+        rows = x.shape[0]
+        ct = torch.promote_types(x.dtype, torch.float32)
+        v = x.reshape(rows, -1).to(ct)
+        s, g = s.reshape(rows, 1).to(ct), g.reshape(rows, 1).to(ct)
+        if self.norm == 'l1':
+            raw = v.abs().sum(1, keepdim=True)
+        else:
+            ss = (v * v).sum(1, keepdim=True)
+            # sqrt has no finite slope at 0: an all-zero channel takes the constant branch, value and gradient
+            raw = torch.where(ss > 0, torch.sqrt(torch.where(ss > 0, ss, torch.ones_like(ss))), torch.zeros_like(ss))
+        n = torch.where(raw > self.NORM_MIN, raw, torch.full_like(raw, self.NORM_MIN))
+        t_bound = self.pre_scaling_impl.upper_bound()
+        if math.isinf(t_bound):
+            gp = g  # (g <= inf; and the unused branch T s must not turn a zero gradient into 0 * inf)
+        else:
+            ts = s * t_bound
+            gp = torch.where(g <= ts, g, ts)  # a tie goes to g
+        p = (s * n) / gp
+        t = v / p
+        r = round_to_zero_ste(t) if self.norm == 'l1' else round_ste(t)
+        lo, hi = torch.full((), -qmax, dtype=ct, device=x.device), torch.full((), qmax, dtype=ct, device=x.device)
+        q = tensor_clamp_ste(r, lo, hi) if self.clamp_ste else tensor_clamp(r, lo, hi)
+        y = (q * s).to(x.dtype).reshape(x.shape)
+        return y, n, p, q
+
+    def _operands(self, x: Tensor):
+        self._check(x)
+        bit_width = self.msb_clamp_bit_width_impl()
+        return bit_width, self._qmax(bit_width), self.scaling_impl(x), self.pre_scaling_impl(x)
+
+    def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        self._check(x)
+        bit_width = self.msb_clamp_bit_width_impl()
+        call = self._fused_call(x, bit_width)
+        if call is not None:
+            y, scale, _ = _fused.WeightNormFakeQuantFn.apply(x, *call)
+        else:
+            scale, g = self.scaling_impl(x), self.pre_scaling_impl(x)
+            y = self.composed(x, scale, g, self._qmax(bit_width))[0]
+        return y, scale, self.zero_point_impl(x, scale, bit_width), bit_width
+
+    def pre_scale(self, weight: Tensor) -> Tensor:
+        """the per-channel pre-scale p = s n / g' of `weight`, shaped like the scale (composed route, no gradient)"""
+        with torch.no_grad():
+            _, qmax, scale, g = self._operands(weight)
+            return self.composed(weight, scale, g, qmax)[2].reshape(scale.shape)
+
+    def int_weight(self, weight: Tensor) -> Tensor:
+        """the integer codes q of `weight`, int8 up to 8 bits and int32 above, shaped like it (composed route)"""
+        with torch.no_grad():
+            bit_width, qmax, scale, g = self._operands(weight)
+            q = self.composed(weight, scale, g, qmax)[3]
+            return q.reshape(weight.shape).to(torch.int8 if bit_width.bvq_host_value <= 8 else torch.int32)
 
 
 class PrescaledRestrictIntQuantWithInputBitWidth(torch.nn.Module):

@@ -2,7 +2,7 @@
 (mirror of B/core/scaling/)."""
 from brevitas_amd.core.stats import SCALAR_SHAPE  # noqa: F401  re-exported like the reference does
 
-from . import int_scaling, runtime, standalone
+from . import int_scaling, pre_scaling, runtime, standalone
 
 SCALING_STATS_REDUCE_DIM = 1  # per-channel statistics reduce along dim 1 of the [C, -1] view
 
@@ -12,3 +12,5 @@ RuntimeDynamicStatsScaling = runtime.RuntimeDynamicStatsScaling
 _StatsScaling = runtime._StatsScaling
 ConstScaling, ParameterScaling = standalone.ConstScaling, standalone.ParameterScaling
 ParameterFromRuntimeStatsScaling = standalone.ParameterFromRuntimeStatsScaling
+ParameterPreScalingWeightNorm = pre_scaling.ParameterPreScalingWeightNorm
+AccumulatorAwareParameterPreScaling = pre_scaling.AccumulatorAwareParameterPreScaling

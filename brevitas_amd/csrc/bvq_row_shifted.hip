@@ -4,7 +4,7 @@
 // The arithmetic is that of bvq_group_shifted.hip with "group" read as "row": the statistics -> scale -> zero-point
 // chain and the steps of the backward are those of bvq_group_shifted.h, the forward chain of a chunk that of
 // bvq_group_quant.h.  What differs is who holds a row.  A row of C = H * sizeof(T) / 16 chunks does not fit a fraction
-// of one wave load; it fits the registers of one workgroup:
+// of one wave load; it fits the registers of one workgroup (the row walk, bvq_row_walk.h):
 //
 //   C <=  128   kW = 1, kD = 2   one wave per row, four rows per workgroup, no LDS, no barrier
 //   C <=  512   kW = 4, kD = 2   one workgroup per row
@@ -32,66 +32,14 @@
 //   backward  reads g and x, writes dx once  (+ 2 values per row, + gscale / gzp when given)
 // No workspace, no atomics, no arrival words, no second kernel, nothing between workgroups.
 #include "bvq_group_shifted.h"
+#include "bvq_row_walk.h"
 
 namespace bvq {
-
-constexpr int64_t kRowMaxBytes = 32768;
 
 struct RowShiftedArgs : GroupShiftedArgs {
   int64_t rows;
   uint32_t cpr;  // 16-byte chunks per row
 };
-
-// where a wave stands: its row, its place among the row's kW waves, its lanes' first chunk
-template <int kW>
-struct RowSlot {
-  int64_t row;
-  uint32_t wave;  // within the row
-  uint32_t c0;    // the lane's chunk of load 0
-  __device__ __forceinline__ bool init(const RowShiftedArgs& a) {
-    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if constexpr (kW == 1) {
-      row = (int64_t)blockIdx.x * kWavesPerBlock + w;
-      wave = 0;
-    } else {
-      static_assert(kW == kWavesPerBlock, "a row is held by one wave or by the whole workgroup");
-      row = blockIdx.x;
-      wave = w;
-    }
-    c0 = wave * kWave + (threadIdx.x & 63);
-    return row < a.rows;  // (kW > 1: always, the grid is the rows -- every wave reaches the barrier)
-  }
-  // first chunk of the wave in load j (wave-uniform), and the lane's
-  __device__ __forceinline__ uint32_t first(int j) const { return (uint32_t)j * (kW * kWave) + wave * kWave; }
-  __device__ __forceinline__ uint32_t chunk(int j) const { return (uint32_t)j * (kW * kWave) + c0; }
-  template <typename T>
-  __device__ __forceinline__ buf_t elems(const void* p, const RowShiftedArgs& a) const {
-    return make_buf(reinterpret_cast<const T*>(p) + row * ((int64_t)a.cpr * elem<T>::vec), a.cpr * 16u);
-  }
-};
-
-// n values per wave across the kW waves of the row: ex[w][i] written by lane 0 of wave w, one barrier, all read by all
-template <int kW, int N>
-__device__ __forceinline__ void row_exchange(uint32_t (&ex)[kW][4], uint32_t wave, const uint32_t (&mine)[N],
-                                             uint32_t (&all)[kW][N]) {
-  static_assert(N <= 4, "row_exchange: up to four words per wave");
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) ex[wave][i] = mine[i];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < kW; ++w)
-#pragma unroll
-    for (int i = 0; i < N; ++i) all[w][i] = ex[w][i];
-}
-
-__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ float uniform_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
 
 template <typename T, int kW, int kD, bool NT>
 __global__ __launch_bounds__(kBlock) void row_shifted_fwd_kernel(RowShiftedArgs a) {
@@ -239,23 +187,6 @@ static RowShiftedArgs row_args(const bvq_quant_desc* d, double min_val, int use_
   a.cpr = (uint32_t)(d->inner * dtype_size(d->x_dtype) / 16);
   return a;
 }
-
-// the launch: f(type_tag<T>, int_c<kW>, int_c<kD>, std::bool_constant<NT>, grid) for the geometry of the row length;
-// chunk_bytes: what the kernel moves per 16-byte chunk of the tensor, for the NT decision
-template <typename F>
-static int row_launch(const char* what, int dtype, const RowShiftedArgs& a, int chunk_bytes, F&& f) {
-  const bool nt = a.chunks * chunk_bytes >= nt_threshold_bytes();
-  const unsigned one_wave = (unsigned)((a.rows + kWavesPerBlock - 1) / kWavesPerBlock), whole = (unsigned)a.rows;
-  const int rc = with_dtype(dtype, [&](auto t) {
-    return with_bool(nt, [&](auto ntc) {
-      if (a.cpr <= 2 * kWave) return call_rc(f, t, int_c<1>{}, int_c<2>{}, ntc, one_wave);
-      if (a.cpr <= 2 * kBlock) return call_rc(f, t, int_c<kWavesPerBlock>{}, int_c<2>{}, ntc, whole);
-      return call_rc(f, t, int_c<kWavesPerBlock>{}, int_c<8>{}, ntc, whole);
-    });
-  });
-  return rc ? rc : check_launch(what);
-}
-static_assert(8 * kBlock * 16 == kRowMaxBytes, "the deepest geometry holds the longest row");
 
 }  // namespace bvq
 

@@ -45,6 +45,22 @@ class _QuantWeightMixin:
                              'ShiftedUint8DynamicActPerGroupFloat, ...) cannot be combined with an externally scaled bias '
                              'quantizer (Int8Bias ... Int32Bias); use a per-tensor dynamic input quantizer or a bias '
                              'quantizer with internal scaling')
+        from brevitas_amd.core.quant.int import WeightNormIntQuant
+        if isinstance(self.weight_quant, WeightNormIntQuant) and self.weight_quant.input_bit_width is not None and \
+                self.input_quant is not None:
+            # an accumulator-aware weight quantizer bounds sum |q| for inputs of a stated width and signedness: an input
+            # quantizer whose constant bit width or signedness says otherwise would void the guarantee silently
+            want_bw, want_signed = self.weight_quant.input_bit_width, self.weight_quant.input_signed
+            bw_impl = getattr(self.input_quant, 'msb_clamp_bit_width_impl', None)
+            got_bw = getattr(bw_impl, '_host_value', None)
+            got_signed = getattr(getattr(self.input_quant, 'int_quant', None), 'signed', None)
+            if (got_bw is not None and got_bw != want_bw) or (got_signed is not None and got_signed != want_signed):
+                def say(bw, signed):
+                    return '%s-bit %s' % ('?' if bw is None else bw,
+                                          '(un)signed' if signed is None else 'signed' if signed else 'unsigned')
+                raise ValueError('the accumulator-aware weight quantizer assumes %s inputs (input_bit_width, '
+                                 'input_signed), the input quantizer produces %s ones'
+                                 % (say(want_bw, want_signed), say(got_bw, got_signed)))
 
     def _quant_all(self, x):
         """-> (x, w, bias) as the float op consumes them (B/nn/quant_layer.py:302-333)"""

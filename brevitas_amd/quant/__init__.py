@@ -14,9 +14,10 @@ from brevitas_amd.core.bit_width import BitWidthConst
 from brevitas_amd.core.function_wrapper import (CeilSte, OverOutputChannelView, OverSubChannelBlockView, OverTensorView,
                                                 RoundSte, TensorClamp, TensorClampSte)
 from brevitas_amd.core.quant import (DynamicActIntQuant, GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant, IntQuant,
-                                     MXQuant, PrescaledRestrictIntQuant, RescalingIntQuant)
+                                     MXQuant, PrescaledRestrictIntQuant, RescalingIntQuant, WeightNormIntQuant)
 from brevitas_amd.core.restrict_val import FloatRestrictValue, PowerOfTwoRestrictValue
-from brevitas_amd.core.scaling import (IntScaling, ParameterFromRuntimeStatsScaling, ParameterScaling,
+from brevitas_amd.core.scaling import (AccumulatorAwareParameterPreScaling, IntScaling,
+                                       ParameterFromRuntimeStatsScaling, ParameterPreScalingWeightNorm, ParameterScaling,
                                        PowerOfTwoIntScaling, RuntimeDynamicStatsScaling, RuntimeStatsScaling,
                                        StatsFromParameterScaling)
 from brevitas_amd.core.stats import (AbsMax, AbsMinMax, AbsPercentile, NegativeMinOrZero, NegativePercentileOrZero,
@@ -39,7 +40,8 @@ __all__ = ['Int8WeightPerChannelFloat', 'Int4WeightPerChannelFloat', 'Int8Weight
            'MXInt8Act',
            'Int8DynamicActPerTensorFloat', 'Int8DynamicActPerRowFloat', 'Int8DynamicActPerGroupFloat',
            'ShiftedUint8DynamicActPerTensorFloat', 'ShiftedUint8DynamicActPerRowFloat',
-           'ShiftedUint8DynamicActPerGroupFloat']
+           'ShiftedUint8DynamicActPerGroupFloat',
+           'Int8WeightNormL2PerChannelFloat', 'Int8AccumulatorAwareWeightQuant', 'Int4AccumulatorAwareWeightQuant']
 
 SCALING_MIN_VAL = 1e-10  # B/quant/base.py:115-123, 169-182
 
@@ -199,6 +201,49 @@ def MXFloat4e2m1Act(group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
 
 def MXInt8Act(group_size: int = 32, scale_rule: str = 'floor') -> MXQuant:
     return _mx_act('int8', group_size, scale_rule)
+
+
+def _weight_norm_scaling(weights, bit_width: int) -> tuple:
+    """(the one tracked weight, its learned per-channel scale starting at absmax_c / qmax) of a weight-norm quantizer"""
+    tracked = _params(weights)
+    if len(tracked) != 1:
+        raise ValueError('a weight-norm quantizer tracks exactly one weight, got a list of %d' % len(tracked))
+    w = tracked[0]
+    if w.dim() < 2 or w.numel() == 0:
+        raise ValueError('a weight-norm quantizer needs a weight of at least 2 dimensions, got shape %s'
+                         % (tuple(w.shape),))
+    shape = (w.shape[0],) + (1,) * (w.dim() - 1)
+    absmax = w.detach().reshape(w.shape[0], -1).float().abs().max(dim=1).values.reshape(shape)
+    init = torch.clamp_min(absmax, SCALING_MIN_VAL) / float(2 ** (bit_width - 1) - 1)
+    return w, ParameterScaling(init, shape, FloatRestrictValue(), scaling_min_val=SCALING_MIN_VAL)
+
+
+def Int8WeightNormL2PerChannelFloat(weights, bit_width: int = 8) -> WeightNormIntQuant:
+    """Per output channel w = g * v / ||v||_2 quantized with a learned scale s to the narrow signed range, half-even
+    rounding, straight-through clamp (Int8WeightNormL2PerChannelFloat of later Brevitas releases; not in this reference
+    snapshot).  g starts at ||v||_2 and s at absmax / (2^(b-1) - 1), so that y reproduces v to within one code step at
+    step 0.  Parameters: scaling_impl.value (s) and pre_scaling_impl.value (g), both (out, 1, ..., 1)."""
+    w, scaling = _weight_norm_scaling(weights, bit_width)
+    return WeightNormIntQuant(scaling, ParameterPreScalingWeightNorm(w, 'l2'), BitWidthConst(bit_width), 'l2')
+
+
+def Int8AccumulatorAwareWeightQuant(weights, accumulator_bit_width: int = 32, input_bit_width: int = 8,
+                                    input_signed: bool = False, bit_width: int = 8) -> WeightNormIntQuant:
+    """A2Q (Int8AccumulatorAwareWeightQuant of later Brevitas releases; not in this reference snapshot): the weight-norm
+    quantizer over the L1 norm with round-to-zero, its g capped at T * s, T = (2^(P-1) - 1) * 2^(sigma - N) for a P-bit
+    accumulator and N-bit inputs (sigma = 1 when they are signed), so that the integer weights of every output channel
+    satisfy sum |q| <= T and a dot product with such inputs cannot overflow the accumulator.  In a layer:
+    weight_quant=functools.partial(Int8AccumulatorAwareWeightQuant, accumulator_bit_width=16); the layer checks its
+    input quantizer against input_bit_width / input_signed."""
+    w, scaling = _weight_norm_scaling(weights, bit_width)
+    pre = AccumulatorAwareParameterPreScaling(w, accumulator_bit_width, input_bit_width, input_signed)
+    return WeightNormIntQuant(scaling, pre, BitWidthConst(bit_width), 'l1')
+
+
+def Int4AccumulatorAwareWeightQuant(weights, accumulator_bit_width: int = 32, input_bit_width: int = 8,
+                                    input_signed: bool = False) -> WeightNormIntQuant:
+    """Int8AccumulatorAwareWeightQuant with bit_width = 4"""
+    return Int8AccumulatorAwareWeightQuant(weights, accumulator_bit_width, input_bit_width, input_signed, bit_width=4)
 
 
 def Int8WeightPerTensorFloat(weights, bit_width: int = 8) -> RescalingIntQuant:

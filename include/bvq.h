@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 7
+#define BVQ_ABI_VERSION 8
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -810,6 +810,44 @@ int bvq_row_shifted_fwd(const bvq_quant_desc* desc, const void* x, double min_va
 int bvq_row_shifted_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* stat,
                         const void* gscale, const void* gzp, double min_val, int use_min, double thr_div, void* dx,
                         bvq_stream_t stream);
+
+/* ---- weight-normalised weights: per output channel w = g * v / norm(v), quantized with a learned scale ------------------
+ * The weight-norm quantizer (L2 norm, half-even rounding) and the accumulator-aware quantizer A2Q (Colbert et al. 2023:
+ * L1 norm, round-to-zero, g capped at T * s) of later Brevitas releases; no reference counterpart.  x is the weight
+ * viewed [rows, K], contiguous, of dtype T; the descriptor has outer = 1, channels = rows, inner = K, x_dtype = T,
+ * ct_dtype = scale_dtype = BVQ_F32, scale_per_channel = 1, zp_per_channel = 0, qmin = -qmax (narrow signed range),
+ * round_mode = BVQ_ROUND_TO_ZERO with BVQ_NORM_L1 and BVQ_ROUND with BVQ_NORM_L2.  scale (s > 0), g (> 0), norm, dscale
+ * and dg are float32 [rows].  Every operation is a float32 operation, whatever T (x is widened exactly):
+ *     n   = norm(x) > norm_min ? norm(x) : norm_min       norm = sum |x_i| (L1) or sqrt(sum x_i^2) (L2)
+ *     g'  = g <= T * s ? g : T * s                         T = (float)t_bound; a tie goes to g; +inf never caps
+ *     p   = (s * n) / g'                                   two operations, in this order
+ *     t_i = x_i / p (IEEE division);  r_i = R(t_i);  q_i = clamp(r_i, -qmax, qmax);  y_i = T(q_i * s)
+ *   bvq_weight_norm_fwd: y like x, norm[row] = n.  In real arithmetic sum |q_i| <= sum |t_i| = g' / s <= T for L1.
+ *   bvq_weight_norm_bwd, given gy = dL/dy in T and the forward's norm (p, t, r, q are rebuilt with the same bits);
+ *   m_i = clamp_ste or not (r_i > qmax or r_i < -qmax):
+ *     A = sum gy_i * m_i * t_i;  B = sum gy_i * q_i;  c1 = g' / n;  sA = s * A;  c2 = n > norm_min ? sA / n : 0
+ *     dx_i = T(gy_i * m_i * c1 - c2 * sign(x_i))  (L1, sign(0) = 0)   |   T(gy_i * m_i * c1 - (c2 / n) * x_i)  (L2)
+ *     dg' = sA / g';  g <= T * s: dscale = B - A, dg = dg';  otherwise: dscale = (B - A) + T * dg', dg = 0
+ * Geometry and exchanges are those of the asymmetric per-row entries above: a row of C = K * sizeof(T) / 16 chunks in the
+ * registers of one wave (C <= 128) or one workgroup of four waves (C <= 512: two loads per lane, C <= 2048: eight).
+ * Sum order (the norm's sum, A and B alike).  In a lane, the terms of its chunks in ascending load j, inside a chunk in
+ * ascending element pairs, element 2k to the first and 2k + 1 to the second half of a pair accumulator, then the halves;
+ * across the 64 lanes, the xor butterfly 32, 16, 8, 4, 2, 1; across the row's waves, ((w0 + w1) + w2) + w3.  It depends
+ * on K, T and the geometry alone: the same inputs give the same bits on every run.
+ * ONE launch each way: x (and gy) read once, y (dx) written once; no workspace, no atomics, nothing between workgroups.
+ * Covered: T float32, bfloat16 or float16; x, y, gy and dx on 16-byte boundaries; K * sizeof(T) any multiple of 16 from 16
+ * up to bvq_row_shifted_max_row_bytes(); any rows >= 1; t_bound > 0 (+inf allowed) and norm_min > 0.  A null descriptor
+ * or pointer, an unknown norm kind, t_bound or norm_min not positive: BVQ_ERR_INVALID; anything else not covered:
+ * BVQ_ERR_UNSUPPORTED; both with a bvq_last_error() text, found before anything touches the device.
+ * bvq_weight_norm_supported answers 1 / 0 for a descriptor, the scalars and x. */
+typedef enum bvq_norm_kind { BVQ_NORM_L1 = 0, BVQ_NORM_L2 = 1 } bvq_norm_kind;
+int bvq_weight_norm_supported(const bvq_quant_desc* desc, int norm_kind, double t_bound, double norm_min,
+                              const void* x);
+int bvq_weight_norm_fwd(const bvq_quant_desc* desc, int norm_kind, double t_bound, double norm_min, const void* x,
+                        const float* scale, const float* g, void* y, float* norm, bvq_stream_t stream);
+int bvq_weight_norm_bwd(const bvq_quant_desc* desc, int norm_kind, double t_bound, double norm_min, const void* gy,
+                        const void* x, const float* scale, const float* g, const float* norm, void* dx, float* dscale,
+                        float* dg, bvq_stream_t stream);
 
 /* ---- GPTQ: the column loop of one block of up to 128 input columns -----------------------------------------------------
  * GPTQ (Frantar et al. 2022; `gptq_mode` of later Brevitas releases, no reference counterpart) quantizes a weight one

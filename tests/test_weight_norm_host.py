@@ -1,0 +1,281 @@
+"""Weight-norm and accumulator-aware (A2Q) weight quantizers without a device: the composed route against a float64
+restatement on hand-made rows, the initialisation, the overflow bound, the autograd of the composed route against the
+closed forms, state dicts and layers, and the argument checks of the C ABI.  tests/weight_norm_ref.py restates the
+semantics and derives the bounds."""
+import ctypes
+import functools
+import math
+
+import pytest
+import torch
+
+import weight_norm_ref as R
+
+# (accumulator bits P, input bits N, signed inputs, weight bits b); the last leaves g unclamped
+BOUND_SETTINGS = [(16, 8, False, 8), (12, 4, True, 4), (32, 8, False, 8)]
+
+
+def a2q(w, acc=32, n_in=8, signed=False, bits=8):
+    import brevitas_amd.quant as Q
+    return Q.Int8AccumulatorAwareWeightQuant(w, acc, n_in, signed, bit_width=bits)
+
+
+def set_params(q, s, g):
+    with torch.no_grad():
+        q.scaling_impl.value.copy_(torch.as_tensor(s, dtype=torch.float32).reshape(q.scaling_impl.value.shape))
+        q.pre_scaling_impl.value.copy_(torch.as_tensor(g, dtype=torch.float32).reshape(q.pre_scaling_impl.value.shape))
+
+
+# ---- known answers --------------------------------------------------------------------------------------------------
+
+def known_rows():
+    """hand-made rows of 8 weights, dyadic values whose quotients stay clear of the integers by far more than a
+    float32 rounding, so that float32 and float64 give the same codes: row 0 all zero; row 1 with g far above T s;
+    row 2 with g == T s exactly; rows 3 and 4 with a value at +qmax and at -qmax"""
+    T = R.t_bound(16, 8, False)   # (2^15 - 1) / 256 = 127.99609375
+    v = torch.tensor([[0.0] * 8,
+                      [0.5, -0.25, 0.125, 0.0, 0.0, 0.0, 0.0, 0.125],     # n = 1
+                      [1.0, -0.5, 0.25, 0.0, 0.0, 0.0, 0.125, 0.125],     # n = 2
+                      [127 / 128, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0],     # n = 127 / 128 = g: p = s, t = 127
+                      [0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -127 / 128]])
+    s = torch.tensor([0.5, 0.5, 0.25, 1 / 128, 1 / 128])
+    g = torch.tensor([0.5, 1024.0, T * 0.25, 127 / 128, 127 / 128])
+    return v, s, g, T
+
+
+def test_known_answers_of_the_composed_route():
+    v, s, g, T = known_rows()
+    w = torch.nn.Parameter(v.clone())
+    q = a2q(w, 16, 8, False)
+    assert q.pre_scaling_impl.upper_bound() == T
+    set_params(q, s, g)
+    y, scale, zp, bw = q(w)
+    assert torch.equal(scale.reshape(-1), s) and float(zp) == 0.0 and float(bw) == 8.0
+    assert not torch.isnan(y).any()
+    # the float64 restatement from the float64 norm
+    n64 = torch.maximum(R.norm64(v, 'l1'), torch.tensor(R.NORM_MIN, dtype=torch.float64))
+    t, r, qq, gp, capped, p = R.chain(v.double(), s.double(), g.double(), n64, T, 127.0, 'l1')
+    want = qq * s.double().reshape(-1, 1)
+    assert torch.equal(y.double(), want)
+    assert capped.reshape(-1).tolist() == [False, True, False, False, False]     # the tie goes to g
+    assert torch.equal(y[0], torch.zeros(8))                                     # n clamped to norm_min, y = 0
+    assert torch.allclose(q.pre_scale(w).reshape(-1).double(), p.reshape(-1), rtol=1e-6, atol=0)
+    codes = q.int_weight(w)
+    assert codes.dtype == torch.int8
+    # row 1: g' = T s, p = 1 / T, t = v T = 63.998, -31.999, 15.9995: rounded to zero, sum |q| = 124 <= T
+    assert codes[1].tolist() == [63, -31, 15, 0, 0, 0, 0, 15]
+    # row 2: g' = g = T s, p = 2 / T, t = v T / 2
+    assert codes[2].tolist() == [63, -31, 15, 0, 0, 0, 7, 7]
+    # rows 3, 4: t = +-127 = +-qmax exactly
+    assert codes[3].tolist() == [127] + [0] * 7 and codes[4].tolist() == [0] * 7 + [-127]
+    assert bool((codes.long().abs().sum(1) <= T).all())
+    assert y[3, 0] == 127 / 128 and y[4, 7] == -127 / 128
+
+
+def test_the_l2_quantizer_rounds_half_to_even_at_qmax():
+    import brevitas_amd.quant as Q
+    v = torch.tensor([[3.0, 4.0, 0.0, 0.0], [0.5, 1.5, 2.5, 127.5]])
+    w = torch.nn.Parameter(v.clone())
+    q = Q.Int8WeightNormL2PerChannelFloat(w)
+    set_params(q, [1.0, 1.0], [5.0, float(torch.sqrt((v[1] * v[1]).sum()))])   # g = n: p = s = 1, t = v
+    y = q(w)[0]
+    assert y[0].tolist() == [3.0, 4.0, 0.0, 0.0]
+    assert y[1].tolist() == [0.0, 2.0, 2.0, 127.0]   # half to even, then the clamp at qmax
+
+
+# ---- initialisation -------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('shape', [(7, 40), (6, 5, 3, 3)])
+def test_the_l2_factory_reproduces_the_weight_within_one_code_step(shape):
+    import brevitas_amd.quant as Q
+    torch.manual_seed(3)
+    w = torch.nn.Parameter(torch.randn(shape) * 0.05)
+    q = Q.Int8WeightNormL2PerChannelFloat(w)
+    y, scale, _, _ = q(w)
+    assert scale.shape == (shape[0],) + (1,) * (len(shape) - 1)
+    absmax = w.detach().reshape(shape[0], -1).abs().max(1).values
+    assert torch.allclose(scale.reshape(-1), absmax / 127)
+    assert bool(((y - w).abs() <= scale).all())
+    # and to within half a step but for the roundings of p
+    assert bool(((y - w).abs() <= scale * (0.5 + 1e-3)).all())
+
+
+# ---- overflow bound -------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('acc,n_in,signed,bits', BOUND_SETTINGS)
+def test_the_integer_weights_respect_the_accumulator_bound(acc, n_in, signed, bits):
+    torch.manual_seed(acc)
+    w = torch.nn.Parameter(torch.randn(12, 256) * 0.03)
+    q = a2q(w, acc, n_in, signed, bits)
+    with torch.no_grad():
+        q.pre_scaling_impl.value.mul_(8.0)
+    T = q.pre_scaling_impl.upper_bound()
+    assert T == R.t_bound(acc, n_in, signed) or acc == 32     # (P = 32: rounded toward zero to float32)
+    assert T <= R.t_bound(acc, n_in, signed)
+    codes = q.int_weight(w).long()
+    qmax = 2 ** (bits - 1) - 1
+    assert int(codes.abs().max()) <= qmax
+    sums = codes.abs().sum(1)
+    assert bool((sums <= T).all()), (sums.max(), T)
+    g, s = q.pre_scaling_impl(w).reshape(-1), q.scaling_impl(w).reshape(-1)
+    clamped = g > T * s
+    assert bool(clamped.all()) if acc < 32 else not bool(clamped.any())
+    # the bound is what limits the codes, not a vacuous one: the clamped channels come within K of it
+    if acc < 32:
+        assert bool((sums >= T - 256).all())
+    # y is the codes times the scale
+    y = q(w)[0]
+    assert torch.equal(y, codes.float() * s.reshape(-1, 1))
+
+
+# ---- autograd -------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('norm', ['l1', 'l2'])
+@pytest.mark.parametrize('clamp_ste', [True, False])
+def test_autograd_of_the_composed_route_equals_the_closed_forms(norm, clamp_ste):
+    """float64 weights run the composed route in float64: the gradients autograd derives from the torch ops equal the
+    closed forms of the issue to rounding.  Rows: clipped values (g = 1.5 n), g capped by T, an all-zero row (n clamped:
+    no gradient through the norm, and none that is not finite)."""
+    import brevitas_amd.quant as Q
+    torch.manual_seed(11)
+    rows, k = 6, 48
+    v = torch.randn(rows, k, dtype=torch.float64) * 0.05
+    v[5] = 0.0
+    w = torch.nn.Parameter(v.clone())
+    q = a2q(w, 22, 8, False) if norm == 'l1' else Q.Int8WeightNormL2PerChannelFloat(w)
+    q.clamp_ste = clamp_ste
+    with torch.no_grad():
+        q.pre_scaling_impl.value.mul_(torch.tensor([1.0, 1.5, 0.7, 40.0, 1.0, 1.0]).reshape(-1, 1))
+    T = q.pre_scaling_impl.upper_bound()
+    gy = torch.randn(rows, k, dtype=torch.float64)
+    y = q(w)[0]
+    assert y.dtype == torch.float64
+    y.backward(gy)
+    s, g = q.scaling_impl(w).detach().reshape(-1), q.pre_scaling_impl(w).detach().reshape(-1)   # (restricted: > 0)
+    n = torch.maximum(R.norm64(v, norm), torch.tensor(R.NORM_MIN, dtype=torch.float64))
+    ref = R.closed_forms(v, s, g, gy, n, T, 127.0, norm, clamp_ste)
+    if norm == 'l1':
+        assert bool((g.double() > T * s.double())[3]) and not bool((g.double() > T * s.double())[0])
+    # (s and g are float32 parameters: their gradients arrive rounded to float32, 2^-24 relative)
+    for got, want, rel, name in ((w.grad, ref['dv'], 1e-12, 'dv'),
+                                 (q.scaling_impl.value.grad.reshape(-1), ref['ds'], 2.0 ** -23, 'ds'),
+                                 (q.pre_scaling_impl.value.grad.reshape(-1), ref['dg'], 2.0 ** -23, 'dg')):
+        assert torch.isfinite(got).all(), name
+        slack = 1e-12 * ref['SA'].max() if want.dim() == 1 else 1e-12 * ref['SA'].reshape(-1, 1)
+        assert bool(((got.double() - want).abs() <= rel * want.abs() + slack).all()), name
+    assert float(ref['dg'].abs().max()) > 0 and float(ref['ds'].abs().max()) > 0
+    assert torch.allclose(w.grad[5], gy[5] * (g[5].double() / n[5]), rtol=1e-12, atol=0)   # the zero row: direct term only
+
+
+# ---- state and layers -----------------------------------------------------------------------------------------------
+
+def test_state_dict_round_trip():
+    torch.manual_seed(5)
+    w = torch.nn.Parameter(torch.randn(5, 24) * 0.1)
+    a = a2q(w, 16)
+    assert sorted(a.state_dict()) == ['pre_scaling_impl.value', 'scaling_impl.value']
+    with torch.no_grad():
+        a.scaling_impl.value.mul_(1.25)
+        a.pre_scaling_impl.value.mul_(0.5)
+    b = a2q(torch.nn.Parameter(torch.randn(5, 24)), 16)
+    b.load_state_dict(a.state_dict())
+    assert torch.equal(a(w)[0], b(w)[0])
+
+
+def test_the_layer_checks_its_input_quantizer_against_the_bound():
+    import brevitas_amd.quant as Q
+    from brevitas_amd.nn import QuantLinear
+    wq = functools.partial(Q.Int8AccumulatorAwareWeightQuant, accumulator_bit_width=16, input_bit_width=8,
+                           input_signed=False)
+    QuantLinear(32, 8, weight_quant=wq, input_quant=Q.Uint8ActPerTensorFloat())         # agrees
+    QuantLinear(32, 8, weight_quant=wq)                                                 # nothing to contradict
+    with pytest.raises(ValueError, match='accumulator-aware'):
+        QuantLinear(32, 8, weight_quant=wq, input_quant=Q.Int8ActPerTensorFloat())      # signed inputs
+    with pytest.raises(ValueError, match='accumulator-aware'):
+        QuantLinear(32, 8, weight_quant=wq, input_quant=Q.Uint8ActPerTensorFloat(bit_width=4))
+    # the plain weight-norm quantizer states nothing about the input
+    QuantLinear(32, 8, weight_quant=Q.Int8WeightNormL2PerChannelFloat, input_quant=Q.Int8ActPerTensorFloat())
+
+
+@pytest.mark.parametrize('layer', ['linear', 'conv'])
+def test_layers_forward_and_backward_with_an_externally_scaled_bias(layer):
+    import brevitas_amd.quant as Q
+    from brevitas_amd.nn import QuantConv2d, QuantLinear
+    torch.manual_seed(8)
+    wq = functools.partial(Q.Int8AccumulatorAwareWeightQuant, accumulator_bit_width=16)
+    iq = Q.Uint8ActPerTensorFloatMaxInit(2.0)
+    if layer == 'linear':
+        m = QuantLinear(48, 6, weight_quant=wq, input_quant=iq, bias_quant=Q.Int8Bias())
+        x = torch.rand(5, 48, requires_grad=True)
+    else:
+        m = QuantConv2d(4, 6, 3, weight_quant=wq, input_quant=iq, bias_quant=Q.Int8Bias())
+        x = torch.rand(2, 4, 7, 7, requires_grad=True)
+    out = m(x)
+    out.sum().backward()
+    for name, t in (('x', x.grad), ('weight', m.weight.grad), ('s', m.weight_quant.scaling_impl.value.grad),
+                    ('g', m.weight_quant.pre_scaling_impl.value.grad)):
+        assert t is not None and torch.isfinite(t).all(), name
+    assert float(m.weight.grad.abs().max()) > 0 and float(m.weight_quant.scaling_impl.value.grad.abs().max()) > 0
+    # the float op ran on the dequantized integer weights
+    wq_, ws, _, _ = m.quant_weight()
+    codes = m.weight_quant.int_weight(m.weight)
+    assert torch.equal(wq_, codes.float() * ws)
+    assert bool((codes.reshape(6, -1).long().abs().sum(1) <= m.weight_quant.pre_scaling_impl.upper_bound()).all())
+
+
+# ---- the C ABI's argument checks (no device is touched) -------------------------------------------------------------
+
+def desc_for(rows, k, dt=None, round_mode=None, norm='l1'):
+    from brevitas_amd import _native as nat
+    dt = nat.F32 if dt is None else dt
+    rm = (nat.ROUND_TO_ZERO if norm == 'l1' else nat.ROUND) if round_mode is None else round_mode
+    return nat.QuantDesc(outer=1, channels=rows, inner=k, x_dtype=dt, ct_dtype=nat.F32, scale_dtype=nat.F32,
+                         zp_dtype=nat.F32, scale_per_channel=1, zp_per_channel=0, qmin=-127.0, qmax=127.0,
+                         round_mode=rm, scalar_mode=0, clamp_ste=1, out_kind=nat.OUT_DEQUANT, pre_op=nat.PRE_NONE)
+
+
+def test_abi_rejects_bad_arguments_before_a_device_is_touched():
+    from brevitas_amd import _native as nat
+    lib = nat.lib
+    fake = ctypes.c_void_p(4096)   # never dereferenced: every call below is refused first
+    inf = math.inf
+
+    def fwd(d, kind, t=inf, nmin=1e-10, x=fake):
+        return lib.bvq_weight_norm_fwd(None if d is None else ctypes.byref(d), kind, t, nmin, x, fake, fake, fake, fake,
+                                       None)
+
+    def bwd(d, kind):
+        return lib.bvq_weight_norm_bwd(None if d is None else ctypes.byref(d), kind, inf, 1e-10, fake, fake, fake, fake,
+                                       fake, fake, fake, fake, None)
+
+    good = desc_for(4, 64)
+    assert lib.bvq_weight_norm_supported(ctypes.byref(good), nat.NORM_L1, inf, 1e-10, fake) == 1
+    assert lib.bvq_weight_norm_supported(ctypes.byref(good), nat.NORM_L1, 127.5, 1e-10, ctypes.c_void_p(4104)) == 0
+    for call in (fwd, bwd):
+        assert call(None, nat.NORM_L1) == -1 and 'descriptor' in nat.last_error()
+        assert call(desc_for(4, 2), nat.NORM_L1) == -2 and '8 bytes' in nat.last_error()           # a row of 8 bytes
+        assert call(desc_for(4, 8196), nat.NORM_L1) == -2 and '32784 bytes' in nat.last_error()    # 32 KiB + 16
+        assert call(desc_for(4, 16388, nat.BF16), nat.NORM_L1) == -2 and '32776' in nat.last_error()
+        assert call(good, 2) == -1 and 'norm kind' in nat.last_error()
+        assert call(good, -1) == -1
+    assert lib.bvq_weight_norm_supported(None, nat.NORM_L1, inf, 1e-10, fake) == 0
+    assert lib.bvq_weight_norm_supported(ctypes.byref(desc_for(4, 8192)), nat.NORM_L1, inf, 1e-10, fake) == 1  # 32 KiB
+    assert lib.bvq_weight_norm_supported(ctypes.byref(desc_for(4, 8196)), nat.NORM_L1, inf, 1e-10, fake) == 0
+    # the rounding goes with the norm; bounds and the floor of the norm are positive; null pointers
+    assert fwd(desc_for(4, 64, round_mode=nat.ROUND), nat.NORM_L1) == -2 and 'round_mode' in nat.last_error()
+    assert fwd(desc_for(4, 64, norm='l2'), nat.NORM_L2, x=None) == -1 and 'null pointer' in nat.last_error()
+    assert fwd(good, nat.NORM_L1, t=0.0) == -1 and fwd(good, nat.NORM_L1, nmin=0.0) == -1
+    assert fwd(good, nat.NORM_L1, t=float('nan')) == -1
+    assert fwd(good, nat.NORM_L1, x=ctypes.c_void_p(4104)) == -2 and '16-byte' in nat.last_error()
+    bad_ct = desc_for(4, 64, nat.BF16)
+    bad_ct.ct_dtype = nat.BF16
+    assert fwd(bad_ct, nat.NORM_L1) == -2 and 'float32' in nat.last_error()
+
+
+def test_cpu_tensors_and_refused_shapes_do_not_reach_the_kernels(monkeypatch):
+    from brevitas_amd import _native as nat
+    calls = []
+    monkeypatch.setattr(nat, 'weight_norm_fwd', lambda *a, **k: calls.append(1))
+    w = torch.nn.Parameter(torch.randn(4, 64) * 0.1)
+    a2q(w, 16)(w)
+    assert not calls
