@@ -587,6 +587,28 @@ class GroupwiseMSEIntQuant(GroupwiseRescalingIntQuant):
         return y.reshape(x.shape), scale, self.zero_point_impl(x, scale, bit_width), bit_width
 
 
+class _PreScaleFn(torch.autograd.Function):
+    """p = (s n) / g' of the composed weight-norm route: the forward and the backward of the two torch ops, term for
+    term, except that a row which receives no gradient hands none on.  An overflowed norm (n = inf, p = inf, every
+    t = 0, A = B = 0) has ds = B - A = 0 and dg' = s A / g' = 0 by the closed forms of DESIGN.md §9; autograd's chain
+    rule would form 0 * inf for both."""
+
+    @staticmethod
+    def forward(ctx, s, n, gp):
+        a = s * n
+        ctx.save_for_backward(s, n, gp, a)
+        return a / gp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gpn):
+        s, n, gp, a = ctx.saved_tensors
+        none = gpn == 0   # (handed on as it is, sign included)
+        ga = gpn / gp
+        return (torch.where(none, gpn, ga * n), torch.where(none, gpn, ga * s),
+                torch.where(none, -gpn, -gpn * ((a / gp) / gp)))
+
+
 class WeightNormIntQuant(torch.nn.Module):
     """Weight-normalised weight quantizer: per output channel c (dim 0), with v the channel's K weights, s the learned
     scale (`scaling_impl`, a ParameterScaling) and g the learned norm parameter (`pre_scaling_impl`), all arithmetic in
@@ -697,7 +719,7 @@ class WeightNormIntQuant(torch.nn.Module):
         else:
             ts = s * t_bound
             gp = torch.where(g <= ts, g, ts)  # a tie goes to g
-        p = (s * n) / gp
+        p = _PreScaleFn.apply(s, n, gp)   # (s * n) / gp
         t = v / p
         r = round_to_zero_ste(t) if self.norm == 'l1' else round_ste(t)
         lo, hi = torch.full((), -qmax, dtype=ct, device=x.device), torch.full((), qmax, dtype=ct, device=x.device)

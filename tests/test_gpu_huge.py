@@ -187,3 +187,139 @@ def test_group_walk_past_2_32_bytes():
         y1, s1, dw1 = W.group_step(x[lo:hi], g[lo:hi], gs[glo:ghi], gsz, bits, True)
         assert W.bits_equal(y[lo:hi], y1) and W.bits_equal(scale[glo:ghi], s1), 'forward, piece at element %d' % lo
         assert W.bits_equal(dw[lo:hi], dw1), 'backward, piece at element %d' % lo
+
+
+# ---- the row walk past 2^32 bytes -----------------------------------------------------------------------------------
+# The row walk (csrc/bvq_row_walk.h) forms a row's base as row * cpr * vec in 64 bits and indexes the per-row outputs by
+# the 64-bit row.  The smallest bfloat16 tensors whose row bases pass 2^32 bytes, one geometry each so that both forms of
+# RowSlot::init are covered; x, g, y and dx together are about 17 GB.  Both calls stream more than the non-temporal
+# threshold, their pieces less: the NT instantiations against the plain ones as well.
+
+def _fill_randn(n, gen, std=1.0):
+    """a bfloat16 device tensor of n elements, randn * std, filled in pieces"""
+    t = torch.empty(n, device=DEV, dtype=torch.bfloat16)
+    step = 1 << 27   # (a float32 randn of the whole tensor would need another 8.6 GB)
+    for lo in range(0, n, step):
+        m = min(step, n - lo)
+        t[lo:lo + m] = (torch.randn(m, device=DEV, generator=gen) * std).to(torch.bfloat16)
+    return t
+
+
+def _seams(rows, row_bytes):
+    """the first two rows, the two sides of byte offsets 2^31 and 2^32, and the last row"""
+    a, b = 2 ** 31 // row_bytes, 2 ** 32 // row_bytes
+    assert a * row_bytes == 2 ** 31 and b < rows - 1
+    return [0, 1, a - 1, a, b - 1, b, rows - 1]
+
+
+def test_row_shifted_walk_past_2_32_bytes():
+    """the asymmetric per-token kernels, 8 bit, rows of 16384 bfloat16 (C = 2048: one workgroup per row), 2^17 + 5 rows,
+    gradients arriving through scale and zero-point: the rows at the seams, with the ties and extrema of
+    test_gpu_dynamic_act.plant among them, against the per-channel route (compare, with its derived deposit_ulps); the
+    whole tensor, 2048 rows at a time, against the same wrappers bit for bit (rows are independent and the sum order is
+    fixed by H)."""
+    import test_gpu_dynamic_act as DA
+    import test_gpu_group_walk as W
+    from brevitas_amd import _native as nat
+    from brevitas_amd.core.quant import _fused
+    free, _ = torch.cuda.mem_get_info()
+    if free < 40 << 30:
+        pytest.skip('needs 40 GB of free device memory')
+    h, rows, bits, ste, piece = 16384, 2 ** 17 + 5, 8, False, 2048
+    assert rows * h * 2 > 2 ** 32
+    qmax = 2.0 ** bits - 1
+    seams = _seams(rows, h * 2)
+    gen = torch.Generator(device=DEV).manual_seed(123460)
+    x = _fill_randn(rows * h, gen, 0.02).view(rows, h)
+    g = _fill_randn(rows * h, gen).view(rows, h)
+    gscale = torch.randn(rows, device=DEV, generator=gen).to(x.dtype)
+    gzp = (torch.randn(rows, device=DEV, generator=gen) * 0.01).to(x.dtype)
+    xs = x[seams].cpu()
+    DA.plant(xs[:6], 'bf16')
+    xs[6, h - 1] = (xs[6].abs().max().float() * 1.25).to(xs.dtype)   # the last row's maximum on the tensor's last element
+    x[seams] = xs.to(DEV)
+
+    def run(xp, gp, gsp, gzpp):
+        desc, thr_div = _fused.row_shifted_call(xp, qmax, 0.0, qmax, ste)
+        assert nat.row_shifted_supported(desc, xp)
+        y, scale, zp, stat = nat.row_shifted_fwd(desc, xp, 1e-10, thr_div)
+        return y, scale, zp, stat, nat.row_shifted_bwd(desc, gp, xp, stat, gsp, gzpp, 1e-10, thr_div)
+
+    y, scale, zp, stat, dx = run(x, g, gscale, gzp)
+    xs, gr, gss, gzs = x[seams].contiguous(), g[seams].contiguous(), gscale[seams].contiguous(), gzp[seams].contiguous()
+    got = (y[seams], scale[seams].view(-1, 1), zp[seams].view(-1, 1), dx[seams])
+    worst = DA.compare(got, DA.per_channel_step(xs, bits, ste, gr, gss, gzs), xs, gr, h, bits, 'bf16', gss, gzs)
+    print('ROW_SHIFTED_DEPOSIT_ULPS huge bf16 C=2048 rows=%d bits=%d ste=%d worst=%.3f' % (rows, bits, ste, worst))
+    assert torch.equal(stat[:rows][seams].float(), xs.max(dim=1).values.float())
+    assert torch.equal(stat[rows:][seams].float(), xs.min(dim=1).values.float())
+    for lo in range(0, rows, piece):
+        hi = min(lo + piece, rows)
+        y1, s1, z1, st1, dx1 = run(x[lo:hi], g[lo:hi], gscale[lo:hi], gzp[lo:hi])
+        where = 'piece at row %d' % lo
+        assert W.bits_equal(y[lo:hi], y1) and W.bits_equal(scale[lo:hi], s1) and W.bits_equal(zp[lo:hi], z1), where
+        assert W.bits_equal(stat[lo:hi], st1[:hi - lo]) and W.bits_equal(stat[rows + lo:rows + hi], st1[hi - lo:]), where
+        assert W.bits_equal(dx[lo:hi], dx1), where
+
+
+def test_weight_norm_walk_past_2_32_bytes():
+    """the weight-norm kernels, rows of 1024 bfloat16 (C = 128: one wave per row, four rows per workgroup), 2^21 + 7
+    rows, the L1 and then the L2 norm on the same tensors: the rows at the seams, which hold the planted rows of
+    test_gpu_weight_norm.case, against the bars of weight_norm_ref; the whole tensor, 2^15 rows at a time, against the
+    same wrappers bit for bit."""
+    import test_gpu_group_walk as W
+    import test_gpu_weight_norm as WN
+    import weight_norm_ref as R
+    from brevitas_amd import _native as nat
+    free, _ = torch.cuda.mem_get_info()
+    if free < 40 << 30:
+        pytest.skip('needs 40 GB of free device memory')
+    k, rows, piece = 1024, 2 ** 21 + 7, 2 ** 15
+    assert rows * k * 2 > 2 ** 32
+    seams = _seams(rows, k * 2)
+    gen = torch.Generator(device=DEV).manual_seed(123461)
+    v = _fill_randn(rows * k, gen, 0.02).view(rows, k)
+    gy = _fill_randn(rows * k, gen).view(rows, k)
+    vs = v[seams].cpu()
+    vs[0] = 0.0
+    vs[1] = 0.015625
+    vs[2, 0] = (vs[2].float().abs().max() * 1.25).to(vs.dtype)
+    vs[3, k - 1] = -(vs[3].float().abs().max() * 1.25).to(vs.dtype)
+    vs[6, k - 1] = (vs[6].float().abs().max() * 1.25).to(vs.dtype)   # the last row's abs-max on the tensor's last element
+    v[seams] = vs.to(DEV)
+    absmax = torch.empty(rows, device=DEV)
+    norm0 = {'l1': torch.empty(rows, device=DEV), 'l2': torch.empty(rows, device=DEV)}
+    for lo in range(0, rows, piece):
+        p = v[lo:lo + piece].double()
+        absmax[lo:lo + piece] = p.abs().amax(1).float()
+        norm0['l1'][lo:lo + piece] = p.abs().sum(1).float()
+        norm0['l2'][lo:lo + piece] = torch.sqrt((p * p).sum(1)).float()
+    del p
+    s = torch.clamp_min(absmax, 1e-10) / WN.QMAX
+    factor = 0.6 + 0.9 * torch.rand(rows, device=DEV, generator=gen)
+    for norm in ('l1', 'l2'):
+        gpar = torch.clamp_min(norm0[norm], 1e-10) * factor
+        T = float((2.0 * (gpar / s).max()).float())
+        gpar[seams[4]] = 3.0 * T * s[seams[4]]                     # capped
+        gpar[seams[5]] = torch.tensor(T, device=DEV) * s[seams[5]]   # the tie, which goes to g
+        kind = WN.kind_of(norm)
+
+        def run(vp, gyp, sp, gp):
+            desc = WN.desc_of(vp, norm, False)
+            assert nat.weight_norm_supported(desc, kind, T, R.NORM_MIN, vp)
+            y, n = nat.weight_norm_fwd(desc, kind, T, R.NORM_MIN, vp, sp, gp)
+            return (y, n) + tuple(nat.weight_norm_bwd(desc, kind, T, R.NORM_MIN, gyp, vp, sp, gp, n))
+
+        out = run(v, gy, s, gpar)
+        c = dict(k=k, v=vs, s=s[seams].cpu(), g=gpar[seams].cpu(), gy=gy[seams].cpu(), T=T, dn='bf16', norm=norm,
+                 clamp_ste=False, chunks=128, rows=len(seams))
+        c.update({name: t[seams].cpu() for name, t in zip(WN.OUTPUTS, out)})
+        c['ref'] = R.closed_forms(c['v'], c['s'], c['g'], c['gy'], c['n'], T, WN.QMAX, norm, False)
+        WN.check_norm(c, 'WEIGHT_NORM huge n')
+        WN.check_forward(c)
+        WN.check_backward(c, 'WEIGHT_NORM huge bwd')
+        for lo in range(0, rows, piece):
+            hi = min(lo + piece, rows)
+            part = run(v[lo:hi], gy[lo:hi], s[lo:hi], gpar[lo:hi])
+            for name, a, b in zip(WN.OUTPUTS, out, part):
+                assert W.bits_equal(a[lo:hi], b), '%s %s, piece at row %d' % (norm, name, lo)
+        del out, part

@@ -45,40 +45,104 @@ def case(chunks, rows, dn, norm, clamp_ste=False):
     unchanged.  Rows, as many as there are: 0 all zero, 1 constant, 2 +absmax at the first position, 3 -absmax at the
     last, 4 with g > T s (capped), 5 with g == T s exactly (the tie); the others have g = n * (0.6 .. 1.5), so some of
     their values clip.  T is twice the largest g / s before rows 4 and 5 are planted."""
-    from brevitas_amd import _native as nat
     k = chunks * 16 // SIZE[dn]
     gen = torch.Generator().manual_seed(1000 * chunks + rows)
     v = (torch.randn(rows, k, generator=gen) * 0.02).to(DT[dn])
     if rows > 1:
         v[0] = 0.0
         v[1] = 0.015625
+    if rows > 2:
         v[2, 0] = (v[2].float().abs().max() * 1.25).to(DT[dn])
+    if rows > 3:
         v[3, k - 1] = -(v[3].float().abs().max() * 1.25).to(DT[dn])
     absmax = v.float().abs().max(1).values
     s = torch.clamp_min(absmax, 1e-10) / QMAX
     n0 = torch.clamp_min(R.norm64(v, norm), 1e-10).float()
     g = n0 * (0.6 + 0.9 * torch.rand(rows, generator=gen))
     T = float((2.0 * (g / s).max()).float())
-    if rows > 1:
+    if rows > 4:
         g[4] = 3.0 * T * s[4]
+    if rows > 5:
         g[5] = torch.tensor(T) * s[5]
     gy = torch.randn(rows, k, generator=gen).to(DT[dn])
-    xd, sd, gd, gyd = v.to(DEV), s.to(DEV), g.to(DEV), gy.to(DEV)
-    desc = desc_of(xd, norm, clamp_ste)
-    assert nat.weight_norm_supported(desc, kind_of(norm), T, R.NORM_MIN, xd)
-    y, n = nat.weight_norm_fwd(desc, kind_of(norm), T, R.NORM_MIN, xd, sd, gd)
-    dv, ds, dg = nat.weight_norm_bwd(desc, kind_of(norm), T, R.NORM_MIN, gyd, xd, sd, gd, n)
-    y2, n2 = nat.weight_norm_fwd(desc, kind_of(norm), T, R.NORM_MIN, xd, sd, gd)
-    dv2, ds2, dg2 = nat.weight_norm_bwd(desc, kind_of(norm), T, R.NORM_MIN, gyd, xd, sd, gd, n2)
-    torch.cuda.synchronize()
-    out = dict(k=k, v=v, s=s, g=g, gy=gy, T=T, y=y.cpu(), n=n.cpu(), dv=dv.cpu(), ds=ds.cpu(), dg=dg.cpu(),
-               again=[t.cpu() for t in (y2, n2, dv2, ds2, dg2)])
+    out = dict(k=k, v=v, s=s, g=g, gy=gy, T=T, dn=dn, norm=norm, clamp_ste=clamp_ste, chunks=chunks, rows=rows)
+    out.update(run_kernels(out))
+    out['again'] = [run_kernels(out)[name] for name in OUTPUTS]
     out['ref'] = R.closed_forms(v, s, g, gy, out['n'], T, QMAX, norm, clamp_ste)
     return out
 
 
+OUTPUTS = ('y', 'n', 'dv', 'ds', 'dg')
+
+
+def run_kernels(c, v=None):
+    """one forward and one backward launch on the inputs of the case `c` (v: another weight in the place of c['v'])
+    through the library brevitas_amd._native stands on at the time of the call -> the five outputs, copied to the CPU"""
+    from brevitas_amd import _native as nat
+    norm = c['norm']
+    xd, sd, gd, gyd = ((c['v'] if v is None else v).to(DEV), c['s'].to(DEV), c['g'].to(DEV), c['gy'].to(DEV))
+    desc = desc_of(xd, norm, c['clamp_ste'])
+    assert nat.weight_norm_supported(desc, kind_of(norm), c['T'], R.NORM_MIN, xd)
+    y, n = nat.weight_norm_fwd(desc, kind_of(norm), c['T'], R.NORM_MIN, xd, sd, gd)
+    dv, ds, dg = nat.weight_norm_bwd(desc, kind_of(norm), c['T'], R.NORM_MIN, gyd, xd, sd, gd, n)
+    torch.cuda.synchronize()
+    return dict(zip(OUTPUTS, (t.cpu() for t in (y, n, dv, ds, dg))))
+
+
 def bits(t):
     return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+# ---- the bars, stated once: `c` is a case, or a case whose outputs were replaced by those of another run -------------
+
+def check_norm(c, tag='WEIGHT_NORM n'):
+    """|n - n64| <= (K + 4) 2^-24 n64: every term of the sum is non-negative, so the bound holds for any order of the
+    additions (weight_norm_ref, "Norm"); a norm below norm_min is reported as norm_min"""
+    n64 = R.norm64(c['v'], c['norm'])
+    nmin = float(torch.tensor(R.NORM_MIN, dtype=torch.float32))
+    want = torch.where(n64 > nmin, n64, torch.full_like(n64, nmin))
+    err = (c['n'].double() - want).abs() / want
+    print('%s %s %s C=%d rows=%d worst=%.3g of %.3g' % (tag, c['dn'], c['norm'], c['chunks'], c['rows'], float(err.max()),
+                                                        (c['k'] + 4) * R.U))
+    assert bool((err <= (c['k'] + 4) * R.U).all())
+    if c['rows'] > 1:
+        assert float(c['n'][0]) == nmin
+
+
+def check_forward(c):
+    """given the kernel's own n, the bits of the float32 chain on torch CPU ops, no element excepted"""
+    want = R.forward_from_n(c['v'], c['s'], c['g'], c['n'], c['T'], QMAX, c['norm'])
+    assert torch.equal(bits(c['y']), bits(want))
+    assert not torch.isnan(c['y'].float()).any()
+    if c['rows'] > 1:
+        assert float(c['y'][0].float().abs().max()) == 0.0                       # the all-zero row
+
+
+def check_backward(c, tag='WEIGHT_NORM bwd'):
+    """ds, dg and dv within the bounds of weight_norm_ref against c['ref'], the closed forms at c['n']"""
+    ref, k, dt = c['ref'], c['k'], DT[c['dn']]
+    for name in ('ds', 'dg', 'dv'):
+        assert torch.isfinite(c[name].float()).all(), name
+    ds_err = (c['ds'].double() - ref['ds']).abs()
+    ds_bound = R.sum_bound(k) * (ref['SA'] + ref['SB'])
+    dg_err = (c['dg'].double() - ref['dg']).abs()
+    dg_bound = ref['s_over_gp'] * R.sum_bound(k) * ref['SA']
+    dv_err = (c['dv'].double() - ref['dv']).abs()
+    dv_bound = R.dv_bound(ref, k, dt)
+    print('%s %s %s C=%d rows=%d ds %.3g dg %.3g dv %.3g (worst share of the bound)'
+          % (tag, c['dn'], c['norm'], c['chunks'], c['rows'], float((ds_err / ds_bound.clamp_min(1e-300)).max()),
+             float((dg_err / dg_bound.clamp_min(1e-300)).max()), float((dv_err / dv_bound.clamp_min(1e-300)).max())))
+    assert bool((ds_err <= ds_bound).all())
+    assert bool((dg_err <= dg_bound).all())
+    assert bool((dv_err <= dv_bound).all())
+    if c['rows'] > 4:
+        assert float(c['dg'][4]) == 0.0                                          # capped: g gets nothing
+    if c['rows'] > 5:
+        assert float(c['dg'][5]) != 0.0                                          # the tie: g gets it
+    if c['rows'] > 1:
+        # the all-zero row: n was clamped, no gradient through the norm: dv = gy * g' / n, rounded once
+        want0 = (c['gy'][0].double() * (c['g'][0].double() / c['n'][0].double()))
+        assert bool(((c['dv'][0].double() - want0).abs() <= 3 * R.U * want0.abs() + R.half_ulp(want0, dt) * 1.01).all())
 
 
 # ---- the kernels at every geometry ----------------------------------------------------------------------------------
@@ -89,16 +153,7 @@ def bits(t):
 def test_norm_against_float64(chunks, rows, dn, norm):
     """|n - n64| <= (K + 4) 2^-24 n64: every term of the sum is non-negative, so the bound holds for any order of the
     additions (weight_norm_ref, "Norm"); a norm below norm_min is reported as norm_min"""
-    c = case(chunks, rows, dn, norm)
-    n64 = R.norm64(c['v'], norm)
-    nmin = float(torch.tensor(R.NORM_MIN, dtype=torch.float32))
-    want = torch.where(n64 > nmin, n64, torch.full_like(n64, nmin))
-    err = (c['n'].double() - want).abs() / want
-    print('WEIGHT_NORM n %s %s C=%d rows=%d worst=%.3g of %.3g' % (dn, norm, chunks, rows, float(err.max()),
-                                                                    (c['k'] + 4) * R.U))
-    assert bool((err <= (c['k'] + 4) * R.U).all())
-    if rows > 1:
-        assert float(c['n'][0]) == nmin
+    check_norm(case(chunks, rows, dn, norm))
 
 
 @shapes
@@ -106,11 +161,8 @@ def test_norm_against_float64(chunks, rows, dn, norm):
 @norms
 def test_forward_has_the_bits_of_the_float32_chain(chunks, rows, dn, norm):
     c = case(chunks, rows, dn, norm)
-    want = R.forward_from_n(c['v'], c['s'], c['g'], c['n'], c['T'], QMAX, norm)
-    assert torch.equal(bits(c['y']), bits(want))
-    assert not torch.isnan(c['y'].float()).any()
+    check_forward(c)
     if rows > 1:
-        assert float(c['y'][0].float().abs().max()) == 0.0                       # the all-zero row
         t, r, q, gp, capped, p = R.chain(c['v'], c['s'], c['g'], c['n'], c['T'], QMAX, norm)
         assert capped.reshape(-1)[:6].tolist() == [False, False, False, False, True, False]   # the tie goes to g
         assert float(q.abs().max()) == QMAX                                      # something sits at the clamp
@@ -120,27 +172,7 @@ def test_forward_has_the_bits_of_the_float32_chain(chunks, rows, dn, norm):
 @dtypes
 @norms
 def test_backward_within_the_bounds(chunks, rows, dn, norm):
-    c = case(chunks, rows, dn, norm)
-    ref, k = c['ref'], c['k']
-    for name in ('ds', 'dg', 'dv'):
-        assert torch.isfinite(c[name].float()).all(), name
-    ds_err = (c['ds'].double() - ref['ds']).abs()
-    ds_bound = R.sum_bound(k) * (ref['SA'] + ref['SB'])
-    dg_err = (c['dg'].double() - ref['dg']).abs()
-    dg_bound = ref['s_over_gp'] * R.sum_bound(k) * ref['SA']
-    dv_err = (c['dv'].double() - ref['dv']).abs()
-    dv_bound = R.dv_bound(ref, k, DT[dn])
-    print('WEIGHT_NORM bwd %s %s C=%d rows=%d ds %.3g dg %.3g dv %.3g (worst share of the bound)'
-          % (dn, norm, chunks, rows, float((ds_err / ds_bound.clamp_min(1e-300)).max()),
-             float((dg_err / dg_bound.clamp_min(1e-300)).max()), float((dv_err / dv_bound.clamp_min(1e-300)).max())))
-    assert bool((ds_err <= ds_bound).all())
-    assert bool((dg_err <= dg_bound).all())
-    assert bool((dv_err <= dv_bound).all())
-    if rows > 1:
-        assert float(c['dg'][4]) == 0.0 and float(c['dg'][5]) != 0.0   # capped: g gets nothing; the tie: g gets it
-        # the all-zero row: n was clamped, no gradient through the norm: dv = gy * g' / n, rounded once
-        want0 = (c['gy'][0].double() * (c['g'][0].double() / c['n'][0].double()))
-        assert bool(((c['dv'][0].double() - want0).abs() <= 3 * R.U * want0.abs() + R.half_ulp(want0, DT[dn]) * 1.01).all())
+    check_backward(case(chunks, rows, dn, norm))
 
 
 @shapes

@@ -167,6 +167,48 @@ def test_autograd_of_the_composed_route_equals_the_closed_forms(norm, clamp_ste)
     assert torch.allclose(w.grad[5], gy[5] * (g[5].double() / n[5]), rtol=1e-12, atol=0)   # the zero row: direct term only
 
 
+# ---- rows that are not finite ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('norm', ['l1', 'l2'])
+def test_the_norm_of_a_row_that_is_not_finite_on_the_composed_route(norm):
+    """n = norm > norm_min ? norm : norm_min sends a NaN norm to norm_min; a norm that overflows float32 is inf, the row
+    comes out all zero and -- A = B = 0 in the closed forms -- its ds, dg and dv are zero, not 0 * inf.  Row 1 holds one
+    NaN, row 2 an inf at its last element, row 3 is finite with a norm beyond float32; row 0 is ordinary."""
+    import brevitas_amd.quant as Q
+    torch.manual_seed(13)
+    rows, k = 4, 24
+    v = torch.randn(rows, k) * 0.05
+    w0 = torch.nn.Parameter(v.clone())
+    q = a2q(w0, 32) if norm == 'l1' else Q.Int8WeightNormL2PerChannelFloat(w0)   # s and g of the finite weight
+    q.clamp_ste = False
+    v[1, 5] = float('nan')
+    v[2, k - 1] = float('inf')
+    v[3] = torch.where(torch.rand(k) < 0.5, -1.0, 1.0) * (3e38 if norm == 'l1' else 2e19)
+    assert bool(torch.isfinite(v[3]).all()) and math.isfinite(float(R.norm64(v, norm)[3]))
+    w = torch.nn.Parameter(v.clone())
+    s, g = q.scaling_impl(w), q.pre_scaling_impl(w)
+    y, n, p, codes = q.composed(w, s, g, 127.0)
+    n = n.detach().reshape(-1)
+    nmin = float(torch.tensor(R.NORM_MIN, dtype=torch.float32))
+    assert float(n[1]) == nmin   # exactly norm_min, as float32 holds it
+    assert float(n[2]) == math.inf and float(n[3]) == math.inf
+    want = R.forward_from_n(v, s.detach().reshape(-1), g.detach().reshape(-1), n, q.pre_scaling_impl.upper_bound(), 127.0,
+                            norm)
+    assert torch.equal(torch.isnan(y), torch.isnan(want))
+    assert torch.equal(y.detach().nan_to_num(0.0), want.nan_to_num(0.0))
+    assert torch.isnan(y[1]).nonzero().reshape(-1).tolist() == [5] and torch.isnan(y[2]).nonzero().reshape(-1).tolist() == [k - 1]
+    assert float(y[3].abs().max()) == 0.0 and float(y[0].abs().max()) > 0.0
+    gy = torch.randn(rows, k)
+    y.backward(gy)
+    ds, dg = q.scaling_impl.value.grad.reshape(-1), q.pre_scaling_impl.value.grad.reshape(-1)
+    ref = R.closed_forms(v, s.detach().reshape(-1), g.detach().reshape(-1), gy, n, q.pre_scaling_impl.upper_bound(), 127.0,
+                         norm, False)
+    for got, name in ((w.grad, 'dv'), (ds, 'ds'), (dg, 'dg')):
+        assert torch.equal(torch.isnan(got), torch.isnan(ref[name])), name
+    assert float(ds[3]) == 0.0 and float(dg[3]) == 0.0 and float(w.grad[3].abs().max()) == 0.0
+    assert bool(torch.isfinite(w.grad[0]).all()) and math.isfinite(float(ds[0])) and math.isfinite(float(dg[0]))
+
+
 # ---- state and layers -----------------------------------------------------------------------------------------------
 
 def test_state_dict_round_trip():

@@ -87,13 +87,15 @@ def closed_forms(v, s, g, gy, n, T, qmax, norm, clamp_ste):
     ds = B - A + torch.where(cap, float(T) * dgp if math.isfinite(T) else torch.zeros_like(dgp), torch.zeros_like(dgp))
     dg = torch.where(cap, torch.zeros_like(dgp), dgp)
     v64 = v.double()
-    kept = (n64 > float(torch.tensor(NORM_MIN, dtype=torch.float32))).double()
+    # c2 = n > norm_min ? s A / n : 0 is a choice, not a product with 0 or 1: where n was clamped, an A that is not finite
+    # (a NaN in the row) stays out of dv
+    kept = n64 > float(torch.tensor(NORM_MIN, dtype=torch.float32))
     dn = torch.sign(v64) if norm == 'l1' else v64 / n64.reshape(-1, 1)
     c1 = (gp64 / n64).reshape(-1, 1)
-    c2 = (kept * s64 * A / n64).reshape(-1, 1)
+    c2 = torch.where(kept, s64 * A / n64, torch.zeros_like(A)).reshape(-1, 1)
     c1gm, c2dn = gm.double() * c1, c2 * dn
-    return dict(A=A, B=B, SA=SA, SB=SB, ds=ds, dg=dg, dv=c1gm - c2dn, c1gm=c1gm, c2dn=c2dn, dn=dn * kept.reshape(-1, 1),
-                s_over_n=s64 / n64, s_over_gp=s64 / gp64)
+    return dict(A=A, B=B, SA=SA, SB=SB, ds=ds, dg=dg, dv=c1gm - c2dn, c1gm=c1gm, c2dn=c2dn,
+                dn=dn * kept.double().reshape(-1, 1), s_over_n=s64 / n64, s_over_gp=s64 / gp64, kept=kept)
 
 
 def half_ulp(x64, dtype):
@@ -109,7 +111,9 @@ def sum_bound(k):
 
 def dv_bound(ref, k, dtype):
     sa = ref['SA'].reshape(-1, 1)
-    rest = ref['dn'].abs() * ref['s_over_n'].reshape(-1, 1) * sum_bound(k) * sa \
-        + 6 * U * (ref['c1gm'].abs() + ref['c2dn'].abs())
+    # (A reaches dv through c2 alone: a row whose n was clamped has no such term, whatever its A)
+    through_a = torch.where(ref['kept'].reshape(-1, 1), ref['dn'].abs() * ref['s_over_n'].reshape(-1, 1) * sum_bound(k) * sa,
+                            torch.zeros_like(ref['c1gm']))
+    rest = through_a + 6 * U * (ref['c1gm'].abs() + ref['c2dn'].abs())
     # (the value that is rounded lies within `rest` of dv64: the spacing at the farther end covers a binade crossed)
     return rest + half_ulp(ref['dv'].abs() + rest, dtype)
