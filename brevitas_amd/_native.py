@@ -1,7 +1,8 @@
 """ctypes binding of libbvq.so -- the C-ABI HIP library (include/bvq.h).
 
-This is the ONLY compute backend of the package: there is no CPU or pure-torch fallback.  If the
-library is missing, or a tensor does not live on a ROCm device, the call fails loudly.
+This is the only backend of device tensors: a call here never falls back to torch ops.  If the
+library is missing, or a tensor does not live on a ROCm device, the call fails loudly.  (CPU tensors
+never get here: the modules send them down their composed routes, brevitas_amd/_aten.py.)
 
 PyTorch is used here as plumbing only: device memory (torch.empty), the current HIP stream and the
 device guard.  Signatures carry raw pointers and sizes.

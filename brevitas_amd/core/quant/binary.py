@@ -13,6 +13,7 @@ from brevitas_amd.core.function_wrapper import TensorClamp
 from brevitas_amd.core.quant.delay import DelayWrapper
 from brevitas_amd import _native as nat
 from brevitas_amd.core.quant import _fused
+from brevitas_amd.core.quant._recognise import clamp_ste_of
 from brevitas_amd.core.utils import StatelessBuffer
 from brevitas_amd.function.ops_ste import binary_sign_ste
 
@@ -62,7 +63,7 @@ class ClampedBinaryQuant(torch.nn.Module):
 
     def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
         scale = self.scaling_impl(x)
-        clamp_ste = getattr(self.tensor_clamp_impl, 'bvq_clamp_ste', None)
+        clamp_ste = clamp_ste_of(self.tensor_clamp_impl)
         y = _sign_kernel(x, scale, nat.VAR_CLAMPED_BINARY, clamp_ste) if clamp_ste is not None else None
         if y is None:
             y = self.tensor_clamp_impl(x, -scale, scale)

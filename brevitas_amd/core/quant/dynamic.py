@@ -12,13 +12,9 @@ resolved weight graph applied to x2 = x.reshape(rows, H) as the tracked tensor:
 symmetric (ZeroZeroPoint, AbsMax) or asymmetric (RuntimeDynamicStatsZeroPoint of NegativeMinOrZero, AbsMinMax).  The
 sub-modules carry the reference's attribute names; none of them has a parameter or a buffer.
 
-Routes.  The composed route is the sub-modules applied one after the other to the viewed tensor; it serves CPU tensors,
-config.FUSED_PATHS off, non-contiguous or misaligned inputs and every shape the kernels refuse.  On the device:
-    symmetric, tensor / row    _fused.StatsFakeQuantFn without a running statistic (the per-channel weight kernels)
-    group                      _fused.GroupStatsFakeQuantFn / GroupShiftedFakeQuantFn for a covered group size
-    asymmetric, row            GroupShiftedFakeQuantFn when H itself is a covered group size (several rows share a wave),
-                               else _fused.RowShiftedFakeQuantFn (csrc/bvq_row_shifted.hip)
-    asymmetric, tensor         the composed route: no kernel of its own
+Routes ("Routes", row "dynamic").  The composed route is the sub-modules applied one after the other to
+the viewed tensor; it serves CPU tensors, config.FUSED_PATHS off, non-contiguous or misaligned inputs and every shape the
+kernels refuse.  On the device _route picks the per-channel weight kernels, the group walk or the shifted row kernel.
 """
 from typing import Optional, Tuple
 
@@ -29,16 +25,12 @@ from torch.nn import Module
 import brevitas_amd.config as config
 from brevitas_amd import _native as nat
 from brevitas_amd.core.quant import _fused
-from brevitas_amd.core.quant.delay import _NoDelay
-from brevitas_amd.core.quant.int_base import IntQuant
-from brevitas_amd.core.scaling.int_scaling import IntScaling
+from brevitas_amd.core.quant import _recognise as rec
 from brevitas_amd.core.scaling.runtime import RuntimeDynamicStatsScaling
-from brevitas_amd.core.stats.stats_op import AbsMax, AbsMinMax, NegativeMinOrZero
+from brevitas_amd.core.stats.stats_op import AbsMax
 from brevitas_amd.core.zero_point import RuntimeDynamicStatsZeroPoint, ZeroZeroPoint
-from brevitas_amd.function.ops import int_range_host
 
 GRANULARITIES = ('tensor', 'row', 'group')
-_GROUP_SIZES = (16, 32, 64, 128, 256)  # what the sub-wave group walk covers
 
 
 class DynamicActIntQuant(torch.nn.Module):
@@ -82,54 +74,51 @@ class DynamicActIntQuant(torch.nn.Module):
                              'of the group size %d' % (tuple(x.shape), g))
         return x.reshape(-1, g), tuple(x.shape[:-1]) + (h // g, 1)
 
-    def _fused_args(self, bit_width: Tensor):
-        """(shifted, min_val, int_thr, qmin, qmax, round_mode, clamp_ste) when the sub-modules are the graph the kernels
-        compute (a plain IntQuant with a known rounding and clamp, a host-known bit width, the plain lower bound of the
-        scale, AbsMax with a zero zero-point or AbsMinMax with the quantized NegativeMinOrZero), else None"""
+    def _template(self, bit_width: Tensor):
+        """the rec.DynamicTemplate when the sub-modules are the graph the kernels compute (rec.plain_int_quant, the plain
+        lower bound of the scale, AbsMax or rec.shifted_zero_point), else None; cached like _stats_template"""
         iq, sc, zpi = self.int_quant, self.scaling_impl, self.zero_point_impl
-        bw = getattr(bit_width, 'bvq_host_value', None)
-        if bw is None or type(iq) is not IntQuant or not isinstance(iq.delay_wrapper.delay_impl, _NoDelay):
-            return None
-        round_mode = getattr(iq.float_to_int_impl, 'bvq_round_mode', None)
-        clamp_ste = getattr(iq.tensor_clamp_impl, 'bvq_clamp_ste', None)
-        if round_mode is None or clamp_ste is None or type(self.int_scaling_impl) is not IntScaling or \
-                type(sc) is not RuntimeDynamicStatsScaling:
+        ssz = getattr(zpi, 'scale_shift_zero_point', None)
+        # everything _build_template reads: the sub-modules, the statistics under them and the flags of the graph
+        key = (config.FUSED_PATHS, self.granularity, getattr(iq, 'signed', None), getattr(iq, 'narrow_range', None),
+               id(getattr(sc, 'stats_scaling_impl', None)), id(getattr(getattr(sc, 'stats', None), 'stats_impl', None)),
+               id(getattr(getattr(zpi, 'stats', None), 'stats_impl', None)), id(ssz), id(getattr(ssz, 'int_quant', None)),
+               getattr(ssz, 'quantize_zero_point', None)) + rec.graph_key(self, bit_width)
+        return rec.cached(self, '_bvq_dynamic_template', key, lambda: self._build_template(bit_width))
+
+    def _build_template(self, bit_width: Tensor):
+        iq, sc, zpi = self.int_quant, self.scaling_impl, self.zero_point_impl
+        plain = rec.plain_int_quant(iq, self.int_scaling_impl, bit_width) if config.FUSED_PATHS else None
+        if plain is None or type(sc) is not RuntimeDynamicStatsScaling:
             return None
         min_val = sc.stats_scaling_impl.bvq_plain_min_val()
         if min_val is None:
             return None
-        dim = None if self.granularity == 'tensor' else 1
-        if type(zpi) is ZeroZeroPoint:
-            shifted = False
-            if type(sc.stats.stats_impl) is not AbsMax:
+        dims = (None,) if self.granularity == 'tensor' else (1, -1)
+        shifted = type(zpi) is RuntimeDynamicStatsZeroPoint
+        if shifted:
+            # next to the shared predicate: this class takes any rounding on its symmetric routes, the shifted kernels
+            # round half to even only
+            if plain.round_mode != nat.ROUND or not rec.shifted_zero_point(
+                    iq, sc.stats.stats_impl, zpi.stats.stats_impl, zpi.scale_shift_zero_point, dims):
                 return None
-        elif type(zpi) is RuntimeDynamicStatsZeroPoint:
-            shifted = True
-            ssz = zpi.scale_shift_zero_point
-            if type(sc.stats.stats_impl) is not AbsMinMax or type(zpi.stats.stats_impl) is not NegativeMinOrZero or \
-                    zpi.stats.stats_impl.stats_reduce_dim not in ((None,) if dim is None else (1, -1)) or \
-                    ssz.int_quant is not iq or not ssz.quantize_zero_point or iq.signed or iq.narrow_range or \
-                    round_mode != nat.ROUND:
-                return None
-        else:
+        elif type(zpi) is not ZeroZeroPoint or type(sc.stats.stats_impl) is not AbsMax or \
+                sc.stats.stats_impl.stats_reduce_dim not in dims:
             return None
-        if sc.stats.stats_impl.stats_reduce_dim not in ((None,) if dim is None else (1, -1)):
-            return None
-        qmin, qmax = int_range_host(iq.signed, iq.narrow_range, bw)
-        return shifted, min_val, self.int_scaling_impl.host_value(bw), qmin, qmax, round_mode, clamp_ste
+        return rec.DynamicTemplate(shifted, min_val, plain.int_thr, *plain[:4])   # qmin, qmax, round_mode, clamp_ste
 
     def _route(self, xv: Tensor, bit_width: Tensor):
         """the device route of the viewed tensor -> (y, scale, zero_point or None), or None: the composed route"""
         if not (config.FUSED_PATHS and xv.is_cuda and xv.dtype in _fused._FLOATS and xv.is_contiguous()
                 and xv.data_ptr() % 16 == 0) or torch._C._get_tracing_state() is not None:
             return None
-        fa = self._fused_args(bit_width)
-        if fa is None:
+        tmpl = self._template(bit_width)
+        if tmpl is None:
             return None
-        shifted, min_val, int_thr, qmin, qmax, round_mode, clamp_ste = fa
+        shifted, min_val, int_thr, qmin, qmax, round_mode, clamp_ste = tmpl
         rows, h = xv.shape
-        if self.granularity == 'group' or (shifted and self.granularity == 'row' and h in _GROUP_SIZES):
-            if h not in _GROUP_SIZES or round_mode != nat.ROUND:
+        if self.granularity == 'group' or (shifted and self.granularity == 'row' and h in rec.GROUP_SIZES):
+            if h not in rec.GROUP_SIZES or round_mode != nat.ROUND:
                 return None
             if shifted:
                 return _fused.GroupShiftedFakeQuantFn.apply(xv, h, min_val, int_thr, qmin, qmax, clamp_ste)

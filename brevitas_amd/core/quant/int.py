@@ -5,12 +5,8 @@ Sub-module attribute names (`int_quant`, `scaling_impl`, `int_scaling_impl`, `ze
 `msb_clamp_bit_width_impl`) are the reference's: they are part of state-dict keys and are
 introspected by proxies.
 
-Two recognised graphs skip the op-by-op orchestration and run as statistic kernel + tiny scale
-ops + quantize kernel, with a backward that never materialises torch.max's dense gradient:
-  * weights:      StatsFromParameterScaling(AbsMax) tracking exactly the tensor being quantized
-                  (Int8WeightPerChannelFloat and friends, SURVEY 8a);
-  * activations:  RuntimeStatsScaling(AbsMax) in training mode.
-Everything else takes the generic route below, which is the reference's own sequence.
+Recognised graphs skip the op-by-op orchestration ("Routes": RescalingIntQuant._route and the tables of
+core/quant/_recognise.py); everything else takes the generic route, which is the reference's own sequence.
 """
 import math
 from typing import Sequence, Tuple
@@ -22,14 +18,14 @@ from torch.nn import Module
 import brevitas_amd.config as config
 from brevitas_amd.core.function_wrapper.shape import OverOutputChannelView, OverSubChannelBlockView, OverTensorView
 from brevitas_amd.core.quant import _fused
+from brevitas_amd.core.quant import _recognise as rec
 from brevitas_amd.core.quant.delay import _NoDelay
 from brevitas_amd.core.quant.int_base import IntQuant
-from brevitas_amd.core.scaling.int_scaling import IntScaling
 from brevitas_amd import _aten
 from brevitas_amd import _native as nat
 from brevitas_amd.core.scaling.runtime import RuntimeStatsScaling, StatsFromParameterScaling
 from brevitas_amd.core.scaling.standalone import ConstScaling, ParameterFromRuntimeStatsScaling, ParameterScaling
-from brevitas_amd.core.stats.stats_op import AbsMax, AbsMinMax, NegativeMinOrZero
+from brevitas_amd.core.stats.stats_op import AbsMax
 from brevitas_amd.core.zero_point import StatsFromParameterZeroPoint, ZeroZeroPoint
 from brevitas_amd.function.ops import int_range_host, tensor_clamp
 from brevitas_amd.function.ops_ste import round_ste, round_to_zero_ste, tensor_clamp_ste
@@ -62,41 +58,21 @@ class RescalingIntQuant(torch.nn.Module):
 
     def _stats_template(self, bit_width: Tensor):
         """Structural part of the fused-graph recognition, cached until the module graph, the training
-        flag or the configuration changes: None, or a dict describing the statistic -> scale chain."""
-        iq, sc = self.int_quant, self.scaling_impl
-        bw = getattr(bit_width, 'bvq_host_value', None)
-        key = (config.FUSED_PATHS, id(iq), id(sc), id(self.zero_point_impl), id(self.int_scaling_impl), bw,
-               getattr(sc, 'training', None), id(getattr(iq, 'float_to_int_impl', None)),
-               id(getattr(iq, 'tensor_clamp_impl', None)),
-               id(getattr(getattr(iq, 'delay_wrapper', None), 'delay_impl', None)))
-        cached = self.__dict__.get('_bvq_template')
-        if cached is not None and cached[0] == key:
-            return cached[1]
-        tmpl = self._build_stats_template(bw)
-        self.__dict__['_bvq_template'] = (key, tmpl)
-        return tmpl
+        flag or the configuration changes: None, or the rec.StatsTemplate of the statistic -> scale chain."""
+        training = getattr(self._modules.get('scaling_impl'), 'training', None)   # (not through nn.Module.__getattr__)
+        key = (config.FUSED_PATHS, training) + rec.graph_key(self, bit_width)
+        return rec.cached(self, '_bvq_template', key, lambda: self._build_stats_template(bit_width))
 
-    def _plain_int_quant(self, bw):
-        """(qmin, qmax, round_mode, clamp_ste, int_threshold) on the host if this is a plain IntQuant (no delay, a
-        rounding and a clamp the kernels know) with a zero zero-point, IntScaling and the host-known bit width `bw`;
-        else None"""
-        iq = self.int_quant
-        if bw is None or type(iq) is not IntQuant or not isinstance(iq.delay_wrapper.delay_impl, _NoDelay):
+    def _plain_int_quant(self, bit_width: Tensor):
+        """rec.plain_int_quant with a zero zero-point (the symmetric kernels), else None"""
+        if type(self.zero_point_impl) is not ZeroZeroPoint:
             return None
-        round_mode = getattr(iq.float_to_int_impl, 'bvq_round_mode', None)
-        clamp_ste = getattr(iq.tensor_clamp_impl, 'bvq_clamp_ste', None)
-        if round_mode is None or clamp_ste is None:
-            return None
-        if type(self.zero_point_impl) is not ZeroZeroPoint or type(self.int_scaling_impl) is not IntScaling:
-            return None
-        qmin, qmax = int_range_host(iq.signed, iq.narrow_range, bw)
-        return qmin, qmax, round_mode, clamp_ste, self.int_scaling_impl.host_value(bw)
+        return rec.plain_int_quant(self.int_quant, self.int_scaling_impl, bit_width)
 
-    def _build_stats_template(self, bw):
-        plain = self._plain_int_quant(bw) if config.FUSED_PATHS else None
+    def _build_stats_template(self, bit_width: Tensor):
+        plain = self._plain_int_quant(bit_width) if config.FUSED_PATHS else None
         if plain is None:
             return None
-        qmin, qmax, round_mode, clamp_ste, int_thr = plain
         sc = self.scaling_impl
         runtime, weight, shared = None, None, None
         if type(sc) is RuntimeStatsScaling:
@@ -134,9 +110,8 @@ class RescalingIntQuant(torch.nn.Module):
             return None
         if shared is not None and (post is not None or len(shared) > 8):
             return None
-        return dict(runtime=runtime, weight=weight, shared=shared, view=view, shape=shape, min_val=min_val, post=post,
-                    per_channel=per_channel, int_thr=int_thr, qmin=qmin, qmax=qmax, round_mode=round_mode,
-                    clamp_ste=clamp_ste)
+        return rec.StatsTemplate(runtime, weight, shared, view, shape, min_val, post, per_channel, plain.int_thr,
+                                 plain.qmin, plain.qmax, plain.round_mode, plain.clamp_ste)
 
     def _stats_plan(self, x: Tensor, bit_width: Tensor):
         """(StatsPlan, template) if a recognised fused graph applies to this input, else None"""
@@ -145,26 +120,23 @@ class RescalingIntQuant(torch.nn.Module):
         tmpl = self._stats_template(bit_width)
         if tmpl is None:
             return None
-        w = tmpl['weight']
-        if tmpl['shared'] is not None:
-            # the tensor being quantized is one of the list; every tensor lies [channels, ...] (or flat) in memory
-            same = [i for i, t in enumerate(tmpl['shared'])
-                    if t is x or (t.data_ptr() == x.data_ptr() and t.shape == x.shape and t.stride() == x.stride())]
-            ch0 = x.shape[0] if tmpl['per_channel'] else None
-            if not same or not x.is_contiguous() or any(
+        if tmpl.shared is not None:
+            # the tensor being quantized is one of the list (same_tensor's dtype term adds nothing: every member has x's
+            # dtype below); every tensor lies [channels, ...] (or flat) in memory
+            ch0 = x.shape[0] if tmpl.per_channel else None
+            if not any(rec.same_tensor(t, x) for t in tmpl.shared) or not x.is_contiguous() or any(
                     (not t.is_cuda) or t.device != x.device or t.dtype != x.dtype or not t.is_contiguous()
                     or t.dim() == 0 or t.numel() == 0 or (ch0 is not None and t.shape[0] != ch0)
-                    for t in tmpl['shared']):
+                    for t in tmpl.shared):
                 return None
-            if tmpl['per_channel'] and tmpl['view'].bvq_channel_dim(x.dim()) != 0:
+            if tmpl.per_channel and tmpl.view.bvq_channel_dim(x.dim()) != 0:
                 return None
-        elif w is not None and not (w is x or (w.data_ptr() == x.data_ptr() and w.shape == x.shape
-                                               and w.stride() == x.stride() and w.dtype == x.dtype)):
+        elif tmpl.weight is not None and tmpl.weight is not x and not rec.same_tensor(tmpl.weight, x):
             return None  # the statistic is taken of another tensor than the one being quantized
-        shape = tmpl['shape']
-        if not tmpl['per_channel']:
-            return _fused.StatsPlan(1, 1, x.numel(), shape, tmpl['min_val'], tmpl['int_thr']), tmpl
-        cd = tmpl['view'].bvq_channel_dim(x.dim())
+        shape = tmpl.shape
+        if not tmpl.per_channel:
+            return _fused.StatsPlan(1, 1, x.numel(), shape, tmpl.min_val, tmpl.int_thr), tmpl
+        cd = tmpl.view.bvq_channel_dim(x.dim())
         if cd is None or cd < 0:
             return None
         # the scaling shape must broadcast against x exactly at the channel dim
@@ -174,7 +146,7 @@ class RescalingIntQuant(torch.nn.Module):
             return None
         # (a dense channels_last activation is [N*H*W, C] in memory: the column-mapped kernels)
         outer, channels, inner, nhwc = _fused.split_at_channel(x, cd)
-        return _fused.StatsPlan(outer, channels, inner, shape, tmpl['min_val'], tmpl['int_thr'], nhwc), tmpl
+        return _fused.StatsPlan(outer, channels, inner, shape, tmpl.min_val, tmpl.int_thr, nhwc), tmpl
 
     def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
         if _ACTIVE_GROUP is not None:  # inside `with WeightQuantGroup(...)`: the group may have quantized this weight
@@ -184,15 +156,14 @@ class RescalingIntQuant(torch.nn.Module):
         return self.bvq_forward_pre(x, nat.PRE_NONE)
 
     def _learned_scale_args(self, x: Tensor, bit_width: Tensor):
-        """(value, min_val, Plan, thr_div, scale_dtype, qmin, qmax, round_mode, clamp_ste) if the scale is a learned
-        parameter with a float restriction right now -- scale = |clamp_min(value)| / int_threshold -- and the fused
-        quantizer kernel covers the operands; else None"""
+        """(value, Plan, min_val, thr_div, scale_dtype, qmin, qmax, round_mode, clamp_ste), what LearnedScaleFakeQuantFn
+        takes after x, if the scale is a learned parameter with a float restriction right now -- scale =
+        |clamp_min(value)| / int_threshold -- and the fused quantizer kernel covers the operands; else None"""
         if not config.FUSED_PATHS or not x.is_cuda:
             return None
-        plain = self._plain_int_quant(getattr(bit_width, 'bvq_host_value', None))
+        plain = self._plain_int_quant(bit_width)
         if plain is None:
             return None
-        qmin, qmax, round_mode, clamp_ste, int_thr = plain
         learned = getattr(self.scaling_impl, 'bvq_learned_scale', None)
         found = learned() if learned is not None else None
         if found is None:
@@ -205,19 +176,14 @@ class RescalingIntQuant(torch.nn.Module):
         if p is None or p.zp_pc:
             return None
         # int_threshold has the bit width's dtype: next to a 0-dim value the division sees it as that dtype holds it
-        rule = _fused.scale_rule(value.dtype, value.shape, int_thr, bit_width.dtype, thr_as_stored=True)
-        return value, min_val, p, rule.thr_div, rule.scale_dtype, qmin, qmax, round_mode, clamp_ste
+        rule = _fused.scale_rule(value.dtype, value.shape, plain.int_thr, bit_width.dtype, thr_as_stored=True)
+        return (value, p, min_val, rule.thr_div, rule.scale_dtype) + plain[:4]
 
     def _scale_ignores_input(self) -> bool:
         """True if scaling_impl(x) does not read x right now (learned / constant / frozen statistics)"""
         sc = self.scaling_impl
-        if type(sc) in (ParameterScaling, ConstScaling):
-            return True
-        if type(sc) is RuntimeStatsScaling:
-            return not sc.training
-        if type(sc) is ParameterFromRuntimeStatsScaling:
-            return (not sc.training) or sc.counter >= sc.collect_stats_steps
-        return False
+        return type(sc) in (ParameterScaling, ConstScaling) or (type(sc) is RuntimeStatsScaling and not sc.training) or \
+            (type(sc) is ParameterFromRuntimeStatsScaling and (not sc.training or sc.counter >= sc.collect_stats_steps))
 
     def _collect_only(self, x: Tensor, pre_op: int, bit_width: Tensor):
         """Calibration forward (brevitas_amd.graph.calibrate): advance the statistics of the scale and
@@ -227,35 +193,151 @@ class RescalingIntQuant(torch.nn.Module):
         if not isinstance(self.int_quant.delay_wrapper.delay_impl, _NoDelay):
             raise NotImplementedError('calibration with quant_delay_steps')
         with torch.no_grad():
-            fused = self._stats_plan(x, bit_width)
-            if pre_op in _fused.ACT_PRE_OPS and (fused is None or fused[1]['runtime'] is None or fused[0].nhwc
-                                                 or getattr(self, 'bvq_shard_group', None) is not None
-                                                 or not _fused.act_dtype_ok(x, pre_op) or x.data_ptr() % 16 != 0):
-                # sigmoid / tanh fold into the row-mapped statistic kernels only: materialise them elsewhere
+            plan = self._stats_plan(x, bit_width)
+            if pre_op != nat.PRE_NONE and not self._stats_fold(x, pre_op, plan, statistic_only=True):
                 x, pre_op = _fused.apply_pre_op(x, pre_op), nat.PRE_NONE
-                fused = self._stats_plan(x, bit_width)
-            if fused is not None and fused[1]['runtime'] is not None:
-                sp, tmpl = fused
+                plan = self._stats_plan(x, bit_width)
+            x_act = _fused.apply_pre_op(x, pre_op)
+            if plan is not None and plan[1].runtime is not None:
+                sp, tmpl = plan
                 group = getattr(self, 'bvq_shard_group', None)
                 flat = _fused._memory_order(x, sp.channels, sp.nhwc)[0].reshape(-1)
                 stat, scale = _fused.stats_scale(flat, self.int_scaling_impl(bit_width), sp, group, pre_op)
-                tmpl['runtime'].update_running_stats(stat.view(sp.scaling_shape))
-                x_act = _fused.apply_pre_op(x, pre_op)
+                tmpl.runtime.update_running_stats(stat.view(sp.scaling_shape))
             else:
-                x_act = _fused.apply_pre_op(x, pre_op)
-                threshold = self.scaling_impl(x_act)
-                scale = threshold / self.int_scaling_impl(bit_width)
+                scale = self.scaling_impl(x_act) / self.int_scaling_impl(bit_width)
             zero_point = self.zero_point_impl(x_act, scale, bit_width)
         return x_act, scale, zero_point, bit_width
 
-    def _learned_forward(self, x: Tensor, bit_width: Tensor, learned, pre_op: int):
-        """learned scale (steady state of the default activation quantizers): one launch for the scale, the
-        quantizer kernel; in backward the scale's own chain rides on the last reduction launch"""
-        value, min_val, p, thr_div, scale_dtype, qmin, qmax, round_mode, clamp_ste = learned
-        y, scale = _fused.LearnedScaleFakeQuantFn.apply(x, value, p, min_val, thr_div, scale_dtype, qmin, qmax,
-                                                        round_mode, clamp_ste, pre_op)
+    # ---- routes ("Routes") ---------------------------------------------------------------------
+
+    def _stats_fold(self, x: Tensor, pre_op: int, plan, statistic_only: bool = False) -> bool:
+        """whether the stats-scaled kernels of `plan` take `pre_op` folded.  relu folds into every kernel of one tensor.
+        sigmoid / tanh (csrc/bvq_act.h) fold into the row-mapped statistic kernel alone, which calibration runs on its
+        own (`statistic_only`); the forward's statistic + quantizer pair has no such variant and materialises them."""
+        if plan is None or plan[1].shared is not None:
+            return False  # (the list kernel takes no pre-op)
+        if pre_op not in _fused.ACT_PRE_OPS:
+            return True
+        return statistic_only and plan[1].runtime is not None and not plan[0].nhwc and \
+            getattr(self, 'bvq_shard_group', None) is None and _fused.act_dtype_ok(x, pre_op) and x.data_ptr() % 16 == 0
+
+    def _keep_pre_op(self, x: Tensor, pre_op: int, bit_width: Tensor, plan):
+        """what _route returns when the route's own kernels fold `pre_op`, or None: materialise it"""
+        if plan is not None:
+            return (self._planned(plan), x, pre_op, plan) if self._stats_fold(x, pre_op, plan) else None
+        if pre_op in _fused.ACT_PRE_OPS:
+            # sigmoid / tanh fold into the quantizer kernels of a scale that does not read x: a learned one here, a
+            # constant one or frozen statistics below.  A batch-sharded quantizer materialises them.
+            if getattr(self, 'bvq_shard_group', None) is not None:
+                return None
+            learned = self._learned_scale_args(x, bit_width)
+            if learned is not None:
+                return ('learned', x, pre_op, learned) if _fused.act_fusable(x, learned[1], pre_op) else None
+        if type(self.int_quant) is IntQuant and type(self.zero_point_impl) is ZeroZeroPoint \
+                and self._scale_ignores_input():
+            return 'folded', x, pre_op, None  # IntQuant decides what it covers
+        return None
+
+    @staticmethod
+    def _planned(plan) -> str:
+        return 'post' if plan[1].post is not None else 'stats'
+
+    def _route(self, x: Tensor, pre_op: int, bit_width: Tensor):
+        """-> (route, x, pre_op, plan): the route of this forward -- 'list', 'post', 'stats', 'learned', 'folded' or
+        'generic', a key of _ROUTES -- the tensor and the pre-op its method takes (the pre-op materialised here, once,
+        unless the route folds it) and the route's plan: (StatsPlan, template), _learned_scale_args or None"""
+        plan = self._stats_plan(x, bit_width)
+        if pre_op != nat.PRE_NONE:
+            kept = self._keep_pre_op(x, pre_op, bit_width, plan)
+            if kept is not None:
+                return kept
+            # like the reference does; the plan is of the tensor quantized (a new tensor is no tracked weight)
+            x, pre_op = _fused.apply_pre_op(x, pre_op), nat.PRE_NONE
+            plan = self._stats_plan(x, bit_width)
+        if plan is not None:
+            if plan[1].shared is None:
+                return self._planned(plan), x, pre_op, plan
+            if _fused.list_stats_supported(tuple(plan[1].shared), plan[0]):
+                return 'list', x, pre_op, plan
+            # a list the list kernel does not cover: op by op
+        learned = self._learned_scale_args(x, bit_width)
+        if learned is not None:
+            return 'learned', x, pre_op, learned
+        return 'generic', x, pre_op, None
+
+    def _finish(self, x: Tensor, y: Tensor, scale: Tensor, bit_width: Tensor):
+        return y, scale, self.zero_point_impl(x, scale, bit_width), bit_width
+
+    def _forward_list(self, x: Tensor, pre_op: int, bit_width: Tensor, plan):
+        """a quantizer shared by several weights: the statistic of the whole list in one launch"""
+        sp, t = plan
+        params = tuple(t.shared)
+        # _stats_plan found a member that is x and left only contiguous members of x's dtype: same_tensor's stride and
+        # dtype terms can tell two members apart only if both alias x's storage with x's shape, where either is x
+        index = next(i for i, p in enumerate(params) if rec.same_tensor(p, x))
+        y, scale, _ = _fused.ListStatsFakeQuantFn.apply(x, self.int_scaling_impl(bit_width), sp, t.qmin, t.qmax,
+                                                        t.round_mode, t.clamp_ste, index, *params)
+        return self._finish(x, y, scale, bit_width)
+
+    def _stats_operands(self, bit_width: Tensor, plan):
+        """(int_threshold, runtime, shard group) of a stats-scaled route; the running statistic is marked not yet folded"""
+        runtime = plan[1].runtime
+        if runtime is not None:
+            runtime.bvq_running_folded = False
+        # a batch-sharded activation (brevitas_amd.distributed.shard_over_batch); weights are replicated
+        group = getattr(self, 'bvq_shard_group', None) if runtime is not None else None
+        return self.int_scaling_impl(bit_width), runtime, group
+
+    def _forward_post(self, x: Tensor, pre_op: int, bit_width: Tensor, plan):
+        """statistic kernel, the statistic -> scale map as torch ops on the small tensors, quantizer kernel"""
+        sp, t = plan
+        int_threshold, runtime, group = self._stats_operands(bit_width, plan)
+        if group is not None:
+            raise NotImplementedError('batch-sharded quantizer with a non-trivial statistic -> scale map')
+        y, scale, stat = _fused.StatsGraphFakeQuantFn.apply(x, int_threshold, sp, t.qmin, t.qmax, t.round_mode,
+                                                            t.clamp_ste, pre_op, t.post, *tuple(t.post.parameters()))
+        if runtime is not None:
+            runtime.update_running_stats(stat)
+        return self._finish(x, y, scale, bit_width)
+
+    def _forward_stats(self, x: Tensor, pre_op: int, bit_width: Tensor, plan):
+        """statistic -> plain lower bound -> quantizer: the C++ autograd node where it is built and applies, else the Function"""
+        sp, t = plan
+        int_threshold, runtime, group = self._stats_operands(bit_width, plan)
+        fast = None
+        if runtime is None:          # a weight
+            fast = _fused.fast_stats_fakequant(x, int_threshold, sp, t.qmin, t.qmax, t.round_mode, t.clamp_ste, pre_op)
+        elif config.CPP_AUTOGRAD:    # an activation: statistic kernel + quantizer kernel, same idea
+            fast = _fused.fast_act_stats_fakequant(x, int_threshold, sp, t.qmin, t.qmax, t.round_mode, t.clamp_ste,
+                                                   pre_op, group, runtime)
+        y, scale, stat = fast if fast is not None else _fused.StatsFakeQuantFn.apply(
+            x, int_threshold, sp, t.qmin, t.qmax, t.round_mode, t.clamp_ste, group, pre_op, runtime)
+        if runtime is not None:
+            if runtime.bvq_running_folded:   # updated by the statistic's own finishing launch
+                runtime.first_batch = False
+            else:
+                runtime.update_running_stats(stat)
+        return self._finish(x, y, scale, bit_width)
+
+    def _forward_learned(self, x: Tensor, pre_op: int, bit_width: Tensor, learned):
+        # (steady state of the default activation quantizers) one launch for the scale, the quantizer kernel; in backward
+        # the scale's own chain rides on the last reduction launch
+        y, scale = _fused.LearnedScaleFakeQuantFn.apply(x, *learned, pre_op)
+        return self._finish(x, y, scale, bit_width)
+
+    def _forward_generic(self, x: Tensor, pre_op: int, bit_width: Tensor, plan=None):
+        """the reference's own sequence (B/core/quant/int.py:157-163); 'folded': with the pre-op handed on to IntQuant"""
+        threshold = self.scaling_impl(x)
+        int_threshold = self.int_scaling_impl(bit_width)
+        scale = threshold / int_threshold
         zero_point = self.zero_point_impl(x, scale, bit_width)
-        return y, scale, zero_point, bit_width
+        y = self.int_quant(scale, zero_point, bit_width, x) if pre_op == nat.PRE_NONE else \
+            self.int_quant.bvq_forward_pre(scale, zero_point, bit_width, x, pre_op)
+        return y, scale, zero_point, bit_width  # (_finish would ask zero_point_impl twice)
+
+    _ROUTES = {'list': _forward_list, 'post': _forward_post, 'stats': _forward_stats, 'learned': _forward_learned,
+               'folded': _forward_generic, 'generic': _forward_generic}
 
     def bvq_forward_pre(self, x: Tensor, pre_op: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
         """forward(pre_op(x)) -- FusedActivationQuantProxy.forward (B/proxy/runtime_quant.py:80-84) -- with
@@ -264,92 +346,8 @@ class RescalingIntQuant(torch.nn.Module):
         bit_width = self.msb_clamp_bit_width_impl()
         if getattr(self, 'bvq_collect_only', False):
             return self._collect_only(x, pre_op, bit_width)
-        fused = self._stats_plan(x, bit_width)
-        if pre_op in _fused.ACT_PRE_OPS:
-            # sigmoid / tanh (csrc/bvq_act.h) fold into the quantizer kernels of a scale that does not read x: a learned
-            # one here, a constant one or frozen statistics in the block below (IntQuant decides what it covers).
-            # Stats-scaled graphs and batch-sharded quantizers materialise the activation.
-            shard = getattr(self, 'bvq_shard_group', None) is not None
-            learned = self._learned_scale_args(x, bit_width) if fused is None and not shard else None
-            if learned is not None and _fused.act_fusable(x, learned[2], pre_op):
-                return self._learned_forward(x, bit_width, learned, pre_op)
-            if fused is not None or shard or learned is not None:
-                x, pre_op = _fused.apply_pre_op(x, pre_op), nat.PRE_NONE
-                fused = self._stats_plan(x, bit_width)
-        if fused is None and pre_op != nat.PRE_NONE:
-            if type(self.int_quant) is IntQuant and type(self.zero_point_impl) is ZeroZeroPoint \
-                    and self._scale_ignores_input():
-                threshold = self.scaling_impl(x)
-                int_threshold = self.int_scaling_impl(bit_width)
-                scale = threshold / int_threshold
-                zero_point = self.zero_point_impl(x, scale, bit_width)
-                y = self.int_quant.bvq_forward_pre(scale, zero_point, bit_width, x, pre_op)
-                return y, scale, zero_point, bit_width
-            x = _fused.apply_pre_op(x, pre_op)  # not fusable here: materialise the activation like the reference does
-            pre_op = nat.PRE_NONE
-        if fused is not None:
-            sp, tmpl = fused
-            runtime = tmpl['runtime']
-            int_threshold = self.int_scaling_impl(bit_width)
-            # a batch-sharded activation (brevitas_amd.distributed.shard_over_batch); weights are replicated
-            group = getattr(self, 'bvq_shard_group', None) if runtime is not None else None
-            if runtime is not None:
-                runtime.bvq_running_folded = False
-            fast = None
-            if tmpl['shared'] is not None:
-                params = tuple(tmpl['shared'])
-                index = next(i for i, t in enumerate(params) if t.data_ptr() == x.data_ptr() and t.shape == x.shape)
-                if pre_op == nat.PRE_NONE and _fused.list_stats_supported(params, sp):
-                    y, scale, stat = _fused.ListStatsFakeQuantFn.apply(
-                        x, int_threshold, sp, tmpl['qmin'], tmpl['qmax'], tmpl['round_mode'], tmpl['clamp_ste'], index,
-                        *params)
-                    zero_point = self.zero_point_impl(x, scale, bit_width)
-                    return y, scale, zero_point, bit_width
-                fused = None  # list not covered by the list kernel: op by op
-                if pre_op != nat.PRE_NONE:
-                    x, pre_op = _fused.apply_pre_op(x, pre_op), nat.PRE_NONE
-        if fused is not None:
-            sp, tmpl = fused
-            if tmpl['post'] is not None:
-                if group is not None:
-                    raise NotImplementedError('batch-sharded quantizer with a non-trivial statistic -> scale map')
-                post = tmpl['post']
-                y, scale, stat = _fused.StatsGraphFakeQuantFn.apply(
-                    x, int_threshold, sp, tmpl['qmin'], tmpl['qmax'], tmpl['round_mode'], tmpl['clamp_ste'], pre_op,
-                    post, *tuple(post.parameters()))
-                if runtime is not None:
-                    runtime.update_running_stats(stat)
-                zero_point = self.zero_point_impl(x, scale, bit_width)
-                return y, scale, zero_point, bit_width
-            if runtime is None and group is None:  # a weight: the autograd node in C++ when it is built and applies
-                fast = _fused.fast_stats_fakequant(x, int_threshold, sp, tmpl['qmin'], tmpl['qmax'], tmpl['round_mode'],
-                                                   tmpl['clamp_ste'], pre_op)
-            elif config.CPP_AUTOGRAD:              # an activation: statistic kernel + quantizer kernel, same idea
-                fast = _fused.fast_act_stats_fakequant(x, int_threshold, sp, tmpl['qmin'], tmpl['qmax'],
-                                                       tmpl['round_mode'], tmpl['clamp_ste'], pre_op, group, runtime)
-            if fast is not None:
-                y, scale, stat = fast
-            else:
-                y, scale, stat = _fused.StatsFakeQuantFn.apply(
-                    x, int_threshold, sp, tmpl['qmin'], tmpl['qmax'], tmpl['round_mode'], tmpl['clamp_ste'], group,
-                    pre_op, runtime)
-            if runtime is not None:
-                if runtime.bvq_running_folded:   # updated by the statistic's own finishing launch
-                    runtime.first_batch = False
-                else:
-                    runtime.update_running_stats(stat)
-            zero_point = self.zero_point_impl(x, scale, bit_width)
-            return y, scale, zero_point, bit_width
-        learned = self._learned_scale_args(x, bit_width)
-        if learned is not None:
-            return self._learned_forward(x, bit_width, learned, pre_op)
-        # generic orchestration (B/core/quant/int.py:157-163)
-        threshold = self.scaling_impl(x)
-        int_threshold = self.int_scaling_impl(bit_width)
-        scale = threshold / int_threshold
-        zero_point = self.zero_point_impl(x, scale, bit_width)
-        y = self.int_quant(scale, zero_point, bit_width, x)
-        return y, scale, zero_point, bit_width
+        route, x, pre_op, plan = self._route(x, pre_op, bit_width)
+        return self._ROUTES[route](self, x, pre_op, bit_width, plan)
 
 
 class GroupwiseRescalingIntQuant(RescalingIntQuant):
@@ -380,33 +378,14 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
 
     def _group_template(self, bit_width: Tensor):
         """structural part of the fused-graph recognition, cached like RescalingIntQuant._stats_template"""
-        iq, sc = self.int_quant, self.scaling_impl
-        bw = getattr(bit_width, 'bvq_host_value', None)
-        key = (config.FUSED_PATHS, self.group_size, id(iq), id(sc), id(self.zero_point_impl),
-               id(self.int_scaling_impl), bw, id(getattr(iq, 'float_to_int_impl', None)),
-               id(getattr(iq, 'tensor_clamp_impl', None)),
-               id(getattr(getattr(iq, 'delay_wrapper', None), 'delay_impl', None)))
-        cached = self.__dict__.get('_bvq_group_template')
-        if cached is not None and cached[0] == key:
-            return cached[1]
-        tmpl = self._build_group_template(bw)
-        self.__dict__['_bvq_group_template'] = (key, tmpl)
-        return tmpl
+        key = (config.FUSED_PATHS, self.group_size) + rec.graph_key(self, bit_width)
+        return rec.cached(self, '_bvq_group_template', key, lambda: self._build_group_template(bit_width))
 
-    def _build_group_template(self, bw):
-        if not config.FUSED_PATHS or bw is None:
-            return None
-        iq, sc = self.int_quant, self.scaling_impl
-        if type(iq) is not IntQuant or not isinstance(iq.delay_wrapper.delay_impl, _NoDelay):
-            return None
-        if getattr(iq.float_to_int_impl, 'bvq_round_mode', None) != nat.ROUND or \
-                getattr(iq.tensor_clamp_impl, 'bvq_clamp_ste', None) is None:
-            return None
-        zpi = self.zero_point_impl
-        if type(zpi) not in (ZeroZeroPoint, StatsFromParameterZeroPoint) or \
-                type(self.int_scaling_impl) is not IntScaling:
-            return None
-        if type(sc) is not StatsFromParameterScaling:
+    def _build_group_template(self, bit_width: Tensor):
+        iq, sc, zpi = self.int_quant, self.scaling_impl, self.zero_point_impl
+        plain = rec.plain_int_quant(iq, self.int_scaling_impl, bit_width) if config.FUSED_PATHS else None
+        if plain is None or plain.round_mode != nat.ROUND or type(sc) is not StatsFromParameterScaling or \
+                type(zpi) not in (ZeroZeroPoint, StatsFromParameterZeroPoint):
             return None
         pls = sc.parameter_list_stats
         view, stats = pls.first_tracked_param.view_shape_impl, pls.stats
@@ -414,31 +393,25 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
                 view.bvq_group_size != self.group_size:
             return None
         shifted = type(zpi) is StatsFromParameterZeroPoint
-        if type(stats.stats_impl) is not (AbsMinMax if shifted else AbsMax) or \
-                stats.stats_impl.stats_reduce_dim not in (1, -1):
-            return None
         if shifted:
-            # the asymmetric graph: the zero-point is NegativeMinOrZero of the same weight over the same groups,
-            # quantized by this quantizer's own to_int, whose "+ min_int" is "+ 0" for the unsigned full range
-            zls, ssz = zpi.parameter_list_stats, zpi.scale_shift_zero_point
+            # next to the shared predicate, a weight quantizer has two tracked-parameter lists that could differ: the
+            # zero-point must be a statistic of the same weight over the same groups, shaped like the scale's
+            zls = zpi.parameter_list_stats
             zview, zstats = zls.first_tracked_param.view_shape_impl, zls.stats
             if zls.extra_tracked_params_list is not None or type(zview) is not OverSubChannelBlockView or \
                     zview.bvq_group_size != self.group_size or \
-                    zls.first_tracked_param.parameter is not pls.first_tracked_param.parameter:
-                return None
-            if type(zstats.stats_impl) is not NegativeMinOrZero or \
-                    zstats.stats_impl.stats_reduce_dim not in (1, -1) or \
+                    zls.first_tracked_param.parameter is not pls.first_tracked_param.parameter or \
                     tuple(zstats.stats_output_shape) != tuple(stats.stats_output_shape):
                 return None
-            if ssz.int_quant is not iq or not ssz.quantize_zero_point or iq.signed or iq.narrow_range:
+            if not rec.shifted_zero_point(iq, stats.stats_impl, zstats.stats_impl, zpi.scale_shift_zero_point, (1, -1)):
                 return None
-        min_val = sc.stats_scaling_impl.bvq_plain_min_val()
-        if min_val is None or self.group_size not in (16, 32, 64, 128, 256):
+        elif type(stats.stats_impl) is not AbsMax or stats.stats_impl.stats_reduce_dim not in (1, -1):
             return None
-        qmin, qmax = int_range_host(iq.signed, iq.narrow_range, bw)
-        return dict(weight=pls.first_tracked_param.parameter, shape=tuple(stats.stats_output_shape), min_val=min_val,
-                    int_thr=self.int_scaling_impl.host_value(bw), qmin=qmin, qmax=qmax,
-                    clamp_ste=iq.tensor_clamp_impl.bvq_clamp_ste, shifted=shifted)
+        min_val = sc.stats_scaling_impl.bvq_plain_min_val()
+        if min_val is None or self.group_size not in rec.GROUP_SIZES:
+            return None
+        return rec.GroupTemplate(pls.first_tracked_param.parameter, tuple(stats.stats_output_shape), min_val,
+                                 plain.int_thr, plain.qmin, plain.qmax, plain.clamp_ste, shifted)
 
     def _group_plan(self, x: Tensor, bit_width: Tensor):
         """the template if the one-kernel route applies to this input, else None"""
@@ -447,11 +420,9 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
         tmpl = self._group_template(bit_width)
         if tmpl is None:
             return None
-        w = tmpl['weight']
-        if not (w is x or (w.data_ptr() == x.data_ptr() and w.shape == x.shape and w.stride() == x.stride()
-                           and w.dtype == x.dtype)):
+        if not rec.same_tensor(tmpl.weight, x):
             return None  # the statistic is taken of another tensor than the one being quantized
-        if tmpl['shape'] != (x.numel() // self.group_size, 1):
+        if tmpl.shape != (x.numel() // self.group_size, 1):
             return None
         return tmpl
 
@@ -468,12 +439,12 @@ class GroupwiseRescalingIntQuant(RescalingIntQuant):
         bit_width = self.msb_clamp_bit_width_impl()
         tmpl = self._group_plan(x, bit_width)
         zero_point = None
-        if tmpl is not None and tmpl['shifted']:
+        if tmpl is not None and tmpl.shifted:
             y, scale, zero_point = _fused.GroupShiftedFakeQuantFn.apply(
-                x, g, tmpl['min_val'], tmpl['int_thr'], tmpl['qmin'], tmpl['qmax'], tmpl['clamp_ste'])
+                x, g, tmpl.min_val, tmpl.int_thr, tmpl.qmin, tmpl.qmax, tmpl.clamp_ste)
         elif tmpl is not None:
-            y, scale = _fused.GroupStatsFakeQuantFn.apply(x, g, tmpl['min_val'], tmpl['int_thr'], tmpl['qmin'],
-                                                          tmpl['qmax'], tmpl['clamp_ste'])
+            y, scale = _fused.GroupStatsFakeQuantFn.apply(x, g, tmpl.min_val, tmpl.int_thr, tmpl.qmin,
+                                                          tmpl.qmax, tmpl.clamp_ste)
         else:
             # the existing modules on the regrouped tensor (the reference's own sequence, B/core/quant/int.py:157-163)
             xg = x.reshape(-1, g)
@@ -566,18 +537,17 @@ class GroupwiseMSEIntQuant(GroupwiseRescalingIntQuant):
         g = self._check_groups(x)
         bit_width = self.msb_clamp_bit_width_impl()
         tmpl = self._group_plan(x, bit_width)
-        if tmpl is not None and tmpl['shifted']:
-            tmpl = None  # the clip search is built for the symmetric graph alone
-        if tmpl is not None:
-            desc, _ = _fused.group_quant_call(x, g, tmpl['int_thr'], tmpl['qmin'], tmpl['qmax'], tmpl['clamp_ste'])
-            if not nat.group_mse_supported(desc, x, len(self.mse_ratios)):
-                tmpl = None
+        # the clip search is built for the symmetric graph alone
+        if tmpl is not None and (tmpl.shifted or not nat.group_mse_supported(
+                _fused.group_quant_call(x, g, tmpl.int_thr, tmpl.qmin, tmpl.qmax, tmpl.clamp_ste)[0], x,
+                len(self.mse_ratios))):
+            tmpl = None
         if tmpl is not None:
             table = self.__dict__.get('_bvq_mse_table')
             if table is None:
                 table = self.__dict__['_bvq_mse_table'] = nat.mse_ratio_table(self.mse_ratios)
-            y, scale, idx = _fused.GroupMSEFakeQuantFn.apply(x, g, tmpl['min_val'], tmpl['int_thr'], tmpl['qmin'],
-                                                             tmpl['qmax'], tmpl['clamp_ste'], table)
+            y, scale, idx = _fused.GroupMSEFakeQuantFn.apply(x, g, tmpl.min_val, tmpl.int_thr, tmpl.qmin,
+                                                             tmpl.qmax, tmpl.clamp_ste, table)
         else:
             xg, stat, scale_of, quantize = self._mse_callables(x, bit_width)
             idx = _aten.group_mse_index(xg, self.mse_ratios, stat, scale_of, quantize)
@@ -847,7 +817,7 @@ class TruncIntQuant(torch.nn.Module):
         # kernel, its autograd one more (include/bvq.h, bvq_variant_fwd: BVQ_VAR_TRUNC)
         in_bw = getattr(input_bit_width, 'bvq_host_value', None)
         out_bw = getattr(output_bit_width, 'bvq_host_value', None)
-        round_mode = getattr(self.float_to_int_impl, 'bvq_round_mode', None)
+        round_mode = rec.round_mode_of(self.float_to_int_impl)
         if in_bw is not None and out_bw is not None and round_mode is not None and \
                 _fused.scalar_zero_point_ok(zero_point, x=x):
             p = _fused.variant_plan(x, scale)

@@ -16,6 +16,7 @@ import brevitas_amd.config as config
 from brevitas_amd import _native as nat
 from brevitas_amd.core.function_wrapper import LearnedRoundSte, RoundSte, TensorClamp
 from brevitas_amd.core.quant import _fused
+from brevitas_amd.core.quant import _recognise as rec
 from brevitas_amd.core.quant.delay import DelayWrapper, _NoDelay
 from brevitas_amd.function.ops import int_range_host, max_int, min_int
 
@@ -65,18 +66,12 @@ class IntQuant(torch.nn.Module):
 
     def _fused_args(self, scale: Tensor, zero_point: Tensor, bit_width: Tensor, x: Tensor):
         """(plan, qmin, qmax, round_mode, clamp_ste) if the fused kernel covers this call, else None"""
-        if not config.FUSED_PATHS:
-            return None
-        round_mode = getattr(self.float_to_int_impl, 'bvq_round_mode', None)
-        clamp_ste = getattr(self.tensor_clamp_impl, 'bvq_clamp_ste', None)
-        bw = getattr(bit_width, 'bvq_host_value', None)
-        if round_mode is None or clamp_ste is None or bw is None:
-            return None
-        p = _fused.plan(x, scale, zero_point)
+        k = rec.kernel_int_quant(self, bit_width) if config.FUSED_PATHS else None
+        p = _fused.plan(x, scale, zero_point) if k is not None else None
         if p is None:
             return None
-        qmin, qmax = int_range_host(self.signed, self.narrow_range, bw)
-        return p, qmin, qmax, round_mode, clamp_ste
+        qmin, qmax = int_range_host(self.signed, self.narrow_range, k.bw)
+        return p, qmin, qmax, k.round_mode, k.clamp_ste
 
     def _learned_round_args(self, scale: Tensor, zero_point: Tensor, bit_width: Tensor, x: Tensor):
         """(value, plan, qmin, qmax, clamp_ste, impl kind, impl constants, hard) if float_to_int_impl is a LearnedRoundSte
@@ -89,11 +84,11 @@ class IntQuant(torch.nn.Module):
         if not isinstance(lr, LearnedRoundSte):
             return None
         found = lr.bvq_learned_round()
-        clamp_ste = getattr(self.tensor_clamp_impl, 'bvq_clamp_ste', None)
-        bw = getattr(bit_width, 'bvq_host_value', None)
-        if found is None or clamp_ste is None or bw is None:
+        k = rec.kernel_int_quant(self, bit_width, rounding=False)   # (the rounding is the learned one)
+        if found is None or k is None:
             return None
         kind, consts, value = found
+        clamp_ste = k.clamp_ste
         if x.dtype == torch.float16 and not lr.learned_round_impl.bvq_f16_ok():
             return None  # torch's float16 kernels are not one function of their inputs there
         grad = torch.is_grad_enabled()
@@ -108,7 +103,7 @@ class IntQuant(torch.nn.Module):
         if not value.is_cuda or value.device != x.device or value.dtype != x.dtype or value.numel() != x.numel() or \
                 not value.is_contiguous():
             return None
-        qmin, qmax = int_range_host(self.signed, self.narrow_range, bw)
+        qmin, qmax = int_range_host(self.signed, self.narrow_range, k.bw)
         desc = _fused.make_desc(p, x, scale, zero_point, qmin, qmax, nat.FLOOR, clamp_ste, nat.OUT_DEQUANT)
         if not nat.learned_round_supported(desc, x, value):
             return None
@@ -228,14 +223,11 @@ class IntQuant(torch.nn.Module):
         """(plan, round_mode, clamp_ste) if the fused kernels can take the integer range from device tensors"""
         if not config.FUSED_PATHS or not bit_width.is_cuda or bit_width.numel() != 1 or zero_point.requires_grad:
             return None
-        round_mode = getattr(self.float_to_int_impl, 'bvq_round_mode', None)
-        clamp_ste = getattr(self.tensor_clamp_impl, 'bvq_clamp_ste', None)
-        if round_mode is None or clamp_ste is None:
-            return None
-        p = _fused.plan(x, scale, zero_point)
+        k = rec.kernel_int_quant(self, bit_width, host_bw=False)   # (the range is read from device memory)
+        p = _fused.plan(x, scale, zero_point) if k is not None else None
         if p is None or p.zp_pc:
             return None
-        return p, round_mode, clamp_ste
+        return p, k.round_mode, k.clamp_ste
 
 
 class DecoupledIntQuant(torch.nn.Module):
@@ -274,10 +266,8 @@ class DecoupledIntQuant(torch.nn.Module):
 
     def _fused_forward(self, pre_scale, pre_zero_point, scale, zero_point, bit_width, x):
         """the whole chain as one kernel (and its autograd as one more), or None if not covered"""
-        round_mode = getattr(self.float_to_int_impl, 'bvq_round_mode', None)
-        clamp_ste = getattr(self.tensor_clamp_impl, 'bvq_clamp_ste', None)
-        bw = getattr(bit_width, 'bvq_host_value', None)
-        if round_mode is None or clamp_ste is None or bw is None or bit_width.requires_grad:
+        k = rec.kernel_int_quant(self, bit_width)
+        if k is None or bit_width.requires_grad:
             return None
         if not _fused.scalar_zero_point_ok(zero_point, pre_zero_point, x=x):
             return None
@@ -287,10 +277,10 @@ class DecoupledIntQuant(torch.nn.Module):
         ct = torch.result_type(x, pre_scale)
         if not (ct == x.dtype or ct == torch.float32) or zero_point.dtype != pre_zero_point.dtype:
             return None
-        qmin, qmax = int_range_host(self.signed, self.narrow_range, bw)
+        qmin, qmax = int_range_host(self.signed, self.narrow_range, k.bw)
         return _fused.VariantFn.apply(x, scale, pre_scale, zero_point, pre_zero_point, p,
-                                      dict(kind=nat.VAR_DECOUPLED, ct=ct, round_mode=round_mode, clamp_ste=clamp_ste,
-                                           qmin=qmin, qmax=qmax))
+                                      dict(kind=nat.VAR_DECOUPLED, ct=ct, round_mode=k.round_mode,
+                                           clamp_ste=k.clamp_ste, qmin=qmin, qmax=qmax))
 
     def forward(self, pre_scale: Tensor, pre_zero_point: Tensor, scale: Tensor, zero_point: Tensor, bit_width: Tensor,
                 x: Tensor) -> Tensor:

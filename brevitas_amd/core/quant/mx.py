@@ -42,6 +42,7 @@ from brevitas_amd import _native as nat
 from brevitas_amd.core.utils import StatelessBuffer
 
 from . import _fused
+from ._recognise import GROUP_SIZES
 
 __all__ = ['MXQuant', 'MX_FORMATS', 'MXFormat', 'MXPacked', 'mx_dequantize']
 
@@ -64,7 +65,6 @@ MX_FORMATS = {
     'int8': MXFormat(nat.MX_INT8, 6, None, 0, 127.0 / 64.0, 8),
 }
 SCALE_RULES = {'floor': nat.MX_FLOOR, 'ceil': nat.MX_CEIL}
-FUSED_GROUP_SIZES = (16, 32, 64, 128, 256)
 _E_MIN, _E_MAX = -126, 127
 
 
@@ -286,7 +286,7 @@ class MXQuant(torch.nn.Module):
     def fused_route(self, x: Tensor) -> bool:
         """the one-kernel route applies to this (contiguous) tensor"""
         return bool(config.FUSED_PATHS and x.is_cuda and x.dtype in _fused._FLOATS
-                    and self.group_size in FUSED_GROUP_SIZES and x.data_ptr() % 16 == 0 and x.numel() > 0)
+                    and self.group_size in GROUP_SIZES and x.data_ptr() % 16 == 0 and x.numel() > 0)
 
     def forward(self, x: Tensor) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor], Tensor]:
         bit_width = self._bit_width()
@@ -359,7 +359,7 @@ class MXQuant(torch.nn.Module):
             raise ValueError('MX quantizer: %d code bytes and %d scale bytes do not hold a tensor of shape %s in %s with '
                              'groups of %d' % (codes.numel(), scale.numel(), shape, self.element_format, self.group_size))
         codes, scale = codes.contiguous().reshape(-1), scale.contiguous().reshape(-1)
-        if config.FUSED_PATHS and codes.is_cuda and self.group_size in FUSED_GROUP_SIZES and \
+        if config.FUSED_PATHS and codes.is_cuda and self.group_size in GROUP_SIZES and \
                 codes.data_ptr() % 16 == 0 and scale.data_ptr() % 16 == 0:
             y = nat.mx_decode(codes, scale, self.group_size, self.format.code, dtype)
         else:

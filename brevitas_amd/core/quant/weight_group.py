@@ -61,7 +61,7 @@ class _WeightList:
         self.int_thresholds = [e.quant.int_scaling_impl(e.bit_width) for e in entries]
         w0 = entries[0].weight
         self.scale_dtype = w0.dtype  # a dimensioned scale keeps the weight's dtype (_fused.stats_scale)
-        self.round_mode = entries[0].tmpl['round_mode']
+        self.round_mode = entries[0].tmpl.round_mode
         # chunks: one list call each way, at most WEIGHT_LIST_MAX weights whose channels fit one arrival buffer
         self.chunks, self.chunk_of = [], []
         lo, off = 0, 0
@@ -78,12 +78,12 @@ class _WeightList:
             it.min_val = float(sp.min_val or 0.0)
             it.use_min = int(bool(sp.min_val))
             it.int_threshold = _fused.scale_rule(w0.dtype, sp.scaling_shape, sp.int_threshold).thr_div
-            it.qmin, it.qmax = t['qmin'], t['qmax']
-            it.clamp_ste = int(t['clamp_ste'])
+            it.qmin, it.qmax = t.qmin, t.qmax
+            it.clamp_ste = int(t.clamp_ste)
             self.offsets.append(off)
             off += sp.channels
-            self.descs.append(_fused.channel_desc(sp.outer, sp.channels, sp.inner, w0.dtype, t['qmin'], t['qmax'],
-                                                  t['round_mode'], t['clamp_ste']))
+            self.descs.append(_fused.channel_desc(sp.outer, sp.channels, sp.inner, w0.dtype, t.qmin, t.qmax,
+                                                  t.round_mode, t.clamp_ste))
             self.sps.append(_fused._SpLike(sp.outer, sp.channels, sp.inner, sp.int_threshold))
         self.chunks.append((lo, n))
 
@@ -93,7 +93,7 @@ class _Entry(NamedTuple):
     quant: RescalingIntQuant
     weight: torch.Tensor
     sp: '_fused.StatsPlan'
-    tmpl: dict
+    tmpl: tuple   # _recognise.StatsTemplate
     bit_width: torch.Tensor
 
 
@@ -121,7 +121,7 @@ class WeightQuantGroup:
             # (a group-wise quantizer is no member: it keeps its own one-kernel route)
             if isinstance(m, RescalingIntQuant) and not isinstance(m, GroupwiseRescalingIntQuant):
                 tmpl = m._stats_template(m.msb_clamp_bit_width_impl())
-                w = tmpl.get('weight') if tmpl is not None else None
+                w = tmpl.weight if tmpl is not None else None
                 self._members.append(_Member(m, owners.get(id(w)) if w is not None else None))
                 self._names.append(names.get(id(m), ''))
         self._lists = {}        # (device, dtype, round mode) -> (weights' keys, quantizers, _WeightList, covered mask)
@@ -145,15 +145,15 @@ class WeightQuantGroup:
         tmpl = q._stats_template(bw)
         if tmpl is None:
             return None, 'not a recognised stats-scaled graph (learned scale, another statistic, no host bit width...)'
-        if tmpl['runtime'] is not None:
+        if tmpl.runtime is not None:
             return None, 'activation quantizer'
-        if tmpl['shared'] is not None:
+        if tmpl.shared is not None:
             return None, 'quantizer shared by several weights'
-        if tmpl['post'] is not None:
+        if tmpl.post is not None:
             return None, 'statistic -> scale map is not a plain lower bound'
-        if not tmpl['per_channel']:
+        if not tmpl.per_channel:
             return None, 'per-tensor scale'
-        w = tmpl['weight']
+        w = tmpl.weight
         if w is None:
             return None, 'no tracked weight'
         if not w.is_cuda:
@@ -211,7 +211,7 @@ class WeightQuantGroup:
         for mem in self._members:
             e, _ = self._entry(mem)
             if e is not None:
-                groups.setdefault((e.weight.device, e.weight.dtype, e.tmpl['round_mode']), []).append(e)
+                groups.setdefault((e.weight.device, e.weight.dtype, e.tmpl.round_mode), []).append(e)
         results = {}
         for gkey, entries in groups.items():
             keys, quants, tmpls = [e.key for e in entries], [e.quant for e in entries], [e.tmpl for e in entries]

@@ -32,6 +32,7 @@ from torch import Tensor
 import brevitas_amd.config as config
 from brevitas_amd import _native as nat
 from brevitas_amd.core.quant import _fused
+from brevitas_amd.core.quant._recognise import GROUP_SIZES, clamp_ste_of, round_mode_of
 from brevitas_amd.core.quant.int import GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant, RescalingIntQuant
 from brevitas_amd.core.quant.int_base import IntQuant
 from brevitas_amd.core.scaling.runtime import StatsFromParameterScaling
@@ -41,7 +42,7 @@ from brevitas_amd.function.ops import int_range_host
 __all__ = ['gptq_mode', 'gptq_quantize_weight', 'GPTQResult', 'freeze_weight_quant', 'unfreeze_weight_quant']
 
 BLOCK = nat.GPTQ_BLOCK
-_FUSED_GROUPS = (16, 32, 64, 128)  # a group never straddles a block
+_FUSED_GROUPS = tuple(g for g in GROUP_SIZES if g <= BLOCK)  # a group never straddles a block
 
 
 class GPTQResult(NamedTuple):
@@ -75,7 +76,7 @@ def _plan(quantizer, k: int, static_groups: bool) -> _Plan:
     host_bw = getattr(bw, 'bvq_host_value', None)
     if host_bw is None:
         raise TypeError('gptq: %s with a learned bit width is not covered' % name)
-    if type(iq) is not IntQuant or getattr(iq.float_to_int_impl, 'bvq_round_mode', None) != nat.ROUND:
+    if type(iq) is not IntQuant or round_mode_of(iq.float_to_int_impl) != nat.ROUND:
         raise TypeError('gptq: %s with the integer quantizer %s is not covered (IntQuant with half-even rounding only)'
                         % (name, type(iq).__name__))
     if type(zpi) not in (ZeroZeroPoint, StatsFromParameterZeroPoint):
@@ -216,15 +217,15 @@ def fused_block_args(plan: _Plan, rows: int, k: int, dtype: torch.dtype) -> Opti
         return None
     groups = rows * (k // plan.group)
     min_val, thr_div = None, 1.0
-    clamp_ste = getattr(plan.quant.int_quant.tensor_clamp_impl, 'bvq_clamp_ste', None)
+    clamp_ste = clamp_ste_of(plan.quant.int_quant.tensor_clamp_impl)
     if clamp_ste is None:
         return None
     if plan.computed:
         # the loop computes what the one-kernel route of the group-wise quantizer computes: the same recognised graph
         tmpl = plan.quant._group_template(plan.bit_width)
-        if tmpl is None or plan.group not in _FUSED_GROUPS or tmpl['shifted'] != plan.shifted:
+        if tmpl is None or plan.group not in _FUSED_GROUPS or tmpl.shifted != plan.shifted:
             return None
-        min_val, thr_div = tmpl['min_val'], _fused.scale_rule(dtype, (groups, 1), tmpl['int_thr']).thr_div
+        min_val, thr_div = tmpl.min_val, _fused.scale_rule(dtype, (groups, 1), tmpl.int_thr).thr_div
     desc = _fused.channel_desc(1, groups, plan.group, dtype, plan.qmin, plan.qmax, nat.ROUND,
                                bool(clamp_ste), zp_dtype=dtype if plan.shifted else torch.float32, zp_pc=plan.shifted)
     return _FusedArgs(desc, min_val, thr_div)

@@ -151,7 +151,7 @@ def test_group_and_group_shifted_descriptors(dtype):
 def test_weight_list_descriptors():
     from brevitas_amd.core.quant.weight_group import _Entry, _WeightList
     quant = SimpleNamespace(int_scaling_impl=lambda bw: bw)
-    tmpl = dict(qmin=-128.0, qmax=127.0, round_mode=nat.FLOOR, clamp_ste=True)
+    tmpl = SimpleNamespace(qmin=-128.0, qmax=127.0, round_mode=nat.FLOOR, clamp_ste=True)
     entries = [_Entry(None, quant, torch.empty(c, 9, dtype=BF16), _fused.StatsPlan(1, c, 9, (c, 1), 1e-8, 32767.0), tmpl,
                       torch.tensor(16.0)) for c in (8, 24)]
     wl = _WeightList(entries)

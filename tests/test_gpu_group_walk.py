@@ -163,8 +163,8 @@ def group_template(bits):
     q = Q.Int8WeightPerGroupFloat(torch.nn.Parameter(torch.zeros(2, 64)), group_size=64, bit_width=bits)
     t = q._group_template(q.msb_clamp_bit_width_impl())
     thr = 2.0 ** (bits - 1) - 1
-    assert t is not None and (t['int_thr'], t['qmin'], t['qmax']) == (thr, -thr, thr), t
-    return t['min_val'], t['int_thr'], t['qmin'], t['qmax']
+    assert t is not None and (t.int_thr, t.qmin, t.qmax) == (thr, -thr, thr), t
+    return t.min_val, t.int_thr, t.qmin, t.qmax
 
 
 def group_step(w, grad, gscale, g, bits, ste):

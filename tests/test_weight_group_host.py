@@ -163,7 +163,7 @@ def test_chunks_respect_the_list_size_and_the_arrival_buffer():
 
     def entries(channels):
         quant = SimpleNamespace(int_scaling_impl=lambda bw: bw)
-        tmpl = dict(qmin=-128.0, qmax=127.0, round_mode=nat.ROUND, clamp_ste=True)
+        tmpl = SimpleNamespace(qmin=-128.0, qmax=127.0, round_mode=nat.ROUND, clamp_ste=True)
         return [_Entry(None, quant, torch.empty(c, 8), _fused.StatsPlan(1, c, 8, (c, 1), 1e-8, 127.0), tmpl,
                        torch.tensor(8.0)) for c in channels]
 

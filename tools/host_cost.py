@@ -118,13 +118,14 @@ def main():
     bw = tq.msb_clamp_bit_width_impl()
     rows.append(('  msb_clamp_bit_width_impl()', per_call(lambda: tq.msb_clamp_bit_width_impl())))
     rows.append(('  _stats_plan(x, bit_width)', per_call(lambda: tq._stats_plan(w, bw))))
+    rows.append(('  _route(x, PRE_NONE, bit_width)', per_call(lambda: tq._route(w, nat.PRE_NONE, bw))))
     rows.append(('  int_scaling_impl(bit_width)', per_call(lambda: tq.int_scaling_impl(bw))))
     sp, tmpl = tq._stats_plan(w, bw)
     thr = tq.int_scaling_impl(bw)
 
     def apply_only():
-        return _fused.StatsFakeQuantFn.apply(w, thr, sp, tmpl['qmin'], tmpl['qmax'], tmpl['round_mode'],
-                                             tmpl['clamp_ste'], None, nat.PRE_NONE, None)
+        return _fused.StatsFakeQuantFn.apply(w, thr, sp, tmpl.qmin, tmpl.qmax, tmpl.round_mode,
+                                             tmpl.clamp_ste, None, nat.PRE_NONE, None)
     rows.append(('  StatsFakeQuantFn.apply (forward, recording)', per_call(apply_only)))
     def fn_step():
         w.grad = None
