@@ -8,8 +8,10 @@ PyTorch is used here as plumbing only: device memory (torch.empty), the current 
 device guard.  Signatures carry raw pointers and sizes.
 """
 import ctypes
+import functools
 import operator
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -522,33 +524,89 @@ def stats_fakequant_fwd(desc, x, min_val, int_threshold, scale_dtype):
     return stat, scale, y
 
 
-def group_quant_supported(desc, x):
-    """the group-wise kernels cover this descriptor (outer 1, channels = groups, inner = group size) and tensor"""
-    return bool(lib.bvq_group_quant_supported(ctypes.byref(desc), ptr(x)))
+# ---- the per-unit families: one value per group or per row, one launch each way ---------------------------------
+# A unit is a group of consecutive elements or a row; the descriptor has outer 1, channels = units, inner = the unit's
+# length.  Every family has three entries, bvq_<stem>_supported / _fwd / _bwd, with one argument order (include/bvq.h):
+#   fwd: desc, x, [extra], min_val, use_min, int_threshold, y, the per-unit outputs
+#   bwd: desc, g, x, the saved per-unit outputs, the side gradients, [extra], min_val, use_min, int_threshold, dx
+# The public wrappers take their arguments in that order too, so the plain ones ARE the generic wrapper with the
+# family bound (functools.partial: no frame of their own on the path of every layer and step).  DESIGN.md §9 has the
+# table in words.
+
+class UnitOut(NamedTuple):
+    name: str
+    per_unit: int = 1                      # elements per unit
+    dtype: Optional[torch.dtype] = None    # None: x's
 
 
-def group_quant_fwd(desc, x, min_val, thr_div):
-    """abs-max per group, scale and quantize-dequantize in ONE launch -> (y like x, scale [groups], stat [groups])"""
+class UnitFamily(NamedTuple):
+    supported: str        # the three entries, spelled out so that a search for an entry finds its family; the
+    fwd: str              # wrappers of this module have their names without the bvq_
+    bwd: str
+    outs: tuple           # UnitOuts the forward writes after y, in header order
+    saved: tuple          # names of those the backward takes after x, in header order
+    side: tuple           # the gradients that follow them, each None or [units] in x's dtype
+    extra: tuple = ()     # host arguments in front of the scale arguments, both ways
+    # what the Functions of core/quant/_fused.py read
+    zp_per_unit: bool = False   # the descriptor has one zero-point per unit, in x's dtype
+    align_side: bool = False    # the .hip file's group_aligned: side gradients must sit on 16-byte boundaries
+
+
+_SHIFTED_OUTS = (UnitOut('scale'), UnitOut('zp'), UnitOut('stat', 2))  # stat: the maxima, then the minima
+GROUP_QUANT = UnitFamily('bvq_group_quant_supported', 'bvq_group_quant_fwd', 'bvq_group_quant_bwd',
+                         (UnitOut('scale'), UnitOut('stat')), ('scale', 'stat'), ('gscale',))
+GROUP_MSE = UnitFamily('bvq_group_mse_supported', 'bvq_group_mse_fwd', 'bvq_group_mse_bwd',
+                       (UnitOut('scale'), UnitOut('stat'), UnitOut('idx', 1, torch.uint8)), ('stat', 'idx'), ('gscale',),
+                       extra=('ratios', 'n_ratios'))
+GROUP_SHIFTED = UnitFamily('bvq_group_shifted_supported', 'bvq_group_shifted_fwd', 'bvq_group_shifted_bwd',
+                           _SHIFTED_OUTS, ('stat',), ('gscale', 'gzp'), zp_per_unit=True)
+ROW_SHIFTED = UnitFamily('bvq_row_shifted_supported', 'bvq_row_shifted_fwd', 'bvq_row_shifted_bwd',
+                         _SHIFTED_OUTS, ('stat',), ('gscale', 'gzp'), zp_per_unit=True, align_side=True)
+UNIT_FAMILIES = (GROUP_QUANT, GROUP_MSE, GROUP_SHIFTED, ROW_SHIFTED)
+
+
+def unit_supported(fam, desc, x, *extra):
+    """the family's kernels cover this descriptor, tensor and extra arguments"""
+    return bool(getattr(lib, fam.supported)(ctypes.byref(desc), ptr(x), *extra))
+
+
+def unit_fwd(fam, desc, x, *rest):
+    """statistic per unit, scale (zero-point) and quantize-dequantize in ONE launch -> (y like x, *fam.outs), an output
+    of `per_unit` elements per unit flat.  rest: fam.extra, min_val, thr_div"""
     dev = require_device(x)
-    assert x.is_contiguous()
-    groups = int(desc.channels)
-    y = torch.empty_like(x)
-    scale = torch.empty(groups, dtype=x.dtype, device=dev)
-    stat = torch.empty(groups, dtype=x.dtype, device=dev)
-    _launch(dev, 'bvq_group_quant_fwd', 'bvq_group_quant_fwd', ctypes.byref(desc), ptr(x),
-            *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(stat))
-    return y, scale, stat
+    assert x.is_contiguous() and len(rest) == len(fam.extra) + 2
+    units, dt = int(desc.channels), x.dtype
+    res = [torch.empty_like(x)]
+    for _, per_unit, dtype in fam.outs:
+        res.append(torch.empty(per_unit * units, dtype=dtype or dt, device=dev))
+    _launch(dev, fam.fwd, fam.fwd, ctypes.byref(desc), ptr(x), *rest[:-2], *_scale_args(rest[-2], rest[-1]),
+            *map(ptr, res))
+    return tuple(res)
 
 
-def group_quant_bwd(desc, g, x, scale, stat, gscale, min_val, thr_div):
-    """backward of group_quant_fwd in ONE launch -> dx (the statistic's gradient of every group deposited on the first
-    element attaining it); gscale: None, or the gradient arriving through `scale`, [groups] in x's dtype"""
-    dev = require_device(g, x, scale, stat, gscale)
-    assert g.is_contiguous() and x.is_contiguous() and (gscale is None or gscale.is_contiguous())
+def unit_bwd(fam, desc, g, x, *rest):
+    """backward of unit_fwd in ONE launch -> dx (each statistic's gradient of every unit deposited on the first element
+    attaining it).  rest: the tensors of fam.saved, the gradients of fam.side that arrived through the per-unit outputs
+    (None: none did), fam.extra, min_val, thr_div"""
+    n = len(fam.saved) + len(fam.side)
+    assert len(rest) == n + len(fam.extra) + 2
+    tensors = rest[:n]
+    dev = require_device(g, x, *tensors)
+    assert g.is_contiguous() and x.is_contiguous()
+    for t in tensors:
+        assert t is None or t.is_contiguous()
     dx = torch.empty_like(x)
-    _launch(dev, 'bvq_group_quant_bwd', 'bvq_group_quant_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(scale),
-            ptr(stat), ptr(gscale), *_scale_args(min_val, thr_div), ptr(dx))
+    _launch(dev, fam.bwd, fam.bwd, ctypes.byref(desc), ptr(g), ptr(x), *map(ptr, tensors), *rest[n:-2],
+            *_scale_args(rest[-2], rest[-1]), ptr(dx))
     return dx
+
+
+# (desc, x): outer 1, channels = groups, inner = group size
+group_quant_supported = functools.partial(unit_supported, GROUP_QUANT)
+# (desc, x, min_val, thr_div): abs-max per group -> (y, scale [groups], stat [groups])
+group_quant_fwd = functools.partial(unit_fwd, GROUP_QUANT)
+# (desc, g, x, scale, stat, gscale, min_val, thr_div) -> dx
+group_quant_bwd = functools.partial(unit_bwd, GROUP_QUANT)
 
 
 def mse_ratio_table(ratios):
@@ -557,69 +615,27 @@ def mse_ratio_table(ratios):
 
 
 def group_mse_supported(desc, x, n_ratios):
-    """the clip-search group kernels cover this descriptor (as group_quant_supported), tensor and candidate count"""
-    return bool(lib.bvq_group_mse_supported(ctypes.byref(desc), ptr(x), int(n_ratios)))
+    """as group_quant_supported, and the candidate count"""
+    return unit_supported(GROUP_MSE, desc, x, int(n_ratios))
 
 
 def group_mse_fwd(desc, x, table, min_val, thr_div):
-    """abs-max per group, the search over the candidate thresholds abs-max * table[i], scale and quantize-dequantize in
-    ONE launch -> (y like x, scale [groups], stat [groups], idx uint8 [groups]: the chosen candidate)"""
-    dev = require_device(x)
-    assert x.is_contiguous()
-    groups = int(desc.channels)
-    y = torch.empty_like(x)
-    scale = torch.empty(groups, dtype=x.dtype, device=dev)
-    stat = torch.empty(groups, dtype=x.dtype, device=dev)
-    idx = torch.empty(groups, dtype=torch.uint8, device=dev)
-    _launch(dev, 'bvq_group_mse_fwd', 'bvq_group_mse_fwd', ctypes.byref(desc), ptr(x), ctypes.addressof(table),
-            len(table), *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(stat), ptr(idx))
-    return y, scale, stat, idx
+    """abs-max per group and the search over the candidate thresholds abs-max * table[i] -> (y, scale [groups],
+    stat [groups], idx uint8 [groups]: the chosen candidate)"""
+    return unit_fwd(GROUP_MSE, desc, x, ctypes.addressof(table), len(table), min_val, thr_div)
 
 
 def group_mse_bwd(desc, g, x, stat, idx, gscale, table, min_val, thr_div):
-    """backward of group_mse_fwd in ONE launch -> dx (idx is a constant; the statistic's gradient of every group, scaled
-    by the chosen ratio, deposited on the first element attaining the statistic); gscale as in group_quant_bwd"""
-    dev = require_device(g, x, stat, idx, gscale)
-    assert g.is_contiguous() and x.is_contiguous() and idx.is_contiguous() and idx.dtype == torch.uint8
-    assert gscale is None or gscale.is_contiguous()
-    dx = torch.empty_like(x)
-    _launch(dev, 'bvq_group_mse_bwd', 'bvq_group_mse_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(stat), ptr(idx),
-            ptr(gscale), ctypes.addressof(table), len(table), *_scale_args(min_val, thr_div), ptr(dx))
-    return dx
+    """idx is a constant; the statistic's gradient is scaled by the chosen ratio"""
+    assert idx.dtype == torch.uint8
+    return unit_bwd(GROUP_MSE, desc, g, x, stat, idx, gscale, ctypes.addressof(table), len(table), min_val, thr_div)
 
 
-def group_shifted_supported(desc, x):
-    """the asymmetric group-wise kernels cover this descriptor (that of group_quant_supported with one zero-point per
-    group in x's dtype) and tensor"""
-    return bool(lib.bvq_group_shifted_supported(ctypes.byref(desc), ptr(x)))
-
-
-def group_shifted_fwd(desc, x, min_val, thr_div):
-    """max and min per group, scale, integer zero-point and quantize-dequantize in ONE launch -> (y like x, scale [groups],
-    zp [groups], stat [2 * groups]: the maxima then the minima), all in x's dtype"""
-    dev = require_device(x)
-    assert x.is_contiguous()
-    groups = int(desc.channels)
-    y = torch.empty_like(x)
-    scale = torch.empty(groups, dtype=x.dtype, device=dev)
-    zp = torch.empty(groups, dtype=x.dtype, device=dev)
-    stat = torch.empty(2 * groups, dtype=x.dtype, device=dev)
-    _launch(dev, 'bvq_group_shifted_fwd', 'bvq_group_shifted_fwd', ctypes.byref(desc), ptr(x),
-            *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(zp), ptr(stat))
-    return y, scale, zp, stat
-
-
-def group_shifted_bwd(desc, g, x, stat, gscale, gzp, min_val, thr_div):
-    """backward of group_shifted_fwd in ONE launch -> dx (the gradients of a group's maximum and minimum deposited on the
-    first element equal to each); gscale / gzp: None, or the gradient arriving through `scale` / `zp`, [groups] in x's
-    dtype"""
-    dev = require_device(g, x, stat, gscale, gzp)
-    assert g.is_contiguous() and x.is_contiguous() and stat.is_contiguous()
-    assert (gscale is None or gscale.is_contiguous()) and (gzp is None or gzp.is_contiguous())
-    dx = torch.empty_like(x)
-    _launch(dev, 'bvq_group_shifted_bwd', 'bvq_group_shifted_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(stat),
-            ptr(gscale), ptr(gzp), *_scale_args(min_val, thr_div), ptr(dx))
-    return dx
+# as group_quant_*, with one zero-point per group in x's dtype: max and min per group, integer zero-point
+# fwd -> (y, scale [groups], zp [groups], stat [2 * groups]);  bwd (desc, g, x, stat, gscale, gzp, min_val, thr_div)
+group_shifted_supported = functools.partial(unit_supported, GROUP_SHIFTED)
+group_shifted_fwd = functools.partial(unit_fwd, GROUP_SHIFTED)
+group_shifted_bwd = functools.partial(unit_bwd, GROUP_SHIFTED)
 
 
 def row_shifted_max_row_bytes():
@@ -627,38 +643,10 @@ def row_shifted_max_row_bytes():
     return int(lib.bvq_row_shifted_max_row_bytes())
 
 
-def row_shifted_supported(desc, x):
-    """the asymmetric per-row kernels cover this descriptor (outer 1, channels = rows, inner = H, one scale and one
-    zero-point per row in x's dtype) and tensor"""
-    return bool(lib.bvq_row_shifted_supported(ctypes.byref(desc), ptr(x)))
-
-
-def row_shifted_fwd(desc, x, min_val, thr_div):
-    """max and min per row, scale, integer zero-point and quantize-dequantize in ONE launch -> (y like x, scale [rows],
-    zp [rows], stat [2 * rows]: the maxima then the minima), all in x's dtype"""
-    dev = require_device(x)
-    assert x.is_contiguous()
-    rows = int(desc.channels)
-    y = torch.empty_like(x)
-    scale = torch.empty(rows, dtype=x.dtype, device=dev)
-    zp = torch.empty(rows, dtype=x.dtype, device=dev)
-    stat = torch.empty(2 * rows, dtype=x.dtype, device=dev)
-    _launch(dev, 'bvq_row_shifted_fwd', 'bvq_row_shifted_fwd', ctypes.byref(desc), ptr(x),
-            *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(zp), ptr(stat))
-    return y, scale, zp, stat
-
-
-def row_shifted_bwd(desc, g, x, stat, gscale, gzp, min_val, thr_div):
-    """backward of row_shifted_fwd in ONE launch -> dx (the gradients of a row's maximum and minimum deposited on the
-    first element equal to each); gscale / gzp: None, or the gradient arriving through `scale` / `zp`, [rows] in x's
-    dtype"""
-    dev = require_device(g, x, stat, gscale, gzp)
-    assert g.is_contiguous() and x.is_contiguous() and stat.is_contiguous()
-    assert (gscale is None or gscale.is_contiguous()) and (gzp is None or gzp.is_contiguous())
-    dx = torch.empty_like(x)
-    _launch(dev, 'bvq_row_shifted_bwd', 'bvq_row_shifted_bwd', ctypes.byref(desc), ptr(g), ptr(x), ptr(stat),
-            ptr(gscale), ptr(gzp), *_scale_args(min_val, thr_div), ptr(dx))
-    return dx
+# group_shifted_* with a row in the place of a group: outer 1, channels = rows, inner = H
+row_shifted_supported = functools.partial(unit_supported, ROW_SHIFTED)
+row_shifted_fwd = functools.partial(unit_fwd, ROW_SHIFTED)
+row_shifted_bwd = functools.partial(unit_bwd, ROW_SHIFTED)
 
 
 def weight_norm_supported(desc, norm_kind, t_bound, norm_min, x):

@@ -323,9 +323,7 @@ class LearnedRoundFakeQuantFn(Function):
     @staticmethod
     def backward(ctx, gy):
         x, value, sc, zc = ctx.saved_tensors
-        gy = gy.to(x.dtype).contiguous()
-        if gy.data_ptr() % 16 != 0:
-            gy = gy.clone()
+        gy, _ = _group_grads(x, gy, [])
         dvalue, dx = nat.learned_round_bwd(ctx.desc, gy, x, value, sc, zc, ctx.kind, ctx.consts,
                                            ctx.needs_input_grad[0])
         return (dx, dvalue.view(value.shape) if ctx.needs_input_grad[1] else None) + (None,) * 9
@@ -551,12 +549,29 @@ class StatsFakeQuantFn(Function):
         return dx, None, None, None, None, None, None, None, None, None
 
 
+def unit_call(x: Tensor, unit_len: int, zp_per_unit: bool, int_threshold: float, qmin: float, qmax: float, clamp_ste):
+    """-> (descriptor, threshold divisor) that the wrappers of a per-unit family (nat.UnitFamily) take for x as
+    numel / unit_len units of `unit_len` consecutive elements: one scale per unit and, zp_per_unit, one zero-point, in
+    x's dtype"""
+    units = x.numel() // unit_len
+    desc = channel_desc(1, units, unit_len, x.dtype, qmin, qmax, nat.ROUND, clamp_ste,
+                        zp_dtype=x.dtype if zp_per_unit else torch.float32, zp_pc=zp_per_unit)
+    return desc, scale_rule(x.dtype, (units, 1), int_threshold).thr_div
+
+
 def group_quant_call(x: Tensor, group_size: int, int_threshold: float, qmin: float, qmax: float, clamp_ste):
-    """-> (descriptor, threshold divisor) that nat.group_quant_fwd / group_quant_bwd take for x in groups of `group_size`
-    (GroupStatsFakeQuantFn, and the tests that launch the kernels through those wrappers)"""
-    groups = x.numel() // group_size
-    desc = channel_desc(1, groups, group_size, x.dtype, qmin, qmax, nat.ROUND, clamp_ste)
-    return desc, scale_rule(x.dtype, (groups, 1), int_threshold).thr_div
+    """unit_call for nat.group_quant_* and group_mse_*: x in groups of `group_size`"""
+    return unit_call(x, group_size, False, int_threshold, qmin, qmax, clamp_ste)
+
+
+def group_shifted_call(x: Tensor, group_size: int, int_threshold: float, qmin: float, qmax: float, clamp_ste):
+    """unit_call for nat.group_shifted_*: one zero-point per group"""
+    return unit_call(x, group_size, True, int_threshold, qmin, qmax, clamp_ste)
+
+
+def row_shifted_call(x: Tensor, int_threshold: float, qmin: float, qmax: float, clamp_ste):
+    """unit_call for nat.row_shifted_*: x as [rows, H] = [numel / shape[-1], shape[-1]], one zero-point per row"""
+    return unit_call(x, x.shape[-1], True, int_threshold, qmin, qmax, clamp_ste)
 
 
 def _group_grads(x: Tensor, gy, side, side_dtype=None, align_side=False):
@@ -584,7 +599,7 @@ class GroupStatsFakeQuantFn(Function):
     @staticmethod
     def forward(ctx, x, group_size, min_val, int_threshold, qmin, qmax, clamp_ste):
         ctx.set_materialize_grads(False)  # an unused `scale` output must not cost a zero-fill + add
-        desc, thr_div = group_quant_call(x, group_size, int_threshold, qmin, qmax, clamp_ste)
+        desc, thr_div = unit_call(x, group_size, False, int_threshold, qmin, qmax, clamp_ste)
         y, scale, stat = nat.group_quant_fwd(desc, x, min_val, thr_div)
         ctx.desc, ctx.min_val, ctx.thr_div = desc, min_val, thr_div
         ctx.save_for_backward(x, scale, stat)
@@ -593,20 +608,12 @@ class GroupStatsFakeQuantFn(Function):
     @staticmethod
     def backward(ctx, gy, gscale):
         x, scale, stat = ctx.saved_tensors
-        grads = _group_grads(x, gy, [gscale])
+        grads = _group_grads(x, gy, [gscale], align_side=nat.GROUP_QUANT.align_side)
         if grads is None:
             return (None,) * 7
         gy, (gscale,) = grads
         dx = nat.group_quant_bwd(ctx.desc, gy, x, scale, stat, gscale, ctx.min_val, ctx.thr_div)
         return (dx,) + (None,) * 6
-
-
-def group_shifted_call(x: Tensor, group_size: int, int_threshold: float, qmin: float, qmax: float, clamp_ste):
-    """group_quant_call for the asymmetric kernels (nat.group_shifted_fwd / group_shifted_bwd): one zero-point per
-    group, in x's dtype"""
-    groups = x.numel() // group_size
-    desc = channel_desc(1, groups, group_size, x.dtype, qmin, qmax, nat.ROUND, clamp_ste, zp_dtype=x.dtype, zp_pc=True)
-    return desc, scale_rule(x.dtype, (groups, 1), int_threshold).thr_div
 
 
 class GroupShiftedFakeQuantFn(Function):
@@ -620,7 +627,7 @@ class GroupShiftedFakeQuantFn(Function):
     @staticmethod
     def forward(ctx, x, group_size, min_val, int_threshold, qmin, qmax, clamp_ste):
         ctx.set_materialize_grads(False)  # unused `scale` / `zero_point` outputs must not cost a zero-fill + add
-        desc, thr_div = group_shifted_call(x, group_size, int_threshold, qmin, qmax, clamp_ste)
+        desc, thr_div = unit_call(x, group_size, True, int_threshold, qmin, qmax, clamp_ste)
         y, scale, zp, stat = nat.group_shifted_fwd(desc, x, min_val, thr_div)
         ctx.desc, ctx.min_val, ctx.thr_div = desc, min_val, thr_div
         ctx.save_for_backward(x, stat)
@@ -629,21 +636,12 @@ class GroupShiftedFakeQuantFn(Function):
     @staticmethod
     def backward(ctx, gy, gscale, gzp):
         x, stat = ctx.saved_tensors
-        grads = _group_grads(x, gy, [gscale, gzp])
+        grads = _group_grads(x, gy, [gscale, gzp], align_side=nat.GROUP_SHIFTED.align_side)
         if grads is None:
             return (None,) * 7
         gy, (gscale, gzp) = grads
         dx = nat.group_shifted_bwd(ctx.desc, gy, x, stat, gscale, gzp, ctx.min_val, ctx.thr_div)
         return (dx,) + (None,) * 6
-
-
-def row_shifted_call(x: Tensor, int_threshold: float, qmin: float, qmax: float, clamp_ste):
-    """group_shifted_call for the asymmetric per-row kernels (nat.row_shifted_fwd / row_shifted_bwd): x as
-    [rows, H] = [numel / shape[-1], shape[-1]], one scale and one zero-point per row, in x's dtype"""
-    h = x.shape[-1]
-    rows = x.numel() // h
-    desc = channel_desc(1, rows, h, x.dtype, qmin, qmax, nat.ROUND, clamp_ste, zp_dtype=x.dtype, zp_pc=True)
-    return desc, scale_rule(x.dtype, (rows, 1), int_threshold).thr_div
 
 
 class RowShiftedFakeQuantFn(Function):
@@ -655,7 +653,7 @@ class RowShiftedFakeQuantFn(Function):
     @staticmethod
     def forward(ctx, x, min_val, int_threshold, qmin, qmax, clamp_ste):
         ctx.set_materialize_grads(False)  # unused `scale` / `zero_point` outputs must not cost a zero-fill + add
-        desc, thr_div = row_shifted_call(x, int_threshold, qmin, qmax, clamp_ste)
+        desc, thr_div = unit_call(x, x.shape[-1], True, int_threshold, qmin, qmax, clamp_ste)
         y, scale, zp, stat = nat.row_shifted_fwd(desc, x, min_val, thr_div)
         ctx.desc, ctx.min_val, ctx.thr_div = desc, min_val, thr_div
         ctx.save_for_backward(x, stat)
@@ -664,7 +662,7 @@ class RowShiftedFakeQuantFn(Function):
     @staticmethod
     def backward(ctx, gy, gscale, gzp):
         x, stat = ctx.saved_tensors
-        grads = _group_grads(x, gy, [gscale, gzp], align_side=True)
+        grads = _group_grads(x, gy, [gscale, gzp], align_side=nat.ROW_SHIFTED.align_side)
         if grads is None:
             return (None,) * 6
         gy, (gscale, gzp) = grads
@@ -711,9 +709,7 @@ class WeightNormFakeQuantFn(Function):
         s_shape, s_dtype, g_shape, g_dtype = ctx.like
         if gy is None:   # only the returned scale was used downstream
             return (None, gscale, None) + (None,) * 6
-        gy = gy.to(x.dtype).contiguous()
-        if gy.data_ptr() % 16 != 0:
-            gy = gy.clone()
+        gy, _ = _group_grads(x, gy, [])
         dx, dscale, dg = nat.weight_norm_bwd(ctx.desc, *ctx.call, gy, x, s, g, n)
         dscale = dscale.reshape(s_shape).to(s_dtype)
         if gscale is not None:
@@ -731,7 +727,7 @@ class GroupMSEFakeQuantFn(Function):
     @staticmethod
     def forward(ctx, x, group_size, min_val, int_threshold, qmin, qmax, clamp_ste, table):
         ctx.set_materialize_grads(False)  # an unused `scale` output must not cost a zero-fill + add
-        desc, thr_div = group_quant_call(x, group_size, int_threshold, qmin, qmax, clamp_ste)
+        desc, thr_div = unit_call(x, group_size, False, int_threshold, qmin, qmax, clamp_ste)
         y, scale, stat, idx = nat.group_mse_fwd(desc, x, table, min_val, thr_div)
         ctx.desc, ctx.min_val, ctx.thr_div, ctx.table = desc, min_val, thr_div, table
         ctx.save_for_backward(x, stat, idx)
@@ -741,7 +737,7 @@ class GroupMSEFakeQuantFn(Function):
     @staticmethod
     def backward(ctx, gy, gscale, _gidx):
         x, stat, idx = ctx.saved_tensors
-        grads = _group_grads(x, gy, [gscale])
+        grads = _group_grads(x, gy, [gscale], align_side=nat.GROUP_MSE.align_side)
         if grads is None:
             return (None,) * 8
         gy, (gscale,) = grads

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import dynamic_golden as D
-from test_gpu_group_shifted import assert_same_bits, compare, set_clamp, step
+from test_gpu_group_shifted import assert_same_bits, compare, compare_without_gy, set_clamp, step
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -128,7 +128,7 @@ def row_step(x0, bits, ste, grad, gscale=None, gzp=None):
     x = x0.clone().requires_grad_(True)
     qmax = float(2 ** bits - 1)
     y, scale, zp = _fused.RowShiftedFakeQuantFn.apply(x, 1e-10, qmax, 0.0, qmax, ste)
-    outs, grads = [y], [grad]
+    outs, grads = ([y], [grad]) if grad is not None else ([], [])   # None: y receives no gradient
     if gscale is not None:
         outs, grads = outs + [scale], grads + [gscale.view(scale.shape)]
     if gzp is not None:
@@ -150,7 +150,7 @@ def per_channel_step(x0, bits, ste, grad, gscale=None, gzp=None):
     h = x0.shape[-1]
     w = torch.nn.Parameter(x0.detach().contiguous().view(-1, h).clone())
     q = set_clamp(Q.ShiftedUint8WeightPerChannelFloat(w, bit_width=bits).to(DEV), ste)
-    return step(q, w, grad.contiguous().view(-1, h), gscale, gzp)
+    return step(q, w, None if grad is None else grad.contiguous().view(-1, h), gscale, gzp)
 
 
 def test_the_cap_is_the_one_the_shapes_assume():
@@ -234,6 +234,22 @@ def test_gradients_through_scale_and_zero_point(dn, ste, fused_calls):
         print('ROW_SHIFTED_DEPOSIT_ULPS %s C=67 gscale=%d gzp=%d ste=%d worst=%.3f'
               % (dn, gs is not None, gz is not None, ste, worst))
     assert len(fused_calls) == 4
+
+
+@dtypes
+@pytest.mark.parametrize('chunks', [17, 67, 130], ids=['C17', 'C67', 'C130'])   # one wave; one wave; four waves
+@pytest.mark.parametrize('ste', [True, False], ids=['clamp_ste', 'clamp'])
+def test_gradients_through_scale_or_zero_point_alone(dn, chunks, ste, fused_calls):
+    """y receives no gradient: the kernel takes zeros for it, and dx is the deposits alone"""
+    x, _, gscale, gzp = make_input(chunks, 12, dn)
+    h = x.shape[1]
+    for gs, gz in ((gscale, None), (None, gzp)):
+        got = row_step(x, 4, ste, None, gs, gz)
+        worst = compare_without_gy(got, per_channel_step(x, 4, ste, None, gs, gz), x, h, 4, dn, gs, gz)
+        assert bool(got[3].float().nan_to_num().any())  # the gradient arrived
+        print('ROW_SHIFTED_DEPOSIT_ULPS %s C=%d no gy gscale=%d gzp=%d ste=%d worst=%.3f'
+              % (dn, chunks, gs is not None, gz is not None, ste, worst))
+    assert len(fused_calls) == 2
 
 
 @dtypes

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from test_group_mse_host import check_index, make_groups, ratios_of, restate, same_bits
+from test_gpu_group_quant import zero_off_the_deposits
 from test_gpu_group_walk import use_nt0  # noqa: F401  (fixture: the forced-NT build of the library)
 
 pytestmark = pytest.mark.gpu
@@ -125,9 +126,12 @@ def quantizer(w, g, bits, ratios, ste=True):
 
 
 def backward(w, y, scale, grad, gscale):
+    """grad None: y receives no gradient, the loss uses the returned scale alone"""
     w.grad = None
     if gscale is None:
         y.backward(grad.view(y.shape))
+    elif grad is None:
+        scale.backward(gscale.view(scale.shape))
     else:
         torch.autograd.backward([y, scale], [grad.view(y.shape), gscale.view(scale.shape)])
     return w.grad.detach().clone()
@@ -201,16 +205,23 @@ def test_candidate_counts_and_widths(dn, n, step, bits, fused_calls):
 
 @dtypes
 @pytest.mark.parametrize('ste', [True, False], ids=['clamp_ste', 'clamp'])
-@pytest.mark.parametrize('through_scale', [False, True], ids=['y', 'y_and_scale'])
+@pytest.mark.parametrize('through_scale', [False, True, 'alone'], ids=['y', 'y_and_scale', 'scale_alone'])
 def test_backward_against_the_composed_route(dn, ste, through_scale, fused_calls):
     shape, g, bits = (48, 192), 64, 4
     w, grad, gscale = make_weight(shape, g, dn)
-    wd, gd = w.to(DEV), grad.to(DEV)
+    wd = w.to(DEV)
+    gd = None if through_scale == 'alone' else grad.to(DEV)   # None: y receives no gradient
     gsd = gscale.to(DEV) if through_scale else None
     y, scale, dw, idx = fused_step(wd, g, bits, RATIOS, ste, gd, gsd)
     assert fused_calls == {'fwd': 1, 'bwd': 1}
     y_c, scale_c, dw_c = composed_step(wd, g, bits, RATIOS, ste, gd, gsd, idx)
     assert same_bits(y, y_c) and same_bits(scale, scale_c)
+    if gd is None:
+        # dw is the deposits alone
+        dw0, dw_c0, skip = zero_off_the_deposits(dw, dw_c, scale_c, w, g)
+        assert bool(dw.float().nan_to_num().any())  # the scale's gradient arrived
+        assert_dw(dw0, dw_c0, w, torch.zeros_like(grad), g, bits, dn, skip_groups=skip)
+        return
     assert_dw(dw, dw_c, w, grad, g, bits, dn)
     if through_scale:
         _, _, dw_plain, _ = fused_step(wd, g, bits, RATIOS, ste, gd)

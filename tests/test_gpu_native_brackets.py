@@ -46,6 +46,23 @@ def _cases(nat):
     assert nat.group_quant_supported(gd, xg) and nat.mx_quant_supported(xg, GSIZE, nat.MX_E4M3)
     _, gscale, gstat = nat.group_quant_fwd(gd, xg, 1e-10, 7.0)
     codes, e8m0 = nat.mx_encode(xg, GSIZE, nat.MX_E4M3, nat.MX_FLOOR)
+    # the other per-unit families on the same tensors: one zero-point per group, per row of xg as [4, 512], two candidates
+    from brevitas_amd.core.quant import _fused
+    sd = nat.QuantDesc(1, GROUPS, GSIZE, code, code, code, code, 1, 1, 0.0, 15.0, 0, 0, 0, nat.OUT_DEQUANT, 0)
+    rd = nat.QuantDesc(1, 4, 512, code, code, code, code, 1, 1, 0.0, 255.0, 0, 0, 0, nat.OUT_DEQUANT, 0)
+    table = nat.mse_ratio_table([1.0, 0.75])
+    xw, gw = xg.view(4, 512), gg.view(4, 512)
+    assert nat.group_shifted_supported(sd, xg) and nat.row_shifted_supported(rd, xw)
+    assert nat.group_mse_supported(gd, xg, len(table))
+    sstat = nat.group_shifted_fwd(sd, xg, 1e-10, 15.0)[3]
+    rstat = nat.row_shifted_fwd(rd, xw, 1e-10, 255.0)[3]
+    _, _, mstat, midx = nat.group_mse_fwd(gd, xg, table, 1e-10, 7.0)
+    wd = _fused.weight_norm_call(xw, 127.0, nat.ROUND_TO_ZERO, True)
+    wn = (nat.NORM_L1, 2.0 ** 23 / 256, 1e-10)
+    assert nat.weight_norm_supported(wd, *wn, xw)
+    ws = (xw.float().abs().max(1).values / 127).contiguous()
+    wg = xw.float().abs().sum(1).contiguous()
+    wnorm = nat.weight_norm_fwd(wd, *wn, xw, ws, wg)[1]
 
     def some(fn):  # a route that may answer "not covered" must not do so here
         def run_it():
@@ -105,6 +122,17 @@ def _cases(nat):
         ('group_quant_fwd', some(lambda: nat.group_quant_fwd(gd, xg, 1e-10, 7.0)), ['bvq_group_quant_fwd']),
         ('group_quant_bwd', some(lambda: nat.group_quant_bwd(gd, gg, xg, gscale, gstat, None, 1e-10, 7.0)),
          ['bvq_group_quant_bwd']),
+        ('group_shifted_fwd', some(lambda: nat.group_shifted_fwd(sd, xg, 1e-10, 15.0)), ['bvq_group_shifted_fwd']),
+        ('group_shifted_bwd', some(lambda: nat.group_shifted_bwd(sd, gg, xg, sstat, None, None, 1e-10, 15.0)),
+         ['bvq_group_shifted_bwd']),
+        ('row_shifted_fwd', some(lambda: nat.row_shifted_fwd(rd, xw, 1e-10, 255.0)), ['bvq_row_shifted_fwd']),
+        ('row_shifted_bwd', some(lambda: nat.row_shifted_bwd(rd, gw, xw, rstat, None, None, 1e-10, 255.0)),
+         ['bvq_row_shifted_bwd']),
+        ('group_mse_fwd', some(lambda: nat.group_mse_fwd(gd, xg, table, 1e-10, 7.0)), ['bvq_group_mse_fwd']),
+        ('group_mse_bwd', some(lambda: nat.group_mse_bwd(gd, gg, xg, mstat, midx, None, table, 1e-10, 7.0)),
+         ['bvq_group_mse_bwd']),
+        ('weight_norm_fwd', some(lambda: nat.weight_norm_fwd(wd, *wn, xw, ws, wg)), ['bvq_weight_norm_fwd']),
+        ('weight_norm_bwd', some(lambda: nat.weight_norm_bwd(wd, *wn, gw, xw, ws, wg, wnorm)), ['bvq_weight_norm_bwd']),
         ('mx_quant_fwd', some(lambda: nat.mx_quant_fwd(xg, GSIZE, nat.MX_E4M3, nat.MX_FLOOR)), ['bvq_mx_quant_fwd']),
         ('mx_quant_bwd', some(lambda: nat.mx_quant_bwd(gg, xg, None, GSIZE, nat.MX_E4M3, nat.MX_FLOOR, False)),
          ['bvq_mx_quant_bwd']),

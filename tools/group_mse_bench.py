@@ -16,7 +16,9 @@ import os
 import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import rounds
+from rounds import ROOT
+
 ROUNDS = 9
 
 
@@ -102,26 +104,7 @@ def main():
         '(c) plain group kernels bwd': lambda: nat.group_quant_bwd(d, gf, x, scale_c, stat_c, None, min_val, thr),
     }
 
-    def ev():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
-
-    for fn in cands.values():   # warm-up
-        fn()
-    torch.cuda.synchronize()
-    res = {name: [] for name in cands}
-    for _ in range(ROUNDS):
-        pairs = []
-        for name, fn in cands.items():
-            fn()
-            a = ev()
-            out = fn()
-            pairs.append((name, a, ev()))
-            del out
-        torch.cuda.synchronize()
-        for name, a, b_ in pairs:
-            res[name].append(a.elapsed_time(b_))
+    res = rounds.timed_rounds(cands, ROUNDS)
     med = {name: statistics.median(ts) for name, ts in res.items()}
     launches = {name: kernel_launches(fn) for name, fn in cands.items()}
     nbytes = x.numel() * x.element_size()

@@ -11,13 +11,11 @@ An [8192, 8192] weight in bf16 and f16, group sizes 128 and 32, forward and back
   (d) tools/yardstick.hip: the same bytes with no arithmetic, read + write and two reads + write, best of a small sweep.
 Interleaved rounds in one process, one warm call in front of every timed call (the queue is never empty when the timed
 launch starts), HIP events on the launching stream, median / min over the rounds."""
-import ctypes
-import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, 'build', 'tools', 'libyardstick.so')
+import rounds
+from rounds import ROOT
+
 ROUNDS = 9
 
 
@@ -25,21 +23,11 @@ def main():
     import torch
     sys.path.insert(0, ROOT)
     from brevitas_amd import _native as nat
-    yl = ctypes.CDLL(SO)
-    yl.yardstick.restype = ctypes.c_int
-    yl.yardstick.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
     dev = 'cuda:0'
     out_f, k = 8192, 8192
     bits, thr, min_val = 4, 7.0, 1e-10
     qmax = float(2 ** (bits - 1) - 1)
     zp = torch.zeros(1, device=dev)
-    sink = torch.zeros(4, device=dev, dtype=torch.int32)
-    stream = torch.cuda.current_stream().cuda_stream
-
-    def ev():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
 
     print('# tools/group_quant_bench.py: [%d, %d] weight, int%d, one MI355X; median / min ms over %d interleaved rounds'
           % (out_f, k, bits, ROUNDS))
@@ -75,11 +63,6 @@ def main():
                 return dx
             return fwd, bwd
 
-        def yard(mode, nt, ch, form, blocks):
-            rc = yl.yardstick(mode, nt, ch, form, blocks, x.data_ptr(), g.data_ptr(), o.data_ptr(), sink.data_ptr(),
-                              nbytes, stream)
-            assert rc == 0, rc
-
         cands = {}
         for gs in (128, 32):
             d = desc(x.numel() // gs, gs)
@@ -94,38 +77,10 @@ def main():
         f, b = per_channel(out_f, k)
         cands['(c) per-channel [8192, 8192] fwd'] = f
         cands['(c) per-channel [8192, 8192] bwd'] = b
-        for mode, mname in ((1, 'copy'), (2, 'triad')):
-            for nt in (1, 0):
-                for ch in (2, 4, 8):
-                    cands['(d) %s unit nt=%d ch=%d' % (mname, nt, ch)] = lambda m=mode, n=nt, c=ch: yard(m, n, c, 0, 0)
-                cands['(d) %s persistent nt=%d ch=4 blocks=2048' % (mname, nt)] = \
-                    lambda m=mode, n=nt: yard(m, n, 4, 1, 2048)
-
-        for fn in cands.values():   # warm-up
-            fn()
-        torch.cuda.synchronize()
-        res = {name: [] for name in cands}
-        for _ in range(ROUNDS):
-            pairs = []
-            for name, fn in cands.items():
-                fn()
-                a = ev()
-                out = fn()
-                pairs.append((name, a, ev()))
-                del out
-            torch.cuda.synchronize()
-            for name, a, b_ in pairs:
-                res[name].append(a.elapsed_time(b_))
+        cands.update(rounds.yardstick_cands(rounds.yardstick(x, g, o)))
+        res = rounds.timed_rounds(cands, ROUNDS)
         print('== %s (%d MiB per tensor)' % (dn, nbytes >> 20))
-        med = {name: statistics.median(ts) for name, ts in res.items()}
-        best = {}
-        for name, ts in res.items():
-            passes = 3 if ('bwd' in name or 'triad' in name) else 2
-            print('%-46s %8.4f / %8.4f ms  %5.2f TB/s' % (name, med[name], min(ts), passes * nbytes / med[name] / 1e9))
-            if name.startswith('(d)'):
-                kind = name.split(' ')[1]
-                if kind not in best or med[name] < best[kind]:
-                    best[kind] = med[name]
+        med, best = rounds.report(res, nbytes, 46)
         for gs in (128, 32):
             for way, kind in (('fwd', 'copy'), ('bwd', 'triad')):
                 a = med['(a) group kernels g=%d %s' % (gs, way)]

@@ -13,13 +13,11 @@ An [8192, 8192] weight in bf16 and f16, 4 bits, group sizes 128 and 32, forward 
   (d)  tools/yardstick.hip: the same bytes with no arithmetic, read + write and two reads + write, best of a small sweep.
 Interleaved rounds in one process, one warm call in front of every timed call (the queue is never empty when the timed
 launch starts), HIP events on the launching stream, median / min over the rounds."""
-import ctypes
-import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, 'build', 'tools', 'libyardstick.so')
+import rounds
+from rounds import ROOT
+
 ROUNDS = 7
 
 
@@ -29,19 +27,9 @@ def main():
     from brevitas_amd import _native as nat
     import brevitas_amd.quant as Q
     from brevitas_amd.core.quant import _fused
-    yl = ctypes.CDLL(SO)
-    yl.yardstick.restype = ctypes.c_int
-    yl.yardstick.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
     dev = 'cuda:0'
     out_f, k = 8192, 8192
     bits, min_val = 4, 1e-10
-    sink = torch.zeros(4, device=dev, dtype=torch.int32)
-    stream = torch.cuda.current_stream().cuda_stream
-
-    def ev():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
 
     print('# tools/group_shifted_bench.py: [%d, %d] weight, %d bits, one MI355X; median / min ms over %d interleaved '
           'rounds' % (out_f, k, bits, ROUNDS))
@@ -51,26 +39,6 @@ def main():
         g = torch.randn(out_f, k, device=dev).to(dt).reshape(-1)
         o = torch.empty_like(x)
         nbytes = x.numel() * x.element_size()
-
-        def yard(mode, nt, ch, form, blocks):
-            rc = yl.yardstick(mode, nt, ch, form, blocks, x.data_ptr(), g.data_ptr(), o.data_ptr(), sink.data_ptr(),
-                              nbytes, stream)
-            assert rc == 0, rc
-
-        def module_pair(q, w, grad):
-            """forward and backward of a quantizer module as two timed calls; the backward runs on the graph the last
-            forward left"""
-            state = {}
-
-            def fwd():
-                w.grad = None
-                state['y'] = q(w)[0]
-
-            def bwd():
-                if 'y' not in state:
-                    fwd()
-                state.pop('y').backward(grad)
-            return fwd, bwd
 
         cands = {}
         for gs in (128, 32):
@@ -82,11 +50,11 @@ def main():
             cands['(a) shifted group kernels g=%d bwd' % gs] = \
                 lambda d=ds, t=thr_s, s=stat_s: nat.group_shifted_bwd(d, g, x, s, None, None, min_val, t)
             wg = torch.nn.Parameter(x.view(out_f, k))
-            f, b = module_pair(Q.ShiftedUint4WeightPerGroupFloat(wg, group_size=gs).to(dev), wg, g.view(out_f, k))
+            f, b = rounds.module_pair(Q.ShiftedUint4WeightPerGroupFloat(wg, group_size=gs).to(dev), wg, g.view(out_f, k))
             cands["(a') shifted group module g=%d fwd" % gs] = f
             cands["(a') shifted group module g=%d bwd" % gs] = b
             wc = torch.nn.Parameter(x.view(-1, gs))
-            f, b = module_pair(Q.ShiftedUint8WeightPerChannelFloat(wc, bit_width=bits).to(dev), wc, g.view(-1, gs))
+            f, b = rounds.module_pair(Q.ShiftedUint8WeightPerChannelFloat(wc, bit_width=bits).to(dev), wc, g.view(-1, gs))
             cands['(b) per-channel module on view(-1, %d) fwd' % gs] = f
             cands['(b) per-channel module on view(-1, %d) bwd' % gs] = b
             dq, thr_q = _fused.group_quant_call(x, gs, 2.0 ** (bits - 1) - 1, -(2.0 ** (bits - 1) - 1),
@@ -96,45 +64,10 @@ def main():
                 lambda d=dq, t=thr_q: nat.group_quant_fwd(d, x, min_val, t)
             cands['(c) symmetric group kernels g=%d bwd' % gs] = \
                 lambda d=dq, t=thr_q, s=scale_q, st=stat_q: nat.group_quant_bwd(d, g, x, s, st, None, min_val, t)
-        for mode, mname in ((1, 'copy'), (2, 'triad')):
-            for nt in (1, 0):
-                for ch in (2, 4, 8):
-                    cands['(d) %s unit nt=%d ch=%d' % (mname, nt, ch)] = lambda m=mode, n=nt, c=ch: yard(m, n, c, 0, 0)
-                cands['(d) %s persistent nt=%d ch=4 blocks=2048' % (mname, nt)] = \
-                    lambda m=mode, n=nt: yard(m, n, 4, 1, 2048)
-
-        names = list(cands)
-        for name in names:   # warm-up (a module's backward needs its forward before it)
-            cands[name]()
-        torch.cuda.synchronize()
-        res = {name: [] for name in names}
-        for _ in range(ROUNDS):
-            pairs = []
-            for name in names:
-                fn = cands[name]
-                if 'module' in name and name.endswith('bwd'):
-                    # a backward consumes its graph: warm call = forward + backward, then a fresh forward, then timed
-                    fn()
-                    cands[name[:-3] + 'fwd']()
-                else:
-                    fn()
-                a = ev()
-                out = fn()
-                pairs.append((name, a, ev()))
-                del out
-            torch.cuda.synchronize()
-            for name, a, b_ in pairs:
-                res[name].append(a.elapsed_time(b_))
+        cands.update(rounds.yardstick_cands(rounds.yardstick(x, g, o)))
+        res = rounds.timed_rounds(cands, ROUNDS)
         print('== %s (%d MiB per tensor)' % (dn, nbytes >> 20))
-        med = {name: statistics.median(ts) for name, ts in res.items()}
-        best = {}
-        for name, ts in res.items():
-            passes = 3 if ('bwd' in name or 'triad' in name) else 2
-            print('%-48s %8.4f / %8.4f ms  %5.2f TB/s' % (name, med[name], min(ts), passes * nbytes / med[name] / 1e9))
-            if name.startswith('(d)'):
-                kind = name.split(' ')[1]
-                if kind not in best or med[name] < best[kind]:
-                    best[kind] = med[name]
+        med, best = rounds.report(res, nbytes, 48)
         for gs in (128, 32):
             for way, kind in (('fwd', 'copy'), ('bwd', 'triad')):
                 a = med['(a) shifted group kernels g=%d %s' % (gs, way)]

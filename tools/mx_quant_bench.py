@@ -11,13 +11,12 @@ An [8192, 8192] tensor in bf16 and f16, groups of 32, formats e4m3 and e2m1, for
   (d) tools/yardstick.hip: the same bytes with no arithmetic, read + write and two reads + write, best of a small sweep.
 Interleaved rounds in one process, one warm call in front of every timed call (the queue is never empty when the timed
 launch starts), HIP events on the launching stream, median / min / max over the rounds."""
-import ctypes
-import os
 import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, 'build', 'tools', 'libyardstick.so')
+import rounds
+from rounds import ROOT, ev
+
 ROUNDS = 9
 COMPOSED_ROUNDS = 3   # (b) is tens of times slower: fewer rounds, same protocol
 
@@ -27,18 +26,8 @@ def main():
     sys.path.insert(0, ROOT)
     from brevitas_amd import _native as nat
     from brevitas_amd.core.quant.mx import MX_FORMATS, MXComposedFn
-    yl = ctypes.CDLL(SO)
-    yl.yardstick.restype = ctypes.c_int
-    yl.yardstick.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
     dev = 'cuda:0'
     out_f, k, gs = 8192, 8192, 32
-    sink = torch.zeros(4, device=dev, dtype=torch.int32)
-    stream = torch.cuda.current_stream().cuda_stream
-
-    def ev():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
 
     print('# tools/mx_quant_bench.py: [%d, %d], groups of %d, one MI355X; median / min / max ms over %d interleaved '
           'rounds (%d for the composed route)' % (out_f, k, gs, ROUNDS, COMPOSED_ROUNDS))
@@ -49,11 +38,6 @@ def main():
         o = torch.empty_like(x)
         nbytes = x.numel() * x.element_size()
         code = nat.dtype_code(dt)
-
-        def yard(mode, nt, ch, form, blocks):
-            rc = yl.yardstick(mode, nt, ch, form, blocks, x.data_ptr(), g.data_ptr(), o.data_ptr(), sink.data_ptr(),
-                              nbytes, stream)
-            assert rc == 0, rc
 
         cands = {}
         for fmt in ('e4m3', 'e2m1'):
@@ -79,12 +63,7 @@ def main():
         _, scale_g, stat_g = nat.group_quant_fwd(d, x, 1e-10, 7.0)
         cands['(c) int4 group kernels g=32 fwd'] = lambda: nat.group_quant_fwd(d, x, 1e-10, 7.0)
         cands['(c) int4 group kernels g=32 bwd'] = lambda: nat.group_quant_bwd(d, g, x, scale_g, stat_g, None, 1e-10, 7.0)
-        for mode, mname in ((1, 'copy'), (2, 'triad')):
-            for nt in (1, 0):
-                for ch in (2, 4, 8):
-                    cands['(d) %s unit nt=%d ch=%d' % (mname, nt, ch)] = lambda m=mode, n=nt, c=ch: yard(m, n, c, 0, 0)
-                cands['(d) %s persistent nt=%d ch=4 blocks=2048' % (mname, nt)] = \
-                    lambda m=mode, n=nt: yard(m, n, 4, 1, 2048)
+        cands.update(rounds.yardstick_cands(rounds.yardstick(x, g, o)))
 
         for name, fn in cands.items():   # warm-up
             if not name.startswith('(b)'):

@@ -15,13 +15,11 @@ backward of
   (d)  tools/yardstick.hip: the same bytes with no arithmetic, read + write and two reads + write, best of a small sweep.
 Interleaved rounds in one process, one warm call in front of every timed call (the queue is never empty when the timed
 launch starts), HIP events on the launching stream, median / min over the rounds."""
-import ctypes
-import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, 'build', 'tools', 'libyardstick.so')
+import rounds
+from rounds import ROOT
+
 ROUNDS = 7
 SHAPES = ((8192, 4096), (8192, 11008), (32768, 1024))
 
@@ -33,19 +31,9 @@ def main():
     import brevitas_amd.quant as Q
     from brevitas_amd.core.function_wrapper import TensorClamp
     from brevitas_amd.core.quant import _fused
-    yl = ctypes.CDLL(SO)
-    yl.yardstick.restype = ctypes.c_int
-    yl.yardstick.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
     dev = 'cuda:0'
     bits, min_val = 8, 1e-10
     qmax = 2.0 ** bits - 1
-    sink = torch.zeros(4, device=dev, dtype=torch.int32)
-    stream = torch.cuda.current_stream().cuda_stream
-
-    def ev():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
 
     print('# tools/row_shifted_bench.py: [tokens, hidden] activations, %d bits, one MI355X; median / min ms over %d '
           'interleaved rounds' % (bits, ROUNDS))
@@ -57,26 +45,6 @@ def main():
             o = torch.empty_like(x)
             nbytes = x.numel() * x.element_size()
 
-            def yard(mode, nt, ch, form, blocks):
-                rc = yl.yardstick(mode, nt, ch, form, blocks, x.data_ptr(), g.data_ptr(), o.data_ptr(), sink.data_ptr(),
-                                  nbytes, stream)
-                assert rc == 0, rc
-
-            def module_pair(q, w):
-                """forward and backward of a quantizer module as two timed calls; the backward runs on the graph the
-                last forward left"""
-                state = {}
-
-                def fwd():
-                    w.grad = None
-                    state['y'] = q(w)[0]
-
-                def bwd():
-                    if 'y' not in state:
-                        fwd()
-                    state.pop('y').backward(g)
-                return fwd, bwd
-
             cands = {}
             desc, thr = _fused.row_shifted_call(x, qmax, 0.0, qmax, False)
             assert nat.row_shifted_supported(desc, x)
@@ -84,57 +52,20 @@ def main():
             cands['(a) row kernels fwd'] = lambda: nat.row_shifted_fwd(desc, x, min_val, thr)
             cands['(a) row kernels bwd'] = lambda: nat.row_shifted_bwd(desc, g, x, stat, None, None, min_val, thr)
             xa = x.clone().requires_grad_(True)
-            f, b = module_pair(Q.ShiftedUint8DynamicActPerRowFloat(bit_width=bits).to(dev), xa)
+            f, b = rounds.module_pair(Q.ShiftedUint8DynamicActPerRowFloat(bit_width=bits).to(dev), xa, g)
             cands["(a') row module fwd"], cands["(a') row module bwd"] = f, b
             wc = torch.nn.Parameter(x.clone())
             qb = Q.ShiftedUint8WeightPerChannelFloat(wc, bit_width=bits).to(dev)
             qb.int_quant.tensor_clamp_impl = TensorClamp()
-            f, b = module_pair(qb, wc)
+            f, b = rounds.module_pair(qb, wc, g)
             cands['(b) per-channel module fwd'], cands['(b) per-channel module bwd'] = f, b
             xc = x.clone().requires_grad_(True)
-            f, b = module_pair(Q.Int8DynamicActPerRowFloat(bit_width=bits).to(dev), xc)
+            f, b = rounds.module_pair(Q.Int8DynamicActPerRowFloat(bit_width=bits).to(dev), xc, g)
             cands['(c) symmetric row module fwd'], cands['(c) symmetric row module bwd'] = f, b
-            for mode, mname in ((1, 'copy'), (2, 'triad')):
-                for nt in (1, 0):
-                    for ch in (2, 4, 8):
-                        cands['(d) %s unit nt=%d ch=%d' % (mname, nt, ch)] = \
-                            lambda m=mode, n=nt, c=ch: yard(m, n, c, 0, 0)
-                    cands['(d) %s persistent nt=%d ch=4 blocks=2048' % (mname, nt)] = \
-                        lambda m=mode, n=nt: yard(m, n, 4, 1, 2048)
-
-            names = list(cands)
-            for name in names:   # warm-up (a module's backward needs its forward before it)
-                cands[name]()
-            torch.cuda.synchronize()
-            res = {name: [] for name in names}
-            for _ in range(ROUNDS):
-                pairs = []
-                for name in names:
-                    fn = cands[name]
-                    if 'module' in name and name.endswith('bwd'):
-                        # a backward consumes its graph: warm call = forward + backward, then a fresh forward, then timed
-                        fn()
-                        cands[name[:-3] + 'fwd']()
-                    else:
-                        fn()
-                    a = ev()
-                    out = fn()
-                    pairs.append((name, a, ev()))
-                    del out
-                torch.cuda.synchronize()
-                for name, a, b_ in pairs:
-                    res[name].append(a.elapsed_time(b_))
+            cands.update(rounds.yardstick_cands(rounds.yardstick(x, g, o)))
+            res = rounds.timed_rounds(cands, ROUNDS)
             print('== [%d, %d] %s (%d MiB per tensor)' % (rows, h, dn, nbytes >> 20))
-            med = {name: statistics.median(ts) for name, ts in res.items()}
-            best = {}
-            for name, ts in res.items():
-                passes = 3 if ('bwd' in name or 'triad' in name) else 2
-                print('%-44s %8.4f / %8.4f ms  %5.2f TB/s'
-                      % (name, med[name], min(ts), passes * nbytes / med[name] / 1e9))
-                if name.startswith('(d)'):
-                    kind = name.split(' ')[1]
-                    if kind not in best or med[name] < best[kind]:
-                        best[kind] = med[name]
+            med, best = rounds.report(res, nbytes, 44)
             for way, kind in (('fwd', 'copy'), ('bwd', 'triad')):
                 a = med['(a) row kernels %s' % way]
                 am = med["(a') row module %s" % way]

@@ -13,14 +13,13 @@ Weights [512, 512, 3, 3] and [4096, 4096] in bf16 and f32, 8 bits:
        two reads + write (3 x 16, the backward), best of a small sweep.
 Steps: host clock around STEPS steps that end in a device synchronise, 50 warm-up steps in front, (a) and (b)
 alternating, median / min over the rounds.  Kernels: HIP events, one warm call in front of every timed call."""
-import ctypes
-import os
 import statistics
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, 'build', 'tools', 'libyardstick.so')
+import rounds
+from rounds import ROOT
+
 ROUNDS, STEPS, WARMUP = 7, 100, 50
 SHAPES = ((512, 512, 3, 3), (4096, 4096))
 
@@ -31,17 +30,7 @@ def main():
     from brevitas_amd import _native as nat
     import brevitas_amd.quant as Q
     from brevitas_amd.core.quant import _fused
-    yl = ctypes.CDLL(SO)
-    yl.yardstick.restype = ctypes.c_int
-    yl.yardstick.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
     dev = 'cuda:0'
-    sink = torch.zeros(4, device=dev, dtype=torch.int32)
-    stream = torch.cuda.current_stream().cuda_stream
-
-    def ev():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
 
     print('# tools/weight_norm_bench.py: 8-bit weights, one MI355X; median / min over %d rounds; steps: ms per step over '
           '%d steps behind %d warm-up steps' % (ROUNDS, STEPS, WARMUP))
@@ -79,11 +68,6 @@ def main():
                     torch.cuda.synchronize()
                     res[name].append((time.perf_counter() - t0) * 1e3 / STEPS)
 
-            def yard(mode, nt, ch, form, blocks):
-                rc = yl.yardstick(mode, nt, ch, form, blocks, w0.data_ptr(), g.data_ptr(), o.data_ptr(), sink.data_ptr(),
-                                  nbytes, stream)
-                assert rc == 0, rc
-
             rows = shape[0]
             desc = _fused.weight_norm_call(w0, 127.0, nat.ROUND_TO_ZERO, True)
             T, nmin = 2.0 ** 23 / 256, 1e-10
@@ -94,40 +78,15 @@ def main():
             n = nat.weight_norm_fwd(desc, nat.NORM_L1, T, nmin, w0, s, gp)[1]
             kern = {"(a') A2Q kernel fwd": lambda: nat.weight_norm_fwd(desc, nat.NORM_L1, T, nmin, w0, s, gp),
                     "(a') A2Q kernel bwd": lambda: nat.weight_norm_bwd(desc, nat.NORM_L1, T, nmin, g, w0, s, gp, n)}
-            for mode, mname in ((1, 'copy'), (2, 'triad')):
-                for nt in (1, 0):
-                    for ch in (2, 4, 8):
-                        kern['(c) %s unit nt=%d ch=%d' % (mname, nt, ch)] = lambda m=mode, n_=nt, c=ch: yard(m, n_, c, 0, 0)
-            for _ in range(WARMUP):
-                for fn in kern.values():
-                    fn()
-            torch.cuda.synchronize()
-            kres = {name: [] for name in kern}
-            for _ in range(ROUNDS):
-                pairs = []
-                for name, fn in kern.items():
-                    fn()
-                    a = ev()
-                    out = fn()
-                    pairs.append((name, a, ev()))
-                    del out
-                torch.cuda.synchronize()
-                for name, a, b in pairs:
-                    kres[name].append(a.elapsed_time(b))
+            kern.update(rounds.yardstick_cands(rounds.yardstick(w0, g, o), '(c)', persistent=False))
+            kres = rounds.timed_rounds(kern, ROUNDS, warmup=WARMUP)
             print('== %s %s (%.1f MiB)' % ('x'.join(map(str, shape)), dn, nbytes / 2 ** 20))
             for name, ts in res.items():
                 print('%-34s %8.4f / %8.4f ms per step' % (name, statistics.median(ts), min(ts)))
-            best = {}
-            for name, ts in kres.items():
-                med = statistics.median(ts)
-                passes = 3 if ('bwd' in name or 'triad' in name) else 2
-                print('%-34s %8.4f / %8.4f ms  %5.2f TB/s' % (name, med, min(ts), passes * nbytes / med / 1e9))
-                if name.startswith('(c)'):
-                    kind = name.split(' ')[1]
-                    best[kind] = min(best.get(kind, med), med)
+            kmed, best = rounds.report(kres, nbytes, 34, '(c)')
             a = statistics.median(res['(a) A2Q module step'])
             b = statistics.median(res['(b) per-channel module step'])
-            kf, kb = (statistics.median(kres["(a') A2Q kernel %s" % way]) for way in ('fwd', 'bwd'))
+            kf, kb = (kmed["(a') A2Q kernel %s" % way] for way in ('fwd', 'bwd'))
             print('%s %s: step (a) %.4f ms (b) %.4f ms (a)/(b) %.2f | kernels fwd %.4f ms = %.2f x copy %.4f, bwd %.4f ms '
                   '= %.2f x triad %.4f | kernels / step %.2f'
                   % ('x'.join(map(str, shape)), dn, a, b, a / b, kf, kf / best['copy'], best['copy'], kb,
