@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "../../include/bvq.h"
@@ -365,6 +366,38 @@ constexpr int kColsFwdVec16 = BVQ_COLS_FWD_VEC16;
 static inline unsigned grid_for_units(int64_t units) {
   return (unsigned)((units + kWavesPerBlock - 1) / kWavesPerBlock);
 }
+
+// ---- workspaces: one layout, counted or carved (Workspaces) -------------------------------------------
+// An entry's layout function take()s its arrays from a Carve.  Its *_workspace_bytes query runs that function on a null
+// base (`used` counts) for every route the entry can take; the entry runs it on the caller's buffer and checks fits().
+struct Carve {
+  char* base;        // null: measure only
+  int64_t used = 0;  // bytes from base to the end of the last array taken
+  explicit Carve(void* workspace) : base(reinterpret_cast<char*>(workspace)) {}
+  // `count` elements of T, aligned as T: on the address, so that any base will do (a measured layout starts at 0)
+  template <typename T>
+  T* take(int64_t count) {
+    const uintptr_t a = alignof(T), at = (reinterpret_cast<uintptr_t>(base) + (uintptr_t)used + a - 1) / a * a;
+    used = (int64_t)(at - reinterpret_cast<uintptr_t>(base)) + count * (int64_t)sizeof(T);
+    return base ? reinterpret_cast<T*>(at) : nullptr;
+  }
+  bool fits(int64_t workspace_bytes) const { return base && used <= workspace_bytes; }
+};
+// bytes of what layout(Carve&) lays out; the larger of layout(Carve&, vec) at the two widths a call can come out with
+template <typename F>
+static inline int64_t measured(F&& layout) {
+  Carve c(nullptr);
+  layout(c);
+  return c.used;
+}
+template <typename F>
+static inline int64_t measured_widths(int dtype, F&& layout) {
+  return std::max(measured([&](Carve& c) { layout(c, 16 / (dtype == BVQ_F32 ? 4 : 2)); }),
+                  measured([&](Carve& c) { layout(c, 1); }));
+}
+// what every query adds to its largest measured layout: a layout is measured from an aligned base, and in a caller's
+// buffer that starts on no boundary take() skips a few bytes more (less than 8 per change of element type)
+constexpr int64_t kWorkspaceSlack = 64;
 
 // ---- host dispatch: a runtime value -> a template argument -------------------------------------------------
 // Each helper calls the generic lambda f with the value as a compile-time one (a type_tag, or a std::integral_constant)

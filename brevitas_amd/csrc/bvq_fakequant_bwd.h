@@ -167,29 +167,6 @@ __device__ __forceinline__ f2 bwd_elem2(f2 xf, f2 gf, const Div& div, S s, S z, 
 }
 
 // ---- the stats-scaled backward finished in the same launch (kBwdDsArrive) ------------------------------------------
-// a store / load that is performed at agent scope (global_store / global_load ... sc1): written through to, read from
-// the memory every XCD sees (MI355X_MICROARCH.md, inter-workgroup visibility: sc1 stores and sc1 loads on both sides
-// of a hand-off, the storing wave's vmcnt(0) wait before its arrival add)
-template <typename T>
-__device__ __forceinline__ void store_through(T* p, T v) {
-  if constexpr (sizeof(T) == 2) {
-    __hip_atomic_store(reinterpret_cast<uint16_t*>(p), __builtin_bit_cast(uint16_t, v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    __hip_atomic_store(reinterpret_cast<uint32_t*>(p), __builtin_bit_cast(uint32_t, v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-template <typename T>
-__device__ __forceinline__ T load_through(const T* p) {
-  if constexpr (sizeof(T) == 2) {
-    return __builtin_bit_cast(T, __hip_atomic_load(reinterpret_cast<const uint16_t*>(p), __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT));
-  } else {
-    return __builtin_bit_cast(T, __hip_atomic_load(reinterpret_cast<const uint32_t*>(p), __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT));
-  }
-}
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -213,6 +190,8 @@ __device__ __forceinline__ void channel_finish(const QuantArgs& a, int32_t c, in
   const int64_t ppr = a.t.ppr;
   double acc = 0.0;
   unsigned long long pmin = ~0ull;
+  // (partial_unit, dscale_to_gstat and deposit_abs_at spelled out: called here, they rename the scalar registers of the
+  //  whole streaming kernel this cold block is inlined into, hot loop included -- profiles/bwd_plan.md)
   for (int64_t k = lane; k < n; k += kWave) {
     int64_t unit;
     if (a.t.nob == 1) {
@@ -788,8 +767,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BVQ_COLS
 
 // Finish of the stats-scaled backward in ONE launch (per-channel layouts): per channel, sum the units'
 // dscale partials (double, fixed order), take the first position attaining the statistic, turn dscale into
-// the statistic's gradient (the backward of scale = clamp_min_ste(stat) / int_threshold, same rounding
-// points as gstat_value) and deposit it on that element of dx.  Replaces tie_init + channel_sum + tie_apply.
+// the statistic's gradient (dscale_to_gstat) and deposit it on that element of dx.  Replaces tie_init + channel_sum +
+// tie_apply.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void bwd_stats_finish_kernel(const float* __restrict__ ds_part,
                                                                   const unsigned long long* __restrict__ pos_part,
@@ -803,13 +782,7 @@ __global__ __launch_bounds__(kBlock) void bwd_stats_finish_kernel(const float* _
   double acc = 0.0;
   unsigned long long pmin = ~0ull;
   for (int64_t k = threadIdx.x; k < n; k += kBlock) {
-    int64_t unit;
-    if (nob == 1) {
-      unit = (int64_t)c * ppr + k;
-    } else {
-      const int64_t o = k / ppr, p = k - o * ppr;
-      unit = (o * channels + c) * ppr + p;
-    }
+    const int64_t unit = partial_unit(c, k, nob, ppr, channels);
     acc += (double)ds_part[unit];
     const unsigned long long q = pos_part[unit];
     pmin = q < pmin ? q : pmin;
@@ -829,18 +802,9 @@ __global__ __launch_bounds__(kBlock) void bwd_stats_finish_kernel(const float* _
     const float ds = (float)sh[0];
     dscale[c] = ds;
     const unsigned long long pos = shp[0];
-    if (pos != ~0ull) {  // ~0: no element equals the statistic (e.g. NaN)
-      float v = round_rt(ds, gs.scale_dtype);
-      v = round_rt(v / gs.int_threshold, gs.quot_dtype);
-      const float g = rnd<T>(v);
-      const int64_t o = (int64_t)(pos / (unsigned long long)inner);
-      const int64_t i = (int64_t)(pos - (unsigned long long)o * inner);
-      const int64_t flat = (o * channels + c) * inner + i;
-      const T* xp = reinterpret_cast<const T*>(x);
-      T* dp = reinterpret_cast<T*>(dx);
-      const float term = deposit<T, BVQ_MATCH_ABS>(g, xp[flat], gs.pre_relu != 0);
-      dp[flat] = from_f<T>(to_f<T>(dp[flat]) + term);
-    }
+    if (pos != ~0ull)  // ~0: no element equals the statistic (e.g. NaN)
+      deposit_abs_at<T>(dscale_to_gstat<T>(ds, gs.scale_dtype, gs.quot_dtype, gs.int_threshold), pos, c, channels,
+                        inner, x, dx, gs.pre_relu != 0);
   }
 }
 
@@ -877,16 +841,8 @@ __global__ void shard_unpack_deposit_kernel(const double* __restrict__ all, int3
   if (dscale_total) dscale_total[c] = ds;
   const long long pos = first_pos[c];
   if (owner != (double)rank || pos < 0 || !x) return;  // (x null: an empty shard, which owns nothing)
-  float v = round_rt(ds, gs.scale_dtype);
-  v = round_rt(v / gs.int_threshold, gs.quot_dtype);
-  const float g = rnd<T>(v);
-  const int64_t o = (int64_t)(pos / inner);
-  const int64_t i = (int64_t)(pos - o * inner);
-  const int64_t flat = (o * channels + c) * inner + i;
-  const T* xp = reinterpret_cast<const T*>(x);
-  T* dp = reinterpret_cast<T*>(dx);
-  const float term = deposit<T, BVQ_MATCH_ABS>(g, xp[flat], gs.pre_relu != 0);
-  dp[flat] = from_f<T>(to_f<T>(dp[flat]) + term);
+  deposit_abs_at<T>(dscale_to_gstat<T>(ds, gs.scale_dtype, gs.quot_dtype, gs.int_threshold), (unsigned long long)pos,
+                    c, channels, inner, x, dx, gs.pre_relu != 0);
 }
 
 // the backward's decomposition: quantizer-style tiling with every unit addressable through 32-bit buffer offsets
@@ -895,6 +851,64 @@ static inline Tiling bwd_tiling(int64_t outer, int32_t channels, int64_t row_len
   Tiling t = make_tiling(outer, channels, row_len, vec, 0, true);
   cap_unit_extent(t, 4);
   return t;
+}
+
+// non-temporal policy of a backward call: by the bytes it streams (x, g and dx)
+static inline bool bwd_nt(const bvq_quant_desc* d) {
+  return d->outer * d->channels * d->inner * (int64_t)(2 * dtype_size(d->x_dtype) + dtype_size(d->ct_dtype)) >=
+         nt_threshold_bytes();
+}
+
+// How the row-mapped backward runs one call: vector width, tiling, cache policy.  The entries, their workspace queries
+// (force_vec: the plan at that width, whatever the pointers) and the list form's items all take it from here.
+struct BwdRowPlan {
+  int vec;
+  Tiling t;
+  bool nt;
+};
+static inline BwdRowPlan bwd_row_plan(const bvq_quant_desc* d, const void* x, const void* g, const void* dx,
+                                      int force_vec = 0) {
+  int64_t outer, row_len;
+  int32_t channels;
+  rows_of(d, outer, row_len, channels);
+  const void* ptrs[3] = {x, g, dx};
+  const int els[3] = {dtype_size(d->x_dtype), dtype_size(d->ct_dtype), dtype_size(d->x_dtype)};
+  const int full = 16 / dtype_size(d->x_dtype);
+  const int vec = force_vec ? force_vec : snap_vec(pick_vec(full, outer * channels, row_len, ptrs, els, 3, true), full);
+  return {vec, bwd_tiling(outer, channels, row_len, vec), bwd_nt(d)};
+}
+// ---- workspace layouts of the backward entries (Carve, bvq_common.h): one function per route ------------------
+struct BwdWs {
+  float *ds, *dzp, *dq;     // per-unit (row-mapped) or per-(partial row, column) partials; dzp / dq: d(qmin) / d(qmax) too
+  float* fold;              // column-mapped: scratch of the fold of the partial rows
+  unsigned long long* pos;  // first positions attaining the statistic: per unit, or per column
+  double* mid;              // middle stage of the channel sums
+};
+// scale / zero-point (or bound) gradient sums, row-mapped
+static inline BwdWs bwd_sums_layout(Carve& c, const Tiling& t, bool bounds) {
+  BwdWs w = {};
+  w.ds = c.take<float>(t.units);
+  w.dzp = c.take<float>(t.units);
+  if (bounds) w.dq = c.take<float>(t.units);
+  w.mid = take_channel_sums_mid(c, t.nob * t.ppr, t.channels);
+  return w;
+}
+// the stats-scaled backward, row-mapped (one tensor, or one item of a list)
+static inline BwdWs bwd_stats_row_layout(Carve& c, const Tiling& t) {
+  BwdWs w = {};
+  w.ds = c.take<float>(t.units);
+  w.pos = c.take<unsigned long long>(t.units);
+  return w;
+}
+// column-mapped: partial rows and the scratch of their fold; then (stats) one first position per column, or the mid
+// stage of the sums of the folded row, which is their (nob = 1, ppr = inner) layout
+static inline BwdWs bwd_cols_layout(Carve& c, const ColsPlan& cp, bool stats, int64_t inner, int64_t channels) {
+  BwdWs w = {};
+  w.ds = c.take<float>(cp.prows * cp.L);
+  w.fold = c.take<float>(cols_fold_scratch_rows(cp.prows) * cp.L);
+  if (stats) w.pos = c.take<unsigned long long>(cp.L);
+  if (!stats) w.mid = take_channel_sums_mid(c, inner, channels);
+  return w;
 }
 
 // the row-mapped backward of one MODE under the streaming instantiation policy (with_stream_variant); the one-launch

@@ -12,51 +12,111 @@ extern template BVQ_LAUNCH_BWD(f16_t, float);
 
 using namespace bvq;
 
-static int launch_bwd_pair(const bvq_quant_desc* d, const QuantArgs& a, int vec, int mode, bool nt, hipStream_t st) {
-  return with_pair(d->x_dtype, d->ct_dtype, [&](auto xt, auto ct) {
-    return launch_bwd<typename decltype(xt)::type, typename decltype(ct)::type>(a, vec, mode, nt, st);
+// the tensors every backward entry takes
+struct BwdTensors { const void *g, *x, *scale, *zp; void* dx; };
+struct ShardOut {  // batch-sharded tensors: the all-gather message instead of the deposit (null: unsharded)
+  double* msg;
+  long long* pos;
+  int32_t rank;
+};
+
+// the row-mapped kernel of `mode` on a's units
+static int launch_bwd_rows(const bvq_quant_desc* d, const QuantArgs& a, const BwdRowPlan& p, int mode, hipStream_t st,
+                           const char* what) {
+  const int rc = with_pair(d->x_dtype, d->ct_dtype, [&](auto xt, auto ct) {
+    return launch_bwd<typename decltype(xt)::type, typename decltype(ct)::type>(a, p.vec, mode, p.nt, st);
   });
+  return rc ? rc : check_launch(what);
 }
 
-static int64_t bwd_units(const bvq_quant_desc* d) {
-  int64_t outer, row_len;
-  int32_t channels;
-  rows_of(d, outer, row_len, channels);
-  // upper bound over the vector widths the launcher may pick
-  const int full = 16 / dtype_size(d->x_dtype);
-  const int64_t a = bwd_tiling(outer, channels, row_len, full).units;
-  const int64_t b = bwd_tiling(outer, channels, row_len, 1).units;
-  return a > b ? a : b;
+// the arguments of the row-mapped backward: partials from the layout w, the message of a shard
+static QuantArgs rows_bwd_args(const bvq_quant_desc* d, const Tiling& t, const BwdTensors& T, const void* tie_stat,
+                               int64_t* tie_info, const BwdWs& w, const ShardOut* shard = nullptr) {
+  QuantArgs a = {};
+  a.t = t;
+  a.x = T.x;
+  a.g = T.g;
+  a.scale = T.scale;
+  a.zp = T.zp;
+  a.y = T.dx;
+  a.tie_stat = tie_stat;
+  a.tie_info = reinterpret_cast<unsigned long long*>(tie_info);
+  fill_args(a, d);
+  a.ds_part = w.ds;
+  a.dzp_part = w.dzp;
+  a.dq_part = w.dq;
+  a.pos_part = w.pos;
+  a.arrive_per_channel = (uint32_t)(t.nob * t.ppr);
+  if (shard) {
+    a.shard_msg = shard->msg;
+    a.shard_pos = shard->pos;
+    a.shard_rank = shard->rank;
+  }
+  return a;
 }
 
-// the column-mapped backward's scale-gradient workspace: the partial rows and their fold (floats), then, 8-byte aligned,
-// the double-precision middle stage of the per-channel sums (rows of more than kSumSlice columns per channel)
-static int64_t cols_bwd_mid_off(const ColsPlan& cp) {
-  return (((cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L * (int64_t)sizeof(float) + 7) / 8) * 8;
+// the column-mapped backward on cp's units, its partials from the layout w
+static int launch_bwd_cols(const bvq_quant_desc* d, const ColsPlan& cp, const BwdTensors& T, const void* tie_stat,
+                           int64_t* tie_info, const BwdWs& w, hipStream_t st, const char* what) {
+  ColsQuantArgs ca = {};
+  fill_cols_args(ca, cp, d);
+  ca.x = T.x;
+  ca.g = T.g;
+  ca.y = T.dx;
+  ca.scale = T.scale;
+  ca.zp = T.zp;
+  ca.ds_part = w.ds;
+  ca.pos_part = w.pos;
+  ca.tie_stat = tie_stat;
+  ca.tie_info = reinterpret_cast<unsigned long long*>(tie_info);
+  const int rc = with_cols_variant(d, bwd_nt(d), [&](auto t, auto rm, auto ntc) {
+    fakequant_bwd_cols_kernel<typename decltype(t)::type, rm, ntc><<<(unsigned)cp.units, kBlock, 0, st>>>(ca);
+  });
+  return rc ? rc : check_launch(what);
 }
-static int64_t cols_bwd_sum_bytes(const ColsPlan& cp, int64_t inner, int64_t channels) {
-  return cols_bwd_mid_off(cp) + channel_sums_mid_bytes(inner, channels);
+static float* fold_cols_sums(const ColsPlan& cp, const BwdWs& w, hipStream_t st) {
+  float* folded = nullptr;
+  launch_cols_fold_sum_min(w.ds, nullptr, cp.prows, cp.L, w.fold, nullptr, &folded, nullptr, st);
+  return folded;
+}
+
+// a shard's all-gather message from a's partials: one wave per channel (the message path touches no tensor element)
+static int launch_channel_finish(const QuantArgs& a, hipStream_t st, const char* what) {
+  const dim3 cgrid((unsigned)((a.t.channels + kWavesPerBlock - 1) / kWavesPerBlock));
+  channel_finish_kernel<float><<<cgrid, dim3(kBlock), 0, st>>>(a);
+  return check_launch(what);
+}
+// ... where no row-mapped launch wrote them: the folded columns, or none (an empty shard: zero sums, no owner)
+static QuantArgs shard_finish_args(const ShardOut& so, int32_t channels, int64_t per_channel, float* ds,
+                                   unsigned long long* pos) {
+  QuantArgs fa = {};
+  fa.t.nob = 1;
+  fa.t.channels = channels;
+  fa.t.ppr = per_channel;
+  fa.arrive_per_channel = (uint32_t)per_channel;
+  fa.ds_part = ds;
+  fa.pos_part = pos;
+  fa.shard_msg = so.msg;
+  fa.shard_pos = so.pos;
+  fa.shard_rank = so.rank;
+  return fa;
 }
 
 extern "C" int64_t bvq_fakequant_bwd_workspace_bytes(const bvq_quant_desc* d) {
   if (validate(d, true)) return -1;
-  int64_t outer, row_len;
-  int32_t channels;
-  rows_of(d, outer, row_len, channels);
-  const int64_t units = bwd_units(d);
-  const int64_t mid = channel_sums_mid_bytes(units / channels + 1, channels) + 16;
-  int64_t bytes = 3 * units * (int64_t)sizeof(float) + mid + 256;  // (a third partial array: bvq_fakequant_bwd_bounds)
+  // (with the third partial array of bvq_fakequant_bwd_bounds)
+  int64_t bytes = measured_widths(d->x_dtype, [&](Carve& c, int vec) {
+    bwd_sums_layout(c, bwd_row_plan(d, nullptr, nullptr, nullptr, vec).t, true);
+  });
   const ColsPlan cp = cols_quant_plan(d, nullptr, nullptr, nullptr, false, true);
-  if (cp.ok && cols_bwd_sum_bytes(cp, d->inner, channels) + 256 > bytes)
-    bytes = cols_bwd_sum_bytes(cp, d->inner, channels) + 256;
-  return bytes;
+  if (cp.ok) bytes = std::max(bytes, measured([&](Carve& c) { bwd_cols_layout(c, cp, false, d->inner, d->channels); }));
+  return bytes + kWorkspaceSlack;
 }
 
-static int fakequant_bwd_impl(const bvq_quant_desc* d, const void* g, const void* x, const void* scale,
-                             const void* zp, void* dx, float* dscale, float* dzp, const void* tie_stat,
-                             int64_t* tie_info, void* workspace, int64_t workspace_bytes, bvq_stream_t stream,
-                             const LearnedScaleEpilogue* epilogue, const float* bounds = nullptr,
-                             float* dbounds = nullptr) {
+static int fakequant_bwd_impl(const bvq_quant_desc* d, const BwdTensors& T, float* dscale, float* dzp,
+                              const void* tie_stat, int64_t* tie_info, void* workspace, int64_t workspace_bytes,
+                              bvq_stream_t stream, const LearnedScaleEpilogue* epilogue, const float* bounds = nullptr,
+                              float* dbounds = nullptr) {
   int rc = validate(d, true);
   if (rc) return rc;
   const bool act = d->pre_op >= BVQ_PRE_SIGMOID;  // bvq_act.h: the row-mapped kernel, dx and dscale only
@@ -90,7 +150,7 @@ static int fakequant_bwd_impl(const bvq_quant_desc* d, const void* g, const void
     if (dzp) (void)hipMemsetAsync(dzp, 0, sizeof(float) * channels, st);
     return BVQ_OK;
   }
-  if (!g || !x || !scale || !zp || !dx) {
+  if (!T.g || !T.x || !T.scale || !T.zp || !T.dx) {
     set_error("bvq_fakequant_bwd: null pointer");
     return BVQ_ERR_INVALID;
   }
@@ -98,95 +158,46 @@ static int fakequant_bwd_impl(const bvq_quant_desc* d, const void* g, const void
     set_error("bvq_fakequant_bwd: the bound gradients ride on the dscale variant (dscale set, dzp / tie_stat null)");
     return BVQ_ERR_UNSUPPORTED;
   }
+  Carve ws(workspace);
+  BwdWs w = {};
+  const auto short_of = [&](bool carved) {
+    if (!carved || ws.fits(workspace_bytes)) return false;
+    set_error("bvq_fakequant_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)ws.used);
+    return true;
+  };
   if (!dzp && !bounds && !act) {
-    const ColsPlan cp = cols_quant_plan(d, x, g, dx, !dscale && !tie_stat, true);
+    const ColsPlan cp = cols_quant_plan(d, T.x, T.g, T.dx, !dscale && !tie_stat, true);
     if (cp.ok) {
-      const int64_t need = dscale ? cols_bwd_sum_bytes(cp, d->inner, channels) : 0;
-      if (dscale && (!workspace || workspace_bytes < need)) {
-        set_error("bvq_fakequant_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
-        return BVQ_ERR_WORKSPACE;
-      }
-      ColsQuantArgs ca = {};
-      fill_cols_args(ca, cp, d);
-      ca.x = x;
-      ca.g = g;
-      ca.y = dx;
-      ca.scale = scale;
-      ca.zp = zp;
-      ca.ds_part = dscale ? reinterpret_cast<float*>(workspace) : nullptr;
-      ca.tie_stat = tie_stat;
-      ca.tie_info = reinterpret_cast<unsigned long long*>(tie_info);
-      const bool cnt = n * (int64_t)(3 * dtype_size(d->x_dtype)) >= nt_threshold_bytes();
-      rc = with_cols_variant(d, cnt, [&](auto t, auto rm, auto ntc) {
-        fakequant_bwd_cols_kernel<typename decltype(t)::type, rm, ntc><<<(unsigned)cp.units, kBlock, 0, st>>>(ca);
-      });
-      if (!rc) rc = check_launch("bvq_fakequant_bwd/cols");
-      if (rc) return rc;
-      if (dscale) {
-        float* folded = nullptr;
-        launch_cols_fold_sum_min(ca.ds_part, nullptr, cp.prows, cp.L, ca.ds_part + cp.prows * cp.L, nullptr, &folded,
-                                 nullptr, st);
-        launch_channel_sums(folded, nullptr, dscale, nullptr, 1, channels, d->inner,
-                            reinterpret_cast<char*>(workspace) + cols_bwd_mid_off(cp), st, epilogue);
-        rc = check_launch("bvq_fakequant_bwd/cols_sum");
-      }
-      return rc;
+      if (dscale) w = bwd_cols_layout(ws, cp, false, d->inner, channels);
+      if (short_of(dscale != nullptr)) return BVQ_ERR_WORKSPACE;
+      rc = launch_bwd_cols(d, cp, T, tie_stat, tie_info, w, st, "bvq_fakequant_bwd/cols");
+      if (rc || !dscale) return rc;
+      launch_channel_sums(fold_cols_sums(cp, w, st), nullptr, dscale, nullptr, 1, channels, d->inner, w.mid, st, epilogue);
+      return check_launch("bvq_fakequant_bwd/cols_sum");
     }
   }
-  const void* ptrs[3] = {x, g, dx};
-  const int els[3] = {dtype_size(d->x_dtype), dtype_size(d->ct_dtype), dtype_size(d->x_dtype)};
-  const int full = 16 / dtype_size(d->x_dtype);
-  const int vec = snap_vec(pick_vec(full, outer * channels, row_len, ptrs, els, 3, true), full);
-  QuantArgs a = {};
-  a.t = bwd_tiling(outer, channels, row_len, vec);
-  int64_t mid_off = 0;
-  if (need_sums) {
-    // float partials (8-byte aligned end), then the doubles of a split reduction
-    mid_off = (((dbounds ? 3 : 2) * a.t.units * (int64_t)sizeof(float) + 7) / 8) * 8;
-    const int64_t need = mid_off + channel_sums_mid_bytes(a.t.nob * a.t.ppr, channels);
-    if (!workspace || workspace_bytes < need) {
-      set_error("bvq_fakequant_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                (long long)need);
-      return BVQ_ERR_WORKSPACE;
-    }
-    a.ds_part = reinterpret_cast<float*>(workspace);
-    a.dzp_part = a.ds_part + a.t.units;
-    a.dq_part = a.dzp_part + a.t.units;
-  }
-  a.x = x;
-  a.g = g;
-  a.scale = scale;
-  a.zp = zp;
-  a.y = dx;
+  const BwdRowPlan p = bwd_row_plan(d, T.x, T.g, T.dx);
+  if (need_sums) w = bwd_sums_layout(ws, p.t, dbounds != nullptr);
+  if (short_of(need_sums)) return BVQ_ERR_WORKSPACE;
+  QuantArgs a = rows_bwd_args(d, p.t, T, tie_stat, tie_info, w);
   a.bounds = bounds;
-  a.tie_stat = tie_stat;
-  a.tie_info = reinterpret_cast<unsigned long long*>(tie_info);
-  fill_args(a, d);
   const int mode = dbounds ? kBwdDsBounds : (tie_stat ? kBwdDsTies : (dzp ? kBwdDsDzp : (dscale ? kBwdDs : kBwdDx)));
-  const bool nt =
-      n * (int64_t)(2 * dtype_size(d->x_dtype) + dtype_size(d->ct_dtype)) >= nt_threshold_bytes();
-  rc = launch_bwd_pair(d, a, vec, mode, nt, st);
-  if (!rc) rc = check_launch("bvq_fakequant_bwd");
-  if (rc) return rc;
-  if (need_sums) {
-    // dbounds: [d(qmin) per channel | d(qmax) per channel] (the bounds themselves are scalars: the caller adds the
-    // channels up)
-    launch_channel_sums(dscale ? a.ds_part : nullptr, (dzp || dbounds) ? a.dzp_part : nullptr, dscale,
-                        dbounds ? dbounds : dzp, a.t.nob, channels, a.t.ppr,
-                        reinterpret_cast<char*>(workspace) + mid_off, st, epilogue);
-    if (dbounds)
-      launch_channel_sums(a.dq_part, nullptr, dbounds + channels, nullptr, a.t.nob, channels, a.t.ppr,
-                          reinterpret_cast<char*>(workspace) + mid_off, st, nullptr);
-    rc = check_launch("bvq_fakequant_bwd/channel_sum");
-  }
-  return rc;
+  rc = launch_bwd_rows(d, a, p, mode, st, "bvq_fakequant_bwd");
+  if (rc || !need_sums) return rc;
+  // dbounds: [d(qmin) per channel | d(qmax) per channel] (the bounds themselves are scalars: the caller adds the
+  // channels up)
+  launch_channel_sums(dscale ? w.ds : nullptr, (dzp || dbounds) ? w.dzp : nullptr, dscale, dbounds ? dbounds : dzp,
+                      p.t.nob, channels, p.t.ppr, w.mid, st, epilogue);
+  if (dbounds)
+    launch_channel_sums(w.dq, nullptr, dbounds + channels, nullptr, p.t.nob, channels, p.t.ppr, w.mid, st, nullptr);
+  return check_launch("bvq_fakequant_bwd/channel_sum");
 }
 
 extern "C" int bvq_fakequant_bwd(const bvq_quant_desc* d, const void* g, const void* x,
                                  const void* scale, const void* zp, void* dx, float* dscale,
                                  float* dzp, const void* tie_stat, int64_t* tie_info, void* workspace,
                                  int64_t workspace_bytes, bvq_stream_t stream) {
-  return fakequant_bwd_impl(d, g, x, scale, zp, dx, dscale, dzp, tie_stat, tie_info, workspace, workspace_bytes,
+  return fakequant_bwd_impl(d, {g, x, scale, zp, dx}, dscale, dzp, tie_stat, tie_info, workspace, workspace_bytes,
                             stream, nullptr);
 }
 
@@ -197,7 +208,7 @@ extern "C" int bvq_fakequant_bwd_bounds(const bvq_quant_desc* d, const void* g, 
     set_error("bvq_fakequant_bwd_bounds: null pointer");
     return BVQ_ERR_INVALID;
   }
-  return fakequant_bwd_impl(d, g, x, scale, zp, dx, dscale, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+  return fakequant_bwd_impl(d, {g, x, scale, zp, dx}, dscale, nullptr, nullptr, nullptr, workspace, workspace_bytes,
                             stream, nullptr, bounds, dbounds);
 }
 
@@ -223,58 +234,131 @@ extern "C" int bvq_fakequant_bwd_learned(const bvq_quant_desc* d, const void* g,
   ep.use_min = use_min;
   ep.min_val = round_host((float)min_val, value_dtype);    // python scalar -> the parameter's dtype
   ep.int_threshold = (float)int_threshold;                  // the caller rounds it to the division's dtype
-  return fakequant_bwd_impl(d, g, x, scale, zp, dx, dscale, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+  return fakequant_bwd_impl(d, {g, x, scale, zp, dx}, dscale, nullptr, nullptr, nullptr, workspace, workspace_bytes,
                             stream, &ep);
 }
 
-static bool bwd_stats_supported(const bvq_quant_desc* d, int64_t& units, int64_t& per_channel) {
+// The stats-scaled backward covers per-channel scales with a scalar zero-point.  cp: the column-mapped plan where the
+// layout goes that way; row-mapped, one workgroup of bwd_stats_finish_kernel per channel walks the channel's units.
+static bool bwd_stats_supported(const bvq_quant_desc* d, ColsPlan& cp) {
   if (!(d->scale_per_channel && d->channels > 1) || d->zp_per_channel) return false;
-  const ColsPlan cp = cols_quant_plan(d, nullptr, nullptr, nullptr, false, true);
-  if (cp.ok) {  // column-mapped partials: [prows][L] plus their fold [L]; first positions [L]
-    units = (cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L;
-    per_channel = d->inner;
-    return true;
-  }
-  units = bwd_units(d);
-  per_channel = units / d->channels;
-  return per_channel <= 4096;  // one workgroup of bwd_stats_finish_kernel per channel walks them
+  cp = cols_quant_plan(d, nullptr, nullptr, nullptr, false, true);
+  const int full = 16 / dtype_size(d->x_dtype);
+  return cp.ok || std::max(bwd_row_plan(d, nullptr, nullptr, nullptr, full).t.units,
+                           bwd_row_plan(d, nullptr, nullptr, nullptr, 1).t.units) / d->channels <= 4096;
 }
 
 extern "C" int64_t bvq_fakequant_bwd_stats_workspace_bytes(const bvq_quant_desc* d) {
   if (validate(d)) return -1;
-  int64_t units, per_channel;
-  if (!bwd_stats_supported(d, units, per_channel)) return 0;  // use bvq_fakequant_bwd + bvq_stat_tie_apply_dscale
-  const ColsPlan cp = cols_quant_plan(d, nullptr, nullptr, nullptr, false, true);
-  if (cp.ok)  // float partial rows and their fold, then one first position per column
-    return units * (int64_t)sizeof(float) + cp.L * (int64_t)sizeof(unsigned long long) + 256;
-  return units * (int64_t)(sizeof(float) + sizeof(unsigned long long)) + 256;
+  ColsPlan cp;
+  if (!bwd_stats_supported(d, cp)) return 0;  // use bvq_fakequant_bwd + bvq_stat_tie_apply_dscale
+  if (cp.ok) return measured([&](Carve& c) { bwd_cols_layout(c, cp, true, d->inner, d->channels); }) + kWorkspaceSlack;
+  return kWorkspaceSlack + measured_widths(d->x_dtype, [&](Carve& c, int vec) {
+           bwd_stats_row_layout(c, bwd_row_plan(d, nullptr, nullptr, nullptr, vec).t);
+         });
 }
 
-struct ShardOut {  // batch-sharded tensors: the all-gather message instead of the deposit (null: unsharded)
-  double* msg;
-  long long* pos;
-  int32_t rank;
-};
-static int bwd_stats_impl(const bvq_quant_desc* d, const void* g, const void* x, const void* scale, const void* zp,
-                          const void* stat, void* dx, float* dscale, int scale_dtype, double int_threshold,
-                          int quot_dtype, void* workspace, int64_t workspace_bytes, uint32_t* arrive,
-                          int64_t arrive_words, bvq_stream_t stream, const ShardOut* shard = nullptr);
+extern "C" int bvq_fakequant_bwd_stats_onepass_supported(const bvq_quant_desc* d) {
+  ColsPlan cp;
+  if (validate(d) || !bwd_stats_supported(d, cp)) return 0;
+  if (cols_quant_plan(d, nullptr, nullptr, nullptr).ok) return 0;  // column-mapped layouts: two launches
+  // the one-launch kernel's instantiations (x's alignment, which may still narrow the vector width, is checked at launch)
+  const int full = 16 / dtype_size(d->x_dtype);
+  return stream_full_rne(full, full, d->round_mode) ? 1 : 0;
+}
+
+// dscale and the deposit from finished partials: one workgroup per channel
+static int launch_bwd_stats_finish(const bvq_quant_desc* d, const float* ds, const unsigned long long* pos,
+                                   float* dscale, const GstatSrc& gs, const BwdTensors& T, int64_t nob, int64_t ppr,
+                                   hipStream_t st, const char* what) {
+  const int rc = with_dtype(d->x_dtype, [&](auto t) {
+    bwd_stats_finish_kernel<typename decltype(t)::type><<<(unsigned)d->channels, kBlock, 0, st>>>(
+        ds, pos, dscale, gs, T.x, T.dx, nob, (int32_t)d->channels, ppr, d->inner);
+  });
+  return rc ? rc : check_launch(what);
+}
+
+static int bwd_stats_impl(const bvq_quant_desc* d, const BwdTensors& T, const void* stat, float* dscale,
+                          int scale_dtype, double int_threshold, int quot_dtype, void* workspace,
+                          int64_t workspace_bytes, uint32_t* arrive, bvq_stream_t stream,
+                          const ShardOut* shard = nullptr) {
+  int rc = validate(d);
+  if (rc) return rc;
+  ColsPlan cp;
+  if (!bwd_stats_supported(d, cp)) {
+    set_error("bvq_fakequant_bwd_stats: layout not covered (per-tensor scale or too many units per channel)");
+    return BVQ_ERR_UNSUPPORTED;
+  }
+  if (scale_dtype < BVQ_F32 || scale_dtype > BVQ_F16 || quot_dtype < BVQ_F32 || quot_dtype > BVQ_F16) {
+    set_error("bvq_fakequant_bwd_stats: bad dtype");
+    return BVQ_ERR_INVALID;
+  }
+  const int64_t n = d->outer * d->channels * d->inner;
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t channels = (int32_t)d->channels;
+  if (n == 0) {
+    if (shard)
+      return launch_channel_finish(shard_finish_args(*shard, channels, 0, nullptr, nullptr), st,
+                                   "bvq_fakequant_bwd_shard/empty");
+    if (dscale) (void)hipMemsetAsync(dscale, 0, sizeof(float) * channels, st);
+    return BVQ_OK;
+  }
+  if (!T.g || !T.x || !T.scale || !T.zp || !stat || !T.dx || !dscale || !workspace) {
+    set_error("bvq_fakequant_bwd_stats: null pointer");
+    return BVQ_ERR_INVALID;
+  }
+  const GstatSrc gs = dscale_src(scale_dtype, quot_dtype, int_threshold, d->pre_op);
+  Carve ws(workspace);
+  if (cp.ok) {
+    if (!cols_quant_plan(d, T.x, T.g, T.dx, false, true).ok) {
+      set_error("bvq_fakequant_bwd_stats: the column-mapped route needs 16-byte aligned x, g and dx");
+      return BVQ_ERR_UNSUPPORTED;
+    }
+    const BwdWs w = bwd_cols_layout(ws, cp, true, d->inner, channels);
+    if (!ws.fits(workspace_bytes)) {
+      set_error("bvq_fakequant_bwd_stats: workspace too small");
+      return BVQ_ERR_WORKSPACE;
+    }
+    launch_tie_init(w.pos, cp.L, st);
+    rc = launch_bwd_cols(d, cp, T, stat, nullptr, w, st, "bvq_fakequant_bwd_stats/cols");
+    if (rc) return rc;
+    float* ds_fold = fold_cols_sums(cp, w, st);
+    if (shard)  // this shard's message from the folded partials
+      return launch_channel_finish(shard_finish_args(*shard, channels, d->inner, ds_fold, w.pos), st,
+                                   "bvq_fakequant_bwd_shard/cols_finish");
+    return launch_bwd_stats_finish(d, ds_fold, w.pos, dscale, gs, T, 1, d->inner, st,
+                                   "bvq_fakequant_bwd_stats/cols_finish");
+  }
+  const BwdRowPlan p = bwd_row_plan(d, T.x, T.g, T.dx);
+  const BwdWs w = bwd_stats_row_layout(ws, p.t);
+  if (!ws.fits(workspace_bytes)) {
+    set_error("bvq_fakequant_bwd_stats: workspace too small");
+    return BVQ_ERR_WORKSPACE;
+  }
+  QuantArgs a = rows_bwd_args(d, p.t, T, stat, nullptr, w, shard);
+  // two launches for the rare forms
+  if (arrive && !stream_full_rne(p.vec, 16 / dtype_size(d->x_dtype), d->round_mode)) arrive = nullptr;
+  if (arrive) {  // one launch: the wave that completes a channel finishes it
+    a.arrive = arrive;
+    a.dscale_out = dscale;
+    a.gs_scale_dtype = scale_dtype;
+    a.gs_quot_dtype = quot_dtype;
+    a.gs_int_threshold = (float)int_threshold;
+    return launch_bwd_rows(d, a, p, kBwdDsArrive, st, "bvq_fakequant_bwd_stats_onepass");
+  }
+  rc = launch_bwd_rows(d, a, p, kBwdDsTies, st, "bvq_fakequant_bwd_stats");
+  if (rc) return rc;
+  if (shard) return launch_channel_finish(a, st, "bvq_fakequant_bwd_shard/finish");
+  return launch_bwd_stats_finish(d, w.ds, w.pos, dscale, gs, T, p.t.nob, p.t.ppr, st,
+                                 "bvq_fakequant_bwd_stats/finish");
+}
 
 extern "C" int bvq_fakequant_bwd_stats(const bvq_quant_desc* d, const void* g, const void* x, const void* scale,
                                        const void* zp, const void* stat, void* dx, float* dscale,
                                        int scale_dtype, double int_threshold, int quot_dtype, void* workspace,
                                        int64_t workspace_bytes, bvq_stream_t stream) {
-  return bwd_stats_impl(d, g, x, scale, zp, stat, dx, dscale, scale_dtype, int_threshold, quot_dtype, workspace,
-                        workspace_bytes, nullptr, 0, stream);
-}
-
-extern "C" int bvq_fakequant_bwd_stats_onepass_supported(const bvq_quant_desc* d) {
-  int64_t units, per_channel;
-  if (validate(d) || !bwd_stats_supported(d, units, per_channel)) return 0;
-  if (cols_quant_plan(d, nullptr, nullptr, nullptr).ok) return 0;  // column-mapped layouts: two launches
-  // the one-launch kernel's instantiations (x's alignment, which may still narrow the vector width, is checked at launch)
-  const int full = 16 / dtype_size(d->x_dtype);
-  return stream_full_rne(full, full, d->round_mode) ? 1 : 0;
+  return bwd_stats_impl(d, {g, x, scale, zp, dx}, stat, dscale, scale_dtype, int_threshold, quot_dtype, workspace,
+                        workspace_bytes, nullptr, stream);
 }
 
 extern "C" int bvq_fakequant_bwd_stats_onepass(const bvq_quant_desc* d, const void* g, const void* x,
@@ -295,8 +379,8 @@ extern "C" int bvq_fakequant_bwd_stats_onepass(const bvq_quant_desc* d, const vo
               (long long)d->channels);
     return BVQ_ERR_WORKSPACE;
   }
-  return bwd_stats_impl(d, g, x, scale, zp, stat, dx, dscale, scale_dtype, int_threshold, quot_dtype, workspace,
-                        workspace_bytes, arrive, arrive_words, stream);
+  return bwd_stats_impl(d, {g, x, scale, zp, dx}, stat, dscale, scale_dtype, int_threshold, quot_dtype, workspace,
+                        workspace_bytes, arrive, stream);
 }
 
 extern "C" int bvq_fakequant_bwd_shard(const bvq_quant_desc* d, const void* g, const void* x, const void* scale,
@@ -308,10 +392,10 @@ extern "C" int bvq_fakequant_bwd_shard(const bvq_quant_desc* d, const void* g, c
     return BVQ_ERR_INVALID;
   }
   if (arrive && (!bvq_fakequant_bwd_stats_onepass_supported(d) || arrive_words < d->channels)) arrive = nullptr;
-  ShardOut so = {message, reinterpret_cast<long long*>(first_pos), rank};
+  const ShardOut so = {message, reinterpret_cast<long long*>(first_pos), rank};
   float unused = 0.f;
-  return bwd_stats_impl(d, g, x, scale, zp, stat, dx, &unused, BVQ_F32, 1.0, BVQ_F32, workspace, workspace_bytes, arrive,
-                        arrive_words, stream, &so);
+  return bwd_stats_impl(d, {g, x, scale, zp, dx}, stat, &unused, BVQ_F32, 1.0, BVQ_F32, workspace, workspace_bytes,
+                        arrive, stream, &so);
 }
 
 extern "C" int bvq_shard_unpack_deposit(int dtype, const void* x, void* dx, const double* gathered, int world,
@@ -325,13 +409,8 @@ extern "C" int bvq_shard_unpack_deposit(int dtype, const void* x, void* dx, cons
     set_error("bvq_shard_unpack_deposit: bad argument");
     return BVQ_ERR_INVALID;
   }
-  GstatSrc gs = {};
-  gs.from_dscale = 1;
-  gs.scale_dtype = scale_dtype;
-  gs.quot_dtype = quot_dtype;
-  gs.int_threshold = (float)int_threshold;
   if (const int prc = check_pre_op(pre_op, "bvq_shard_unpack_deposit")) return prc;
-  gs.pre_relu = pre_op == BVQ_PRE_RELU;
+  const GstatSrc gs = dscale_src(scale_dtype, quot_dtype, int_threshold, pre_op);
   const dim3 grid((unsigned)((channels + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
   const long long* fp = reinterpret_cast<const long long*>(first_pos);
@@ -341,158 +420,3 @@ extern "C" int bvq_shard_unpack_deposit(int dtype, const void* x, void* dx, cons
   });
   return rc ? rc : check_launch("bvq_shard_unpack_deposit");
 }
-
-static int bwd_stats_impl(const bvq_quant_desc* d, const void* g, const void* x, const void* scale, const void* zp,
-                          const void* stat, void* dx, float* dscale, int scale_dtype, double int_threshold,
-                          int quot_dtype, void* workspace, int64_t workspace_bytes, uint32_t* arrive,
-                          int64_t arrive_words, bvq_stream_t stream, const ShardOut* shard) {
-  int rc = validate(d);
-  if (rc) return rc;
-  int64_t units, per_channel;
-  if (!bwd_stats_supported(d, units, per_channel)) {
-    set_error("bvq_fakequant_bwd_stats: layout not covered (per-tensor scale or too many units per channel)");
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (scale_dtype < BVQ_F32 || scale_dtype > BVQ_F16 || quot_dtype < BVQ_F32 || quot_dtype > BVQ_F16) {
-    set_error("bvq_fakequant_bwd_stats: bad dtype");
-    return BVQ_ERR_INVALID;
-  }
-  const int64_t n = d->outer * d->channels * d->inner;
-  hipStream_t st = (hipStream_t)stream;
-  const int32_t channels = (int32_t)d->channels;
-  if (n == 0) {
-    if (shard) {  // an empty shard claims nothing: zero sums, no owner, no position (dscale is the entry's dummy)
-      QuantArgs fa = {};
-      fa.t.nob = 1;
-      fa.t.channels = channels;
-      fa.arrive_per_channel = 0;  // no partials: channel_finish reads none and writes acc = 0, pmin = ~0
-      fa.shard_msg = shard->msg;
-      fa.shard_pos = shard->pos;
-      fa.shard_rank = shard->rank;
-      const dim3 cgrid((unsigned)((channels + kWavesPerBlock - 1) / kWavesPerBlock));
-      channel_finish_kernel<float><<<cgrid, dim3(kBlock), 0, st>>>(fa);
-      return check_launch("bvq_fakequant_bwd_shard/empty");
-    }
-    if (dscale) (void)hipMemsetAsync(dscale, 0, sizeof(float) * channels, st);
-    return BVQ_OK;
-  }
-  if (!g || !x || !scale || !zp || !stat || !dx || !dscale || !workspace) {
-    set_error("bvq_fakequant_bwd_stats: null pointer");
-    return BVQ_ERR_INVALID;
-  }
-  GstatSrc gs = {};
-  gs.from_dscale = 1;
-  gs.scale_dtype = scale_dtype;
-  gs.quot_dtype = quot_dtype;
-  gs.int_threshold = (float)int_threshold;
-  gs.pre_relu = d->pre_op == BVQ_PRE_RELU;
-  const bool nt =
-      n * (int64_t)(2 * dtype_size(d->x_dtype) + dtype_size(d->ct_dtype)) >= nt_threshold_bytes();
-  {
-    const ColsPlan cp = cols_quant_plan(d, x, g, dx, false, true);
-    const ColsPlan sized = cols_quant_plan(d, nullptr, nullptr, nullptr, false, true);
-    if (sized.ok && !cp.ok) {
-      set_error("bvq_fakequant_bwd_stats: the column-mapped route needs 16-byte aligned x, g and dx");
-      return BVQ_ERR_UNSUPPORTED;
-    }
-    if (cp.ok) {
-      const int64_t words = (cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L;
-      const int64_t pos_off_c = ((words * (int64_t)sizeof(float) + 7) / 8) * 8;
-      if (workspace_bytes < pos_off_c + cp.L * (int64_t)sizeof(unsigned long long)) {
-        set_error("bvq_fakequant_bwd_stats: workspace too small");
-        return BVQ_ERR_WORKSPACE;
-      }
-      ColsQuantArgs ca = {};
-      fill_cols_args(ca, cp, d);
-      ca.x = x;
-      ca.g = g;
-      ca.y = dx;
-      ca.scale = scale;
-      ca.zp = zp;
-      ca.ds_part = reinterpret_cast<float*>(workspace);
-      // first positions attaining the statistic: one entry per column, taken by atomic min from the few lanes that see it
-      ca.pos_part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + pos_off_c);
-      ca.tie_stat = stat;
-      launch_tie_init(ca.pos_part, cp.L, st);
-      rc = with_cols_variant(d, nt, [&](auto t, auto rm, auto ntc) {
-        fakequant_bwd_cols_kernel<typename decltype(t)::type, rm, ntc><<<(unsigned)cp.units, kBlock, 0, st>>>(ca);
-      });
-      if (!rc) rc = check_launch("bvq_fakequant_bwd_stats/cols");
-      if (rc) return rc;
-      float* ds_fold = nullptr;
-      unsigned long long* pos_fold = ca.pos_part;
-      launch_cols_fold_sum_min(ca.ds_part, nullptr, cp.prows, cp.L, ca.ds_part + cp.prows * cp.L, nullptr, &ds_fold,
-                               nullptr, st);
-      if (shard) {  // this shard's all-gather message from the folded partials: one wave per channel
-        QuantArgs fa = {};
-        fa.t.nob = 1;
-        fa.t.channels = channels;
-        fa.t.ppr = d->inner;
-        fa.arrive_per_channel = (uint32_t)d->inner;
-        fa.ds_part = ds_fold;
-        fa.pos_part = pos_fold;
-        fa.shard_msg = shard->msg;
-        fa.shard_pos = shard->pos;
-        fa.shard_rank = shard->rank;
-        const dim3 cgrid((unsigned)((channels + kWavesPerBlock - 1) / kWavesPerBlock));
-        channel_finish_kernel<float><<<cgrid, dim3(kBlock), 0, st>>>(fa);  // (the message path touches no tensor element)
-        return check_launch("bvq_fakequant_bwd_shard/cols_finish");
-      }
-      rc = with_dtype(d->x_dtype, [&](auto t) {
-        bwd_stats_finish_kernel<typename decltype(t)::type><<<(unsigned)channels, kBlock, 0, st>>>(
-            ds_fold, pos_fold, dscale, gs, x, dx, 1, channels, d->inner, d->inner);
-      });
-      return rc ? rc : check_launch("bvq_fakequant_bwd_stats/cols_finish");
-    }
-  }
-  const void* ptrs[3] = {x, g, dx};
-  const int els[3] = {dtype_size(d->x_dtype), dtype_size(d->ct_dtype), dtype_size(d->x_dtype)};
-  const int full = 16 / dtype_size(d->x_dtype);
-  const int vec = snap_vec(pick_vec(full, d->outer * channels, d->inner, ptrs, els, 3, true), full);
-  QuantArgs a = {};
-  a.t = bwd_tiling(d->outer, channels, d->inner, vec);
-  const int64_t pos_off = ((a.t.units * (int64_t)sizeof(float) + 7) / 8) * 8;
-  if (workspace_bytes < pos_off + a.t.units * (int64_t)sizeof(unsigned long long)) {
-    set_error("bvq_fakequant_bwd_stats: workspace too small");
-    return BVQ_ERR_WORKSPACE;
-  }
-  a.ds_part = reinterpret_cast<float*>(workspace);
-  a.pos_part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + pos_off);
-  a.x = x;
-  a.g = g;
-  a.scale = scale;
-  a.zp = zp;
-  a.y = dx;
-  a.tie_stat = stat;
-  fill_args(a, d);
-  a.arrive_per_channel = (uint32_t)(a.t.nob * a.t.ppr);
-  if (shard) {
-    a.shard_msg = shard->msg;
-    a.shard_pos = shard->pos;
-    a.shard_rank = shard->rank;
-  }
-  if (arrive && !stream_full_rne(vec, full, d->round_mode)) arrive = nullptr;  // two launches for the rare forms
-  if (arrive) {  // one launch: the wave that completes a channel finishes it
-    a.arrive = arrive;
-    a.dscale_out = dscale;
-    a.gs_scale_dtype = scale_dtype;
-    a.gs_quot_dtype = quot_dtype;
-    a.gs_int_threshold = (float)int_threshold;
-    rc = launch_bwd_pair(d, a, vec, kBwdDsArrive, nt, st);
-    return rc ? rc : check_launch("bvq_fakequant_bwd_stats_onepass");
-  }
-  rc = launch_bwd_pair(d, a, vec, kBwdDsTies, nt, st);
-  if (!rc) rc = check_launch("bvq_fakequant_bwd_stats");
-  if (rc) return rc;
-  if (shard) {
-    const dim3 cgrid((unsigned)((channels + kWavesPerBlock - 1) / kWavesPerBlock));
-    channel_finish_kernel<float><<<cgrid, dim3(kBlock), 0, st>>>(a);  // (the message path touches no tensor element)
-    return check_launch("bvq_fakequant_bwd_shard/finish");
-  }
-  rc = with_dtype(d->x_dtype, [&](auto t) {
-    bwd_stats_finish_kernel<typename decltype(t)::type><<<(unsigned)channels, kBlock, 0, st>>>(
-        a.ds_part, a.pos_part, dscale, gs, x, dx, a.t.nob, channels, a.t.ppr, d->inner);
-  });
-  return rc ? rc : check_launch("bvq_fakequant_bwd_stats/finish");
-}
-

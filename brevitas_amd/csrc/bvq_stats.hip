@@ -782,9 +782,7 @@ __global__ void tie_apply_first_kernel(const void* x, GstatSrc gstat, const unsi
   if (c >= channels) return;
   const unsigned long long pos = info[c];
   if (pos == ~0ull) return;  // no element equals the statistic (e.g. NaN)
-  const int64_t o = (int64_t)(pos / (unsigned long long)inner);
-  const int64_t i = (int64_t)(pos - (unsigned long long)o * inner);
-  const int64_t flat = (o * channels + c) * inner + i;
+  const int64_t flat = pos_to_flat(pos, c, channels, inner);
   const T* xp = reinterpret_cast<const T*>(x);
   T* dp = reinterpret_cast<T*>(dx);
   const float term = deposit<T, MATCH>(gstat_value<T>(gstat, c), xp[flat], gstat.pre_relu != 0);
@@ -848,11 +846,22 @@ static Tiling stat_tiling(int dtype, const void* x, const void* dx, int64_t oute
   return make_tiling(r.outer, (int32_t)channels, r.row_len, vec);
 }
 
-static int64_t worst_units(int dtype, int64_t outer, int64_t channels, int64_t inner) {
+// ... at a given width, whatever the pointers (the workspace queries)
+static Tiling stat_tiling_at(int dtype, int64_t outer, int64_t channels, int64_t inner, int vec) {
   const RowView r = row_view(dtype, outer, channels, inner);
-  const int64_t a = make_tiling(r.outer, (int32_t)channels, r.row_len, 16 / dtype_size(dtype)).units;
-  const int64_t b = make_tiling(r.outer, (int32_t)channels, r.row_len, 1).units;
-  return a > b ? a : b;
+  return make_tiling(r.outer, (int32_t)channels, r.row_len, vec);
+}
+
+static int64_t worst_units(int dtype, int64_t outer, int64_t channels, int64_t inner) {
+  return std::max(stat_tiling_at(dtype, outer, channels, inner, 16 / dtype_size(dtype)).units,
+                  stat_tiling_at(dtype, outer, channels, inner, 1).units);
+}
+
+// workspace of bvq_abs_moments: the partials of the two sums, then the middle stage of the channel sums.  Row-mapped:
+// one partial per unit; column-mapped: [partial rows + fold scratch][L] each, folded to the (nob = 1, ppr = inner) layout
+static SumsWs moments_row_layout(Carve& c, const Tiling& t) { return take_sums(c, t.units, t.nob * t.ppr, t.channels); }
+static SumsWs moments_cols_layout(Carve& c, const ColsPlan& cp, int64_t inner, int64_t channels) {
+  return take_sums(c, (cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L, inner, channels);
 }
 
 // the abs-max kernels stream with the default cache policy under a ReLU pre-op: f(std::bool_constant<NT>,
@@ -1347,15 +1356,12 @@ extern "C" int64_t bvq_abs_moments_workspace_bytes(int dtype, int64_t outer, int
     set_error("bvq_abs_moments_workspace_bytes: bad argument");
     return -1;
   }
-  const int64_t units = worst_units(dtype, outer, channels, inner);
-  int64_t need = 2 * units * (int64_t)sizeof(float) + 8 + channel_sums_mid_bytes(units / channels + 1, channels) + 256;
+  int64_t need = measured_widths(dtype, [&](Carve& c, int vec) {
+    moments_row_layout(c, stat_tiling_at(dtype, outer, channels, inner, vec));
+  });
   const ColsPlan cp = cols_plan(dtype, outer, channels, inner);
-  if (cp.ok) {  // column-mapped: two [partial rows + fold scratch][L] float arrays
-    const int64_t cols = 2 * (cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L * (int64_t)sizeof(float) + 8 +
-                         channel_sums_mid_bytes(inner, channels) + 256;
-    if (cols > need) need = cols;
-  }
-  return need;
+  if (cp.ok) need = std::max(need, measured([&](Carve& c) { moments_cols_layout(c, cp, inner, channels); }));
+  return need + kWorkspaceSlack;
 }
 
 extern "C" int bvq_abs_moments(int dtype, const void* x, int64_t outer, int64_t channels, int64_t inner,
@@ -1379,21 +1385,21 @@ extern "C" int bvq_abs_moments(int dtype, const void* x, int64_t outer, int64_t 
     return BVQ_ERR_INVALID;
   }
   const bool nt = n * (int64_t)dtype_size(dtype) >= nt_threshold_bytes();
+  Carve ws(workspace);
   // channel axis last (or nearly): column-mapped units
   const ColsPlan cp =
       (reinterpret_cast<uintptr_t>(x) & 15) == 0 ? cols_plan(dtype, outer, channels, inner) : ColsPlan{};
   if (cp.ok) {
-    const int64_t rows_all = cp.prows + cols_fold_scratch_rows(cp.prows);
-    const int64_t mid_off_c = ((2 * rows_all * cp.L * (int64_t)sizeof(float) + 7) / 8) * 8;
-    if (workspace_bytes < mid_off_c + channel_sums_mid_bytes(inner, channels)) {
+    const SumsWs w = moments_cols_layout(ws, cp, inner, channels);
+    if (!ws.fits(workspace_bytes)) {
       set_error("bvq_abs_moments: workspace too small");
       return BVQ_ERR_WORKSPACE;
     }
     ColsMomentArgs ca;
     ca.p = cp;
     ca.x = x;
-    ca.part1 = reinterpret_cast<float*>(workspace);
-    ca.part2 = ca.part1 + rows_all * cp.L;
+    ca.part1 = w.a;
+    ca.part2 = w.b;
     ca.pivot = sums + 2 * channels;
     ca.inner = inner;
     const dim3 cgrid(grid_for_units(cp.units)), cblock(kBlock);
@@ -1408,22 +1414,20 @@ extern "C" int bvq_abs_moments(int dtype, const void* x, int64_t outer, int64_t 
     launch_cols_fold_sum_min(ca.part1, nullptr, cp.prows, cp.L, ca.part1 + cp.prows * cp.L, nullptr, &f1, nullptr, st);
     launch_cols_fold_sum_min(ca.part2, nullptr, cp.prows, cp.L, ca.part2 + cp.prows * cp.L, nullptr, &f2, nullptr, st);
     // the folded rows are the (nob = 1, channels, ppr = inner) layout of the finishing sums
-    launch_channel_sums(f1, f2, sums, sums + channels, 1, (int32_t)channels, inner,
-                        reinterpret_cast<char*>(workspace) + mid_off_c, st);
+    launch_channel_sums(f1, f2, sums, sums + channels, 1, (int32_t)channels, inner, w.mid, st);
     return check_launch("bvq_abs_moments/cols_sums");
   }
   int vec;
   StatArgs a;
   a.t = stat_tiling(dtype, x, nullptr, outer, channels, inner, vec);
-  const int64_t mid_off = ((2 * a.t.units * (int64_t)sizeof(float) + 7) / 8) * 8;
-  const int64_t need = mid_off + channel_sums_mid_bytes(a.t.nob * a.t.ppr, channels);
-  if (workspace_bytes < need) {
-    set_error("bvq_abs_moments: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+  const SumsWs w = moments_row_layout(ws, a.t);
+  if (!ws.fits(workspace_bytes)) {
+    set_error("bvq_abs_moments: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)ws.used);
     return BVQ_ERR_WORKSPACE;
   }
   a.x = x;
-  a.part_a = reinterpret_cast<uint32_t*>(workspace);
-  a.part_b = a.part_a + a.t.units;
+  a.part_a = reinterpret_cast<uint32_t*>(w.a);
+  a.part_b = reinterpret_cast<uint32_t*>(w.b);
   a.pivot = sums + 2 * channels;
   int rc = with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
@@ -1433,9 +1437,7 @@ extern "C" int bvq_abs_moments(int dtype, const void* x, int64_t outer, int64_t 
   });
   if (!rc) rc = check_launch("bvq_abs_moments");
   if (rc) return rc;
-  launch_channel_sums(reinterpret_cast<const float*>(a.part_a), reinterpret_cast<const float*>(a.part_b), sums,
-                      sums + channels, a.t.nob, (int32_t)channels, a.t.ppr,
-                      reinterpret_cast<char*>(workspace) + mid_off, st);
+  launch_channel_sums(w.a, w.b, sums, sums + channels, a.t.nob, (int32_t)channels, a.t.ppr, w.mid, st);
   return check_launch("bvq_abs_moments/sums");
 }
 
@@ -1737,14 +1739,8 @@ extern "C" int bvq_stat_tie_apply_dscale(int pre_op, int dtype, const void* x, c
     return BVQ_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
-  GstatSrc src = {};
-  src.p = dscale;
-  src.from_dscale = 1;
-  src.scale_dtype = scale_dtype;
-  src.quot_dtype = quot_dtype;
-  src.int_threshold = (float)int_threshold;
   if (const int prc = check_pre_op(pre_op, "bvq_stat_tie_apply_dscale")) return prc;
-  src.pre_relu = pre_op == BVQ_PRE_RELU;
+  const GstatSrc src = dscale_src(scale_dtype, quot_dtype, int_threshold, pre_op, dscale);
   rc = with_dtype(dtype, [&](auto t) {
     run_tie_apply<typename decltype(t)::type, BVQ_MATCH_ABS>(x, stat, src, reinterpret_cast<const unsigned long long*>(tie_info),
                                                              reinterpret_cast<const unsigned long long*>(total_ties), dx,

@@ -2,7 +2,7 @@
 // (dscale / dzp) and the moment statistics.
 #pragma once
 
-#include "bvq_common.h"
+#include "bvq_ties.h"
 
 namespace bvq {
 
@@ -38,18 +38,14 @@ struct LearnedScaleEpilogue {
   int32_t value_dtype, scale_dtype, use_min;
 };
 
-__device__ __forceinline__ float round_to_dtype(float v, int dt) {
-  return dt == BVQ_F32 ? v : (dt == BVQ_BF16 ? rnd<bf16_t>(v) : rnd<f16_t>(v));
-}
-
 __device__ __forceinline__ void learned_scale_bwd_elem(const LearnedScaleEpilogue& ep, int32_t c, float dscale) {
-  float ds = round_to_dtype(dscale, ep.scale_dtype);
-  if (ep.gscale) ds = round_to_dtype(ds + load_scalar_as_f(ep.gscale, ep.scale_dtype, c), ep.scale_dtype);
-  const float dt = round_to_dtype(round_to_dtype(ds / ep.int_threshold, ep.scale_dtype), ep.value_dtype);
+  float ds = round_rt(dscale, ep.scale_dtype);
+  if (ep.gscale) ds = round_rt(ds + load_scalar_as_f(ep.gscale, ep.scale_dtype, c), ep.scale_dtype);
+  const float dt = round_rt(round_rt(ds / ep.int_threshold, ep.scale_dtype), ep.value_dtype);
   float v = load_scalar_as_f(ep.value, ep.value_dtype, c);
   if (ep.use_min && v < ep.min_val) v = ep.min_val;  // NaN passes, like torch.clamp_min
   const float sign = (float)(v >= 0.f) - (float)(v < 0.f);  // binary_sign: +1 at 0, 0 for NaN (B/function/ops.py:31-34)
-  const float dv = round_to_dtype(sign * dt, ep.value_dtype);
+  const float dv = round_rt(sign * dt, ep.value_dtype);
   if (ep.value_dtype == BVQ_F32)
     reinterpret_cast<float*>(ep.dvalue)[c] = dv;
   else if (ep.value_dtype == BVQ_BF16)
@@ -80,16 +76,8 @@ __global__ __launch_bounds__(kBlock) void channel_sum_kernel(const PT* __restric
 #pragma unroll
     for (int j = 0; j < kU; ++j) {
       const int64_t k = kb + (int64_t)j * kBlock;
-      int64_t unit = 0;
       const bool in = k < k1;
-      if (in) {
-        if (nob == 1) {
-          unit = (int64_t)c * ppr + k;
-        } else {
-          const int64_t o = k / ppr, p = k - o * ppr;
-          unit = (o * channels + c) * ppr + p;
-        }
-      }
+      const int64_t unit = in ? partial_unit(c, k, nob, ppr, channels) : 0;
       v0[j] = (in && part0) ? part0[unit] : (PT)0;
       v1[j] = (in && part1) ? part1[unit] : (PT)0;
     }
@@ -127,6 +115,17 @@ __global__ __launch_bounds__(kBlock) void channel_sum_kernel(const PT* __restric
 static inline int64_t channel_sums_mid_bytes(int64_t partials_per_channel, int64_t channels) {
   const int32_t splits = sum_splits(partials_per_channel);
   return splits > 1 ? 2 * channels * (int64_t)splits * (int64_t)sizeof(double) : 0;
+}
+// that stage as the next array of a workspace layout: the `mid` of launch_channel_sums
+static inline double* take_channel_sums_mid(Carve& c, int64_t partials_per_channel, int64_t channels) {
+  return c.take<double>(channel_sums_mid_bytes(partials_per_channel, channels) / (int64_t)sizeof(double));
+}
+// the workspace of an entry that sums two quantities per channel: `count` float partials of each, then the mid stage
+struct SumsWs { float *a, *b; double* mid; };
+static inline SumsWs take_sums(Carve& c, int64_t count, int64_t partials_per_channel, int64_t channels) {
+  float* a = c.take<float>(count);
+  float* b = c.take<float>(count);
+  return {a, b, take_channel_sums_mid(c, partials_per_channel, channels)};
 }
 
 // out0[c] = sum of part0 over channel c's units (same for part1/out1; either pair may be null).

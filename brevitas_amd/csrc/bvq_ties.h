@@ -81,16 +81,26 @@ struct GstatSrc {
   int32_t pre_relu;  // the statistic was taken of relu(x): the deposit's sign is sgn(relu(x))
 };
 
+// the source of the fused quantizer backward's finishing steps (p: the sums, where the kernel reads them from there)
+static inline GstatSrc dscale_src(int scale_dtype, int quot_dtype, double int_threshold, int pre_op,
+                                  const float* dscale = nullptr) {
+  return GstatSrc{dscale, 1, scale_dtype, quot_dtype, (float)int_threshold, pre_op == BVQ_PRE_RELU};
+}
+
 __device__ __forceinline__ float round_rt(float v, int dt) {
   return dt == BVQ_F32 ? v : (dt == BVQ_BF16 ? rnd<bf16_t>(v) : rnd<f16_t>(v));
+}
+
+// a float32 scale-gradient sum -> the statistic's gradient in T: the three rounding points of the chain above
+template <typename T>
+__device__ __forceinline__ float dscale_to_gstat(float ds, int scale_dtype, int quot_dtype, float int_threshold) {
+  return rnd<T>(round_rt(round_rt(ds, scale_dtype) / int_threshold, quot_dtype));
 }
 
 template <typename T>
 __device__ __forceinline__ float gstat_value(const GstatSrc& g, int64_t c) {
   if (!g.from_dscale) return to_f<T>(reinterpret_cast<const T*>(g.p)[c]);
-  float v = round_rt(reinterpret_cast<const float*>(g.p)[c], g.scale_dtype);
-  v = round_rt(v / g.int_threshold, g.quot_dtype);
-  return rnd<T>(v);
+  return dscale_to_gstat<T>(reinterpret_cast<const float*>(g.p)[c], g.scale_dtype, g.quot_dtype, g.int_threshold);
 }
 
 template <typename T, int MATCH>
@@ -100,6 +110,53 @@ __device__ __forceinline__ float deposit(float g, T xv, bool pre_relu = false) {
   } else {
     return g;
   }
+}
+
+// a store / load that is performed at agent scope (global_store / global_load ... sc1): written through to, read from
+// the memory every XCD sees (MI355X_MICROARCH.md, inter-workgroup visibility: sc1 stores and sc1 loads on both sides
+// of a hand-off, the storing wave's vmcnt(0) wait before its arrival add)
+template <typename T>
+__device__ __forceinline__ void store_through(T* p, T v) {
+  if constexpr (sizeof(T) == 2) {
+    __hip_atomic_store(reinterpret_cast<uint16_t*>(p), __builtin_bit_cast(uint16_t, v), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    __hip_atomic_store(reinterpret_cast<uint32_t*>(p), __builtin_bit_cast(uint32_t, v), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+template <typename T>
+__device__ __forceinline__ T load_through(const T* p) {
+  if constexpr (sizeof(T) == 2) {
+    return __builtin_bit_cast(T, __hip_atomic_load(reinterpret_cast<const uint16_t*>(p), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT));
+  } else {
+    return __builtin_bit_cast(T, __hip_atomic_load(reinterpret_cast<const uint32_t*>(p), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT));
+  }
+}
+
+// flat element index of channel c's position pos = o * inner + i in x[outer, channels, inner]
+__device__ __forceinline__ int64_t pos_to_flat(unsigned long long pos, int32_t c, int32_t channels, int64_t inner) {
+  const int64_t o = (int64_t)(pos / (unsigned long long)inner);
+  const int64_t i = (int64_t)(pos - (unsigned long long)o * (unsigned long long)inner);
+  return (o * channels + c) * inner + i;
+}
+
+// dx[channel c's position pos] += the abs-max statistic's gradient g with the element's sign
+template <typename T>
+__device__ __forceinline__ void deposit_abs_at(float g, unsigned long long pos, int32_t c, int32_t channels,
+                                               int64_t inner, const void* x, void* dx, bool pre_relu) {
+  const int64_t flat = pos_to_flat(pos, c, channels, inner);
+  T* dp = reinterpret_cast<T*>(dx) + flat;
+  *dp = from_f<T>(to_f<T>(*dp) + deposit<T, BVQ_MATCH_ABS>(g, reinterpret_cast<const T*>(x)[flat], pre_relu));
+}
+
+// the unit that holds partial k (of nob * ppr) of channel c: units are (outer block, channel, piece)
+__device__ __forceinline__ int64_t partial_unit(int32_t c, int64_t k, int64_t nob, int64_t ppr, int32_t channels) {
+  if (nob == 1) return (int64_t)c * ppr + k;
+  const int64_t o = k / ppr, p = k - o * ppr;
+  return (o * channels + c) * ppr + p;
 }
 
 #endif

@@ -252,15 +252,25 @@ static int var_validate(const char* fn, const bvq_variant_desc* d) {
   return BVQ_OK;
 }
 
-static void var_fill(VarArgs& a, const bvq_variant_desc* d, const void* const* ptrs, const int* els, int nptr, int& vec) {
+// the tiling of a variant call at the width its tensors allow -- or (force_vec: the workspace query) at that width
+static Tiling var_tiling(const bvq_variant_desc* d, const void* const* ptrs, const int* els, int nptr, int& vec,
+                         int force_vec = 0) {
   const bool pc = d->scale_per_channel && d->channels > 1;
   const int64_t outer = pc ? d->outer : 1;
   const int32_t channels = pc ? (int32_t)d->channels : 1;
   const int64_t row_len = pc ? d->inner : d->outer * d->channels * d->inner;
   const int full = 16 / dtype_size(d->x_dtype);
-  vec = pick_vec(full, outer * channels, row_len, ptrs, els, nptr, true);
+  vec = force_vec ? force_vec : pick_vec(full, outer * channels, row_len, ptrs, els, nptr, true);
   vec = vec == full ? full : 1;
-  a.t = make_tiling(outer, channels, row_len, vec, 0, true);
+  return make_tiling(outer, channels, row_len, vec, 0, true);
+}
+
+// workspace of the backward: the units' partials of the two scale gradients, then the middle stage of their sums
+static SumsWs var_bwd_layout(Carve& c, const Tiling& t) { return take_sums(c, t.units, t.nob * t.ppr, t.channels); }
+
+static void var_fill(VarArgs& a, const bvq_variant_desc* d, const void* const* ptrs, const int* els, int nptr, int& vec) {
+  const bool pc = d->scale_per_channel && d->channels > 1;
+  a.t = var_tiling(d, ptrs, els, nptr, vec);
   a.qmin = d->qmin;
   a.qmax = d->qmax;
   a.threshold = d->threshold;
@@ -314,22 +324,12 @@ extern "C" int bvq_variant_fwd(const bvq_variant_desc* d, const void* x, const v
   return rc ? rc : check_launch("bvq_variant_fwd");
 }
 
-static int64_t var_units(const bvq_variant_desc* d) {
-  const bool pc = d->scale_per_channel && d->channels > 1;
-  const int64_t outer = pc ? d->outer : 1;
-  const int32_t channels = pc ? (int32_t)d->channels : 1;
-  const int64_t row_len = pc ? d->inner : d->outer * d->channels * d->inner;
-  const int full = 16 / dtype_size(d->x_dtype);
-  const int64_t u0 = make_tiling(outer, channels, row_len, full, 0, true).units;
-  const int64_t u1 = make_tiling(outer, channels, row_len, 1, 0, true).units;
-  return u0 > u1 ? u0 : u1;
-}
-
 extern "C" int64_t bvq_variant_bwd_workspace_bytes(const bvq_variant_desc* d) {
   if (var_validate("bvq_variant_bwd_workspace_bytes", d)) return -1;
-  const int64_t units = var_units(d);
-  const int64_t channels = (d->scale_per_channel && d->channels > 1) ? d->channels : 1;
-  return ((2 * units * (int64_t)sizeof(float) + 7) / 8) * 8 + channel_sums_mid_bytes(units / channels + 1, channels) + 64;
+  int unused;
+  return kWorkspaceSlack + measured_widths(d->x_dtype, [&](Carve& c, int vec) {
+           var_bwd_layout(c, var_tiling(d, nullptr, nullptr, 0, unused, vec));
+         });
 }
 
 extern "C" int bvq_variant_bwd(const bvq_variant_desc* d, const void* g, const void* x, const void* scale,
@@ -357,16 +357,16 @@ extern "C" int bvq_variant_bwd(const bvq_variant_desc* d, const void* g, const v
   const int els[3] = {dtype_size(d->x_dtype), dtype_size(d->ct_dtype), dtype_size(d->x_dtype)};
   int vec;
   var_fill(a, d, ptrs, els, 3, vec);
-  int64_t mid_off = 0;
+  SumsWs w = {};
   if (dscale || dpre_scale) {
-    mid_off = ((2 * a.t.units * (int64_t)sizeof(float) + 7) / 8) * 8;
-    const int64_t need = mid_off + channel_sums_mid_bytes(a.t.nob * a.t.ppr, channels);
-    if (!workspace || workspace_bytes < need) {
-      set_error("bvq_variant_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+    Carve ws(workspace);
+    w = var_bwd_layout(ws, a.t);
+    if (!ws.fits(workspace_bytes)) {
+      set_error("bvq_variant_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)ws.used);
       return BVQ_ERR_WORKSPACE;
     }
-    a.part_a = dscale ? reinterpret_cast<float*>(workspace) : nullptr;
-    a.part_b = dpre_scale ? reinterpret_cast<float*>(workspace) + a.t.units : nullptr;
+    a.part_a = dscale ? w.a : nullptr;
+    a.part_b = dpre_scale ? w.b : nullptr;
   }
   a.x = x;
   a.g = g;
@@ -379,8 +379,7 @@ extern "C" int bvq_variant_bwd(const bvq_variant_desc* d, const void* g, const v
   if (!rc) rc = check_launch("bvq_variant_bwd");
   if (rc) return rc;
   if (dscale || dpre_scale) {
-    launch_channel_sums(a.part_a, a.part_b, dscale, dpre_scale, a.t.nob, (int32_t)channels, a.t.ppr,
-                        reinterpret_cast<char*>(workspace) + mid_off, st);
+    launch_channel_sums(a.part_a, a.part_b, dscale, dpre_scale, a.t.nob, (int32_t)channels, a.t.ppr, w.mid, st);
     rc = check_launch("bvq_variant_bwd/channel_sum");
   }
   return rc;

@@ -159,19 +159,15 @@ extern "C" int bvq_weight_quant_list_fwd(int dtype, int scale_dtype, int round_m
   return fused_list_fwd(n, descs, items, (hipStream_t)stream);
 }
 
-// where tensor i's partials lie in the workspace: float dscale partials, then (8-byte aligned) first positions, as in
-// bwd_stats_impl; each tensor's block starts on 16 bytes
-static int64_t item_ws_bytes(const Tiling& t) {
-  const int64_t pos_off = ((t.units * (int64_t)sizeof(float) + 7) / 8) * 8;
-  return ((pos_off + t.units * (int64_t)sizeof(unsigned long long) + 15) / 16) * 16;
-}
-
 extern "C" int64_t bvq_weight_quant_list_bwd_workspace_bytes(int dtype, int n, const bvq_weight_item* items) {
   if (check_list("bvq_weight_quant_list_bwd_workspace_bytes", dtype, n, items, false, false)) return -1;
-  const int full = 16 / dtype_size(dtype);
-  int64_t bytes = 256;
-  for (int i = 0; i < n; ++i) bytes += item_ws_bytes(bwd_tiling(1, (int32_t)items[i].channels, items[i].inner, full));
-  return bytes;
+  // every item's partials as its own stats-scaled backward lays them out (full width: the list takes no other item)
+  return kWorkspaceSlack + measured([&](Carve& c) {
+           for (int i = 0; i < n; ++i) {
+             const bvq_quant_desc d = item_desc(dtype, dtype, BVQ_ROUND, items[i]);
+             bwd_stats_row_layout(c, bwd_row_plan(&d, nullptr, nullptr, nullptr, 16 / dtype_size(dtype)).t);
+           }
+         });
 }
 
 extern "C" int bvq_weight_quant_list_bwd(int dtype, int scale_dtype, int quot_dtype, int round_mode, int n,
@@ -190,11 +186,11 @@ extern "C" int bvq_weight_quant_list_bwd(int dtype, int scale_dtype, int quot_dt
   }
   const int full = 16 / dtype_size(dtype);
   WeightBwdListArgs la = {};
+  Carve ws(workspace);
   la.n = n;
   la.scale_dtype = scale_dtype;
   la.quot_dtype = quot_dtype;
-  char* ws = reinterpret_cast<char*>(workspace);
-  int64_t ws_used = 0, slots = 0, chan = 0, bytes = 0;
+  int64_t slots = 0, chan = 0, bytes = 0;
   for (int i = 0; i < n; ++i) {
     const bvq_weight_item& src = items[i];
     const bvq_quant_desc d = item_desc(dtype, scale_dtype, round_mode, src);
@@ -202,20 +198,17 @@ extern "C" int bvq_weight_quant_list_bwd(int dtype, int scale_dtype, int quot_dt
       set_error("bvq_weight_quant_list_bwd: item %d not covered", i);
       return BVQ_ERR_UNSUPPORTED;
     }
-    // the vector width the single-tensor call picks (full: covered rows are whole, aligned 16-byte chunks)
-    const void* ptrs[3] = {src.x, src.g, src.dx};
-    const int els[3] = {dtype_size(dtype), dtype_size(dtype), dtype_size(dtype)};
-    const int vec = snap_vec(pick_vec(full, d.channels, d.inner, ptrs, els, 3, true), full);
-    if (!stream_full_rne(vec, full, round_mode)) {
+    // the plan of the single-tensor call (full width: covered rows are whole, aligned 16-byte chunks)
+    const BwdRowPlan p = bwd_row_plan(&d, src.x, src.g, src.dx);
+    if (!stream_full_rne(p.vec, full, round_mode)) {
       set_error("bvq_weight_quant_list_bwd: item %d has no one-launch kernel", i);
       return BVQ_ERR_UNSUPPORTED;
     }
     WeightBwdItem& it = la.it[i];
-    it.t = bwd_tiling(1, (int32_t)d.channels, d.inner, vec);
-    const int64_t pos_off = ((it.t.units * (int64_t)sizeof(float) + 7) / 8) * 8;
-    it.ds_part = reinterpret_cast<float*>(ws + ws_used);
-    it.pos_part = reinterpret_cast<unsigned long long*>(ws + ws_used + pos_off);
-    ws_used += item_ws_bytes(it.t);
+    it.t = p.t;
+    const BwdWs w = bwd_stats_row_layout(ws, it.t);
+    it.ds_part = w.ds;
+    it.pos_part = w.pos;
     it.x = src.x;
     it.g = src.g;
     it.scale = src.scale;
@@ -233,8 +226,8 @@ extern "C" int bvq_weight_quant_list_bwd(int dtype, int scale_dtype, int quot_dt
     bytes += d.channels * d.inner * (int64_t)(3 * dtype_size(dtype));
   }
   la.start[n] = slots;
-  if (workspace_bytes < ws_used) {
-    set_error("bvq_weight_quant_list_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)ws_used);
+  if (!ws.fits(workspace_bytes)) {
+    set_error("bvq_weight_quant_list_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)ws.used);
     return BVQ_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
