@@ -234,6 +234,87 @@ def group_mse_quantize_at(ratios, idx, stat, scale_of, quantize):
     return quantize(scale), scale
 
 
+# ---- group-wise HQO zero-point (core/quant/int.py: GroupwiseHQOIntQuant), the composed route ------------------
+# The search takes the module's own integer conversion as a callable, to_int(zero_point [groups, 1]) -> q [groups, g], so
+# it runs the same ops as the plain asymmetric quantizer.  It serves CPU and device tensors alike and defines what the
+# one-launch kernels compute ("Group-wise HQO zero-point").
+
+def tree_sum(v, chunk):
+    """the sum over dim 1 of v [groups, g] in the fixed order of the group walk's kernels -> [groups].  Within each run
+    of `chunk` consecutive elements (a 16-byte chunk of the weight's dtype) the even-indexed elements are added in order
+    into one accumulator and the odd-indexed into another, the two are added, and the per-chunk values are reduced by
+    halves, t[:h] + t[h:], until one is left (g / chunk is a power of two)."""
+    c = v.reshape(v.shape[0], -1, chunk)
+    even, odd = c[:, :, 0], c[:, :, 1]
+    for k in range(2, chunk, 2):
+        even = even + c[:, :, k]
+        odd = odd + c[:, :, k + 1]
+    t = even + odd
+    while t.shape[1] > 1:
+        h = t.shape[1] // 2
+        if 2 * h != t.shape[1]:
+            raise ValueError('tree_sum: %d chunks per group is no power of two' % (v.shape[1] // chunk))
+        t = t[:, :h] + t[:, h:]
+    return t[:, 0]
+
+
+def group_hqo_search(xg, inv_beta, p, scale, zp0, to_int):
+    """Half-quadratic optimisation of the zero-point of every group of xg [groups, g] at the fixed scale [groups, 1],
+    from the integer zero-point zp0 [groups, 1] on -> (zero_point [groups, 1] in xg's dtype T, idx uint8 [groups], the
+    kept candidate's float32 error [groups], candidate 0's [groups]).  No gradient.
+
+    inv_beta: the n + 1 float32 values 1 / (beta * kappa^i); p: the norm, in (0, 1].  Candidates i = 0 .. n, every
+    float32 op rounded on its own:
+        zp_i = T(z_i), q_i = to_int(zp_i), y_i = T(T(q_i - zp_i) * scale), r = float32(x) - float32(y_i), e_i = tree(|r|)
+        the first candidate is the best so far; a later one is if the group is live and e_i < e_best (strict; a NaN
+        error is below nothing), and a group whose error did not fall is finished for good.  A constant group (every
+        element equal to the first: its scale is the lower bound, the grid has collapsed) is finished after candidate 0
+        thr = inv_beta[i] * |r|^(p - 1): inv_beta[i] for p = 1, inv_beta[i] / sqrt(|r|) for p = 0.5 (the correctly rounded
+        root), torch.pow otherwise
+        w_e = sign(r) * max(|r| - thr, 0);  z_{i+1} = tree(float32(q_i) - (float32(x) - w_e) * (1 / scale)) * (1 / g)
+    An explicit loop over all candidates: the groups that are finished are carried along and masked."""
+    with torch.no_grad():
+        g, dt = xg.shape[1], xg.dtype
+        chunk = 16 // xg.element_size()
+        xf = xg.float()
+        inv_s = 1.0 / scale.float()
+        z = zp0.float()
+        n = len(inv_beta) - 1
+        for i in range(n + 1):
+            zp = z.to(dt)
+            q = to_int(zp)
+            y = (q - zp) * scale
+            r = xf - y.float()
+            ar = r.abs()
+            e = tree_sum(ar, chunk)
+            if i == 0:
+                e0 = e_best = e
+                zp_best = zp
+                idx = torch.zeros(xg.shape[0], dtype=torch.uint8, device=xg.device)
+                live = ~(xg == xg[:, :1]).all(dim=1)  # a constant group is not searched
+            else:
+                better = live & (e < e_best)
+                e_best = torch.where(better, e, e_best)
+                zp_best = torch.where(better.reshape(-1, 1), zp, zp_best)
+                idx = torch.where(better, torch.full_like(idx, i), idx)
+                live = better
+            if i == n:
+                break
+            ib = torch.tensor(float(inv_beta[i]), dtype=torch.float32, device=xg.device)
+            if p == 1.0:
+                thr = ib
+            elif p == 0.5:
+                # the correctly rounded float32 root: torch's vectorized float32 sqrt on the CPU is not, the float64 root
+                # rounded once is (53 >= 2 * 24 + 2 bits: the second rounding cannot change the result)
+                thr = ib / torch.sqrt(ar.double()).float()
+            else:
+                thr = ib * torch.pow(ar, p - 1.0)
+            sign = (r > 0).float() - (r < 0).float()
+            w_e = sign * torch.clamp_min(ar - thr, 0.0)
+            z = (tree_sum(q.float() - (xf - w_e) * inv_s, chunk) * (1.0 / g)).reshape(-1, 1)
+    return zp_best, idx, e_best, e0
+
+
 import sys  # noqa: E402
 
 _SELF = sys.modules[__name__]

@@ -39,7 +39,7 @@ MX_FLOOR, MX_CEIL = 0, 1
 LR_HARD_SIGMOID, LR_SIGMOID = 0, 1  # bvq_learned_round_impl
 NORM_L1, NORM_L2 = 0, 1  # bvq_norm_kind
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -183,6 +183,9 @@ _SIG = {
     'bvq_group_shifted_supported': (_i32, [_qd, _vp]),
     'bvq_group_shifted_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
     'bvq_group_shifted_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
+    'bvq_group_hqo_supported': (_i32, [_qd, _vp, _i32, _i32]),
+    'bvq_group_hqo_fwd': (_i32, [_qd, _vp, _vp, _i32, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_group_hqo_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
     'bvq_row_shifted_max_row_bytes': (_i64, []),
     'bvq_row_shifted_supported': (_i32, [_qd, _vp]),
     'bvq_row_shifted_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
@@ -547,6 +550,7 @@ class UnitFamily(NamedTuple):
     saved: tuple          # names of those the backward takes after x, in header order
     side: tuple           # the gradients that follow them, each None or [units] in x's dtype
     extra: tuple = ()     # host arguments in front of the scale arguments, both ways
+    bwd_extra: Optional[tuple] = None   # the backward's, where they differ from the forward's (None: `extra`)
     # what the Functions of core/quant/_fused.py read
     zp_per_unit: bool = False   # the descriptor has one zero-point per unit, in x's dtype
     align_side: bool = False    # the .hip file's group_aligned: side gradients must sit on 16-byte boundaries
@@ -563,6 +567,14 @@ GROUP_SHIFTED = UnitFamily('bvq_group_shifted_supported', 'bvq_group_shifted_fwd
 ROW_SHIFTED = UnitFamily('bvq_row_shifted_supported', 'bvq_row_shifted_fwd', 'bvq_row_shifted_bwd',
                          _SHIFTED_OUTS, ('stat',), ('gscale', 'gzp'), zp_per_unit=True, align_side=True)
 UNIT_FAMILIES = (GROUP_QUANT, GROUP_MSE, GROUP_SHIFTED, ROW_SHIFTED)
+# GROUP_SHIFTED with a searched zero-point.  The same record type, served by the same unit_fwd / unit_bwd, but kept out
+# of UNIT_FAMILIES: that tuple is the set of families whose public wrappers ARE the generic ones and whose Functions
+# return every per-unit output shaped [units, 1] and differentiable, which tests/test_unit_families_host.py walks; this
+# family's zero-point and index are constants of the backward and its backward takes none of the forward's host
+# arguments (bwd_extra), so tests/test_group_hqo_host.py holds its record on its own.
+GROUP_HQO = UnitFamily('bvq_group_hqo_supported', 'bvq_group_hqo_fwd', 'bvq_group_hqo_bwd',
+                       _SHIFTED_OUTS + (UnitOut('idx', 1, torch.uint8),), ('stat', 'zp'), ('gscale',),
+                       extra=('inv_beta', 'n_iters', 'lp'), bwd_extra=(), zp_per_unit=True)
 
 
 def unit_supported(fam, desc, x, *extra):
@@ -589,7 +601,7 @@ def unit_bwd(fam, desc, g, x, *rest):
     attaining it).  rest: the tensors of fam.saved, the gradients of fam.side that arrived through the per-unit outputs
     (None: none did), fam.extra, min_val, thr_div"""
     n = len(fam.saved) + len(fam.side)
-    assert len(rest) == n + len(fam.extra) + 2
+    assert len(rest) == n + len(fam.extra if fam.bwd_extra is None else fam.bwd_extra) + 2
     tensors = rest[:n]
     dev = require_device(g, x, *tensors)
     assert g.is_contiguous() and x.is_contiguous()
@@ -636,6 +648,33 @@ def group_mse_bwd(desc, g, x, stat, idx, gscale, table, min_val, thr_div):
 group_shifted_supported = functools.partial(unit_supported, GROUP_SHIFTED)
 group_shifted_fwd = functools.partial(unit_fwd, GROUP_SHIFTED)
 group_shifted_bwd = functools.partial(unit_bwd, GROUP_SHIFTED)
+
+
+HQO_LP = {1.0: 0, 0.5: 1}   # the `lp` codes of the bvq_group_hqo_* entries: the norms their kernels are built for
+HQO_MAX_ITERS = 63
+
+
+def hqo_beta_table(beta, kappa, n_iters):
+    """the host array float32(1 / (beta * kappa^i)), i = 0 .. n_iters, that bvq_group_hqo_fwd takes: each entry formed
+    in double precision and rounded once (keep it alive over the call)"""
+    return (ctypes.c_float * (int(n_iters) + 1))(*[1.0 / (float(beta) * float(kappa) ** i)
+                                                   for i in range(int(n_iters) + 1)])
+
+
+def group_hqo_supported(desc, x, n_iters, lp):
+    """as group_shifted_supported, and the iteration count and the norm's code"""
+    return unit_supported(GROUP_HQO, desc, x, int(n_iters), int(lp))
+
+
+def group_hqo_fwd(desc, x, table, lp, min_val, thr_div):
+    """the statistics of group_shifted_fwd and the zero-point search of len(table) - 1 proximal steps -> (y, scale
+    [groups], zp [groups]: the kept zero-point, stat [2 * groups], idx uint8 [groups]: the kept candidate)"""
+    return unit_fwd(GROUP_HQO, desc, x, ctypes.addressof(table), len(table) - 1, int(lp), min_val, thr_div)
+
+
+def group_hqo_bwd(desc, g, x, stat, zp, gscale, min_val, thr_div):
+    """zp is a constant: dx and the scale statistics' gradients at (scale, zp)"""
+    return unit_bwd(GROUP_HQO, desc, g, x, stat, zp, gscale, min_val, thr_div)
 
 
 def row_shifted_max_row_bytes():

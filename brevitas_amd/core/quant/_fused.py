@@ -745,6 +745,37 @@ class GroupMSEFakeQuantFn(Function):
         return (dx,) + (None,) * 7
 
 
+class GroupHQOFakeQuantFn(Function):
+    """Asymmetric group-wise weights with a searched zero-point (GroupwiseHQOIntQuant): GroupShiftedFakeQuantFn with,
+    per group, the zero-point moved by up to len(table) - 1 half-quadratic proximal steps and the first candidate with
+    the smallest summed |error| kept; x -> (y like x, scale [groups, 1], zero_point [groups, 1]: the kept one, a value
+    of x's dtype, idx uint8 [groups]: the kept candidate).  One launch each way (csrc/bvq_group_hqo.hip): the search
+    runs on the registers that hold the group.  zero_point and idx are constants of the backward.  `table`:
+    nat.hqo_beta_table, `lp`: nat.HQO_LP.  The caller has checked what the kernels cover
+    (GroupwiseHQOIntQuant.forward)."""
+
+    @staticmethod
+    def forward(ctx, x, group_size, min_val, int_threshold, qmin, qmax, clamp_ste, table, lp):
+        ctx.set_materialize_grads(False)  # an unused `scale` output must not cost a zero-fill + add
+        desc, thr_div = unit_call(x, group_size, True, int_threshold, qmin, qmax, clamp_ste)
+        y, scale, zp, stat, idx = nat.group_hqo_fwd(desc, x, table, lp, min_val, thr_div)
+        ctx.desc, ctx.min_val, ctx.thr_div = desc, min_val, thr_div
+        ctx.save_for_backward(x, stat, zp)
+        zp = zp.view(-1, 1)
+        ctx.mark_non_differentiable(zp, idx)
+        return y, scale.view(-1, 1), zp, idx
+
+    @staticmethod
+    def backward(ctx, gy, gscale, _gzp, _gidx):
+        x, stat, zp = ctx.saved_tensors
+        grads = _group_grads(x, gy, [gscale], align_side=nat.GROUP_HQO.align_side)
+        if grads is None:
+            return (None,) * 9
+        gy, (gscale,) = grads
+        dx = nat.group_hqo_bwd(ctx.desc, gy, x, stat, zp, gscale, ctx.min_val, ctx.thr_div)
+        return (dx,) + (None,) * 8
+
+
 class MXQuantFn(Function):
     """MX block-scaled quantizer (core/quant/mx.py): x -> (y like x, float32 scale [groups]).  One launch each way
     (csrc/bvq_mx_quant.hip); the backward recomputes each group's abs-max and exponent from x, so only x is saved.  The

@@ -557,6 +557,117 @@ class GroupwiseMSEIntQuant(GroupwiseRescalingIntQuant):
         return y.reshape(x.shape), scale, self.zero_point_impl(x, scale, bit_width), bit_width
 
 
+class GroupwiseHQOIntQuant(GroupwiseRescalingIntQuant):
+    """The asymmetric GroupwiseRescalingIntQuant whose zero-point is searched per group by half-quadratic optimisation
+    (HQQ; HalfQuadraticOptimizerZeroPoint of later Brevitas releases): from the integer zero-point of the parent on, up
+    to `hqo_iters` proximal steps with the shrinkage of the l_p norm, p = `hqo_lp_norm`, at the strength
+    beta_i = hqo_beta * hqo_kappa^i move a real-valued zero-point, and a group keeps the first candidate with the
+    smallest summed |x - y| reached before its error stops falling.  Data-free; the scale stays the parent's.
+    DESIGN.md, "Group-wise HQO zero-point", states the semantics; _aten.group_hqo_search is their composition from the
+    sub-modules.  No parameter, no buffer, the parent's state-dict keys.  The returned zero_point is a value of the
+    weight's dtype, in general no integer, shaped like the scale, and a constant of the backward.  `last_hqo_index`: the
+    candidates the last forward kept, uint8 [out, K / group_size] (a plain attribute; None before the first forward).
+
+    With 8-bit codes in bfloat16 the zero-point, a bfloat16 value near 128, has almost no fractional bits: nearly every
+    group keeps candidate 0 there.
+
+    On the graph the parent recognises, with p = 1 or 0.5 (bvq_group_hqo_supported), search and quantization run as one
+    kernel each way (_fused.GroupHQOFakeQuantFn); everything else -- CPU tensors, non-contiguous or misaligned weights,
+    other norms, config.FUSED_PATHS off -- takes the composed route, with the same bits where both apply."""
+
+    def __init__(self, int_quant: Module, scaling_impl: Module, int_scaling_impl: Module, zero_point_impl: Module,
+                 bit_width_impl: Module, group_size: int, hqo_iters: int = 20, hqo_beta: float = 10.0,
+                 hqo_kappa: float = 1.01, hqo_lp_norm: float = 0.5):
+        super().__init__(int_quant, scaling_impl, int_scaling_impl, zero_point_impl, bit_width_impl, group_size)
+        if type(scaling_impl) is not StatsFromParameterScaling or \
+                type(zero_point_impl) is not StatsFromParameterZeroPoint or int_quant.signed or int_quant.narrow_range:
+            raise TypeError('GroupwiseHQOIntQuant searches the zero-point of the asymmetric graph (StatsFromParameterScaling, '
+                            'StatsFromParameterZeroPoint, unsigned full-range codes), got %s, %s, signed=%r, '
+                            'narrow_range=%r' % (type(scaling_impl).__name__, type(zero_point_impl).__name__,
+                                                 int_quant.signed, int_quant.narrow_range))
+        if not isinstance(int_quant.delay_wrapper.delay_impl, _NoDelay):
+            raise ValueError('GroupwiseHQOIntQuant: quant_delay_steps is not supported (the search quantizes the weight '
+                             'once per candidate)')
+        if self.group_size not in rec.GROUP_SIZES:
+            raise ValueError('GroupwiseHQOIntQuant: group_size %d (the fixed order of the search\'s sums is defined for '
+                             '%s)' % (self.group_size, ', '.join(map(str, rec.GROUP_SIZES))))
+        if isinstance(hqo_iters, bool) or int(hqo_iters) != hqo_iters or not 0 <= hqo_iters <= nat.HQO_MAX_ITERS:
+            raise ValueError('hqo_iters must be an integer from 0 to %d, got %r' % (nat.HQO_MAX_ITERS, hqo_iters))
+        for name, v in (('hqo_beta', hqo_beta), ('hqo_kappa', hqo_kappa)):
+            if not (math.isfinite(v) and v > 0):
+                raise ValueError('%s must be finite and positive, got %r' % (name, v))
+        if not (math.isfinite(hqo_lp_norm) and 0.0 < hqo_lp_norm <= 1.0):
+            raise ValueError('hqo_lp_norm must be in (0, 1], got %r' % (hqo_lp_norm,))
+        self.hqo_iters, self.hqo_beta, self.hqo_kappa = int(hqo_iters), float(hqo_beta), float(hqo_kappa)
+        self.hqo_lp_norm = float(hqo_lp_norm)
+        try:
+            table = list(nat.hqo_beta_table(self.hqo_beta, self.hqo_kappa, self.hqo_iters))
+        except OverflowError:
+            table = [0.0]
+        if not all(math.isfinite(v) and v > 0 for v in table):
+            raise ValueError('hqo_beta * hqo_kappa^i leaves the float32 range within %d iterations' % self.hqo_iters)
+        self.last_hqo_index = None
+
+    def _hqo_table(self):
+        """nat.hqo_beta_table of the module's constants, built once"""
+        table = self.__dict__.get('_bvq_hqo_table')
+        if table is None:
+            table = self.__dict__['_bvq_hqo_table'] = nat.hqo_beta_table(self.hqo_beta, self.hqo_kappa, self.hqo_iters)
+        return table
+
+    def _hqo_operands(self, x: Tensor, bit_width: Tensor):
+        """(xg, scale [groups, 1]) from the module's own sub-modules, as the parent's generic route forms them"""
+        if x.dtype not in _fused._FLOATS:
+            raise ValueError('GroupwiseHQOIntQuant: a float32, bfloat16 or float16 weight, got %s' % x.dtype)
+        xg = x.reshape(-1, self.group_size)
+        return xg, self.scaling_impl(xg) / self.int_scaling_impl(bit_width)
+
+    def _hqo_search(self, xg: Tensor, scale: Tensor, bit_width: Tensor):
+        """the composed search -> (zero_point [groups, 1], idx uint8 [groups], kept error, candidate 0's error)"""
+        with torch.no_grad():
+            scale = scale.detach()
+            zp0 = self.zero_point_impl(xg, scale, bit_width)
+            return _aten.group_hqo_search(xg.detach(), list(self._hqo_table()), self.hqo_lp_norm, scale, zp0,
+                                          lambda zp: self.int_quant.to_int(scale, zp, bit_width, xg.detach()))
+
+    def hqo_zero_point(self, x: Tensor) -> Tensor:
+        """the composed search alone -> zero_point (out, K / g, 1) in x's dtype (no gradient)"""
+        self._check_groups(x)
+        bit_width = self.msb_clamp_bit_width_impl()
+        with torch.no_grad():
+            xg, scale = self._hqo_operands(x, bit_width)
+            return self._hqo_search(xg, scale, bit_width)[0].reshape(x.shape[0], -1, 1)
+
+    def quantize_at_zero_point(self, x: Tensor, zp: Tensor) -> Tuple[Tensor, Tensor]:
+        """the composed route at given zero-points (one per group, a constant) -> (y like x, scale (out, K / g, 1)),
+        differentiable through the sub-modules"""
+        self._check_groups(x)
+        bit_width = self.msb_clamp_bit_width_impl()
+        xg, scale = self._hqo_operands(x, bit_width)
+        y = self.int_quant(scale, zp.detach().reshape(-1, 1).to(x.dtype), bit_width, xg)
+        return y.reshape(x.shape), scale.reshape(x.shape[0], -1, 1)
+
+    def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        g = self._check_groups(x)
+        bit_width = self.msb_clamp_bit_width_impl()
+        tmpl = self._group_plan(x, bit_width)
+        lp = nat.HQO_LP.get(self.hqo_lp_norm)
+        if tmpl is not None and (not tmpl.shifted or lp is None or not nat.group_hqo_supported(
+                _fused.group_shifted_call(x, g, tmpl.int_thr, tmpl.qmin, tmpl.qmax, tmpl.clamp_ste)[0], x,
+                self.hqo_iters, lp)):
+            tmpl = None
+        if tmpl is not None:
+            y, scale, zero_point, idx = _fused.GroupHQOFakeQuantFn.apply(
+                x, g, tmpl.min_val, tmpl.int_thr, tmpl.qmin, tmpl.qmax, tmpl.clamp_ste, self._hqo_table(), lp)
+        else:
+            xg, scale = self._hqo_operands(x, bit_width)
+            zero_point, idx, _, _ = self._hqo_search(xg, scale, bit_width)
+            y = self.int_quant(scale, zero_point, bit_width, xg)
+        self.last_hqo_index = idx.reshape(x.shape[0], -1)
+        scale = scale.reshape(x.shape[0], -1, 1)
+        return y.reshape(x.shape), scale, zero_point.reshape(scale.shape), bit_width
+
+
 class _PreScaleFn(torch.autograd.Function):
     """p = (s n) / g' of the composed weight-norm route: the forward and the backward of the two torch ops, term for
     term, except that a row which receives no gradient hands none on.  An overflowed norm (n = inf, p = inf, every

@@ -29,7 +29,8 @@ SOURCES = [('bvq_common.hip', [], 'bvq_common.o'), ('bvq_elementwise.hip', [], '
            ('bvq_fakequant_bwd_f32.hip', [], 'bvq_fakequant_bwd_f32.o'),
            ('bvq_weight_list.hip', [], 'bvq_weight_list.o'),
            ('bvq_group_quant.hip', [], 'bvq_group_quant.o'), ('bvq_group_mse.hip', [], 'bvq_group_mse.o'),
-           ('bvq_group_shifted.hip', [], 'bvq_group_shifted.o'), ('bvq_mx_quant.hip', [], 'bvq_mx_quant.o'),
+           ('bvq_group_shifted.hip', [], 'bvq_group_shifted.o'), ('bvq_group_hqo.hip', [], 'bvq_group_hqo.o'),
+           ('bvq_mx_quant.hip', [], 'bvq_mx_quant.o'),
            ('bvq_gptq.hip', [], 'bvq_gptq.o'), ('bvq_learned_round.hip', [], 'bvq_learned_round.o'),
            ('bvq_row_shifted.hip', [], 'bvq_row_shifted.o'), ('bvq_weight_norm.hip', [], 'bvq_weight_norm.o')]
 HEADERS = ['bvq_common.h', 'bvq_unit_walk.h', 'bvq_act.h', 'bvq_stat_epilogue.h', 'bvq_quant_math.h', 'bvq_ties.h', 'bvq_sums.h', 'bvq_fakequant.h', 'bvq_fakequant_bwd.h',

@@ -26,14 +26,6 @@ struct GroupMseArgs : GroupArgs {
   float ratio[kMseMaxRatios];
 };
 
-// one byte per group through the buffer descriptor (a vector store; dropped at kBufSkip and past the extent)
-__device__ __forceinline__ void buf_store_u8(buf_t b, uint32_t byte_off, uint32_t v) {
-  __builtin_amdgcn_raw_buffer_store_b8((unsigned char)v, b, byte_off, 0, 0);
-}
-__device__ __forceinline__ uint32_t buf_load_u8(buf_t b, uint32_t byte_off) {
-  return __builtin_amdgcn_raw_buffer_load_b8(b, byte_off, 0, 0);
-}
-
 // a candidate's threshold: the statistic (a value of T) times the float32 ratio, formed in float32, rounded once to T
 template <typename T>
 __device__ __forceinline__ float mse_threshold(float stat, float ratio) {

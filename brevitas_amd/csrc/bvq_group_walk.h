@@ -148,6 +148,14 @@ __device__ __forceinline__ void store_group(buf_t b, const GroupPlace& p, S v) {
   buf_store<S, 1>(b, p.head_at(sizeof(S)), o);  // dropped for the groups past the end
 }
 
+// one byte per group (the index of a searched candidate: bvq_group_mse.hip, bvq_group_hqo.hip) through the buffer descriptor (a vector store; dropped at kBufSkip and past the extent)
+__device__ __forceinline__ void buf_store_u8(buf_t b, uint32_t byte_off, uint32_t v) {
+  __builtin_amdgcn_raw_buffer_store_b8((unsigned char)v, b, byte_off, 0, 0);
+}
+__device__ __forceinline__ uint32_t buf_load_u8(buf_t b, uint32_t byte_off) {
+  return __builtin_amdgcn_raw_buffer_load_b8(b, byte_off, 0, 0);
+}
+
 // The kernel frame.  A quantizer Q<T, L> plugs in with
 //   Args                       its argument struct, a WalkArgs
 //   Q(args, window)            its descriptors (GroupWindow::groups) and wave constants, built once

@@ -33,7 +33,8 @@ import brevitas_amd.config as config
 from brevitas_amd import _native as nat
 from brevitas_amd.core.quant import _fused
 from brevitas_amd.core.quant._recognise import GROUP_SIZES, clamp_ste_of, round_mode_of
-from brevitas_amd.core.quant.int import GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant, RescalingIntQuant
+from brevitas_amd.core.quant.int import (GroupwiseHQOIntQuant, GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant,
+                                         RescalingIntQuant)
 from brevitas_amd.core.quant.int_base import IntQuant
 from brevitas_amd.core.scaling.runtime import StatsFromParameterScaling
 from brevitas_amd.core.zero_point import StatsFromParameterZeroPoint, ZeroZeroPoint
@@ -68,6 +69,9 @@ def _plan(quantizer, k: int, static_groups: bool) -> _Plan:
     if isinstance(quantizer, GroupwiseMSEIntQuant):
         raise TypeError('gptq: the clip-search quantizer %s is not covered (its threshold is searched on the finished '
                         'group, which the column loop does not have)' % name)
+    if isinstance(quantizer, GroupwiseHQOIntQuant):
+        raise TypeError('gptq: the zero-point-search quantizer %s is not covered (its zero-point is searched on the '
+                        'finished group, which the column loop does not have)' % name)
     if type(quantizer) not in (RescalingIntQuant, GroupwiseRescalingIntQuant):
         raise TypeError('gptq: the quantizer %s is not covered (integer weight quantizers per tensor, per channel or '
                         'per group only)' % name)

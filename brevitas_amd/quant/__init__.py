@@ -13,8 +13,8 @@ import torch
 from brevitas_amd.core.bit_width import BitWidthConst
 from brevitas_amd.core.function_wrapper import (CeilSte, OverOutputChannelView, OverSubChannelBlockView, OverTensorView,
                                                 RoundSte, TensorClamp, TensorClampSte)
-from brevitas_amd.core.quant import (DynamicActIntQuant, GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant, IntQuant,
-                                     MXQuant, PrescaledRestrictIntQuant, RescalingIntQuant, WeightNormIntQuant)
+from brevitas_amd.core.quant import (DynamicActIntQuant, GroupwiseHQOIntQuant, GroupwiseMSEIntQuant,
+                                     GroupwiseRescalingIntQuant, IntQuant, MXQuant, PrescaledRestrictIntQuant, RescalingIntQuant, WeightNormIntQuant)
 from brevitas_amd.core.restrict_val import FloatRestrictValue, PowerOfTwoRestrictValue
 from brevitas_amd.core.scaling import (AccumulatorAwareParameterPreScaling, IntScaling,
                                        ParameterFromRuntimeStatsScaling, ParameterPreScalingWeightNorm, ParameterScaling,
@@ -31,6 +31,7 @@ __all__ = ['Int8WeightPerChannelFloat', 'Int4WeightPerChannelFloat', 'Int8Weight
            'Int8ActPerTensorFloat', 'Uint8ActPerTensorFloat', 'Int8ActPerChannelFloat',
            'ShiftedUint8WeightPerTensorFloat', 'ShiftedUint8WeightPerChannelFloat', 'ShiftedUint8ActPerTensorFloat',
            'ShiftedUint8WeightPerGroupFloat', 'ShiftedUint4WeightPerGroupFloat',
+           'ShiftedUint8WeightPerGroupFloatHQO', 'ShiftedUint4WeightPerGroupFloatHQO',
            'Int8WeightPerTensorFixedPoint', 'Int8WeightPerChannelFixedPoint', 'Int8ActPerTensorFixedPoint',
            'Int8ActPerTensorFloatMinMaxInit', 'Uint8ActPerTensorFloatMaxInit',
            'Uint8ActPerTensorFixedPoint', 'Uint8ActPerTensorFixedPointMaxInit', 'Int8Bias', 'Int16Bias', 'Int24Bias',
@@ -379,10 +380,16 @@ def ShiftedUint8WeightPerGroupFloat(weights: Union[torch.nn.Parameter, Sequence[
     The range is the reference's max - min: a group of positive values only gets zero-point 0 and clips its upper part,
     one of negative values only gets 2^b - 1 and clips likewise, a constant non-zero group gets the lower bound of the
     scale.  y and the gradients stay finite in all of them."""
+    return GroupwiseRescalingIntQuant(*_shifted_group_weight_modules(weights, group_size, bit_width))
+
+
+def _shifted_group_weight_modules(weights, group_size: int, bit_width: int) -> tuple:
+    """the constructor arguments of the asymmetric GroupwiseRescalingIntQuant for one tracked weight, its shape checked
+    here"""
     tracked, group_size, shape = _group_tracked_weight(weights, group_size)
     int_quant = IntQuant(narrow_range=False, signed=False, float_to_int_impl=RoundSte(),
                          tensor_clamp_impl=TensorClampSte())
-    return GroupwiseRescalingIntQuant(
+    return (
         int_quant,
         StatsFromParameterScaling(AbsMinMax(1), OverSubChannelBlockView(group_size), 1, tracked, FloatRestrictValue(),
                                   shape, affine_rescaling=False, scaling_min_val=SCALING_MIN_VAL),
@@ -395,6 +402,29 @@ def ShiftedUint8WeightPerGroupFloat(weights: Union[torch.nn.Parameter, Sequence[
 def ShiftedUint4WeightPerGroupFloat(weights, group_size: int = 128) -> GroupwiseRescalingIntQuant:
     """ShiftedUint8WeightPerGroupFloat with bit_width = 4: the usual asymmetric weight-only format of LLM-sized layers"""
     return ShiftedUint8WeightPerGroupFloat(weights, group_size=group_size, bit_width=4)
+
+
+def ShiftedUint8WeightPerGroupFloatHQO(weights, group_size: int = 128, bit_width: int = 8, hqo_iters: int = 20,
+                                       hqo_beta: float = 10.0, hqo_kappa: float = 1.01,
+                                       hqo_lp_norm: float = 0.5) -> GroupwiseHQOIntQuant:
+    """ShiftedUint8WeightPerGroupFloat whose zero-point is searched per group by half-quadratic optimisation
+    (core/quant/int.py: GroupwiseHQOIntQuant; HQQ, HalfQuadraticOptimizerZeroPoint of later Brevitas releases, not in
+    this reference snapshot): data-free, up to `hqo_iters` proximal steps of the l_p norm p = `hqo_lp_norm` at the
+    strength hqo_beta * hqo_kappa^i move a real-valued zero-point from the integer one towards a lower summed |w - y|;
+    the scale stays max - min.  Same outputs, state-dict keys and layer use as ShiftedUint8WeightPerGroupFloat:
+    weight_quant=functools.partial(ShiftedUint4WeightPerGroupFloatHQO, group_size=64); zero_point is a value of the
+    weight's dtype, in general no integer, and receives no gradient; the kept candidates of the last forward are
+    `last_hqo_index`.  Group sizes 16, 32, 64, 128 and 256.  With 8 bits in bfloat16 the zero-point has almost no
+    fractional bits and nearly every group keeps the integer one."""
+    return GroupwiseHQOIntQuant(*_shifted_group_weight_modules(weights, group_size, bit_width), hqo_iters=hqo_iters,
+                                hqo_beta=hqo_beta, hqo_kappa=hqo_kappa, hqo_lp_norm=hqo_lp_norm)
+
+
+def ShiftedUint4WeightPerGroupFloatHQO(weights, group_size: int = 128, hqo_iters: int = 20, hqo_beta: float = 10.0,
+                                       hqo_kappa: float = 1.01, hqo_lp_norm: float = 0.5) -> GroupwiseHQOIntQuant:
+    """ShiftedUint8WeightPerGroupFloatHQO with bit_width = 4: where the zero-point's fraction matters most"""
+    return ShiftedUint8WeightPerGroupFloatHQO(weights, group_size=group_size, bit_width=4, hqo_iters=hqo_iters,
+                                              hqo_beta=hqo_beta, hqo_kappa=hqo_kappa, hqo_lp_norm=hqo_lp_norm)
 
 
 def ShiftedUint8ActPerTensorFloat(collect_stats_steps: int = 300, bit_width: int = 8) -> RescalingIntQuant:

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 8
+#define BVQ_ABI_VERSION 9
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -770,6 +770,40 @@ int bvq_group_shifted_fwd(const bvq_quant_desc* desc, const void* x, double min_
 int bvq_group_shifted_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* stat,
                           const void* gscale, const void* gzp, double min_val, int use_min, double thr_div, void* dx,
                           bvq_stream_t stream);
+
+/* ---- asymmetric group-wise weights with a searched zero-point (HQO) ----------------------------------------------------
+ * The asymmetric group-wise quantizer above with the zero-point of each group moved by half-quadratic optimisation (HQQ;
+ * HalfQuadraticOptimizerZeroPoint of later Brevitas releases, no reference counterpart).  Descriptor, min_val / use_min /
+ * thr_div, y, scale and stat as in bvq_group_shifted_fwd; T is x's dtype.  inv_beta: a HOST array of n_iters + 1 floats,
+ * inv_beta[i] = 1 / (beta * kappa^i), every one finite and positive, copied into the kernel's arguments; 0 <= n_iters
+ * <= 63; lp: 0 for the norm p = 1, 1 for p = 0.5.
+ * Forward, per group, with mx, mn, s and the integer zero-point zp_0 of bvq_group_shifted_fwd, xf = float32(x),
+ * inv_s = 1 / float32(s) and z_0 = zp_0, for i = 0 .. n_iters:
+ *     zp_i = T(z_i)
+ *     q_i  = clamp(round_half_even(T(T(x / s) + zp_i)), qmin, qmax);  y_i = T(T(q_i - zp_i) * s)
+ *     r    = xf - float32(y_i);  e_i = tree(|r|)
+ *     better = i == 0 or (live and e_i < e_best)     (strict; a NaN error is below nothing)
+ *     better: (e_i, zp_i, i) is the best so far; not better: the group is finished for good (live = false); a constant
+ *     group (mx == mn: the scale is its lower bound) is finished after candidate 0
+ *     thr  = inv_beta[i] (p = 1) or inv_beta[i] / sqrt(|r|) (p = 0.5);  w_e = sign(r) * max(|r| - thr, 0)
+ *     z_{i+1} = tree(float32(q_i) - (xf - w_e) * inv_s) * (1 / g)
+ *   every float32 operation rounded on its own.  tree(v): within each 16-byte chunk of the group the even-indexed
+ *   elements added in order and the odd-indexed likewise, the two sums added, the per-chunk values then reduced by halves,
+ *   t[:h] + t[h:].  y = y_k, zp = zp_k (a value of T, in general no integer), scale = s, stat as above, idx = k as uint8
+ *   [groups], k the kept index.  With n_iters = 0 every output has the bits of bvq_group_shifted_fwd.
+ * Backward: zp_k is a constant.  dx as in bvq_group_shifted_bwd at (s, zp_k); the group's scale gradient is the rounded
+ * float32 sum (+ gscale, nullable) and goes through / thr_div, the straight-through clamp_min and |mx - mn| to the first
+ * element equal to mx and, negated, to the first equal to mn.  The zero-point has no gradient path.  stat, zp: the
+ * forward's outputs.
+ * One launch each way, no workspace, no atomics.  Covered: what the asymmetric group-wise entries cover, and n_iters, lp
+ * and the table as above; anything else returns BVQ_ERR_UNSUPPORTED with a bvq_last_error() text, found before anything
+ * touches the device; bvq_group_hqo_supported answers 1 / 0 for a descriptor, x, an iteration count and an lp code. */
+int bvq_group_hqo_supported(const bvq_quant_desc* desc, const void* x, int n_iters, int lp);
+int bvq_group_hqo_fwd(const bvq_quant_desc* desc, const void* x, const float* inv_beta, int n_iters, int lp,
+                      double min_val, int use_min, double thr_div, void* y, void* scale, void* zp, void* stat, void* idx,
+                      bvq_stream_t stream);
+int bvq_group_hqo_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* stat, const void* zp,
+                      const void* gscale, double min_val, int use_min, double thr_div, void* dx, bvq_stream_t stream);
 
 /* ---- asymmetric per-row activations: one scale and one integer zero-point per row, from the row itself ----------------
  * The per-token quantizer of the dynamic activation quantizers (ShiftedUint8DynamicActPerRowFloat).  x is [rows, H],
