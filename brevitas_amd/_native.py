@@ -956,7 +956,6 @@ def kth_pair(x, k_first, k_second, outer, channels, inner, abs_key):
 
 
 KTH_EXPLICIT, KTH_HIGH, KTH_LOW = 0, 1, 2
-_KBINS = 2048
 
 
 def scale_from_stat(stat32, stat_dtype, min_val, int_threshold, scale_dtype, running=None, momentum=0.0,
@@ -1109,7 +1108,9 @@ class KthSelectSteps(_KthSteps):
         return self.dt, self.channels, p, self.rule, self.q
 
     def _counters(self, p):
-        return int(lib.bvq_kth_hist_offset(self.dt, self.channels, p)), self.channels * _KBINS
+        # (the counters of a pass end where the next pass's begin; every dtype has at least two passes)
+        at = [int(lib.bvq_kth_hist_offset(self.dt, self.channels, i)) for i in (0, 1, p)]
+        return at[2], (at[1] - at[0]) // 4
 
 
 class KthWideSteps(_KthSteps):

@@ -338,59 +338,73 @@ static bool cols_select_applies(int dtype, const void* x, int64_t outer, int64_t
   return x && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && cols_plan(dtype, outer, channels, inner).ok;
 }
 
-static int passes_for(int dtype) { return dtype == BVQ_F32 ? 3 : 2; }
+// ---- workspace of the select entries (Carve, bvq_common.h; DESIGN.md, Workspaces) ------------------------------
+// The entries publish byte offsets into the workspace (bvq_kth_hist_offset, bvq_kthw_plan) that the caller slices it at,
+// so the layout must not depend on where the buffer starts: the base is on a 16-byte boundary (sel_carve refuses any
+// other), the widest alignment a take() below asks for.  One buffer serves whichever route a call comes out with:
+//   the step state | one channel: the wide state | a channel-last tensor: its transposed copy
+// and a query is the layout measured, with no slack.
+constexpr int kMaxPasses = 3;
+static int passes_for(int dtype) { return dtype == BVQ_F32 ? kMaxPasses : 2; }
 
-// workspace layout (depends on dtype and channels only):
-//   [passes][channels][kBins] uint32 histograms | [channels] int64 remaining rank | [channels] uint32 prefix
-struct SelWorkspace {
-  uint32_t* hist;
-  int64_t* krem;
-  uint32_t* prefix;
-  int64_t hist_words;
-};
-
-static int64_t sel_steps_bytes(int dtype, int64_t channels) {
-  return (int64_t)passes_for(dtype) * channels * kBins * (int64_t)sizeof(uint32_t) +
-         channels * (int64_t)(sizeof(uint32_t) + sizeof(int64_t)) + 256;
-}
-
-// The per-tensor ("wide") route's state, behind the stepwise layout of a one-channel workspace.  This function alone
-// knows where its parts lie: the one-shot route, the bvq_kthw_* steps, bvq_kthw_plan's offsets and the workspace size
-// all take them from here (workspace = nullptr: the pointers are offsets from the workspace base).
+// the per-tensor ("wide") route's state, behind the step state of one channel
 struct WideWs {
-  uint32_t* hist;  // [32768]
-  uint32_t* low;   // [2][kLowStride]
-  int64_t* krem;   // [2]
-  uint32_t* sel;   // [2]
-  int64_t bytes;   // of a workspace that holds all of it
+  uint32_t* counters;  // [counter_words] hist, then low: what a begin zeroes from its start
+  uint32_t* hist;      // [hist_words] first digit
+  uint32_t* low;       // [2][kLowStride] the second read's counters of each rank
+  int64_t hist_words, counter_words;
+  int64_t* krem;       // [2]
+  uint32_t* sel;       // [2]
 };
-static WideWs wide_ws(int dtype, const void* workspace) {
-  const uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
-  uintptr_t p = base + (uintptr_t)((sel_steps_bytes(dtype, 1) + 255) / 256 * 256);
+struct SelWs {
+  uint32_t* counters;         // [passes][channels][kBins], what bvq_kth_begin zeroes
+  uint32_t* hist[kMaxPasses];  // the counters of each pass
+  int64_t pass_words, counter_words;
+  int64_t* krem;     // [channels] remaining rank
+  uint32_t* prefix;  // [channels]
+  WideWs wide;       // channels == 1
+};
+
+// What lies behind the step state starts on the second multiple of 256 bytes past its end: there bvq_kthw_plan has
+// published the wide counters since the route exists, and a sharded caller's slices stay where they were.
+static void sel_skip_line(Carve& c) { c.take<char>((c.used + 255) / 256 * 256 + 256 - c.used); }
+
+static WideWs sel_wide_layout(Carve& c) {
   WideWs w;
-  w.hist = reinterpret_cast<uint32_t*>(p);
-  p += kBins15 * sizeof(uint32_t);
-  w.low = reinterpret_cast<uint32_t*>(p);
-  p += 2 * kLowStride * sizeof(uint32_t);
-  w.krem = reinterpret_cast<int64_t*>(p);
-  p += 2 * sizeof(int64_t);
-  w.sel = reinterpret_cast<uint32_t*>(p);
-  p += 2 * sizeof(uint32_t);
-  w.bytes = (int64_t)((p - base + 63) / 64 * 64);
+  sel_skip_line(c);
+  w.hist_words = kBins15;
+  w.counter_words = w.hist_words + 2 * kLowStride;
+  w.counters = c.take<uint32_t>(w.counter_words);
+  w.hist = w.counters;
+  w.low = w.counters + w.hist_words;
+  w.krem = c.take<int64_t>(2);
+  w.sel = c.take<uint32_t>(2);
   return w;
 }
 
-static int64_t sel_workspace_bytes(int dtype, int64_t channels) {
-  return channels == 1 ? wide_ws(dtype, nullptr).bytes : (sel_steps_bytes(dtype, channels) + 255) / 256 * 256;
+static SelWs sel_layout(Carve& c, int dtype, int64_t channels) {
+  SelWs s = {};
+  s.pass_words = channels * kBins;
+  s.counter_words = passes_for(dtype) * s.pass_words;
+  s.counters = c.take<uint32_t>(s.counter_words);
+  for (int p = 0; p < passes_for(dtype); ++p) s.hist[p] = s.counters + p * s.pass_words;
+  s.krem = c.take<int64_t>(channels);
+  s.prefix = c.take<uint32_t>(channels);
+  if (channels == 1) s.wide = sel_wide_layout(c);
+  return s;
 }
 
-static SelWorkspace sel_workspace(int dtype, int64_t channels, void* workspace) {
-  SelWorkspace w;
-  w.hist = reinterpret_cast<uint32_t*>(workspace);
-  w.hist_words = (int64_t)passes_for(dtype) * channels * kBins;
-  w.krem = reinterpret_cast<int64_t*>(w.hist + ((w.hist_words + 1) / 2) * 2);  // 8-byte aligned
-  w.prefix = reinterpret_cast<uint32_t*>(w.krem + channels);
-  return w;
+// the transposed copy of a channel-last tensor, behind the state; moved in 16-byte accesses
+struct alignas(16) Chunk16 { char b[16]; };
+static void* sel_copy_layout(Carve& c, int64_t bytes) {
+  sel_skip_line(c);
+  return c.take<Chunk16>((bytes + 15) / 16);
+}
+
+// the layout from a stand-in base, never dereferenced: what the offset queries measure from
+alignas(16) static char sel_origin[16];
+static int64_t sel_offset_of(const void* p) {
+  return (int64_t)(reinterpret_cast<uintptr_t>(p) - reinterpret_cast<uintptr_t>(sel_origin));
 }
 
 static void pass_bits(int dtype, int pass, int& bits, int& shift) {
@@ -404,18 +418,26 @@ static void pass_bits(int dtype, int pass, int& bits, int& shift) {
   }
 }
 
-// the workspace of every step, per channel or wide (channels = 1)
-static int sel_check(const char* who, int dtype, int64_t channels, const void* workspace,
-                     int64_t workspace_bytes) {
+// the state of every step, per channel or wide (channels = 1), carved from the caller's workspace
+// (rest: the Carve, for what the caller takes behind the state)
+static int sel_carve(const char* who, int dtype, int64_t channels, void* workspace, int64_t workspace_bytes, SelWs& s,
+                     Carve* rest = nullptr) {
   if (bad_dtype(dtype) || channels < 1) {
     set_error("%s: bad argument", who);
     return BVQ_ERR_INVALID;
   }
-  if (!workspace || workspace_bytes < sel_workspace_bytes(dtype, channels)) {
-    set_error("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes,
-              (long long)sel_workspace_bytes(dtype, channels));
+  Carve ws(workspace);
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) {
+    set_error("%s: the workspace must start on a 16-byte boundary (its published offsets are those of an aligned base)",
+              who);
+    return BVQ_ERR_INVALID;
+  }
+  s = sel_layout(ws, dtype, channels);
+  if (!ws.fits(workspace_bytes)) {
+    set_error("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)ws.used);
     return BVQ_ERR_WORKSPACE;
   }
+  if (rest) *rest = ws;
   return BVQ_OK;
 }
 
@@ -439,38 +461,37 @@ static int launch_store(int abs_key, int dtype, const uint32_t* keys, void* out,
   });
 }
 
-// (the transposed copy of a channel-last tensor sits behind the select's own state; sized whether or not x will turn out
-//  16-byte aligned)
-static int64_t sel_scratch_offset(int dtype, int64_t channels) { return (sel_workspace_bytes(dtype, channels) + 255) / 256 * 256; }
-
 extern "C" int64_t bvq_kth_workspace_bytes(int dtype, int64_t outer, int64_t channels, int64_t inner) {
   if (bad_dtype(dtype) || outer < 0 || channels < 1 || inner < 0) {
     set_error("bvq_kth_workspace_bytes: bad argument");
     return -1;
   }
-  if (cols_plan(dtype, outer, channels, inner).ok)
-    return sel_scratch_offset(dtype, channels) + outer * channels * inner * (int64_t)dtype_size(dtype) + 256;
-  return sel_workspace_bytes(dtype, channels);
+  return measured([&](Carve& c) {
+    sel_layout(c, dtype, channels);
+    // (the copy is sized whether or not x will turn out 16-byte aligned)
+    if (cols_plan(dtype, outer, channels, inner).ok) sel_copy_layout(c, outer * channels * inner * (int64_t)dtype_size(dtype));
+  });
 }
 
 extern "C" int bvq_kth_passes(int dtype) { return bad_dtype(dtype) ? -1 : passes_for(dtype); }
 
 extern "C" int64_t bvq_kth_hist_offset(int dtype, int64_t channels, int pass) {
   if (bad_dtype(dtype) || channels < 1 || pass < 0 || pass >= passes_for(dtype)) return -1;
-  return (int64_t)pass * channels * kBins * (int64_t)sizeof(uint32_t);
+  Carve c(sel_origin);
+  return sel_offset_of(sel_layout(c, dtype, channels).hist[pass]);
 }
 
 extern "C" int bvq_kth_begin(int dtype, int64_t channels, int rule, int64_t k, double q, void* workspace,
                              int64_t workspace_bytes, bvq_stream_t stream) {
-  int rc = sel_check("bvq_kth_begin", dtype, channels, workspace, workspace_bytes);
+  SelWs w;
+  int rc = sel_carve("bvq_kth_begin", dtype, channels, workspace, workspace_bytes, w);
   if (rc) return rc;
   if (bad_rank(rule, k, q)) {
     set_error("bvq_kth_begin: bad rank (rule %d, k %lld, q %g)", rule, (long long)k, q);
     return BVQ_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
-  const SelWorkspace w = sel_workspace(dtype, channels, workspace);
-  launch_zero(w.hist, w.hist_words, st);
+  launch_zero(w.counters, w.counter_words, st);
   kth_init_kernel<<<dim3((unsigned)((channels + 255) / 256)), dim3(256), 0, st>>>(
       w.prefix, w.krem, rule == BVQ_KTH_EXPLICIT ? k : 0, (int32_t)channels);
   return check_launch("bvq_kth_begin");
@@ -479,7 +500,9 @@ extern "C" int bvq_kth_begin(int dtype, int64_t channels, int rule, int64_t k, d
 extern "C" int bvq_kth_hist(int abs_key, int dtype, const void* x, int64_t outer, int64_t channels,
                             int64_t inner, int pass, void* workspace, int64_t workspace_bytes,
                             bvq_stream_t stream) {
-  int rc = sel_check("bvq_kth_hist", dtype, channels, workspace, workspace_bytes);
+  Carve ws(nullptr);
+  SelWs w;
+  int rc = sel_carve("bvq_kth_hist", dtype, channels, workspace, workspace_bytes, w, &ws);
   if (rc) return rc;
   if (outer < 0 || inner < 0 || pass < 0 || pass >= passes_for(dtype)) {
     set_error("bvq_kth_hist: bad argument");
@@ -496,17 +519,14 @@ extern "C" int bvq_kth_hist(int abs_key, int dtype, const void* x, int64_t outer
     return BVQ_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
-  const SelWorkspace w = sel_workspace(dtype, channels, workspace);
   if (cols_select_applies(dtype, x, outer, channels, inner)) {
     // channel-last: pass 0 transposes x into the workspace, every pass reads the copy (outer = 1, inner * outer per channel)
-    const int64_t off = sel_scratch_offset(dtype, channels);
-    const int64_t n_bytes = outer * channels * inner * (int64_t)dtype_size(dtype);
-    if (workspace_bytes < off + n_bytes) {
+    void* copy = sel_copy_layout(ws, outer * channels * inner * (int64_t)dtype_size(dtype));
+    if (!ws.fits(workspace_bytes)) {
       set_error("bvq_kth_hist: workspace %lld < %lld bytes (channel-last layout: bvq_kth_workspace_bytes with the shape)",
-                (long long)workspace_bytes, (long long)(off + n_bytes));
+                (long long)workspace_bytes, (long long)ws.used);
       return BVQ_ERR_WORKSPACE;
     }
-    void* copy = reinterpret_cast<char*>(workspace) + off;
     if (pass == 0) {
       const int64_t L = channels * inner;
       const dim3 tg((unsigned)((outer + kTile - 1) / kTile), (unsigned)((L + kTile - 1) / kTile));
@@ -535,7 +555,7 @@ extern "C" int bvq_kth_hist(int abs_key, int dtype, const void* x, int64_t outer
   a.t = make_tiling(r.outer, (int32_t)channels, r.row_len, vec, kSelUnitCap);
   a.x = x;
   a.prefix = w.prefix;
-  a.hist = w.hist + (int64_t)pass * channels * kBins;
+  a.hist = w.hist[pass];
   int bits, shift;
   pass_bits(dtype, pass, bits, shift);
   a.bits = bits;
@@ -555,32 +575,32 @@ extern "C" int bvq_kth_hist(int abs_key, int dtype, const void* x, int64_t outer
 
 extern "C" int bvq_kth_pick(int dtype, int64_t channels, int pass, int rule, double q, void* workspace,
                             int64_t workspace_bytes, bvq_stream_t stream) {
-  int rc = sel_check("bvq_kth_pick", dtype, channels, workspace, workspace_bytes);
+  SelWs w;
+  int rc = sel_carve("bvq_kth_pick", dtype, channels, workspace, workspace_bytes, w);
   if (rc) return rc;
   if (pass < 0 || pass >= passes_for(dtype) || bad_rule(rule)) {
     set_error("bvq_kth_pick: bad argument");
     return BVQ_ERR_INVALID;
   }
-  const SelWorkspace w = sel_workspace(dtype, channels, workspace);
   int bits, shift;
   pass_bits(dtype, pass, bits, shift);
   // the rank rule applies once, to the count of the first pass; otherwise the rank is the one bvq_kth_begin stored or
   // the last pick left
   kth_pick_kernel<kBlock, kBins><<<dim3((unsigned)channels), dim3(kBlock), 0, (hipStream_t)stream>>>(
-      w.hist + (int64_t)pass * channels * kBins, kBins, bits, pass == 0, 0, w.prefix, w.krem,
+      w.hist[pass], kBins, bits, pass == 0, 0, w.prefix, w.krem,
       pass == 0 ? rule : BVQ_KTH_EXPLICIT, q);
   return check_launch("bvq_kth_pick");
 }
 
 extern "C" int bvq_kth_finish(int abs_key, int dtype, int64_t channels, void* out, void* workspace,
                               int64_t workspace_bytes, bvq_stream_t stream) {
-  int rc = sel_check("bvq_kth_finish", dtype, channels, workspace, workspace_bytes);
+  SelWs w;
+  int rc = sel_carve("bvq_kth_finish", dtype, channels, workspace, workspace_bytes, w);
   if (rc) return rc;
   if (!out) {
     set_error("bvq_kth_finish: null pointer");
     return BVQ_ERR_INVALID;
   }
-  const SelWorkspace w = sel_workspace(dtype, channels, workspace);
   rc = launch_store(abs_key, dtype, w.prefix, out, channels, (unsigned)((channels + 255) / 256), 256, (hipStream_t)stream);
   return rc ? rc : check_launch("bvq_kth_finish");
 }
@@ -644,10 +664,9 @@ static int wide_store(int abs_key, int dtype, void* out, int nk, const WideWs& w
 
 // the steps in order, for a tensor in one piece; out[nk]
 static int wide_select(int abs_key, int dtype, const void* x, int64_t n, const int64_t* ks, int nk, void* out,
-                       void* workspace, hipStream_t st) {
-  const WideWs w = wide_ws(dtype, workspace);
+                       const WideWs& w, hipStream_t st) {
   const int shift = wide_shift(abs_key, dtype);
-  launch_zero(w.hist, kBins15 + (shift ? 2 * kLowStride : 0), st);
+  launch_zero(w.counters, shift ? w.counter_words : w.hist_words, st);
   int rc = BVQ_OK;
   for (int p = 0; !rc && p < wide_passes(abs_key, dtype); ++p) {
     rc = wide_hist(abs_key, dtype, x, n, 0, p, nk, wide_full_grid(p, shift), w, st);
@@ -661,23 +680,26 @@ extern "C" int bvq_kthw_plan(int abs_key, int dtype, int pass, int64_t* hist_off
   if (bad_dtype(dtype)) return -1;
   const int passes = wide_passes(abs_key, dtype);
   if (pass < 0 || pass >= passes) return passes;  // (a query for the pass count alone)
-  const WideWs w = wide_ws(dtype, nullptr);       // (offsets from the workspace base)
-  if (hist_offset_bytes) *hist_offset_bytes = (int64_t)reinterpret_cast<uintptr_t>(pass ? w.low : w.hist);
-  if (hist_words) *hist_words = pass ? (int64_t)1 << wide_shift(abs_key, dtype) : (int64_t)(w.low - w.hist);
+  Carve c(sel_origin);
+  const WideWs w = sel_layout(c, dtype, 1).wide;
+  if (hist_offset_bytes) *hist_offset_bytes = sel_offset_of(pass ? w.low : w.hist);
+  if (hist_words) *hist_words = pass ? (int64_t)1 << wide_shift(abs_key, dtype) : w.hist_words;
   return passes;
 }
 
 extern "C" int bvq_kthw_begin(int abs_key, int dtype, void* workspace, int64_t workspace_bytes, bvq_stream_t stream) {
-  int rc = sel_check("bvq_kthw_begin", dtype, 1, workspace, workspace_bytes);
+  SelWs w;
+  int rc = sel_carve("bvq_kthw_begin", dtype, 1, workspace, workspace_bytes, w);
   if (rc) return rc;
-  const int shift = wide_shift(abs_key, dtype);
-  launch_zero(wide_ws(dtype, workspace).hist, kBins15 + (shift ? (int64_t)1 << shift : 0), (hipStream_t)stream);
+  const int shift = wide_shift(abs_key, dtype);  // (one rank: the first rank's low counters)
+  launch_zero(w.wide.counters, w.wide.hist_words + (shift ? (int64_t)1 << shift : 0), (hipStream_t)stream);
   return check_launch("bvq_kthw_begin");
 }
 
 extern "C" int bvq_kthw_hist(int abs_key, int dtype, const void* x, int64_t n, int pass, void* workspace,
                              int64_t workspace_bytes, bvq_stream_t stream) {
-  int rc = sel_check("bvq_kthw_hist", dtype, 1, workspace, workspace_bytes);
+  SelWs w;
+  int rc = sel_carve("bvq_kthw_hist", dtype, 1, workspace, workspace_bytes, w);
   if (rc) return rc;
   if (n < 0 || pass < 0 || pass >= wide_passes(abs_key, dtype)) {
     set_error("bvq_kthw_hist: bad argument");
@@ -702,31 +724,33 @@ extern "C" int bvq_kthw_hist(int abs_key, int dtype, const void* x, int64_t n, i
   int64_t grid = (chunks + per_group - 1) / per_group;
   grid = grid < 1 ? 1 : (grid > full ? full : grid);
   rc = wide_hist(abs_key, dtype, reinterpret_cast<const char*>(x) + head * es, n - head, (int32_t)head, pass, 1,
-                 (unsigned)grid, wide_ws(dtype, workspace), (hipStream_t)stream);
+                 (unsigned)grid, w.wide, (hipStream_t)stream);
   return rc ? rc : check_launch("bvq_kthw_hist");
 }
 
 extern "C" int bvq_kthw_pick(int abs_key, int dtype, int pass, int rule, int64_t k, double q, void* workspace,
                              int64_t workspace_bytes, bvq_stream_t stream) {
-  int rc = sel_check("bvq_kthw_pick", dtype, 1, workspace, workspace_bytes);
+  SelWs w;
+  int rc = sel_carve("bvq_kthw_pick", dtype, 1, workspace, workspace_bytes, w);
   if (rc) return rc;
   if (pass < 0 || pass >= wide_passes(abs_key, dtype) || (pass == 0 ? bad_rank(rule, k, q) : bad_rule(rule))) {
     set_error("bvq_kthw_pick: bad argument");
     return BVQ_ERR_INVALID;
   }
-  wide_pick(abs_key, dtype, pass, 0, rule, k, q, wide_ws(dtype, workspace), (hipStream_t)stream);
+  wide_pick(abs_key, dtype, pass, 0, rule, k, q, w.wide, (hipStream_t)stream);
   return check_launch("bvq_kthw_pick");
 }
 
 extern "C" int bvq_kthw_finish(int abs_key, int dtype, void* out, void* workspace, int64_t workspace_bytes,
                                bvq_stream_t stream) {
-  int rc = sel_check("bvq_kthw_finish", dtype, 1, workspace, workspace_bytes);
+  SelWs w;
+  int rc = sel_carve("bvq_kthw_finish", dtype, 1, workspace, workspace_bytes, w);
   if (rc) return rc;
   if (!out) {
     set_error("bvq_kthw_finish: null pointer");
     return BVQ_ERR_INVALID;
   }
-  rc = wide_store(abs_key, dtype, out, 1, wide_ws(dtype, workspace), (hipStream_t)stream);
+  rc = wide_store(abs_key, dtype, out, 1, w.wide, (hipStream_t)stream);
   return rc ? rc : check_launch("bvq_kthw_finish");
 }
 
@@ -754,8 +778,9 @@ static int kth_select(const char* who, int abs_key, int dtype, const void* x, in
     return BVQ_ERR_INVALID;
   }
   if (wide_select_applies(channels, per_channel, x)) {
-    const int rc = sel_check(who, dtype, 1, workspace, workspace_bytes);
-    return rc ? rc : wide_select(abs_key, dtype, x, per_channel, ks, nk, out, workspace, (hipStream_t)stream);
+    SelWs w;
+    const int rc = sel_carve(who, dtype, 1, workspace, workspace_bytes, w);
+    return rc ? rc : wide_select(abs_key, dtype, x, per_channel, ks, nk, out, w.wide, (hipStream_t)stream);
   }
   int rc = BVQ_OK;
   for (int i = 0; !rc && i < nk; ++i) {  // the digit passes, once per rank

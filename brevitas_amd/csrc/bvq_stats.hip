@@ -838,23 +838,13 @@ __global__ __launch_bounds__(kBlock) void tie_apply_full_kernel(const void* x, c
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// force_vec: the tiling at that width, whatever the pointers (the workspace queries)
 static Tiling stat_tiling(int dtype, const void* x, const void* dx, int64_t outer, int64_t channels,
-                          int64_t inner, int& vec, bool ragged_ok = false) {
+                          int64_t inner, int& vec, bool ragged_ok = false, int force_vec = 0) {
   const void* ptrs[2] = {x, dx};
   const RowView r = row_view(dtype, outer, channels, inner, ptrs, 2, ragged_ok);
-  vec = r.vec;
+  vec = force_vec ? force_vec : r.vec;
   return make_tiling(r.outer, (int32_t)channels, r.row_len, vec);
-}
-
-// ... at a given width, whatever the pointers (the workspace queries)
-static Tiling stat_tiling_at(int dtype, int64_t outer, int64_t channels, int64_t inner, int vec) {
-  const RowView r = row_view(dtype, outer, channels, inner);
-  return make_tiling(r.outer, (int32_t)channels, r.row_len, vec);
-}
-
-static int64_t worst_units(int dtype, int64_t outer, int64_t channels, int64_t inner) {
-  return std::max(stat_tiling_at(dtype, outer, channels, inner, 16 / dtype_size(dtype)).units,
-                  stat_tiling_at(dtype, outer, channels, inner, 1).units);
 }
 
 // workspace of bvq_abs_moments: the partials of the two sums, then the middle stage of the channel sums.  Row-mapped:
@@ -863,6 +853,79 @@ static SumsWs moments_row_layout(Carve& c, const Tiling& t) { return take_sums(c
 static SumsWs moments_cols_layout(Carve& c, const ColsPlan& cp, int64_t inner, int64_t channels) {
   return take_sums(c, (cp.prows + cols_fold_scratch_rows(cp.prows)) * cp.L, inner, channels);
 }
+
+// How bvq_stats and the entries on it (bvq_stats_pre, bvq_absmax_scale[_running]) run one call: the route, its units and
+// the stages of the finish.  The entries and bvq_stats_workspace_bytes (force_vec: the row-mapped plan at that width,
+// whatever the pointer) both take it from here.
+enum StatRoute {
+  kStatCols,  // channel axis last (or nearly): column-mapped units, partial rows folded to one
+  kStatRows,  // row-mapped short units, one partial each
+  kStatLong,  // a whole-tensor abs-max as at most kFinishSlice long units, each walked by one wave of the software-
+              // pipelined kernel of the one-launch route -- the partials then fit ONE finishing launch (the short-unit
+              // tiling leaves ~10^4-10^5 partials and needs two): [8192,8192] bf16 34 -> 26 us, profiles/r03_onepass.txt
+              // section 5
+};
+struct StatPlan {
+  StatRoute route;
+  ColsPlan cp;     // kStatCols
+  Tiling t;        // the row-mapped routes
+  int vec;
+  int32_t splits;  // slices per channel of the finish; > 1: two stages
+};
+static StatPlan stat_plan(int kind, int pre_op, int dtype, const void* x, int64_t outer, int64_t channels,
+                          int64_t inner, int force_vec = 0) {
+  StatPlan p = {};
+  // sigmoid / tanh (bvq_act.h): the row-mapped statistic kernels + the finishing launch, nothing else
+  const bool act = pre_op >= BVQ_PRE_SIGMOID;
+  if (!force_vec && !act && (reinterpret_cast<uintptr_t>(x) & 15) == 0) p.cp = cols_plan(dtype, outer, channels, inner);
+  if (p.cp.ok) {
+    p.route = kStatCols;
+    return p;
+  }
+  p.route = kStatRows;
+  p.t = stat_tiling(dtype, x, nullptr, outer, channels, inner, p.vec, true, force_vec);
+  if (kind == BVQ_STAT_ABSMAX && channels == 1 && p.vec == 16 / dtype_size(dtype) && p.t.units > kFinishSlice && !act) {
+    Tiling l = p.t;
+    const int64_t quantum = (int64_t)kWave * p.vec;
+    const int64_t piece = (l.row_len + kFinishSlice - 1) / kFinishSlice;
+    l.piece_len = ((piece + quantum - 1) / quantum) * quantum;
+    l.ppr = (l.row_len + l.piece_len - 1) / l.piece_len;
+    l.units = l.nob * channels * l.ppr;
+    if (cap_unit_extent(l, dtype_size(dtype))) {  // (else the short units: no tensor that fits the device gets there)
+      p.t = l;
+      p.route = kStatLong;
+    }
+  }
+  p.splits = finish_splits(p.t.nob * p.t.ppr);
+  return p;
+}
+
+// ---- workspaces of the statistic entries (Carve, bvq_common.h): one function per route ---------------------------
+// row-mapped: one key per unit -- two for min/max (max, min) -- then, for a two-stage finish, the keys of its first
+// stage.  The abs-max kernels and stat_finish_kernel<BVQ_STAT_ABSMAX> touch neither part_b nor mid_b: null there.
+struct StatWs { uint32_t *part_a, *part_b, *mid_a, *mid_b; };
+static StatWs stat_row_layout(Carve& c, const StatPlan& p, int kind) {
+  const bool two = kind != BVQ_STAT_ABSMAX;
+  const int64_t mid = p.splits > 1 ? p.t.channels * (int64_t)p.splits : 0;
+  StatWs w = {};
+  w.part_a = c.take<uint32_t>(p.t.units);
+  if (two) w.part_b = c.take<uint32_t>(p.t.units);
+  if (mid) w.mid_a = c.take<uint32_t>(mid);
+  if (mid && two) w.mid_b = c.take<uint32_t>(mid);
+  return w;
+}
+// column-mapped: [partial rows][width] keys, then the scratch of their fold; a partial row holds one key per column,
+// or (min/max) two rows of them, the keys of the maxima and of the minima
+struct StatColsWs { uint32_t *part, *fold; int64_t width; };
+static StatColsWs stat_cols_layout(Carve& c, const ColsPlan& cp, int kind) {
+  StatColsWs w;
+  w.width = (kind != BVQ_STAT_ABSMAX ? 2 : 1) * cp.L;
+  w.part = c.take<uint32_t>(cp.prows * w.width);
+  w.fold = c.take<uint32_t>(cols_fold_scratch_rows(cp.prows) * w.width);
+  return w;
+}
+// bvq_stat_bwd: the tie_info words (bvq_ties.h) between its scan and its apply
+static int64_t* stat_tie_layout(Carve& c, int64_t channels) { return c.take<int64_t>(tie_info_words(channels)); }
 
 // the abs-max kernels stream with the default cache policy under a ReLU pre-op: f(std::bool_constant<NT>,
 // std::bool_constant<RELU>) for (nt, false) and (false, true)
@@ -902,16 +965,18 @@ extern "C" int64_t bvq_stats_workspace_bytes(int kind, int dtype, int64_t outer,
     set_error("bvq_stats_workspace_bytes: bad argument");
     return -1;
   }
-  (void)kind;
-  const int64_t units = worst_units(dtype, outer, channels, inner);
-  const int64_t mid = channels * (int64_t)finish_splits(units / channels + 1);
-  int64_t partials = 2 * (units + mid) * (int64_t)sizeof(uint32_t);
+  const auto rows = [&](int pre_op) {
+    return measured_widths(dtype, [&](Carve& c, int vec) {
+      stat_row_layout(c, stat_plan(kind, pre_op, dtype, nullptr, outer, channels, inner, vec), kind);
+    });
+  };
+  // the tie words of bvq_stat_bwd, the row-mapped routes, the column-mapped one
+  int64_t need = std::max(measured([&](Carve& c) { stat_tie_layout(c, channels); }), rows(BVQ_PRE_NONE));
+  // (a sigmoid / tanh pre-op keeps the short units where the others take the long ones)
+  if (kind == BVQ_STAT_ABSMAX && channels == 1) need = std::max(need, rows(BVQ_PRE_SIGMOID));
   const ColsPlan cp = cols_plan(dtype, outer, channels, inner);
-  // (min/max keeps two key rows per partial row)
-  if (cp.ok && (cp.prows + cols_fold_scratch_rows(cp.prows)) * 2 * cp.L * (int64_t)sizeof(uint32_t) > partials)
-    partials = (cp.prows + cols_fold_scratch_rows(cp.prows)) * 2 * cp.L * (int64_t)sizeof(uint32_t);
-  const int64_t tie = (channels > 1 ? channels : 2 + kTieCap) * (int64_t)sizeof(int64_t);
-  return partials + tie + 256;
+  if (cp.ok) need = std::max(need, measured([&](Carve& c) { stat_cols_layout(c, cp, kind); }));
+  return need + kWorkspaceSlack;
 }
 
 static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t outer, int64_t channels,
@@ -921,8 +986,6 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
     set_error("bvq_stats: bad pre_op %d", pre_op);
     return BVQ_ERR_INVALID;
   }
-  // sigmoid / tanh (bvq_act.h): the row-mapped statistic kernels + the finishing launch, nothing else
-  const bool act = pre_op >= BVQ_PRE_SIGMOID;
   if (bad_dtype(dtype) || bad_dtype(out_dtype) || outer < 0 || channels < 1 || inner < 0 ||
       (kind != BVQ_STAT_ABSMAX && kind != BVQ_STAT_MINMAX)) {
     set_error("bvq_stats: bad argument");
@@ -943,19 +1006,19 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
   }
   hipStream_t st = (hipStream_t)stream;
   bool nt = n * (int64_t)dtype_size(dtype) >= nt_threshold_bytes();
-  // channel axis last (or nearly): column-mapped units, same finishing kernel
-  const ColsPlan cp =
-      (reinterpret_cast<uintptr_t>(x) & 15) == 0 && !act ? cols_plan(dtype, outer, channels, inner) : ColsPlan{};
-  if (cp.ok) {
-    const int64_t width = (kind == BVQ_STAT_MINMAX ? 2 : 1) * cp.L;  // entries per partial row
-    if (workspace_bytes < (cp.prows + cols_fold_scratch_rows(cp.prows)) * width * (int64_t)sizeof(uint32_t)) {
+  const StatPlan p = stat_plan(kind, pre_op, dtype, x, outer, channels, inner);
+  Carve ws(workspace);
+  if (p.route == kStatCols) {  // same finishing kernel
+    const ColsPlan& cp = p.cp;
+    const StatColsWs w = stat_cols_layout(ws, cp, kind);
+    if (!ws.fits(workspace_bytes)) {
       set_error("bvq_stats: workspace too small");
       return BVQ_ERR_WORKSPACE;
     }
     ColsStatArgs ca;
     ca.p = cp;
     ca.x = x;
-    ca.part = reinterpret_cast<uint32_t*>(workspace);
+    ca.part = w.part;
     const unsigned grid = grid_for_units(cp.units);
     int rc = with_dtype(dtype, [&](auto t) {
       using T = typename decltype(t)::type;
@@ -968,7 +1031,7 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
     });
     if (!rc) rc = check_launch("bvq_stats/cols");
     if (rc) return rc;
-    uint32_t* folded = launch_cols_fold_max(ca.part, cp.prows, width, ca.part + cp.prows * width, st);  // [width]
+    uint32_t* folded = launch_cols_fold_max(w.part, cp.prows, w.width, w.fold, st);  // [width]
     if (kind == BVQ_STAT_MINMAX) {
       minmax_cols_finish_kernel<<<dim3((unsigned)channels), dim3(kWave), 0, st>>>(folded, out, out_dtype,
                                                                                   (int32_t)channels, inner);
@@ -978,34 +1041,18 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
         folded, folded, out, out_dtype, dtype, 1, (int32_t)channels, inner, ep, nullptr, nullptr);
     return check_launch("bvq_stats/finish");
   }
-  int vec;
-  StatArgs a;
-  a.t = stat_tiling(dtype, x, nullptr, outer, channels, inner, vec, true);
-  // A whole-tensor abs-max as long units: at most kFinishSlice pieces, each walked by one wave of the software-pipelined
-  // kernel of the one-launch route -- the partials then fit ONE finishing launch (the short-unit tiling leaves ~10^4-10^5
-  // partials and needs two): [8192,8192] bf16 34 -> 26 us, profiles/r03_onepass.txt section 5.
-  const bool long_units = kind == BVQ_STAT_ABSMAX && channels == 1 && vec == 16 / dtype_size(dtype) &&
-                          a.t.units > kFinishSlice && !act;
-  if (long_units) {
-    const int64_t quantum = (int64_t)kWave * vec;
-    int64_t piece = (a.t.row_len + kFinishSlice - 1) / kFinishSlice;
-    piece = ((piece + quantum - 1) / quantum) * quantum;
-    a.t.piece_len = piece;
-    a.t.ppr = (a.t.row_len + piece - 1) / piece;
-    a.t.units = a.t.nob * channels * a.t.ppr;
-  }
-  const int32_t splits = finish_splits(a.t.nob * a.t.ppr);
-  const int64_t mid_words = splits > 1 ? channels * (int64_t)splits : 0;
-  const int64_t need = 2 * (a.t.units + mid_words) * (int64_t)sizeof(uint32_t);
-  if (workspace_bytes < need) {
-    set_error("bvq_stats: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+  const StatWs w = stat_row_layout(ws, p, kind);
+  if (!ws.fits(workspace_bytes)) {
+    set_error("bvq_stats: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)ws.used);
     return BVQ_ERR_WORKSPACE;
   }
+  StatArgs a;
+  a.t = p.t;
   a.x = x;
-  a.part_a = reinterpret_cast<uint32_t*>(workspace);
-  a.part_b = a.part_a + a.t.units;
+  a.part_a = w.part_a;
+  a.part_b = w.part_b;
   int rc;
-  if (long_units && cap_unit_extent(a.t, dtype_size(dtype))) {
+  if (p.route == kStatLong) {
     ArriveArgs r = {};
     r.part = a.part_a;
     const ScaleEpilogue no_ep = {};
@@ -1019,7 +1066,7 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
     rc = with_dtype(dtype, [&](auto t) {
       using T = typename decltype(t)::type;
       return with_value<BVQ_PRE_NONE, BVQ_PRE_RELU, BVQ_PRE_SIGMOID, BVQ_PRE_TANH>(pre_op, [&](auto pre) {
-        return with_read_variant<elem<T>::vec>(vec, nt, [&](auto v, auto ntc) {
+        return with_read_variant<elem<T>::vec>(p.vec, nt, [&](auto v, auto ntc) {
           if (kind == BVQ_STAT_ABSMAX)
             absmax_kernel<T, v, ntc, pre><<<grid_for_units(a.t.units), kBlock, 0, st>>>(a);
           else
@@ -1030,15 +1077,13 @@ static int stats_impl(int kind, int pre_op, int dtype, const void* x, int64_t ou
   }
   if (!rc) rc = check_launch("bvq_stats");
   if (rc) return rc;
-  uint32_t* mid_a = splits > 1 ? a.part_b + a.t.units : nullptr;
-  uint32_t* mid_b = splits > 1 ? mid_a + mid_words : nullptr;
   const ScaleEpilogue none = {};
   rc = with_value<BVQ_STAT_ABSMAX, BVQ_STAT_MINMAX>(kind, [&](auto k) {
-    if (splits > 1) {
-      stat_finish_kernel<k><<<dim3((unsigned)channels, (unsigned)splits), kBlock, 0, st>>>(
-          a.part_a, a.part_b, out, out_dtype, dtype, a.t.nob, (int32_t)channels, a.t.ppr, none, mid_a, mid_b);
-      stat_finish_kernel<k><<<(unsigned)channels, kBlock, 0, st>>>(mid_a, mid_b, out, out_dtype, dtype, 1,
-                                                                   (int32_t)channels, splits, ep, nullptr, nullptr);
+    if (p.splits > 1) {
+      stat_finish_kernel<k><<<dim3((unsigned)channels, (unsigned)p.splits), kBlock, 0, st>>>(
+          a.part_a, a.part_b, out, out_dtype, dtype, a.t.nob, (int32_t)channels, a.t.ppr, none, w.mid_a, w.mid_b);
+      stat_finish_kernel<k><<<(unsigned)channels, kBlock, 0, st>>>(w.mid_a, w.mid_b, out, out_dtype, dtype, 1,
+                                                                   (int32_t)channels, p.splits, ep, nullptr, nullptr);
     } else {
       stat_finish_kernel<k><<<(unsigned)channels, kBlock, 0, st>>>(a.part_a, a.part_b, out, out_dtype, dtype, a.t.nob,
                                                                    (int32_t)channels, a.t.ppr, ep, nullptr, nullptr);
@@ -1313,9 +1358,10 @@ extern "C" int bvq_absmax_scale_list(int dtype, int n, const void* const* xs, co
               (long long)onepass_arrive_words(channels));
     return BVQ_ERR_WORKSPACE;
   }
-  if (channels == 1 && (!workspace || workspace_bytes < la.start[n] * (int64_t)sizeof(uint32_t))) {
-    set_error("bvq_absmax_scale_list: workspace %lld < %lld bytes", (long long)workspace_bytes,
-              (long long)(la.start[n] * (int64_t)sizeof(uint32_t)));
+  Carve ws(workspace);
+  uint32_t* part = ws.take<uint32_t>(la.start[n]);  // a whole-tensor statistic: one key per unit
+  if (channels == 1 && !ws.fits(workspace_bytes)) {
+    set_error("bvq_absmax_scale_list: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)ws.used);
     return BVQ_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -1326,7 +1372,7 @@ extern "C" int bvq_absmax_scale_list(int dtype, int n, const void* const* xs, co
   r.stat_out = stat_out;
   r.stat_dtype = dtype;
   r.in_dtype = dtype;
-  r.part = channels == 1 ? reinterpret_cast<uint32_t*>(workspace) : nullptr;
+  r.part = channels == 1 ? part : nullptr;
   const ScaleEpilogue ep = scale_epilogue(scale_out, scale_dtype, use_min, min_val, dtype, int_threshold);
   const dim3 grid(grid_for_units(la.start[n])), block(kBlock);
   int rc = with_dtype(dtype, [&](auto t) {
@@ -1357,7 +1403,7 @@ extern "C" int64_t bvq_abs_moments_workspace_bytes(int dtype, int64_t outer, int
     return -1;
   }
   int64_t need = measured_widths(dtype, [&](Carve& c, int vec) {
-    moments_row_layout(c, stat_tiling_at(dtype, outer, channels, inner, vec));
+    moments_row_layout(c, stat_tiling(dtype, nullptr, nullptr, outer, channels, inner, vec, false, vec));
   });
   const ColsPlan cp = cols_plan(dtype, outer, channels, inner);
   if (cp.ok) need = std::max(need, measured([&](Carve& c) { moments_cols_layout(c, cp, inner, channels); }));
@@ -1640,7 +1686,7 @@ static int check_stat_args(const char* fn, int match_flags, int dtype, int64_t o
 
 extern "C" int64_t bvq_tie_info_bytes(int64_t channels) {
   if (channels < 1) return -1;
-  return tie_info_words(channels) * (int64_t)sizeof(int64_t);
+  return measured([&](Carve& c) { stat_tie_layout(c, channels); });
 }
 
 extern "C" int bvq_stat_tie_scan(int match, int dtype, const void* x, const void* stat, int64_t outer,
@@ -1755,11 +1801,12 @@ extern "C" int bvq_stat_bwd(int match, int dtype, const void* x, const void* sta
   int rc = check_stat_args("bvq_stat_bwd", match, dtype, outer, channels, inner);
   if (rc) return rc;
   if (outer * channels * inner == 0) return BVQ_OK;
-  if (!workspace || workspace_bytes < bvq_tie_info_bytes(channels)) {
+  Carve ws(workspace);
+  int64_t* info = stat_tie_layout(ws, channels);
+  if (!ws.fits(workspace_bytes)) {
     set_error("bvq_stat_bwd: workspace too small");
     return BVQ_ERR_WORKSPACE;
   }
-  int64_t* info = reinterpret_cast<int64_t*>(workspace);
   rc = bvq_stat_tie_scan(match, dtype, x, stat, outer, channels, inner, mode_add ? nullptr : dx, info,
                          stream);
   if (rc) return rc;

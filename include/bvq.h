@@ -172,7 +172,9 @@ int bvq_abs_binary_sign_grad_bwd(int dtype, const void* g, const void* x, void* 
 
 /* ---- statistics (seam 2: AbsMax / AbsMinMax) ------------------------------------------------ */
 
-/* bytes of scratch bvq_stats needs for this problem (0 is a valid answer) */
+/* Bytes of workspace that bvq_stats, bvq_stats_pre, bvq_absmax_scale[_running] (kind BVQ_STAT_ABSMAX) and bvq_stat_bwd
+ * need for this problem: the largest of their routes' layouts, measured, plus a few bytes for a buffer that starts on
+ * no boundary.  BVQ_STAT_ABSMAX needs about half of BVQ_STAT_MINMAX (one key per partial, not two).  -1: bad argument. */
 int64_t bvq_stats_workspace_bytes(int kind, int dtype, int64_t outer, int64_t channels, int64_t inner);
 
 /* Per-channel (or whole-tensor, channels == 1) statistic over the `outer` and `inner` axes of
@@ -334,7 +336,10 @@ int bvq_abs_affine_bwd(int dtype, const void* x, const float* a, const float* b,
  * flat tensor / along dim 1 of the [C, -1] view, as used by AbsPercentile, NegativePercentileOrZero and
  * PercentileInterval (B/core/stats/stats_op.py:41-126).  Exact selection (MSD radix select); NaNs order last.
  * Streaming reads of x: channels == 1 (>= 4M elements, 16-byte aligned): 1 for |x| of a 16-bit type, else 2;
- * otherwise 2 for 16-bit types, 3 for float32.  out: dtype of x, `channels` elements. */
+ * otherwise 2 for 16-bit types, 3 for float32.  out: dtype of x, `channels` elements.
+ * bvq_kth_workspace_bytes: the workspace of every select entry below for this problem, to the byte (-1: bad argument).
+ * The workspace starts on a 16-byte boundary: the byte offsets these entries publish are those of an aligned base, and
+ * any other is refused with BVQ_ERR_INVALID before anything is launched. */
 int64_t bvq_kth_workspace_bytes(int dtype, int64_t outer, int64_t channels, int64_t inner);
 int bvq_kth_value(int abs_key, int dtype, const void* x, int64_t outer, int64_t channels, int64_t inner,
                   int64_t k, void* out, void* workspace, int64_t workspace_bytes, bvq_stream_t stream);
@@ -366,7 +371,8 @@ int bvq_kth_pair(int abs_key, int dtype, const void* x, int64_t outer, int64_t c
  *   BVQ_KTH_LOW : k = ceil (.01 * q * n)         NegativePercentileOrZero, PercentileInterval's lower end
  * (B/core/stats/stats_op.py:56,84,114-116), clamped to [1, n] (torch.kthvalue raises for k = 0; callers
  * that need that error check q * n on the host).  Pass the same rule and q to bvq_kth_begin and to every
- * bvq_kth_pick.  The workspace (bvq_kth_workspace_bytes) depends on dtype and channels only.  Counters
+ * bvq_kth_pick.  The workspace (bvq_kth_workspace_bytes, with the shard's shape: a channel-last layout keeps a
+ * transposed copy there) starts on a 16-byte boundary; the counter offsets depend on dtype and channels only.  Counters
  * are 32-bit: fewer than 2^32 elements per channel over all shards -- bvq_kth_value / bvq_kth_pair /
  * bvq_kth_hist return BVQ_ERR_UNSUPPORTED for a call that alone exceeds it; the caller of the sharded
  * protocol checks (elements per channel on a shard) x (shards) before starting. */
@@ -433,7 +439,8 @@ int bvq_stat_bwd(int match, int dtype, const void* x, const void* stat, const vo
 
 /* The two halves of bvq_stat_bwd, for callers that put work between them (batch-sharded tensors:
  * the ranks agree on which shard owns each channel's first maximum before anything is deposited).
- * tie_info: device buffer of bvq_tie_info_bytes(channels) bytes, int64 words:
+ * tie_info: device buffer of bvq_tie_info_bytes(channels) bytes (the words below, measured; -1 for channels < 1),
+ * int64 words:
  *   channels > 1 : word c = smallest (outer*inner + i) position attaining stat[c], or -1 if none;
  *                  setting a word to -1 suppresses that channel's deposit;
  *   channels == 1: word 0 = number of ties found, words 2.. = flat indices of (up to 1024 of) them.

@@ -1,6 +1,6 @@
-"""Every backward entry that carves a workspace runs in a buffer of exactly the queried size, on each of its routes:
-the same bits as with a generous buffer, nothing written outside the slice, and a buffer one byte short of the
-measured layout refused before any launch (Workspaces)."""
+"""Every backward, statistic and select entry that carves a workspace runs in a buffer of exactly the queried size, on
+each of its routes: the same bits as with a generous buffer, nothing written outside the slice, and a buffer one byte
+short of the measured layout refused before any launch (Workspaces)."""
 import ctypes
 import os
 import re
@@ -37,7 +37,8 @@ def tensors(shape, dtype, misaligned):
     x = (torch.randn(n + 8, generator=gen) * 3).to(dtype).to(DEV)[int(misaligned):int(misaligned) + n]
     g = torch.randn(n, generator=gen).to(dtype).to(DEV)
     xv = x.view(outer, ch, inner)
-    xv[:, 1, :] = 0.0
+    if ch > 1:
+        xv[:, 1, :] = 0.0
     xv[outer - 1, 0, inner - 1] = 40.0
     assert (x.data_ptr() % 16 != 0) == misaligned
     return x, g
@@ -51,12 +52,13 @@ def desc(nat, shape, dtype, **kw):
                          f['zp_per_channel'], -128.0, 127.0, 0, 0, 0, nat.OUT_DEQUANT, 0)
 
 
-def run_both(nat, wsb, call, short_is_refused=False):
-    """call(ws_ptr, ws_bytes) -> (rc, outputs) with a 1 MiB workspace and with a guarded slice of exactly wsb bytes:
-    the same bits, both guards intact; optionally the refusal of wsb - slack - 1 bytes"""
-    assert wsb > 0
-    big = torch.zeros(BIG, dtype=torch.uint8, device=DEV)
-    rc, want = call(big.data_ptr(), BIG)
+def run_both(nat, wsb, call, short_is_refused=False, short=None, big_bytes=BIG):
+    """call(ws_ptr, ws_bytes) -> (rc, outputs) with a 1 MiB workspace (big_bytes: a query above that) and with a guarded
+    slice of exactly wsb bytes: the same bits, both guards intact; optionally the refusal of wsb - slack - 1 bytes
+    (short: of that many instead -- a query without slack, or a layout that is not the query's largest)"""
+    assert 0 < wsb <= big_bytes
+    big = torch.zeros(big_bytes, dtype=torch.uint8, device=DEV)
+    rc, want = call(big.data_ptr(), big_bytes)
     assert rc == 0, nat.last_error()
     buf = torch.full((GUARD + wsb + GUARD,), FILL, dtype=torch.uint8, device=DEV)
     rc, got = call(buf.data_ptr() + GUARD, wsb)
@@ -66,8 +68,9 @@ def run_both(nat, wsb, call, short_is_refused=False):
     for i, (a, b) in enumerate(zip(got, want)):
         assert torch.equal(bits(a), bits(b)), 'output %d differs' % i
     assert bool((buf[:GUARD] == FILL).all()) and bool((buf[GUARD + wsb:] == FILL).all())
-    if short_is_refused:
-        rc, _ = call(buf.data_ptr() + GUARD, wsb - slack() - 1)  # (refused by the entry's size check: nothing launches)
+    if short_is_refused or short is not None:
+        # (refused by the entry's size check: nothing launches)
+        rc, _ = call(buf.data_ptr() + GUARD, wsb - slack() - 1 if short is None else short)
         assert rc == ERR_WORKSPACE, (rc, nat.last_error())
 
 
@@ -277,3 +280,176 @@ def test_weight_quant_list_bwd(n_items):
     run_both(nat, wsb, call, short_is_refused=True)  # (one route: every item at full width)
     torch.cuda.synchronize()
     assert int(arrive.count_nonzero()) == 0
+
+
+# ---- the statistic entries ------------------------------------------------------------------------------------------
+def const(name):
+    """an integer constant of the library's sources"""
+    for f in ('bvq_common.hip', 'bvq_stats.hip'):
+        m = re.search(r'(?:#define|constexpr int64_t) %s(?: =)? (\d+)' % name,
+                      open(os.path.join(ROOT, 'brevitas_amd', 'csrc', f)).read())
+        if m:
+            return int(m.group(1))
+    raise KeyError(name)
+
+
+def over_one_finish_slice():
+    """The smallest 16-byte aligned row length of a 16-bit type that a full-width tiling cuts into more than
+    kFinishSlice pieces: pieces are BVQ_PIECE_CHUNKS 16-byte chunks per lane of a 64-lane wave -- 8 * 64 * 8 = 4096
+    elements -- so kFinishSlice = 4096 of them and one more chunk, 16777224 elements (32 MiB).  As the rows of (1, 2, N)
+    that is 4097 partials per channel, a two-stage finish; as the one row of (1, 1, N) 4097 short units, which the
+    whole-tensor abs-max replaces by long ones."""
+    return const('kFinishSlice') * const('BVQ_PIECE_CHUNKS') * 64 * 8 + 8
+
+
+def stat_call(nat, entry, kind, shape, x, out_dtype):
+    """(workspace query, call) of one statistic entry on x[shape]"""
+    outer, ch, inner = shape
+    code, ocode = nat.dtype_code(x.dtype), nat.dtype_code(out_dtype)
+    st = nat.stream_ptr(torch.device(DEV))
+    P = nat.ptr
+    wsb = int(nat.lib.bvq_stats_workspace_bytes(kind, code, *shape))
+    running0 = torch.full((ch,), 0.5, dtype=torch.float32, device=DEV)
+
+    def call(ws, n):
+        out = torch.empty(ch * (2 if kind == nat.STAT_MINMAX else 1), dtype=out_dtype, device=DEV)
+        if entry == 'stats':
+            return nat.lib.bvq_stats(kind, code, P(x), outer, ch, inner, ocode, P(out), ws, n, st), [out]
+        if entry == 'stats_pre':
+            return nat.lib.bvq_stats_pre(kind, nat.PRE_SIGMOID, code, P(x), outer, ch, inner, ocode, P(out), ws, n,
+                                         st), [out]
+        scale = torch.empty(ch, dtype=torch.float32, device=DEV)
+        if entry == 'absmax_scale':
+            rc = nat.lib.bvq_absmax_scale(nat.PRE_NONE, code, P(x), outer, ch, inner, P(out), 1e-10, 1, 128.0, nat.F32,
+                                          P(scale), ws, n, st)
+            return rc, [out, scale]
+        running = running0.clone()
+        rc = nat.lib.bvq_absmax_scale_running(nat.PRE_NONE, code, P(x), outer, ch, inner, P(out), 1e-10, 1, 128.0,
+                                              nat.F32, P(scale), nat.F32, P(running), 0.1, 0, ws, n, st)
+        return rc, [out, scale, running]
+
+    return wsb, call
+
+
+@pytest.mark.parametrize('route', ROUTES, ids=ROUTE_IDS)
+@pytest.mark.parametrize('out_f32', [False, True], ids=['out-x-dtype', 'out-f32'])
+@pytest.mark.parametrize('kind', ['absmax', 'minmax'])
+def test_stats_exact_workspace(kind, out_f32, route):
+    """On each of these shapes the route taken has the query's largest layout -- the row-mapped units are as many at
+    both widths, and no fewer bytes than the tie words; the column-mapped partial rows are more -- so one byte short of
+    the query less the slack is refused."""
+    from brevitas_amd import _native as nat
+    shape, mis = route
+    x, _ = tensors(shape, torch.bfloat16, mis)
+    k = nat.STAT_MINMAX if kind == 'minmax' else nat.STAT_ABSMAX
+    wsb, call = stat_call(nat, 'stats', k, shape, x, torch.float32 if out_f32 else x.dtype)
+    run_both(nat, wsb, call, short_is_refused=True)
+
+
+@pytest.mark.parametrize('entry,shape', [('stats_pre', ROW_FULL), ('absmax_scale', ROW_FULL), ('absmax_scale', COLS_B),
+                                         ('absmax_scale_running', ROW_FULL), ('absmax_scale_running', COLS_B)])
+def test_stats_entries_exact_workspace(entry, shape):
+    from brevitas_amd import _native as nat
+    x, _ = tensors(shape, torch.bfloat16, False)
+    wsb, call = stat_call(nat, entry, nat.STAT_ABSMAX, shape, x, x.dtype)
+    run_both(nat, wsb, call)
+
+
+@pytest.mark.parametrize('channels', [2, 1], ids=['two-stage-finish', 'long-units'])
+def test_stats_exact_workspace_past_one_finish_slice(channels):
+    from brevitas_amd import _native as nat
+    shape = (1, channels, over_one_finish_slice())
+    x, _ = tensors(shape, torch.bfloat16, False)
+    wsb, call = stat_call(nat, 'stats', nat.STAT_ABSMAX, shape, x, x.dtype)
+    run_both(nat, wsb, call)
+
+
+@pytest.mark.parametrize('per_channel', [True, False], ids=['per-channel', 'one-channel-tie'])
+def test_stat_bwd_exact_workspace(per_channel):
+    """the tie words are all bvq_stat_bwd carves: one byte short of them is refused"""
+    from brevitas_amd import _native as nat
+    outer, ch, inner = ROW_FULL
+    x, g = tensors(ROW_FULL, torch.bfloat16, False)
+    if not per_channel:
+        x[7] = -40.0  # (a second element attaining the whole tensor's maximum of |x|)
+        outer, ch, inner = 1, 1, x.numel()
+    code = nat.dtype_code(x.dtype)
+    stat = nat.stats(nat.STAT_ABSMAX, x, outer, ch, inner)
+    gstat = g[:ch].contiguous()
+    st = nat.stream_ptr(torch.device(DEV))
+    P = nat.ptr
+
+    def call(ws, n):
+        dx = torch.empty_like(x)
+        rc = nat.lib.bvq_stat_bwd(0, code, P(x), P(stat), P(gstat), P(dx), outer, ch, inner, 0, ws, n, st)
+        return rc, [dx]
+
+    wsb = int(nat.lib.bvq_stats_workspace_bytes(nat.STAT_ABSMAX, code, outer, ch, inner))
+    run_both(nat, wsb, call, short=int(nat.lib.bvq_tie_info_bytes(ch)) - 1)
+
+
+# ---- the select entries: their queries carry no slack -------------------------------------------------------------
+WIDE = (1, 1, 1 << 22)
+
+
+def select_case(nat, shape, dtype):
+    outer, ch, inner = shape
+    x, _ = tensors(shape, dtype, False)
+    code = nat.dtype_code(dtype)
+    wsb = int(nat.lib.bvq_kth_workspace_bytes(code, *shape))
+    n = outer * inner
+    return x, code, wsb, (max(1, n // 3), n)
+
+
+@pytest.mark.parametrize('entry', ['value', 'pair'])
+@pytest.mark.parametrize('shape,dtype,short', [(ROW_FULL, torch.bfloat16, False), (COLS_B, torch.bfloat16, True),
+                                               (WIDE, torch.float32, True)],
+                         ids=['row-mapped', 'channel-last-copy', 'wide'])
+def test_select_exact_workspace(shape, dtype, short, entry):
+    from brevitas_amd import _native as nat
+    outer, ch, inner = shape
+    x, code, wsb, (k1, k2) = select_case(nat, shape, dtype)
+    st = nat.stream_ptr(torch.device(DEV))
+    P = nat.ptr
+
+    def call(ws, n):
+        out = torch.empty((1 if entry == 'value' else 2) * ch, dtype=dtype, device=DEV)
+        if entry == 'value':
+            return nat.lib.bvq_kth_value(1, code, P(x), outer, ch, inner, k1, P(out), ws, n, st), [out]
+        return nat.lib.bvq_kth_pair(1, code, P(x), outer, ch, inner, k1, k2, P(out), ws, n, st), [out]
+
+    run_both(nat, wsb, call, short=wsb - 1 if short else None, big_bytes=max(BIG, 2 * wsb))
+
+
+@pytest.mark.parametrize('wide', [False, True], ids=['kth-steps', 'kthw-steps'])
+def test_select_steps_exact_workspace(wide):
+    """the steps in order, in the exact buffer: the one-shot entry's bits"""
+    from brevitas_amd import _native as nat
+    shape = (1, 1, 1 << 16) if wide else ROW_FULL
+    outer, ch, inner = shape
+    dtype = torch.float32
+    x, code, wsb, (k, _) = select_case(nat, shape, dtype)
+    st = nat.stream_ptr(torch.device(DEV))
+    P, lib = nat.ptr, nat.lib
+    passes = lib.bvq_kthw_plan(0, code, -1, None, None) if wide else lib.bvq_kth_passes(code)
+
+    def call(ws, n):
+        out = torch.empty(ch, dtype=dtype, device=DEV)
+        rc = lib.bvq_kthw_begin(0, code, ws, n, st) if wide else lib.bvq_kth_begin(code, ch, nat.KTH_EXPLICIT, k, 0.0, ws,
+                                                                                    n, st)
+        for p in range(passes):
+            if wide:
+                rc = rc or lib.bvq_kthw_hist(0, code, P(x), x.numel(), p, ws, n, st)
+                rc = rc or lib.bvq_kthw_pick(0, code, p, nat.KTH_EXPLICIT, k, 0.0, ws, n, st)
+            else:
+                rc = rc or lib.bvq_kth_hist(0, code, P(x), outer, ch, inner, p, ws, n, st)
+                rc = rc or lib.bvq_kth_pick(code, ch, p, nat.KTH_EXPLICIT, 0.0, ws, n, st)
+        rc = rc or (lib.bvq_kthw_finish(0, code, P(out), ws, n, st) if wide else
+                    lib.bvq_kth_finish(0, code, ch, P(out), ws, n, st))
+        return rc, [out]
+
+    run_both(nat, wsb, call, big_bytes=max(BIG, 2 * wsb))
+    buf = torch.zeros(wsb, dtype=torch.uint8, device=DEV)
+    rc, (steps,) = call(buf.data_ptr(), wsb)
+    assert rc == 0, nat.last_error()
+    assert torch.equal(bits(steps), bits(nat.kth_value(x, k, outer, ch, inner, False)))

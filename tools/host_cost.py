@@ -154,6 +154,9 @@ def main():
     gf = g.reshape(-1)
     rows.append(('  nat.fakequant_bwd_stats (3 allocations + 2 ctypes calls)',
                  per_call(lambda: nat.fakequant_bwd_stats(desc, gf, flat, sc, zp, st, dt, thr_div, dt))))
+    # (a workspace query, its allocation and the entry: the statistic and the select, whatever route the step took)
+    rows.append(('  nat.absmax_scale', per_call(lambda: nat.absmax_scale(flat, outer, ch, inner, None, thr_div, dt))))
+    rows.append(('  nat.kth_value', per_call(lambda: nat.kth_value(flat, inner // 2 + 1, outer, ch, inner, True))))
     rows.append(('  torch.empty_like(w)', per_call(lambda: torch.empty_like(w))))
     rows.append(('  nat.QuantDesc(...) construction', per_call(lambda: nat.QuantDesc(
         outer, ch, inner, code, code, code, nat.F32, 1, 0, -128.0, 127.0, 0, 0, 0, nat.OUT_DEQUANT, nat.PRE_NONE))))
