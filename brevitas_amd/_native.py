@@ -39,7 +39,7 @@ MX_FLOOR, MX_CEIL = 0, 1
 LR_HARD_SIGMOID, LR_SIGMOID = 0, 1  # bvq_learned_round_impl
 NORM_L1, NORM_L2 = 0, 1  # bvq_norm_kind
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -186,6 +186,8 @@ _SIG = {
     'bvq_group_hqo_supported': (_i32, [_qd, _vp, _i32, _i32]),
     'bvq_group_hqo_fwd': (_i32, [_qd, _vp, _vp, _i32, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
     'bvq_group_hqo_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
+    'bvq_group_awq_supported': (_i32, [_qd, _vp, _vp, _vp, _i64, _i32]),
+    'bvq_group_awq_fwd': (_i32, [_qd, _vp, _vp, _i64, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp]),
     'bvq_row_shifted_max_row_bytes': (_i64, []),
     'bvq_row_shifted_supported': (_i32, [_qd, _vp]),
     'bvq_row_shifted_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
@@ -675,6 +677,33 @@ def group_hqo_fwd(desc, x, table, lp, min_val, thr_div):
 def group_hqo_bwd(desc, g, x, stat, zp, gscale, min_val, thr_div):
     """zp is a constant: dx and the scale statistics' gradients at (scale, zp)"""
     return unit_bwd(GROUP_HQO, desc, g, x, stat, zp, gscale, min_val, thr_div)
+
+
+AWQ_MAX_CANDIDATES = 64
+
+
+def group_awq_supported(desc, x, table, y=None):
+    """the AWQ candidates kernel covers this descriptor (that of group_quant_* or of group_shifted_*), the weight x
+    [R, K] and the column factors table [n, K]; y: the output, where it exists already"""
+    if table.dim() != 2 or not (x.is_contiguous() and table.is_contiguous()) or table.dtype != x.dtype:
+        return False
+    n, k = table.shape
+    return bool(lib.bvq_group_awq_supported(ctypes.byref(desc), ptr(x), ptr(table), ptr(y), int(k), int(n)))
+
+
+def group_awq_fwd(desc, x, table, min_val, thr_div):
+    """every candidate of table [n, K] in ONE launch: scale the columns of x [R, K], group-quantize, unscale ->
+    (y [n, *x.shape], scale [n, groups], zp [n, groups] or None where the descriptor has no zero-point per group)"""
+    dev = require_device(x, table)
+    assert x.is_contiguous() and table.is_contiguous() and table.dim() == 2 and table.dtype == x.dtype
+    n, k = table.shape
+    groups = int(desc.channels)
+    y = torch.empty((n,) + tuple(x.shape), dtype=x.dtype, device=dev)
+    scale = torch.empty(n, groups, dtype=x.dtype, device=dev)
+    zp = torch.empty(n, groups, dtype=x.dtype, device=dev) if desc.zp_per_channel else None
+    _launch(dev, 'bvq_group_awq_fwd', 'bvq_group_awq_fwd', ctypes.byref(desc), ptr(x), ptr(table), int(k), int(n),
+            *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(zp))
+    return y, scale, zp
 
 
 def row_shifted_max_row_bytes():

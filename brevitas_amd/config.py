@@ -26,3 +26,6 @@ CPP_AUTOGRAD = _env_flag('BREVITAS_AMD_CPP_AUTOGRAD', True)
 # the batch-sharded form of the activation node, which issues its two collectives through c10d from C++; 0: sharded
 # quantizers take the Python Function (bench.py switches it off for the run if its start-up probe of the node fails)
 CPP_AUTOGRAD_SHARDED = _env_flag('BREVITAS_AMD_CPP_SHARDED', True)
+# graph/awq.py: the bytes of candidate weights that one step of an AWQ search holds at a time (a tuning constant, no
+# environment knob): as many candidates per launch as fit, at least one; no result depends on it
+AWQ_CANDIDATE_BYTES = 1 << 30

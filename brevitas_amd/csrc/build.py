@@ -30,6 +30,7 @@ SOURCES = [('bvq_common.hip', [], 'bvq_common.o'), ('bvq_elementwise.hip', [], '
            ('bvq_weight_list.hip', [], 'bvq_weight_list.o'),
            ('bvq_group_quant.hip', [], 'bvq_group_quant.o'), ('bvq_group_mse.hip', [], 'bvq_group_mse.o'),
            ('bvq_group_shifted.hip', [], 'bvq_group_shifted.o'), ('bvq_group_hqo.hip', [], 'bvq_group_hqo.o'),
+           ('bvq_group_awq.hip', [], 'bvq_group_awq.o'),
            ('bvq_mx_quant.hip', [], 'bvq_mx_quant.o'),
            ('bvq_gptq.hip', [], 'bvq_gptq.o'), ('bvq_learned_round.hip', [], 'bvq_learned_round.o'),
            ('bvq_row_shifted.hip', [], 'bvq_row_shifted.o'), ('bvq_weight_norm.hip', [], 'bvq_weight_norm.o')]

@@ -63,37 +63,38 @@ class _Plan(NamedTuple):
     qmax: float
 
 
-def _plan(quantizer, k: int, static_groups: bool) -> _Plan:
-    """what the loop needs to know of `quantizer`, or the TypeError naming what is refused"""
+def _plan(quantizer, k: int, static_groups: bool, who: str = 'gptq') -> _Plan:
+    """what the loop needs to know of `quantizer`, or the TypeError naming what is refused; who: the caller the error
+    speaks for (graph/awq.py plans its composed route with this one)"""
     name = type(quantizer).__name__
     if isinstance(quantizer, GroupwiseMSEIntQuant):
-        raise TypeError('gptq: the clip-search quantizer %s is not covered (its threshold is searched on the finished '
-                        'group, which the column loop does not have)' % name)
+        raise TypeError('%s: the clip-search quantizer %s is not covered (its threshold is searched on the finished '
+                        'group, which the column loop does not have)' % (who, name))
     if isinstance(quantizer, GroupwiseHQOIntQuant):
-        raise TypeError('gptq: the zero-point-search quantizer %s is not covered (its zero-point is searched on the '
-                        'finished group, which the column loop does not have)' % name)
+        raise TypeError('%s: the zero-point-search quantizer %s is not covered (its zero-point is searched on the '
+                        'finished group, which the column loop does not have)' % (who, name))
     if type(quantizer) not in (RescalingIntQuant, GroupwiseRescalingIntQuant):
-        raise TypeError('gptq: the quantizer %s is not covered (integer weight quantizers per tensor, per channel or '
-                        'per group only)' % name)
+        raise TypeError('%s: the quantizer %s is not covered (integer weight quantizers per tensor, per channel or '
+                        'per group only)' % (who, name))
     iq, zpi = quantizer.int_quant, quantizer.zero_point_impl
     bw = quantizer.msb_clamp_bit_width_impl()
     host_bw = getattr(bw, 'bvq_host_value', None)
     if host_bw is None:
-        raise TypeError('gptq: %s with a learned bit width is not covered' % name)
+        raise TypeError('%s: %s with a learned bit width is not covered' % (who, name))
     if type(iq) is not IntQuant or round_mode_of(iq.float_to_int_impl) != nat.ROUND:
-        raise TypeError('gptq: %s with the integer quantizer %s is not covered (IntQuant with half-even rounding only)'
-                        % (name, type(iq).__name__))
+        raise TypeError('%s: %s with the integer quantizer %s is not covered (IntQuant with half-even rounding only)'
+                        % (who, name, type(iq).__name__))
     if type(zpi) not in (ZeroZeroPoint, StatsFromParameterZeroPoint):
-        raise TypeError('gptq: %s with the zero-point %s is not covered' % (name, type(zpi).__name__))
+        raise TypeError('%s: %s with the zero-point %s is not covered' % (who, name, type(zpi).__name__))
     shifted = type(zpi) is StatsFromParameterZeroPoint
     grouped = isinstance(quantizer, GroupwiseRescalingIntQuant)
     if grouped and not static_groups and type(quantizer.scaling_impl) is not StatsFromParameterScaling:
-        raise TypeError('gptq: %s with the scaling %s is not covered where the scales are computed in the loop (a '
+        raise TypeError('%s: %s with the scaling %s is not covered where the scales are computed in the loop (a '
                         'statistic of the group only; static_groups=True takes the quantizer\'s own scales)'
-                        % (name, type(quantizer.scaling_impl).__name__))
+                        % (who, name, type(quantizer.scaling_impl).__name__))
     group = quantizer.group_size if grouped else k
     if k % group:
-        raise ValueError('gptq: %d input columns are no whole groups of %d' % (k, group))
+        raise ValueError('%s: %d input columns are no whole groups of %d' % (who, k, group))
     qmin, qmax = int_range_host(iq.signed, iq.narrow_range, host_bw)
     return _Plan(quantizer, group, grouped and not static_groups, shifted, bw, qmin, qmax)
 
@@ -334,18 +335,38 @@ class gptq_mode:
     def num_layers(self) -> int:
         return len(self.layers)
 
+    # What a mode with the same protocol (graph/awq.py) states for itself: _admit, _reset, _accumulate, _quantize and
+    # _freeze.
+    def _admit(self, name: str, m) -> None:
+        """the refusal of a layer that has a weight quantizer and is not frozen, or nothing"""
+        from brevitas_amd.nn import QuantConv2d, QuantLinear
+        if not isinstance(m, (QuantLinear, QuantConv2d)) or (isinstance(m, QuantConv2d) and m.groups != 1):
+            raise NotImplementedError('gptq_mode: layer %r (%s%s) is not covered: QuantLinear, and QuantConv2d with '
+                                      'groups == 1' % (name, type(m).__name__,
+                                                       ', groups=%d' % m.groups if hasattr(m, 'groups') else ''))
+        _plan(m.weight_quant, m.weight.numel() // m.weight.shape[0], self.static_groups)
+
+    def _reset(self) -> None:
+        """nothing collected for the current layer yet"""
+        self._h, self._n = None, 0
+
+    def _accumulate(self, rows: Tensor) -> None:
+        """one batch of float32 input rows [n, K] of the current layer"""
+        n = rows.shape[0]
+        if self._h is None:
+            self._h = torch.zeros(rows.shape[1], rows.shape[1], dtype=torch.float32, device=rows.device)
+        total = self._n + n
+        self._h = self._h * (self._n / total) + (2.0 / total) * torch.matmul(rows.t(), rows)
+        self._n = total
+
     def __enter__(self):
-        from brevitas_amd.nn import QuantConv2d, QuantLinear, _QuantWeightMixin
+        from brevitas_amd.nn import _QuantWeightMixin
         self.layers = []
         for name, m in self._model.named_modules():
             if not isinstance(m, _QuantWeightMixin) or m.weight_quant is None or \
                     getattr(m, 'frozen_weight_scale', None) is not None:
                 continue
-            if not isinstance(m, (QuantLinear, QuantConv2d)) or (isinstance(m, QuantConv2d) and m.groups != 1):
-                raise NotImplementedError('gptq_mode: layer %r (%s%s) is not covered: QuantLinear, and QuantConv2d with '
-                                          'groups == 1' % (name, type(m).__name__,
-                                                           ', groups=%d' % m.groups if hasattr(m, 'groups') else ''))
-            _plan(m.weight_quant, m.weight.numel() // m.weight.shape[0], self.static_groups)  # refusals, before any work
+            self._admit(name, m)  # refusals, before any work
             self.layers.append((name, m))
         self.current = 0
         self._arm()
@@ -357,7 +378,7 @@ class gptq_mode:
 
     # the current layer's forward is replaced by one that accumulates H and stops
     def _arm(self):
-        self._h, self._n = None, 0
+        self._reset()
         if self.current < len(self.layers):
             self.layers[self.current][1].forward = self._capture
 
@@ -377,13 +398,7 @@ class gptq_mode:
                 rows = cols.transpose(1, 2).reshape(-1, cols.shape[1])
             else:
                 rows = x.reshape(-1, x.shape[-1])
-            rows = rows.float()
-            n = rows.shape[0]
-            if self._h is None:
-                self._h = torch.zeros(rows.shape[1], rows.shape[1], dtype=torch.float32, device=rows.device)
-            total = self._n + n
-            self._h = self._h * (self._n / total) + (2.0 / total) * torch.matmul(rows.t(), rows)
-            self._n = total
+            self._accumulate(rows.float())
         raise _StopForward()
 
     def model(self, *args, **kwargs):
@@ -395,16 +410,24 @@ class gptq_mode:
 
     def update(self):
         """quantize the current layer from the Hessian collected so far, freeze it, move to the next"""
+        who = type(self).__name__
         if self.current >= len(self.layers):
-            raise RuntimeError('gptq_mode.update: every layer has been quantized already')
+            raise RuntimeError('%s.update: every layer has been quantized already' % who)
         name, layer = self.layers[self.current]
         if self._h is None:
-            raise RuntimeError('gptq_mode.update: layer %r has seen no calibration batch' % name)
-        res = gptq_quantize_weight(layer.weight, self._h.to(layer.weight.device), layer.weight_quant,
-                                   percdamp=self.percdamp, static_groups=self.static_groups, name=name)
+            raise RuntimeError('%s.update: layer %r has seen no calibration batch' % (who, name))
+        res = self._quantize(name, layer)
         self._disarm()
         layer.weight.data.copy_(res.q)
-        freeze_weight_quant(layer, res.scale, res.zero_point)
+        self._freeze(layer, res)
         self.current += 1
         self._arm()
         return res
+
+    def _quantize(self, name: str, layer):
+        """the current layer's result from what was collected: q, scale and zero_point at least"""
+        return gptq_quantize_weight(layer.weight, self._h.to(layer.weight.device), layer.weight_quant,
+                                    percdamp=self.percdamp, static_groups=self.static_groups, name=name)
+
+    def _freeze(self, layer, res) -> None:
+        freeze_weight_quant(layer, res.scale, res.zero_point)

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 9
+#define BVQ_ABI_VERSION 10
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -811,6 +811,31 @@ int bvq_group_hqo_fwd(const bvq_quant_desc* desc, const void* x, const float* in
                       bvq_stream_t stream);
 int bvq_group_hqo_bwd(const bvq_quant_desc* desc, const void* g, const void* x, const void* stat, const void* zp,
                       const void* gscale, double min_val, int use_min, double thr_div, void* dx, bvq_stream_t stream);
+
+/* ---- AWQ: the candidates of an activation-aware column-factor search over a group-wise weight ---------------------------
+ * AWQ (Lin et al. 2023; no reference counterpart) multiplies every input column of a linear weight by a factor before the
+ * group-wise quantizer and divides it out behind it.  x is the weight [R, K] of dtype T, contiguous; the descriptor is
+ * that of the group-wise section (symmetric: zp_per_channel = 0) or of the asymmetric one (zp_per_channel = 1, zp_dtype =
+ * T) with channels = R * K / g groups; table: [n, K] column factors of dtype T on the DEVICE, row i those of candidate i;
+ * 1 <= n <= 64; k = K, a multiple of the group size g.  min_val / use_min / thr_div as in the group-wise section.
+ * Candidate i, every operation rounding to T, col = flat index mod K:
+ *     xs = T(x * table[i][col])
+ *     scale (and zp): the statistics -> scale (-> zero-point) chain of bvq_group_quant_fwd (bvq_group_shifted_fwd) on each
+ *         group of xs
+ *     yq = the forward chain of that entry on xs at (scale, zp), rounding points unchanged
+ *     y_i = T(yq / table[i][col])                      the correctly rounded float32 quotient, then rounded to T
+ *   y: [n, R, K]; scale: [n, groups]; zp: [n, groups], asymmetric only (null otherwise), all in T.  n * R * K * sizeof(T)
+ *   may exceed 4 GiB.  There is no backward: AWQ is applied after training and the layer is frozen afterwards.
+ * With n = 1 and factors of one, y, scale and zp have the bits of bvq_group_quant_fwd / bvq_group_shifted_fwd.
+ * One launch: x is read once and kept in registers, the factors come from cache, one y is written per candidate; no LDS,
+ * no workspace, no atomics.  Covered: what the group-wise entries cover; x, table and y on 16-byte boundaries; K a multiple
+ * of g with K * sizeof(T) < 2^31; n as above.  Anything else returns BVQ_ERR_UNSUPPORTED with a bvq_last_error() text,
+ * found before anything touches the device; bvq_group_awq_supported answers 1 / 0 (y may be null there: not yet
+ * allocated). */
+int bvq_group_awq_supported(const bvq_quant_desc* desc, const void* x, const void* table, const void* y, int64_t k,
+                            int n);
+int bvq_group_awq_fwd(const bvq_quant_desc* desc, const void* x, const void* table, int64_t k, int n, double min_val,
+                      int use_min, double thr_div, void* y, void* scale, void* zp, bvq_stream_t stream);
 
 /* ---- asymmetric per-row activations: one scale and one integer zero-point per row, from the row itself ----------------
  * The per-token quantizer of the dynamic activation quantizers (ShiftedUint8DynamicActPerRowFloat).  x is [rows, H],
