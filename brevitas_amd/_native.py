@@ -39,7 +39,7 @@ MX_FLOOR, MX_CEIL = 0, 1
 LR_HARD_SIGMOID, LR_SIGMOID = 0, 1  # bvq_learned_round_impl
 NORM_L1, NORM_L2 = 0, 1  # bvq_norm_kind
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -197,6 +197,8 @@ _SIG = {
     'bvq_weight_norm_bwd': (_i32, [_qd, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'bvq_gptq_block_supported': (_i32, [_qd, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     'bvq_gptq_block': (_i32, [_qd, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    'bvq_gpfq_block_supported': (_i32, [_qd, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    'bvq_gpfq_block': (_i32, [_qd, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     'bvq_learned_round_supported': (_i32, [_qd, _vp, _vp, _vp]),
     'bvq_learned_round_fwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _i32, _vp, _vp]),
     'bvq_learned_round_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp]),
@@ -775,6 +777,29 @@ def gptq_block(desc, wf, u, col0, block_cols, computed, min_val, thr_div, q, sca
     err = torch.empty(rows, block_cols, dtype=torch.float32, device=dev)
     _launch(dev, 'bvq_gptq_block', 'bvq_gptq_block', ctypes.byref(desc), ptr(wf), ptr(u), rows, cols, int(col0),
             int(block_cols), int(computed), *_scale_args(min_val, thr_div), ptr(q), ptr(err), ptr(scale), ptr(zp))
+    return err
+
+
+def gpfq_block_supported(desc, wf, c, h, q, col0, block_cols):
+    """the GPFQ column-loop kernel covers this descriptor (that of gptq_block with given parameters), block and
+    tensors"""
+    rows, cols = wf.shape
+    return bool(lib.bvq_gpfq_block_supported(ctypes.byref(desc), rows, cols, int(col0), int(block_cols), ptr(wf),
+                                             ptr(c), ptr(h), ptr(q)))
+
+
+def gpfq_block(desc, wf, c, h, col0, block_cols, q, scale, zp):
+    """the GPFQ column loop of the block [col0, col0 + block_cols) in ONE launch (include/bvq.h, "GPFQ"): reads wf and c
+    (float32 [rows, cols]), h (float32 [cols, cols]) and scale / zp ([rows, cols / group size]; zp None for a symmetric
+    quantizer), writes the block's columns of q (like wf, in the quantizer's dtype) -> err float32 [rows, block_cols]"""
+    dev = require_device(wf, c, h, q, scale, zp)
+    assert wf.dtype == c.dtype == h.dtype == torch.float32 and wf.is_contiguous() and c.is_contiguous()
+    assert h.is_contiguous() and c.shape == wf.shape and h.shape == (wf.shape[1], wf.shape[1])
+    assert q.is_contiguous() and q.shape == wf.shape and scale.is_contiguous() and (zp is None or zp.is_contiguous())
+    rows, cols = wf.shape
+    err = torch.empty(rows, block_cols, dtype=torch.float32, device=dev)
+    _launch(dev, 'bvq_gpfq_block', 'bvq_gpfq_block', ctypes.byref(desc), ptr(wf), ptr(c), ptr(h), rows, cols, int(col0),
+            int(block_cols), ptr(q), ptr(err), ptr(scale), ptr(zp))
     return err
 
 

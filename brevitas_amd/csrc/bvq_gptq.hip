@@ -10,11 +10,9 @@
 // (bvq_group_quant.h, bvq_group_shifted.h) and their forward chain for the code.  No LDS, no atomics, no workspace.
 //   reads   the block's columns of Wf, the [B, B] triangle of U (+ scale / zero-point where they are given)
 //   writes  the block's columns of Q, E [R, B] float32 (+ the block's scale / zero-point where they are computed)
-#include "bvq_group_shifted.h"
+#include "bvq_column_loop.h"  // the block width, read_lane and the host-side check, shared with bvq_gpfq.hip
 
 namespace bvq {
-
-constexpr int kGptqBlock = 128;  // columns of a block: two per lane
 
 // GroupArgs: x = Wf (float32 [rows, cols]), y = Q (T [rows, cols]), scale = [rows, cols / gsize] of T
 struct GptqArgs : GroupArgs {
@@ -24,10 +22,6 @@ struct GptqArgs : GroupArgs {
   int64_t rows, cols, col0;
   int32_t bc, gsize;
 };
-
-__device__ __forceinline__ float read_lane(float v, int lane) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
 
 // one element as a whole chunk of itself: the chunk statistics of the group walk then give the element's own key
 template <typename T>
@@ -183,64 +177,13 @@ __global__ __launch_bounds__(kBlock) void gptq_block_kernel(GptqArgs a) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------------
-// what the kernel covers apart from the pointers: BVQ_OK, or the error with its text
-static int gptq_check(const bvq_quant_desc* d, const char* what, int64_t rows, int64_t cols, int64_t col0,
-                      int block_cols, int computed) {
-  int rc = validate(d);
-  if (rc) return rc;
-  if (d->outer != 1 || d->channels < 1 || d->inner < 1 || !d->scale_per_channel) {
-    set_error("%s: the descriptor of a grouped tensor is outer 1, channels = groups, inner = group size, one scale per "
-              "channel", what);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (d->round_mode != BVQ_ROUND || d->pre_op != BVQ_PRE_NONE || d->out_kind != BVQ_OUT_DEQUANT) {
-    set_error("%s: half-even rounding, no pre_op and dequantized output only (round_mode=%d pre_op=%d out_kind=%d)", what,
-              d->round_mode, d->pre_op, d->out_kind);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (d->x_dtype != d->ct_dtype || d->scale_dtype != d->x_dtype || (d->zp_per_channel && d->zp_dtype != d->x_dtype)) {
-    set_error("%s: x, compute, scale and zero-point dtype must agree (x=%d ct=%d scale=%d zp=%d)", what, d->x_dtype,
-              d->ct_dtype, d->scale_dtype, d->zp_dtype);
-    return BVQ_ERR_UNSUPPORTED;
-  }
-  if (rows < 1 || cols < 1 || cols % d->inner != 0 || rows * (cols / d->inner) != d->channels) {
-    set_error("%s: rows %lld x cols %lld is not %lld groups of %lld", what, (long long)rows, (long long)cols,
-              (long long)d->channels, (long long)d->inner);
-    return BVQ_ERR_INVALID;
-  }
-  if (block_cols < 1 || block_cols > kGptqBlock) {
-    set_error("%s: block_cols %d (1 .. %d)", what, block_cols, kGptqBlock);
-    return BVQ_ERR_INVALID;
-  }
-  if (col0 < 0 || col0 + block_cols > cols) {
-    set_error("%s: columns %lld .. %lld of %lld", what, (long long)col0, (long long)(col0 + block_cols), (long long)cols);
-    return BVQ_ERR_INVALID;
-  }
-  if (computed) {
-    if (d->inner != 16 && d->inner != 32 && d->inner != 64 && d->inner != 128) {
-      set_error("%s: group size %lld (16, 32, 64 or 128 where scale and zero-point are computed in the loop)", what,
-                (long long)d->inner);
-      return BVQ_ERR_UNSUPPORTED;
-    }
-    if (col0 % d->inner != 0 || block_cols % d->inner != 0) {
-      set_error("%s: col0 %lld and block_cols %d must be multiples of the group size %lld", what, (long long)col0,
-                block_cols, (long long)d->inner);
-      return BVQ_ERR_INVALID;
-    }
-  }
-  return BVQ_OK;
-}
-
 }  // namespace bvq
 
 using namespace bvq;
 
 extern "C" int bvq_gptq_block_supported(const bvq_quant_desc* d, int64_t rows, int64_t cols, int64_t col0,
                                         int block_cols, int computed, const void* wf, const void* u, const void* q) {
-  if (gptq_check(d, "bvq_gptq_block_supported", rows, cols, col0, block_cols, computed)) return 0;
+  if (column_block_check(d, "bvq_gptq_block_supported", rows, cols, col0, block_cols, computed)) return 0;
   return wf && u && q && aligned16(wf) && aligned16(u) && aligned16(q) ? 1 : 0;
 }
 
@@ -248,7 +191,7 @@ extern "C" int bvq_gptq_block(const bvq_quant_desc* d, const float* wf, const fl
                               int64_t col0, int block_cols, int computed, double min_val, int use_min, double thr_div,
                               void* q, float* err, void* scale, void* zp, bvq_stream_t stream) {
   const char* what = "bvq_gptq_block";
-  int rc = gptq_check(d, what, rows, cols, col0, block_cols, computed);
+  int rc = column_block_check(d, what, rows, cols, col0, block_cols, computed);
   const bool shifted = !rc && d->zp_per_channel;
   rc = group_required(what, rc, {wf, u, q, err, scale});
   if (!rc && shifted && !zp) {

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 10
+#define BVQ_ABI_VERSION 11
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -949,6 +949,42 @@ int bvq_gptq_block_supported(const bvq_quant_desc* desc, int64_t rows, int64_t c
 int bvq_gptq_block(const bvq_quant_desc* desc, const float* wf, const float* u, int64_t rows, int64_t cols,
                    int64_t col0, int block_cols, int computed, double min_val, int use_min, double thr_div, void* q,
                    float* err, void* scale, void* zp, bvq_stream_t stream);
+
+/* ---- GPFQ: the column loop of one block of up to 128 input columns -----------------------------------------------------
+ * GPFQ (greedy path-following quantization: Lybrand & Saab 2021; Zhang, Zhou & Saab 2023; `gpfq_mode` of later Brevitas
+ * releases, no reference counterpart) picks each input column's code so that the quantized layer on the quantized
+ * path's input X~ follows the float layer on the float input X.  Definition, which the composed route of
+ * brevitas_amd/graph/gpfq.py and this kernel compute with the same bits:
+ *   W  [R, K] of dtype T (a conv weight flattened to K = in * kh * kw), Wf = float32(W), never changed,
+ *   H  [K, K] float32 = mean X~^T X~,   D [K, K] float32 = mean (X - X~)^T X~, one running-mean weighting for both,
+ *   C  [R, K] float32, the running correction, C = Wf @ triu(D) (diagonal included) as one float32 matrix product,
+ *   scale, zp of the layer's quantizer taken once from W, group size g dividing K; blocks of B = 128 columns.
+ * For each block [c0, c1), for i = c0 .. c1 - 1, for every row r:
+ *   value        v = Wf[r, i] + C[r, i] / H[i, i] where H[i, i] > 0 (IEEE division, then the sum: two roundings),
+ *                else v = Wf[r, i]: a column whose input never fired is rounded to nearest
+ *   quantize     q = the value of T that bvq_group_quant_fwd / bvq_group_shifted_fwd store for the element T(v) at the
+ *                scale, zp of (r, i / g); Q[r, i] = q
+ *   error        e = Wf[r, i] - float32(q), against the original weight, not v; E[r, i - c0] = e
+ *   update       for j = i + 1 .. c1 - 1: C[r, j] = C[r, j] + e * H[i, j], the product rounded to float32, then the sum
+ *                rounded (no fused multiply-add)
+ * and after each block C[:, c1:] += E @ H[c0:c1, c1:] as one float32 matrix product, which is the caller's.
+ * (The textbook numerator sum_j w_j <X_j, X~_i> - sum_j q_j <X~_j, X~_i> is the same number and cancels in float32.)
+ * bvq_gpfq_block runs that loop for ONE block in one launch: one wave per row, the block's columns of wf and c in
+ * registers (two per lane); no workspace, no atomics.  It reads the block's columns of wf and c ([rows, cols] float32),
+ * the [block_cols, block_cols] triangle of h ([cols, cols] float32) and scale, zp ([rows, cols / g] of T; zp required for
+ * an asymmetric quantizer, else ignored), and writes the block's columns of q ([rows, cols] of T) and err ([rows,
+ * block_cols] float32) and nothing else: c is not written.  desc: as for bvq_gptq_block with computed = 0 -- outer 1,
+ * channels = rows * cols / g, inner = g (any g dividing cols; a group may have begun before the block),
+ * scale_per_channel, x_dtype = ct_dtype = scale_dtype; zp_per_channel = 1 with zp_dtype = x_dtype for an asymmetric
+ * quantizer.
+ * Checked before anything touches the device, with a bvq_last_error() text: null pointers (BVQ_ERR_INVALID), wf, c, h, q
+ * or err off a 16-byte boundary (BVQ_ERR_UNSUPPORTED), block_cols outside 1 .. 128 and columns outside the weight
+ * (BVQ_ERR_INVALID).  bvq_gpfq_block_supported answers 1 / 0. */
+int bvq_gpfq_block_supported(const bvq_quant_desc* desc, int64_t rows, int64_t cols, int64_t col0, int block_cols,
+                             const void* wf, const void* c, const void* h, const void* q);
+int bvq_gpfq_block(const bvq_quant_desc* desc, const float* wf, const float* c, const float* h, int64_t rows,
+                   int64_t cols, int64_t col0, int block_cols, void* q, float* err, const void* scale, const void* zp,
+                   bvq_stream_t stream);
 
 /* ---- Learned rounding: IntQuant with floor(t) + h(value), one trainable offset per element ------------------------------
  * AdaRound (Nagel et al. 2020; LearnedRoundSte of later Brevitas releases, no reference counterpart): the weights are
