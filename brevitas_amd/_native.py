@@ -754,7 +754,21 @@ def weight_norm_bwd(desc, norm_kind, t_bound, norm_min, gy, x, scale, g, norm):
     return dx, dscale, dg
 
 
-GPTQ_BLOCK = 128  # columns of one bvq_gptq_block launch
+COLUMN_BLOCK = 128  # columns of one launch of a column-loop kernel (bvq_gptq_block, bvq_gpfq_block)
+
+
+def _column_block(entry, desc, wf, mats, col0, block_cols, scalars, q, scale, zp):
+    """what gptq_block and gpfq_block share: wf and `mats` (float32, contiguous; the last one [cols, cols], those before
+    it shaped like wf) go in in that order, `scalars` between the block and the outputs -> err float32 [rows, block_cols]"""
+    dev = require_device(wf, *mats, q, scale, zp)
+    rows, cols = wf.shape
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (wf, *mats))
+    assert all(t.shape == wf.shape for t in mats[:-1]) and mats[-1].shape == (cols, cols)
+    assert q.is_contiguous() and q.shape == wf.shape and scale.is_contiguous() and (zp is None or zp.is_contiguous())
+    err = torch.empty(rows, block_cols, dtype=torch.float32, device=dev)
+    _launch(dev, entry, entry, ctypes.byref(desc), ptr(wf), *map(ptr, mats), rows, cols, int(col0), int(block_cols),
+            *scalars, ptr(q), ptr(err), ptr(scale), ptr(zp))
+    return err
 
 
 def gptq_block_supported(desc, wf, u, q, col0, block_cols, computed):
@@ -770,14 +784,8 @@ def gptq_block(desc, wf, u, col0, block_cols, computed, min_val, thr_div, q, sca
     (float32 [rows, cols]) and u (float32 [cols, cols]), writes the block's columns of q (like wf, in the quantizer's
     dtype) and, computed, the block's entries of scale / zp ([rows, cols / group size]; given, they are read; zp None for
     a symmetric quantizer) -> err float32 [rows, block_cols]"""
-    dev = require_device(wf, u, q, scale, zp)
-    assert wf.dtype == torch.float32 and u.dtype == torch.float32 and wf.is_contiguous() and u.is_contiguous()
-    assert q.is_contiguous() and q.shape == wf.shape and scale.is_contiguous() and (zp is None or zp.is_contiguous())
-    rows, cols = wf.shape
-    err = torch.empty(rows, block_cols, dtype=torch.float32, device=dev)
-    _launch(dev, 'bvq_gptq_block', 'bvq_gptq_block', ctypes.byref(desc), ptr(wf), ptr(u), rows, cols, int(col0),
-            int(block_cols), int(computed), *_scale_args(min_val, thr_div), ptr(q), ptr(err), ptr(scale), ptr(zp))
-    return err
+    return _column_block('bvq_gptq_block', desc, wf, (u,), col0, block_cols,
+                         (int(computed), *_scale_args(min_val, thr_div)), q, scale, zp)
 
 
 def gpfq_block_supported(desc, wf, c, h, q, col0, block_cols):
@@ -792,15 +800,7 @@ def gpfq_block(desc, wf, c, h, col0, block_cols, q, scale, zp):
     """the GPFQ column loop of the block [col0, col0 + block_cols) in ONE launch (include/bvq.h, "GPFQ"): reads wf and c
     (float32 [rows, cols]), h (float32 [cols, cols]) and scale / zp ([rows, cols / group size]; zp None for a symmetric
     quantizer), writes the block's columns of q (like wf, in the quantizer's dtype) -> err float32 [rows, block_cols]"""
-    dev = require_device(wf, c, h, q, scale, zp)
-    assert wf.dtype == c.dtype == h.dtype == torch.float32 and wf.is_contiguous() and c.is_contiguous()
-    assert h.is_contiguous() and c.shape == wf.shape and h.shape == (wf.shape[1], wf.shape[1])
-    assert q.is_contiguous() and q.shape == wf.shape and scale.is_contiguous() and (zp is None or zp.is_contiguous())
-    rows, cols = wf.shape
-    err = torch.empty(rows, block_cols, dtype=torch.float32, device=dev)
-    _launch(dev, 'bvq_gpfq_block', 'bvq_gpfq_block', ctypes.byref(desc), ptr(wf), ptr(c), ptr(h), rows, cols, int(col0),
-            int(block_cols), ptr(q), ptr(err), ptr(scale), ptr(zp))
-    return err
+    return _column_block('bvq_gpfq_block', desc, wf, (c, h), col0, block_cols, (), q, scale, zp)
 
 
 def learned_round_supported(desc, x, value):

@@ -36,7 +36,7 @@ from brevitas_amd.graph.calibrate import DisableEnableQuantization
 
 __all__ = ['gpfq_mode', 'gpfq_quantize_weight', 'GPFQResult']
 
-BLOCK = nat.GPTQ_BLOCK  # the column-loop kernels share their block width
+BLOCK = gptq.BLOCK
 
 
 class GPFQResult(NamedTuple):
@@ -68,28 +68,20 @@ def composed_block(plan: 'gptq._Plan', wf: Tensor, c: Tensor, h: Tensor, c0: int
     """the column loop of the block [c0, c1) in plain torch ops: wf (float32, read only), the block's columns of c
     (float32, updated in place) -> the block's columns of q, and E [R, c1 - c0].  A group may have begun before the
     block: its parameters are read at the block's first column."""
-    dtype, g, quant = q.dtype, plan.group, plan.quant
+    block = gptq._ComposedBlock(plan, wf, c0, c1, q, scale, zp)
     cb = c[:, c0:c1]
-    err = torch.empty(wf.shape[0], c1 - c0, dtype=torch.float32, device=wf.device)
-    zero = None if plan.shifted else quant.zero_point_impl(wf[:, c0:c1], scale, plan.bit_width)
-    s = z = None
-    for i in range(c1 - c0):
-        col = c0 + i
-        if col % g == 0 or i == 0:
-            s = scale[:, col // g].reshape(-1, 1).contiguous()
-            z = zp[:, col // g].reshape(-1, 1).contiguous() if plan.shifted else zero
+    for i, col, s, z in block.columns():
         w = wf[:, col]
         hd = h[col, col]  # a tensor on wf's device: the division below is IEEE's, no product with a reciprocal
         # the quotient rounded, then the sum; a column whose input never fired is rounded to nearest
         v = torch.where(hd > 0, w + cb[:, i] / hd, w)
-        qc = quant.int_quant(s, z, plan.bit_width, v.to(dtype).reshape(-1, 1).contiguous())[:, 0]
-        q[:, col] = qc
+        qc = plan.quant.int_quant(s, z, plan.bit_width, v.to(q.dtype).reshape(-1, 1).contiguous())[:, 0]
         e = w - qc.float()  # against the original weight, not v
-        err[:, i] = e
+        block.store(i, qc, e)
         if i + 1 < c1 - c0:
             # the product rounded, then the sum: two ops, no fused multiply-add
             cb[:, i + 1:] += e.reshape(-1, 1) * h[col, col + 1:c1].reshape(1, -1)
-    return err
+    return block.err
 
 
 def fused_block_desc(plan: 'gptq._Plan', rows: int, k: int, dtype: torch.dtype) -> Optional['nat.QuantDesc']:
@@ -125,15 +117,10 @@ def gpfq_quantize_weight(weight: Tensor, h: Tensor, d: Tensor, quantizer, *, nam
         q = torch.empty(rows, k, dtype=weight.dtype, device=weight.device)
 
         desc = fused_block_desc(plan, rows, k, weight.dtype) if weight.is_cuda else None
-        if desc is not None and not nat.gpfq_block_supported(desc, wf, c, hf, q, 0, min(BLOCK, k)):
-            desc = None  # misaligned tensors
-        for c0 in range(0, k, BLOCK):
-            c1 = min(c0 + BLOCK, k)
-            if desc is not None:
-                err = fused_block(desc, wf, c, hf, c0, c1, q, scale, zp)
-            else:
-                err = composed_block(plan, wf, c, hf, c0, c1, q, scale, zp)
-            tail_update(c, err, hf, c0, c1)
+        gptq.walk_blocks(k, lambda c0, c1: nat.gpfq_block_supported(desc, wf, c, hf, q, c0, c1 - c0),
+                         None if desc is None else lambda c0, c1: fused_block(desc, wf, c, hf, c0, c1, q, scale, zp),
+                         lambda c0, c1: composed_block(plan, wf, c, hf, c0, c1, q, scale, zp),
+                         lambda err, c0, c1: tail_update(c, err, hf, c0, c1))
         return GPFQResult(q.reshape(weight.shape), scale_out, zp_out, plan.bit_width)
 
 
@@ -150,21 +137,15 @@ class gpfq_mode(gptq.gptq_mode):
     A layer that was frozen before the mode was entered has no original weight left: it runs as it stands in both
     passes, and the float path is then float only from that layer on."""
 
+    who = 'gpfq'
+
     def __init__(self, model: torch.nn.Module):
-        super().__init__(model, static_groups=True)
+        super().__init__(model, static_groups=True)  # given parameters, which is also what gptq_mode._admit plans with
         self._d = None
         self._float_rows = None
         self._float_pass = False
         self._originals = {}  # finished layer -> its original weight
         self._switch = DisableEnableQuantization()
-
-    def _admit(self, name: str, m) -> None:
-        from brevitas_amd.nn import QuantConv2d, QuantLinear
-        if not isinstance(m, (QuantLinear, QuantConv2d)) or (isinstance(m, QuantConv2d) and m.groups != 1):
-            raise NotImplementedError('gpfq_mode: layer %r (%s%s) is not covered: QuantLinear, and QuantConv2d with '
-                                      'groups == 1' % (name, type(m).__name__,
-                                                       ', groups=%d' % m.groups if hasattr(m, 'groups') else ''))
-        _plan(m.weight_quant, m.weight.numel() // m.weight.shape[0])
 
     def _reset(self) -> None:
         super()._reset()

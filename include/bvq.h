@@ -932,7 +932,10 @@ int bvq_weight_norm_bwd(const bvq_quant_desc* desc, int norm_kind, double t_boun
  *                difference rounded (no fused multiply-add)
  * and after each block Wf[:, c1:] -= E @ U[c0:c1, c1:] as one float32 matrix product, which is the caller's.
  * bvq_gptq_block runs that loop for ONE block in one launch: one wave per row, the block's columns in registers (two
- * per lane), a group start as a segmented butterfly; no workspace, no atomics.  It reads the block's columns of wf
+ * per lane), a group start as a segmented butterfly; no workspace, no atomics.  The kernel is the one column-loop frame
+ * of csrc/bvq_column_loop.h, which bvq_gpfq_block below shares, with GPTQ's rule: a rule states what a lane's running
+ * state is (here the working copy itself), the value that is quantized, the error and the update right of i; the loop,
+ * its parameters, prefetch and stores, and the checks of the entry are the frame's.  It reads the block's columns of wf
  * ([rows, cols] float32) and the [block_cols, block_cols] triangle of u ([cols, cols] float32) and writes the block's
  * columns of q ([rows, cols] of T) and err ([rows, block_cols] float32).  desc: outer 1, channels = rows * cols / g,
  * inner = g, scale_per_channel, x_dtype = ct_dtype = scale_dtype; zp_per_channel = 1 with zp_dtype = x_dtype for an
@@ -970,7 +973,9 @@ int bvq_gptq_block(const bvq_quant_desc* desc, const float* wf, const float* u, 
  * and after each block C[:, c1:] += E @ H[c0:c1, c1:] as one float32 matrix product, which is the caller's.
  * (The textbook numerator sum_j w_j <X_j, X~_i> - sum_j q_j <X~_j, X~_i> is the same number and cancels in float32.)
  * bvq_gpfq_block runs that loop for ONE block in one launch: one wave per row, the block's columns of wf and c in
- * registers (two per lane); no workspace, no atomics.  It reads the block's columns of wf and c ([rows, cols] float32),
+ * registers (two per lane); no workspace, no atomics.  The kernel is the frame of bvq_gptq_block with GPFQ's rule: the
+ * running state is c beside the read-only weight, and value, error and update are the three lines above; parameters are
+ * given only.  It reads the block's columns of wf and c ([rows, cols] float32),
  * the [block_cols, block_cols] triangle of h ([cols, cols] float32) and scale, zp ([rows, cols / g] of T; zp required for
  * an asymmetric quantizer, else ignored), and writes the block's columns of q ([rows, cols] of T) and err ([rows,
  * block_cols] float32) and nothing else: c is not written.  desc: as for bvq_gptq_block with computed = 0 -- outer 1,

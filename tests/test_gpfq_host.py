@@ -305,4 +305,4 @@ def test_block_entry_refuses_before_the_device():
     assert lib.bvq_gpfq_block_supported(ctypes.byref(desc(256)), rows, cols, 128, 128, ok, ok, ok, ok) == 1
     assert lib.bvq_gpfq_block_supported(ctypes.byref(desc(32)), rows, cols, 16, 72, ok, ok, ok, ok) == 1
     assert lib.bvq_gpfq_block_supported(ctypes.byref(desc(32)), rows, cols, 0, 128, ok, ctypes.c_void_p(4100), ok, ok) == 0
-    assert P.BLOCK == nat.GPTQ_BLOCK == 128
+    assert P.BLOCK == nat.COLUMN_BLOCK == 128

@@ -6,7 +6,6 @@ route on the device, K on and off the block grid, and gpfq_mode on small models.
 Bars: Q and E of a block are bit-exact against the CPU (the kernel and the composed step compute the same definition
 with the same roundings); the two routes of a whole layer are bit-identical on the device, their first product
 and their tail updates being the same calls on the same bits."""
-import copy
 import functools
 
 import pytest
@@ -17,7 +16,8 @@ from brevitas_amd import quant as Q
 from brevitas_amd.graph import gpfq as P
 from brevitas_amd.graph import gptq as G
 from brevitas_amd.graph import gpfq_mode, gpfq_quantize_weight
-from brevitas_amd.nn import QuantConv2d, QuantLinear, QuantReLU
+
+from column_loop_cases import _same_bits, conv_models, linear_models
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -88,15 +88,6 @@ def _run_block(make, dn, bc, col0, k, plant=None, rows=(5,)):
         assert not q_d[:, :col0].any() and not q_d[:, col0 + bc:].any()
         devs[r] = (q_d[:, col0:col0 + bc].cpu(), err_d.cpu())
     return cpu, devs, plan, scale, zp, w.detach()
-
-
-def _same_bits(a, b, what):
-    assert a.dtype == b.dtype and a.shape == b.shape, what
-    ai = a.contiguous().view(torch.int32 if a.element_size() == 4 else torch.int16)
-    bi = b.contiguous().view(torch.int32 if b.element_size() == 4 else torch.int16)
-    bad = (ai != bi) & ~(a.isnan() & b.isnan())
-    assert not bad.any(), '%s: %d of %d differ, first at %s' % (what, int(bad.sum()), bad.numel(),
-                                                                 bad.nonzero()[0].tolist())
 
 
 def _assert_block(cpu, devs, what=''):
@@ -245,36 +236,6 @@ def _output_errors(model, float_model, rtn, x):
     with torch.no_grad():
         want = float_model(x)
         return float((model(x) - want).norm()), float((rtn(x) - want).norm())
-
-
-def linear_models(dev):
-    """the linear model of the GPTQ tests, its round-to-nearest copy, the float model and correlated inputs"""
-    torch.manual_seed(5)
-    model = torch.nn.Sequential(
-        QuantLinear(64, 96, weight_quant=functools.partial(Q.Int4WeightPerGroupFloat, group_size=32)),
-        QuantReLU(Q.Uint8ActPerTensorFloat(scaling_impl_type='stats', scaling_stats_op='max')),
-        QuantLinear(96, 32, weight_quant=functools.partial(Q.ShiftedUint4WeightPerGroupFloat, group_size=32))).to(dev)
-    rtn = copy.deepcopy(model)
-    float_model = torch.nn.Sequential(torch.nn.Linear(64, 96), torch.nn.ReLU(), torch.nn.Linear(96, 32)).to(dev)
-    float_model[0].load_state_dict({k: v for k, v in model[0].state_dict().items() if k in ('weight', 'bias')})
-    float_model[2].load_state_dict({k: v for k, v in model[2].state_dict().items() if k in ('weight', 'bias')})
-    gen = torch.Generator().manual_seed(6)
-    x = (torch.randn(512, 64, generator=gen) @ (torch.eye(64) + 2 * torch.randn(64, 64, generator=gen) / 8.0)).to(dev)
-    return model, rtn, float_model, x
-
-
-def conv_models(dev):
-    """the conv layer of the GPTQ tests, its round-to-nearest copy, the float layer and correlated inputs"""
-    torch.manual_seed(7)
-    model = torch.nn.Sequential(
-        QuantConv2d(16, 16, 3, padding=1, weight_quant=functools.partial(Q.Int4WeightPerGroupFloat, group_size=16))).to(dev)
-    rtn = copy.deepcopy(model)
-    float_model = torch.nn.Sequential(torch.nn.Conv2d(16, 16, 3, padding=1)).to(dev)
-    float_model[0].load_state_dict({k: v for k, v in model[0].state_dict().items() if k in ('weight', 'bias')})
-    gen = torch.Generator().manual_seed(8)
-    x = torch.randn(4, 16, 12, 12, generator=gen)
-    x = (x + 0.8 * x.roll(1, dims=1) + 0.5 * x.roll(1, dims=3)).to(dev)  # correlated inputs
-    return model, rtn, float_model, x
 
 
 def test_gpfq_mode_on_a_linear_model():

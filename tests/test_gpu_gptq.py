@@ -6,7 +6,6 @@ and gptq_mode on small models.
 Bars: Q, E, scale and zp of a block are bit-exact against the CPU (the kernel and the composed step compute the same
 definition with the same roundings); the two routes of a whole layer are bit-identical on the device, their
 tail updates being the same calls on the same bits."""
-import copy
 import functools
 
 import pytest
@@ -16,7 +15,8 @@ import torch.nn.functional as F
 from brevitas_amd import quant as Q
 from brevitas_amd.graph import gptq as G
 from brevitas_amd.graph import gptq_mode, gptq_quantize_weight
-from brevitas_amd.nn import QuantConv2d, QuantLinear, QuantReLU
+
+from column_loop_cases import _same_bits, conv_models, linear_models
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -103,18 +103,6 @@ def _run_block(name, dn, rows, bc, plant=None, col0=COL0, static=False, make=Non
         g0 = col0 // plan.group
         out.append((q_d[:, col0:].cpu(), err.cpu(), scale_d[:, g0:].cpu(), zp_d[:, g0:].cpu() if zp is not None else None))
     return out
-
-
-def _same_bits(a, b, what):
-    if a is None:
-        assert b is None
-        return
-    assert a.dtype == b.dtype and a.shape == b.shape, what
-    ai = a.contiguous().view(torch.int32 if a.element_size() == 4 else torch.int16)
-    bi = b.contiguous().view(torch.int32 if b.element_size() == 4 else torch.int16)
-    bad = (ai != bi) & ~(a.isnan() & b.isnan())
-    assert not bad.any(), '%s: %d of %d differ, first at %s' % (what, int(bad.sum()), bad.numel(),
-                                                                 bad.nonzero()[0].tolist())
 
 
 @pytest.mark.parametrize('dn', ['f32', 'bf16', 'f16'])
@@ -286,20 +274,7 @@ def _output_errors(model, float_model, make_rtn, x):
 
 
 def test_gptq_mode_on_a_linear_model():
-    torch.manual_seed(5)
-
-    def build():
-        return torch.nn.Sequential(
-            QuantLinear(64, 96, weight_quant=functools.partial(Q.Int4WeightPerGroupFloat, group_size=32)),
-            QuantReLU(Q.Uint8ActPerTensorFloat(scaling_impl_type='stats', scaling_stats_op='max')),
-            QuantLinear(96, 32, weight_quant=functools.partial(Q.ShiftedUint4WeightPerGroupFloat, group_size=32))).to(DEV)
-    model = build()
-    rtn = copy.deepcopy(model)
-    float_model = torch.nn.Sequential(torch.nn.Linear(64, 96), torch.nn.ReLU(), torch.nn.Linear(96, 32)).to(DEV)
-    float_model[0].load_state_dict({k: v for k, v in model[0].state_dict().items() if k in ('weight', 'bias')})
-    float_model[2].load_state_dict({k: v for k, v in model[2].state_dict().items() if k in ('weight', 'bias')})
-    gen = torch.Generator().manual_seed(6)
-    x = (torch.randn(512, 64, generator=gen) @ (torch.eye(64) + 2 * torch.randn(64, 64, generator=gen) / 8.0)).to(DEV)
+    model, rtn, float_model, x = linear_models(DEV)
     with gptq_mode(model) as gptq:
         assert gptq.num_layers == 2
         for _ in range(gptq.num_layers):
@@ -315,15 +290,7 @@ def test_gptq_mode_on_a_linear_model():
 
 
 def test_gptq_mode_on_a_conv_layer():
-    torch.manual_seed(7)
-    model = torch.nn.Sequential(
-        QuantConv2d(16, 16, 3, padding=1, weight_quant=functools.partial(Q.Int4WeightPerGroupFloat, group_size=16))).to(DEV)
-    rtn = copy.deepcopy(model)
-    float_model = torch.nn.Sequential(torch.nn.Conv2d(16, 16, 3, padding=1)).to(DEV)
-    float_model[0].load_state_dict({k: v for k, v in model[0].state_dict().items() if k in ('weight', 'bias')})
-    gen = torch.Generator().manual_seed(8)
-    x = torch.randn(4, 16, 12, 12, generator=gen)
-    x = (x + 0.8 * x.roll(1, dims=1) + 0.5 * x.roll(1, dims=3)).to(DEV)  # correlated inputs
+    model, rtn, float_model, x = conv_models(DEV)
     with gptq_mode(model) as gptq:
         gptq.model(x)
         res = gptq.update()

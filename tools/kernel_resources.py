@@ -36,12 +36,13 @@ def main():
     out = subprocess.run(['c++filt'] + names, capture_output=True, text=True).stdout.splitlines()
     for r_, d in zip(rows, out):
         r_['name'] = d
-    print('%-6s %-6s %-5s %-7s %s' % ('VGPR', 'SGPR', 'occ', 'scratch', 'kernel'))
+    print('%-6s %-6s %-5s %-7s %-5s %s' % ('VGPR', 'SGPR', 'occ', 'scratch', 'LDS', 'kernel'))
     for r_ in rows:
         if filt and not any(f in r_['name'] for f in filt):
             continue
-        print('%-6s %-6s %-5s %-7s %s' % (r_.get('VGPRs'), r_.get('TotalSGPRs'), r_.get('Occupancy [waves/SIMD]'),
-                                         r_.get('ScratchSize [bytes/lane]'), r_['name'][:150]))
+        print('%-6s %-6s %-5s %-7s %-5s %s' % (r_.get('VGPRs'), r_.get('TotalSGPRs'), r_.get('Occupancy [waves/SIMD]'),
+                                              r_.get('ScratchSize [bytes/lane]'), r_.get('LDS Size [bytes/block]'),
+                                              r_['name'][:150]))
 
 
 if __name__ == '__main__':
