@@ -315,6 +315,24 @@ def group_hqo_search(xg, inv_beta, p, scale, zp0, to_int):
     return zp_best, idx, e_best, e0
 
 
+# ---- Hadamard transform (include/bvq.h, "Hadamard transform") ----------------------------------------------
+
+def hadamard(x, block, scale):
+    """scale * (I (x) H_block) x along the last dimension of x, the definition restated on torch ops: float32 from the
+    widening to the multiply, butterfly stages h = 1, 2 .. block / 2 in ascending order, one multiply by float32(scale),
+    one rounding to x.dtype.  Every stage is a float32 addition and a float32 subtraction of the same operands the
+    kernel pairs, so the two routes give the same bits, on a CPU tensor and on a device one."""
+    y = x.to(torch.float32)
+    h = 1
+    while h < block:
+        y = y.reshape(-1, block // (2 * h), 2, h)
+        a, c = y[:, :, 0], y[:, :, 1]
+        y = torch.stack((a + c, a - c), dim=2)
+        h *= 2
+    scale32 = torch.tensor(float(scale), dtype=torch.float64).to(torch.float32).item()
+    return (y.reshape(x.shape) * scale32).to(x.dtype)
+
+
 import sys  # noqa: E402
 
 _SELF = sys.modules[__name__]

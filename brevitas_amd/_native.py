@@ -39,7 +39,7 @@ MX_FLOOR, MX_CEIL = 0, 1
 LR_HARD_SIGMOID, LR_SIGMOID = 0, 1  # bvq_learned_round_impl
 NORM_L1, NORM_L2 = 0, 1  # bvq_norm_kind
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -208,6 +208,8 @@ _SIG = {
     'bvq_mx_encode_supported': (_i32, [_i32, _i64, _i32, _i32, _vp]),
     'bvq_mx_encode': (_i32, [_i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'bvq_mx_decode': (_i32, [_i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'bvq_hadamard_supported': (_i32, [_i32, _i64, _i64, _i64, _vp, _vp]),
+    'bvq_hadamard': (_i32, [_i32, _vp, _i64, _i64, _i64, _dbl, _vp, _vp]),
     'bvq_fakequant_bwd_learned': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _i64, _vp]),
 }
 
@@ -752,6 +754,26 @@ def weight_norm_bwd(desc, norm_kind, t_bound, norm_min, gy, x, scale, g, norm):
     _launch(dev, 'bvq_weight_norm_bwd', 'bvq_weight_norm_bwd', ctypes.byref(desc), int(norm_kind), float(t_bound),
             float(norm_min), ptr(gy), ptr(x), ptr(scale), ptr(g), ptr(norm), ptr(dx), ptr(dscale), ptr(dg))
     return dx, dscale, dg
+
+
+def hadamard_supported(x, rows, cols, block, out=None):
+    """the Hadamard kernel covers x viewed [rows, cols] (contiguous) with blocks of `block`, written to out (x: in place)"""
+    out = x if out is None else out
+    return x.dtype in _DTYPES and out.dtype == x.dtype and \
+        bool(lib.bvq_hadamard_supported(dtype_code(x.dtype), int(rows), int(cols), int(block), ptr(x), ptr(out)))
+
+
+def hadamard(x, rows, cols, block, scale, out=None):
+    """out = float32(scale) * (I (x) H_block) x along the rows of x viewed [rows, cols], ONE launch -> out (a new tensor
+    like x when None; out may be x: a row is whole in registers between its load and its store)"""
+    dev = require_device(x, out)
+    if out is None:
+        out = torch.empty_like(x)
+    assert x.is_contiguous() and out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
+    assert x.numel() == int(rows) * int(cols)
+    _launch(dev, 'bvq_hadamard', 'bvq_hadamard', dtype_code(x.dtype), ptr(x), int(rows), int(cols), int(block),
+            float(scale), ptr(out))
+    return out
 
 
 COLUMN_BLOCK = 128  # columns of one launch of a column-loop kernel (bvq_gptq_block, bvq_gpfq_block)

@@ -34,7 +34,8 @@ SOURCES = [('bvq_common.hip', [], 'bvq_common.o'), ('bvq_elementwise.hip', [], '
            ('bvq_mx_quant.hip', [], 'bvq_mx_quant.o'),
            ('bvq_gptq.hip', [], 'bvq_gptq.o'), ('bvq_gpfq.hip', [], 'bvq_gpfq.o'),
            ('bvq_learned_round.hip', [], 'bvq_learned_round.o'),
-           ('bvq_row_shifted.hip', [], 'bvq_row_shifted.o'), ('bvq_weight_norm.hip', [], 'bvq_weight_norm.o')]
+           ('bvq_row_shifted.hip', [], 'bvq_row_shifted.o'), ('bvq_weight_norm.hip', [], 'bvq_weight_norm.o'),
+           ('bvq_hadamard.hip', [], 'bvq_hadamard.o')]
 HEADERS = ['bvq_common.h', 'bvq_unit_walk.h', 'bvq_act.h', 'bvq_stat_epilogue.h', 'bvq_quant_math.h', 'bvq_ties.h', 'bvq_sums.h', 'bvq_fakequant.h', 'bvq_fakequant_bwd.h',
            'bvq_group_walk.h', 'bvq_group_quant.h', 'bvq_group_shifted.h', 'bvq_row_walk.h', 'bvq_column_loop.h',
            os.path.join(ROOT, 'include', 'bvq.h')]

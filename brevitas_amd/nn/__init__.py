@@ -13,8 +13,10 @@ from brevitas_amd.core.function_wrapper import Identity
 from brevitas_amd.core.quant import RescalingIntQuant
 from brevitas_amd.core.quant.weight_group import WeightQuantGroup
 
+from .hadamard import HadamardClassifier, HadamardRotation, RotatedModule
+
 __all__ = ['QuantConv2d', 'QuantLinear', 'QuantIdentity', 'QuantReLU', 'QuantSigmoid', 'QuantTanh', 'QuantHardTanh',
-           'WeightQuantGroup']
+           'WeightQuantGroup', 'HadamardRotation', 'RotatedModule', 'HadamardClassifier']
 
 WeightQuantFactory = Callable[[torch.nn.Parameter], RescalingIntQuant]
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 11
+#define BVQ_ABI_VERSION 12
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -1109,6 +1109,37 @@ int bvq_mx_encode(int dtype, int64_t groups, int group_size, int format, int sca
                   void* scale_e8m0, bvq_stream_t stream);
 int bvq_mx_decode(int dtype, int64_t groups, int group_size, int format, const void* codes, const void* scale_e8m0,
                   void* y, bvq_stream_t stream);
+
+/* ---- Hadamard transform: y = scale * (I (x) H_b) x along the last dimension ---------------------------------------------
+ * The online rotation of QuaRot / SpinQuant style quantization (brevitas_amd.function.hadamard, nn.RotatedModule) and
+ * the product of the reference's HadamardClassifier (B/nn/hadamard_classifier.py, a dense matrix there).  x is
+ * [rows, cols] of dtype T, contiguous; block (b) is a power of two, 2 <= b <= cols, b | cols; H_b is the Sylvester
+ * (natural-order) +-1 matrix.  Definition, which the composed route of brevitas_amd/_aten.py and this kernel compute with
+ * the same bits:
+ *   1. every element is widened to float32;
+ *   2. stages h = 1, 2, 4 .. b / 2 in this ascending order; in a stage every pair (i, i + h) with (i & h) == 0 inside a
+ *      block becomes (u + v, u - v), u the value at i and v the value at i + h, each one correctly rounded float32
+ *      addition or subtraction;
+ *   3. one float32 multiply by (float)scale;
+ *   4. one rounding to T (nearest even).
+ * Intermediates are float32 from the load to the multiply, through LDS as well.  The transform is symmetric: its
+ * gradient is the same call on the incoming gradient.
+ * Geometry: the row walk of the per-row entries above -- a row of C = cols * sizeof(T) / 16 chunks in the registers of
+ * one wave (C <= 128) or one workgroup of four waves (C <= 512: two loads per lane, C <= 2048: eight), lane l of wave w
+ * holding chunks j * 64 W + 64 w + l.  The bits of an element's index are, from the low end, its place in the chunk, the
+ * lane, the wave, the load j; the stages of the first and last class are register arithmetic, the six lane stages
+ * cross-lane exchanges on the VALU (DPP moves, v_permlane16_swap / v_permlane32_swap), the two wave stages ONE exchange through LDS per load (two alternating float32 slices of one load,
+ * 16 KiB per workgroup for the 16-bit types and 8 KiB for float32, one barrier per load).  A smaller block stops the
+ * sequence early.  A row is whole in registers between its only load and its only store, so y may be x.
+ * ONE launch: x read once, y written once; no workspace, no atomics, nothing between workgroups.
+ * Covered: T float32, bfloat16 or float16; cols * sizeof(T) a multiple of 16 up to 32768 (a longer last dimension is the
+ * caller's to view as [rows * H / c, c], b | c | H: the transform is block-diagonal); x and y on 16-byte boundaries.  A
+ * bad dtype, rows or cols < 1, a block that is no power of two >= 2 or does not divide cols, a null pointer:
+ * BVQ_ERR_INVALID; a row length or an alignment not covered: BVQ_ERR_UNSUPPORTED; both with a bvq_last_error() text,
+ * found before anything touches the device.  bvq_hadamard_supported answers 1 / 0. */
+int bvq_hadamard_supported(int dtype, int64_t rows, int64_t cols, int64_t block, const void* x, const void* y);
+int bvq_hadamard(int dtype, const void* x, int64_t rows, int64_t cols, int64_t block, double scale, void* y,
+                 bvq_stream_t stream);
 
 /* Diagnostic entry (no reference counterpart): the float32 quotient the float16 quantizer kernels compute for a
  * numerator a[i] and a scale scales[j] -- the product with the correctly rounded reciprocal, corrected by one exact
