@@ -333,6 +333,26 @@ def hadamard(x, block, scale):
     return (y.reshape(x.shape) * scale32).to(x.dtype)
 
 
+def hadamard_kron(x, signs, block, scale):
+    """scale * (I (x) (S (x) H_P)) x along the last dimension of x, S the +-1 matrix `signs` [K, K] (a Paley matrix or its
+    transpose) and P = block / K: the definition of include/bvq.h ("Hadamard transform of order K * 2^n") on torch ops.
+    The sub-rows take `hadamard` with block P and scale 1 (exact), kept in float32; then for every output i the K steps
+    acc = acc + s_ij * v_j in ascending j, one float32 addition each; one multiply by float32(scale); one rounding.
+    K^2 tensor ops over the whole of x (1296 for K = 36): the definition for the CPU and for what the kernel refuses,
+    not a route for large tensors."""
+    k = signs.shape[0]
+    v = hadamard(x.to(torch.float32), block // k, 1.0).reshape(-1, k, block // k)
+    s = signs.tolist()
+    out = []
+    for i in range(k):
+        acc = s[i][0] * v[:, 0]
+        for j in range(1, k):
+            acc = acc + s[i][j] * v[:, j]
+        out.append(acc)
+    scale32 = torch.tensor(float(scale), dtype=torch.float64).to(torch.float32).item()
+    return (torch.stack(out, dim=1).reshape(x.shape) * scale32).to(x.dtype)
+
+
 import sys  # noqa: E402
 
 _SELF = sys.modules[__name__]

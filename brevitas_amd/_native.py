@@ -39,7 +39,7 @@ MX_FLOOR, MX_CEIL = 0, 1
 LR_HARD_SIGMOID, LR_SIGMOID = 0, 1  # bvq_learned_round_impl
 NORM_L1, NORM_L2 = 0, 1  # bvq_norm_kind
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -210,6 +210,8 @@ _SIG = {
     'bvq_mx_decode': (_i32, [_i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     'bvq_hadamard_supported': (_i32, [_i32, _i64, _i64, _i64, _vp, _vp]),
     'bvq_hadamard': (_i32, [_i32, _vp, _i64, _i64, _i64, _dbl, _vp, _vp]),
+    'bvq_hadamard_kron_supported': (_i32, [_i32, _i64, _i64, _i64, _i64, _vp, _vp]),
+    'bvq_hadamard_kron': (_i32, [_i32, _vp, _i64, _i64, _i64, _i64, _i32, _dbl, _vp, _vp]),
     'bvq_fakequant_bwd_learned': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _i64, _vp]),
 }
 
@@ -773,6 +775,27 @@ def hadamard(x, rows, cols, block, scale, out=None):
     assert x.numel() == int(rows) * int(cols)
     _launch(dev, 'bvq_hadamard', 'bvq_hadamard', dtype_code(x.dtype), ptr(x), int(rows), int(cols), int(block),
             float(scale), ptr(out))
+    return out
+
+
+def hadamard_kron_supported(x, rows, cols, base, block, out=None):
+    """the kernel of order base * 2^n covers x viewed [rows, cols] (contiguous) with blocks of `block`, written to out"""
+    out = x if out is None else out
+    return x.dtype in _DTYPES and out.dtype == x.dtype and \
+        bool(lib.bvq_hadamard_kron_supported(dtype_code(x.dtype), int(rows), int(cols), int(base), int(block), ptr(x),
+                                             ptr(out)))
+
+
+def hadamard_kron(x, rows, cols, base, block, transpose, scale, out=None):
+    """out = float32(scale) * (I (x) (H_base (x) H_{block / base})) x along the rows of x viewed [rows, cols], H_base
+    transposed when `transpose`, ONE launch -> out (a new tensor like x when None; out may be x)"""
+    dev = require_device(x, out)
+    if out is None:
+        out = torch.empty_like(x)
+    assert x.is_contiguous() and out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
+    assert x.numel() == int(rows) * int(cols)
+    _launch(dev, 'bvq_hadamard_kron', 'bvq_hadamard_kron', dtype_code(x.dtype), ptr(x), int(rows), int(cols), int(base),
+            int(block), int(bool(transpose)), float(scale), ptr(out))
     return out
 
 

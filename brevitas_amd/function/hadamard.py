@@ -5,6 +5,11 @@ Sylvester (natural-order) +-1 matrix; the arithmetic is defined in include/bvq.h
 stages h = 1, 2 .. b / 2 in ascending order, one multiply by float32(scale), one rounding to the tensor's dtype.  A device
 tensor takes the HIP kernel (libbvq.so, bvq_hadamard), everything else the same stages composed of torch ops
 (brevitas_amd._aten.hadamard); the two routes give the same bits.
+
+With `base` = 12, 20, 28 or 36 the matrix of a block is H_base (x) H_P, H_base the Paley matrix of that order
+(paley_hadamard_matrix), for the layer widths that are base * 2^n: after the stages of the sub-rows of P elements, base
+float32 additions per output in ascending order (include/bvq.h, "Hadamard transform of order K * 2^n"; bvq_hadamard_kron
+and brevitas_amd._aten.hadamard_kron, same bits).
 """
 import math
 
@@ -16,9 +21,10 @@ from .. import _aten
 from .. import _native as nat
 from .. import config
 
-__all__ = ['hadamard_transform', 'hadamard_matrix', 'default_block_size']
+__all__ = ['hadamard_transform', 'hadamard_matrix', 'paley_hadamard_matrix', 'default_block_size']
 
 _DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+_PALEY_PRIME = {12: 11, 20: 19, 28: 13, 36: 17}  # the order and the prime q of its Paley construction
 _ROW_MAX_BYTES = 32768  # the longest row the row kernels hold (bvq_row_shifted_max_row_bytes)
 
 
@@ -46,41 +52,64 @@ def _row_view(n, block, itemsize):
     return None
 
 
-def _apply(x, block, scale):
+def _check_kron_block(block_size, base, n):
+    if base not in _PALEY_PRIME:
+        raise ValueError('hadamard_transform: base %s (None, 12, 20, 28 or 36)' % (base,))
+    b = base * default_block_size(n // base) if block_size is None and n % base == 0 else int(block_size or 0)
+    p = b // base
+    if b < base or b % base or p & (p - 1) or n % b:
+        raise ValueError('hadamard_transform: block_size %d must be %d times a power of two and divide the last '
+                         'dimension %d' % (b, base, n))
+    return b
+
+
+def _apply(x, block, scale, base=None, transpose=False):
     x = x.contiguous()
     n = x.shape[-1]
     if x.is_cuda and config.FUSED_PATHS and x.numel() > 0:
         c = _row_view(n, block, x.element_size())
-        if c is not None and nat.hadamard_supported(x, x.numel() // c, c, block):
+        if c is not None and base is None and nat.hadamard_supported(x, x.numel() // c, c, block):
             return nat.hadamard(x, x.numel() // c, c, block, scale)
-    return _aten.hadamard(x, block, scale)
+        if c is not None and base is not None and nat.hadamard_kron_supported(x, x.numel() // c, c, base, block):
+            return nat.hadamard_kron(x, x.numel() // c, c, base, block, transpose, scale)
+    if base is None:
+        return _aten.hadamard(x, block, scale)
+    signs = paley_hadamard_matrix(base)
+    return _aten.hadamard_kron(x, signs.t() if transpose else signs, block, scale)
 
 
 class _HadamardFn(Function):
-    """One node for both routes.  The transform is symmetric: the backward is the forward on the incoming gradient, the
-    same stages in the same order, hence the bits of a direct call."""
+    """One node for both routes.  The backward is the forward with the transposed matrix on the incoming gradient (the
+    Sylvester matrix is symmetric: the same call), the same stages in the same order, hence the bits of a direct call."""
 
     @staticmethod
-    def forward(ctx, x, block, scale):
-        ctx.block, ctx.scale = block, scale
-        return _apply(x, block, scale)
+    def forward(ctx, x, block, scale, base, transpose):
+        ctx.args = block, scale, base, not transpose
+        return _apply(x, block, scale, base, transpose)
 
     @staticmethod
     def backward(ctx, grad_y):
-        return _apply(grad_y, ctx.block, ctx.scale), None, None
+        return _apply(grad_y, *ctx.args), None, None, None, None
 
 
-def hadamard_transform(x: Tensor, block_size=None, scale=None) -> Tensor:
+def hadamard_transform(x: Tensor, block_size=None, scale=None, base=None, transpose=False) -> Tensor:
     """scale * (I (x) H_block_size) x along the last dimension of x (any leading shape; float32, bfloat16, float16).
     block_size: a power of two >= 2 dividing x.shape[-1]; None: the largest one.  scale: None: 1 / sqrt(block_size), the
-    orthonormal transform, which is its own inverse."""
+    orthonormal transform, which is its own inverse.
+    base = 12, 20, 28 or 36: H_block_size = H_base (x) H_P, H_base the Paley matrix; block_size base * P, P a power of
+    two, dividing x.shape[-1]; None: the largest one.  transpose: H_base transposed -- with the default scale the inverse
+    of the plain call (orders 12 and 20 are not symmetric).  Without a base the matrix is symmetric and transpose changes
+    nothing."""
     if x.dtype not in _DTYPES:
         raise TypeError('hadamard_transform: dtype %s (float32, bfloat16, float16)' % x.dtype)
     if x.dim() < 1:
         raise ValueError('hadamard_transform: a tensor with at least one dimension')
-    block = _check_block(block_size, x.shape[-1])
+    if base is None:
+        block = _check_block(block_size, x.shape[-1])
+    else:
+        block = _check_kron_block(block_size, base, x.shape[-1])
     scale = 1.0 / math.sqrt(block) if scale is None else float(scale)
-    return _HadamardFn.apply(x, block, scale)
+    return _HadamardFn.apply(x, block, scale, base, bool(transpose) and base is not None)
 
 
 def hadamard_matrix(n: int, dtype=torch.float32, device=None) -> Tensor:
@@ -92,3 +121,25 @@ def hadamard_matrix(n: int, dtype=torch.float32, device=None) -> Tensor:
     while h.shape[0] < n:
         h = torch.cat((torch.cat((h, h), dim=1), torch.cat((h, -h), dim=1)), dim=0)
     return h
+
+
+def paley_hadamard_matrix(k: int, dtype=torch.float32, device=None) -> Tensor:
+    """the +-1 Hadamard matrix of order k = 12, 20 (Paley I, q = k - 1: H = I + [[0, 1'], [-1, Q]], not symmetric) or
+    k = 28, 36 (Paley II, q = k / 2 - 1: H = S (x) [[1, 1], [1, -1]] + I (x) [[1, -1], [-1, -1]], S = [[0, 1'], [1, Q]],
+    symmetric); Q[i][j] = chi(i - j), chi the Legendre symbol mod q.  H H' = k I."""
+    if k not in _PALEY_PRIME:
+        raise ValueError('paley_hadamard_matrix: order %s (12, 20, 28 or 36)' % (k,))
+    q = _PALEY_PRIME[k]
+    squares = {i * i % q for i in range(1, q)}
+    i = torch.arange(q)
+    d = ((i[:, None] - i[None, :]) % q).tolist()
+    s = torch.ones(q + 1, q + 1, dtype=torch.float64)
+    s[1:, 1:] = torch.tensor([[0.0 if e == 0 else 1.0 if e in squares else -1.0 for e in r] for r in d])
+    s[0, 0] = 0.0
+    if q == k - 1:
+        s[1:, 0] = -1.0
+        h = torch.eye(k, dtype=torch.float64) + s
+    else:
+        two = lambda *rows: torch.tensor(rows, dtype=torch.float64)  # noqa: E731
+        h = torch.kron(s, two([1, 1], [1, -1])) + torch.kron(torch.eye(q + 1, dtype=torch.float64), two([1, -1], [-1, -1]))
+    return h.to(dtype=dtype, device=device)

@@ -5,6 +5,10 @@ fed x, and a layer whose weight is R W (bias R bias) emits R y.  Merged into a w
 merged is paid on every forward by the transform kernel (nn.RotatedModule).  A rotation spreads a few outlier channels
 over all channels of a block before a quantizer sees them.
 
+With base = 12, 20, 28 or 36 the rotation is R = I (x) (H_base (x) H_P) / sqrt(b) (hadamard_transform(.., base=base)), still
+orthogonal but for 12 and 20 not symmetric: the weight fed R x is W R', the transform of the rows of W by R itself
+(row o of W R' is R w_o), so both merges call the plain transform and none the transposed one.
+
 Linear layers only (QuantLinear, torch.nn.Linear), and before quantizing: a frozen layer's weight holds codes.
 """
 import torch
@@ -22,30 +26,30 @@ def _check(layer, what):
                            'before quantizing' % what)
 
 
-def _rotate_last(t, block_size):
-    """t R along the last dimension, computed in float32 and stored in t's dtype"""
-    return hadamard_transform(t.detach().to(torch.float32), block_size).to(t.dtype)
+def _rotate_last(t, block_size, base):
+    """R applied to every vector along the last dimension of t (t R'), computed in float32 and stored in t's dtype"""
+    return hadamard_transform(t.detach().to(torch.float32), block_size, base=base).to(t.dtype)
 
 
 @torch.no_grad()
-def merge_input_rotation(layer, block_size=None):
-    """W <- W R: the layer now expects R x where it expected x"""
+def merge_input_rotation(layer, block_size=None, base=None):
+    """W <- W R': the layer now expects R x where it expected x"""
     _check(layer, 'merge_input_rotation')
-    layer.weight.copy_(_rotate_last(layer.weight, block_size))
+    layer.weight.copy_(_rotate_last(layer.weight, block_size, base))
     return layer
 
 
 @torch.no_grad()
-def merge_output_rotation(layer, block_size=None):
+def merge_output_rotation(layer, block_size=None, base=None):
     """W <- R W, bias <- R bias: the layer now emits R y where it emitted y"""
     _check(layer, 'merge_output_rotation')
-    layer.weight.copy_(_rotate_last(layer.weight.t(), block_size).t())
+    layer.weight.copy_(_rotate_last(layer.weight.t(), block_size, base).t())
     if layer.bias is not None:
-        layer.bias.copy_(_rotate_last(layer.bias, block_size))
+        layer.bias.copy_(_rotate_last(layer.bias, block_size, base))
     return layer
 
 
-def rotate_pair(producer, consumer, block_size=None):
+def rotate_pair(producer, consumer, block_size=None, base=None):
     """the output side of `producer` and the input side of `consumer`: with only linear maps between the two, the
     composition is unchanged, and what flows between them is rotated"""
     _check(producer, 'rotate_pair')
@@ -53,12 +57,12 @@ def rotate_pair(producer, consumer, block_size=None):
     if producer.out_features != consumer.in_features:
         raise ValueError('rotate_pair: the producer emits %d features, the consumer takes %d'
                          % (producer.out_features, consumer.in_features))
-    merge_output_rotation(producer, block_size)
-    merge_input_rotation(consumer, block_size)
+    merge_output_rotation(producer, block_size, base)
+    merge_input_rotation(consumer, block_size, base)
 
 
-def insert_online_rotation(model, name, block_size=None):
-    """merge the input rotation into the layer `name` of model and put RotatedModule(layer, block_size) in its place:
+def insert_online_rotation(model, name, block_size=None, base=None):
+    """merge the input rotation into the layer `name` of model and put RotatedModule(layer, block_size, base) in its place:
     the float function of the model is unchanged, the layer's input quantizer and weight quantizer see rotated
     tensors -> the RotatedModule"""
     from brevitas_amd.nn import RotatedModule
@@ -67,7 +71,7 @@ def insert_online_rotation(model, name, block_size=None):
     parent_name, _, child = name.rpartition('.')
     parent = model.get_submodule(parent_name) if parent_name else model
     layer = getattr(parent, child)
-    merge_input_rotation(layer, block_size)
-    rotated = RotatedModule(layer, block_size)
+    merge_input_rotation(layer, block_size, base)
+    rotated = RotatedModule(layer, block_size, base)
     setattr(parent, child, rotated)
     return rotated

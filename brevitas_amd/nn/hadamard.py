@@ -14,35 +14,35 @@ __all__ = ['HadamardRotation', 'RotatedModule', 'HadamardClassifier']
 
 
 class HadamardRotation(torch.nn.Module):
-    """hadamard_transform(x, block_size, scale) along the last dimension"""
+    """hadamard_transform(x, block_size, scale, base, transpose) along the last dimension"""
 
-    def __init__(self, block_size=None, scale=None):
+    def __init__(self, block_size=None, scale=None, base=None, transpose=False):
         super().__init__()
-        self.block_size, self.scale = block_size, scale
+        self.block_size, self.scale, self.base, self.transpose = block_size, scale, base, transpose
 
     def forward(self, x):
-        return hadamard_transform(x, self.block_size, self.scale)
+        return hadamard_transform(x, self.block_size, self.scale, self.base, self.transpose)
 
     def extra_repr(self):
-        return 'block_size=%s, scale=%s' % (self.block_size, self.scale)
+        return 'block_size=%s, scale=%s, base=%s, transpose=%s' % (self.block_size, self.scale, self.base, self.transpose)
 
 
 class RotatedModule(torch.nn.Module):
-    """layer(hadamard_transform(x, block_size)): the online half of a rotation whose other half is merged into the
+    """layer(hadamard_transform(x, block_size, base=base)): the online half of a rotation whose other half is merged into the
     layer's weight (graph/rotate.py: insert_online_rotation).  The layer stays a registered sub-module, so whatever
     walks named_modules() -- gptq_mode, gpfq_mode, awq_mode, learned_round_mode, the calibration modes -- still finds
     it, and sees the rotated input."""
 
-    def __init__(self, layer: torch.nn.Module, block_size=None):
+    def __init__(self, layer: torch.nn.Module, block_size=None, base=None):
         super().__init__()
         self.layer = layer
-        self.block_size = block_size
+        self.block_size, self.base = block_size, base
 
     def forward(self, x):
-        return self.layer(hadamard_transform(x, self.block_size))
+        return self.layer(hadamard_transform(x, self.block_size, base=self.base))
 
     def extra_repr(self):
-        return 'block_size=%s' % (self.block_size,)
+        return 'block_size=%s, base=%s' % (self.block_size, self.base)
 
 
 class HadamardClassifier(torch.nn.Module):

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 12
+#define BVQ_ABI_VERSION 13
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -1140,6 +1140,41 @@ int bvq_mx_decode(int dtype, int64_t groups, int group_size, int format, const v
 int bvq_hadamard_supported(int dtype, int64_t rows, int64_t cols, int64_t block, const void* x, const void* y);
 int bvq_hadamard(int dtype, const void* x, int64_t rows, int64_t cols, int64_t block, double scale, void* y,
                  bvq_stream_t stream);
+
+/* ---- Hadamard transform of order K * 2^n: y = scale * (I (x) (H_K (x) H_P)) x along the last dimension ------------------
+ * The full-width rotation of the layer widths that are no power of two: 3072 .. 12288 = 12 * 2^n, 5120 = 20 * 256,
+ * 14336 = 28 * 512, 4608 = 36 * 128.  x is [rows, cols] of dtype T, contiguous; base (K) is 12, 20, 28 or 36; block
+ * (b) is K * P, P a power of two, b | cols.  H_P is the Sylvester matrix, H_K the Paley matrix of the order, by formula
+ * (chi the Legendre symbol mod q, Q[i][j] = chi(i - j)):
+ *   Paley I,  K = 12 (q = 11), 20 (q = 19):  S = [[0, 1'], [-1, Q]], H = I + S; not symmetric, H' = I - S;
+ *   Paley II, K = 28 (q = 13), 36 (q = 17):  S = [[0, 1'], [1, Q]], H = S (x) [[1, 1], [1, -1]] + I (x) [[1, -1], [-1, -1]];
+ *                                            symmetric.
+ * A block is viewed [K][P], the K index the high digit.  Definition, which the composed route of brevitas_amd/_aten.py
+ * and this kernel compute with the same bits:
+ *   1. every element is widened to float32;
+ *   2. every sub-row of P elements takes the stages h = 1 .. P / 2 of the Hadamard transform above, in ascending order;
+ *   3. the K stage: for every column m and every output i, acc = s_i0 * v_0, then for j = 1 .. K - 1 in ascending order
+ *      acc = acc + s_ij * v_j, v_j the value of sub-row j at column m -- each step one correctly rounded float32
+ *      addition (the product by +-1 is exact); s = H_K, or its transpose when `transpose` is not 0;
+ *   4. one float32 multiply by (float)scale;
+ *   5. one rounding to T (nearest even).
+ * With transpose and scale = 1 / sqrt(b) the call is the inverse of the plain one, and the gradient of it.
+ * Geometry: one workgroup of four waves per row on the row walk.  The stages of step 2 inside a chunk and across the lanes
+ * are those of bvq_hadamard; every lane then writes the float32 image of its chunks to LDS (4 bytes per element of the row,
+ * at most 64 KiB), the one stage a 32 KiB row leaves above the lanes (K = 12, P = 128 chunks' worth) is read from the image,
+ * and in the K stage thread t takes the columns t, t + 256 ..: K loads at stride P, K accumulators in registers, K stores
+ * over the inputs.  After a barrier every lane reads its chunks back, multiplies, rounds and stores where it loaded, so y
+ * may be x.  The signs are compile-time masks per K.  ONE launch: x read once, y written once; no workspace, no atomics,
+ * nothing between workgroups.
+ * Covered: T float32, bfloat16 or float16; P * sizeof(T) a multiple of 16; cols * sizeof(T) up to 32768 (a longer last
+ * dimension is the caller's to view as [rows * H / c, c], b | c | H); x and y on 16-byte boundaries.  A bad dtype, rows or
+ * cols < 1, a base outside the four, a block that is not base times a power of two or does not divide cols, a null
+ * pointer: BVQ_ERR_INVALID; a row or sub-row length or an alignment not covered: BVQ_ERR_UNSUPPORTED; both with a
+ * bvq_last_error() text, found before anything touches the device.  bvq_hadamard_kron_supported answers 1 / 0. */
+int bvq_hadamard_kron_supported(int dtype, int64_t rows, int64_t cols, int64_t base, int64_t block, const void* x,
+                                const void* y);
+int bvq_hadamard_kron(int dtype, const void* x, int64_t rows, int64_t cols, int64_t base, int64_t block, int transpose,
+                      double scale, void* y, bvq_stream_t stream);
 
 /* Diagnostic entry (no reference counterpart): the float32 quotient the float16 quantizer kernels compute for a
  * numerator a[i] and a scale scales[j] -- the product with the correctly rounded reciprocal, corrected by one exact

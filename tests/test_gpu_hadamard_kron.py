@@ -1,0 +1,107 @@
+"""The kernel of order K * 2^n (bvq_hadamard_kron) against the composed route run on the CPU: BIT equality, both compute
+the definition of include/bvq.h ("Hadamard transform of order K * 2^n"); one case per K against a float64 dense product."""
+import math
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+BASES = (12, 20, 28, 36)
+DTYPES = {'f32': torch.float32, 'bf16': torch.bfloat16, 'f16': torch.float16}
+ROWS = 5
+ROW_MAX_BYTES = 32768
+
+
+def shapes(k, dtype):
+    """(P, cols): the smallest sub-row the kernel takes (16 bytes), the largest one wave load holds and twice it (the stage
+    through LDS; a 32 KiB row has room for twice it at K = 12 only), the largest whose block fits a row; one to three
+    blocks; of the smallest also 512 // k and 512 // k + 1, either side of the 512 chunks where the row walk deepens"""
+    size = torch.empty(0, dtype=dtype).element_size()
+    top = ROW_MAX_BYTES // size // k
+    table = []
+    for p in sorted({16 // size, 1024 // size, 2048 // size, 1 << (top.bit_length() - 1)}):
+        blocks = (1, 2, 3, 512 // k, 512 // k + 1) if p * size == 16 else (1, 2, 3)
+        table += [(p, n * k * p) for n in blocks if n * k * p * size <= ROW_MAX_BYTES]
+    return table
+
+
+def same_bits(a, b):
+    return torch.equal(a.cpu().view(torch.uint8), b.cpu().view(torch.uint8))
+
+
+@pytest.mark.parametrize('transpose', [False, True])
+@pytest.mark.parametrize('dt', list(DTYPES))
+@pytest.mark.parametrize('k', BASES)
+def test_kernel_has_the_bits_of_the_composed_route(k, dt, transpose):
+    from brevitas_amd import _native as nat
+    from brevitas_amd.function.hadamard import hadamard_transform
+    gen = torch.Generator().manual_seed(123456)
+    for p, cols in shapes(k, DTYPES[dt]):
+        b = k * p
+        x = torch.randn(ROWS, cols, generator=gen).to(DTYPES[dt])
+        xd = x.to(DEV)
+        assert nat.hadamard_kron_supported(xd, ROWS, cols, k, b), (cols, b)
+        got = nat.hadamard_kron(xd, ROWS, cols, k, b, transpose, b ** -0.5)
+        want = hadamard_transform(x, b, base=k, transpose=transpose)
+        assert same_bits(got, want), (p, cols, int((got.cpu() != want).sum()))
+        assert nat.hadamard_kron(xd, ROWS, cols, k, b, transpose, b ** -0.5, out=xd) is xd and same_bits(xd, want)  # in place
+
+
+@pytest.mark.parametrize('k', BASES)
+def test_kernel_against_the_dense_product(k):
+    """float32, P = 16: the bound of tests/test_hadamard_kron_host.py"""
+    from brevitas_amd.function.hadamard import hadamard_matrix, hadamard_transform, paley_hadamard_matrix
+    b, scale = 16 * k, 1.0 / math.sqrt(16 * k)
+    x = torch.randn(4, 2 * b, generator=torch.Generator().manual_seed(k))
+    y = hadamard_transform(x.to(DEV), b, base=k).cpu()
+    h = torch.kron(paley_hadamard_matrix(k, torch.float64), hadamard_matrix(16, torch.float64))
+    y64 = (scale * (x.double().reshape(4, 2, b) @ h.t())).reshape(4, 2 * b)
+    l1 = x.double().abs().reshape(4, 2, b).sum(dim=-1, keepdim=True).expand(4, 2, b).reshape(4, 2 * b)
+    assert ((y.double() - y64).abs() <= 1.01 * scale * (4 + k + 1) * 2.0 ** -24 * l1 + 2.0 ** -23 * y64.abs()).all()
+
+
+def test_backward_and_routing(monkeypatch):
+    """backward = transpose call; a wide last dimension is viewed again; misaligned and FUSED_PATHS off: composed route"""
+    from brevitas_amd import _native as nat
+    from brevitas_amd import config
+    from brevitas_amd.function.hadamard import hadamard_transform
+    calls, real = [], nat.hadamard_kron
+    monkeypatch.setattr(nat, 'hadamard_kron', lambda *a, **kw: calls.append(a[1:6]) or real(*a, **kw))
+    gen = torch.Generator().manual_seed(17)
+    x = torch.randn(7, 2 * 320, generator=gen).to(torch.bfloat16)
+    g = torch.randn(7, 2 * 320, generator=gen).to(torch.bfloat16)
+    xd = x.to(DEV).requires_grad_(True)
+    y = hadamard_transform(xd, 320, base=20)
+    y.backward(g.to(DEV))
+    assert [c[-1] for c in calls] == [False, True]
+    assert same_bits(y.detach(), hadamard_transform(x, 320, base=20))
+    assert same_bits(xd.grad, hadamard_transform(g, 320, base=20, transpose=True))
+    del calls[:]
+    wide = torch.randn(3, 36864, generator=gen).to(torch.bfloat16)  # 72 KiB rows, blocks of 12288: [9, 12288]
+    got = hadamard_transform(wide.to(DEV), base=12)
+    assert calls == [(9, 12288, 12, 12288, False)] and same_bits(got, hadamard_transform(wide, base=12))
+    flat = torch.empty(7 * 640 + 1, dtype=torch.bfloat16, device=DEV)
+    mis = flat[1:].view(7, 640)
+    mis.copy_(x)
+    want = hadamard_transform(x, 320, base=20)
+    assert mis.data_ptr() % 16 != 0 and same_bits(hadamard_transform(mis, 320, base=20), want)
+    monkeypatch.setattr(config, 'FUSED_PATHS', False)
+    assert same_bits(hadamard_transform(x.to(DEV), 320, base=20), want) and len(calls) == 1
+    monkeypatch.setattr(config, 'FUSED_PATHS', True)
+    assert same_bits(hadamard_transform(x.to(DEV)[:, ::2], 320, base=20), hadamard_transform(x[:, ::2], 320, base=20))
+    assert len(calls) == 2  # not contiguous: made contiguous, the kernel
+
+
+def test_rotated_module_matches_the_composed_route(monkeypatch):
+    """the output has the bits of the same model whose transform takes the composed route on the device"""
+    from brevitas_amd import _native as nat
+    from brevitas_amd.nn import QuantLinear, RotatedModule
+    from brevitas_amd.quant import Int8DynamicActPerRowFloat
+    torch.manual_seed(19)
+    layer = QuantLinear(448, 48, input_quant=Int8DynamicActPerRowFloat()).to(torch.bfloat16).to(DEV)
+    model = RotatedModule(layer, base=28)
+    x = torch.randn(7, 448).to(torch.bfloat16).to(DEV)
+    y_kernel = model(x).detach()
+    monkeypatch.setattr(nat, 'hadamard_kron_supported', lambda *a, **k: False)
+    assert same_bits(y_kernel, model(x).detach())

@@ -9,7 +9,11 @@ bf16 [8192, 8192] with b = 8192, [8192, 14336] with b = 2048 and [65536, 4096] w
       would be one more pass), O(b) multiply-adds per element;
   (d) out.copy_(x): the same bytes read and written with no arithmetic, the floor of a one-read one-write kernel.
 Interleaved rounds in one process, one warm call in front of every timed call, HIP events on the launching stream,
-median / min over the rounds (tools/rounds.py).  Before anything is timed (a) is held against (b), every bit."""
+median / min over the rounds (tools/rounds.py).  Before anything is timed (a) is held against (b), every bit.
+
+Then the full-width rotations of order K * 2^n (bvq_hadamard_kron) on bf16 [8192, 14336] with base 28 and [8192, 5120]
+with base 20, b the width: next to them the block form of the largest power of two dividing the width (bvq_hadamard,
+b = 2048 and 1024), the dense x @ R' in bf16 (R the scaled b x b matrix) and the copy."""
 import os
 import statistics
 import sys
@@ -19,6 +23,7 @@ from rounds import ROOT
 
 ROUNDS = 9
 CASES = ((8192, 8192, 8192), (8192, 14336, 2048), (65536, 4096, 32))
+KRON_CASES = ((8192, 14336, 28), (8192, 5120, 20))  # rows, cols = b, base
 
 
 def main():
@@ -75,6 +80,43 @@ def main():
         a, bb, cc, d = (med[name] for name in cands)
         say('(a) / (d) %.2f, (b) / (a) %.1f, (c) / (a) %.1f' % (a / d, bb / a, cc / a))
         del x, out, h
+    from brevitas_amd.function.hadamard import hadamard_transform, paley_hadamard_matrix
+    for rows, cols, base in KRON_CASES:
+        torch.manual_seed(0)
+        x = torch.randn(rows, cols, device=dev).to(dt)
+        out = torch.empty_like(x)
+        pow2 = cols & -cols
+        assert nat.hadamard_kron_supported(x, rows, cols, base, cols, out) and nat.hadamard_supported(x, rows, cols, pow2, out)
+        rt = (torch.kron(paley_hadamard_matrix(base, torch.float64), hadamard_matrix(cols // base, torch.float64)).t()
+              / cols ** 0.5).to(dt).to(dev)
+
+        def kron():
+            return nat.hadamard_kron(x, rows, cols, base, cols, False, cols ** -0.5, out=out)
+
+        def block():
+            return nat.hadamard(x, rows, cols, pow2, pow2 ** -0.5, out=out)
+
+        def dense():
+            return torch.matmul(x, rt)
+
+        def copy():
+            return out.copy_(x)
+
+        head = x[:64].cpu()
+        same = torch.equal(kron()[:64].cpu().view(torch.int16),
+                           hadamard_transform(head, cols, base=base).view(torch.int16))
+        nbytes = x.numel() * x.element_size()
+        say('## [%d, %d], base %d, b = %d (%d MiB)' % (rows, cols, base, cols, nbytes >> 20))
+        say('kernel vs the composed route on the CPU, first 64 rows: every bit equal: %s' % same)
+        assert same
+        cands = {'(a) kron kernel, b = %d' % cols: kron, '(b) block form, b = %d' % pow2: block,
+                 "(c) dense x @ R', bf16": dense, '(d) out.copy_(x)': copy}
+        res = rounds.timed_rounds(cands, ROUNDS)
+        say('%-42s %10s %10s  %s' % ('', 'median ms', 'min ms', 'TB/s of x read + y written at the median'))
+        for name, ts in res.items():
+            m = statistics.median(ts)
+            say('%-42s %10.4f %10.4f  %5.2f' % (name, m, min(ts), 2 * nbytes / m / 1e9))
+        del x, out, rt
     if out_path:
         os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
         with open(out_path, 'w') as fh:
