@@ -234,6 +234,30 @@ def group_mse_quantize_at(ratios, idx, stat, scale_of, quantize):
     return quantize(scale), scale
 
 
+def group_clip_index(xg, hb, ratios, stat, scale_of, quantize):
+    """AWQ's clip search (graph/awq.py), composed: group_mse_index with the output error d^T hb[j] d in place of sum d^2.
+    xg [R * K / g, g], hb float32 [K / g, g, g] (group j of every row under block j), the callables as above ->
+    (idx uint8 [R, K / g], losses float32 [R, K / g, n]).  Per candidate one float32 einsum; the first strict minimum is
+    kept and a NaN loss is below nothing."""
+    with torch.no_grad():
+        nj, g = hb.shape[0], hb.shape[1]
+        xf = xg.float().reshape(-1, nj, g)
+        hb = hb.to(device=xg.device, dtype=torch.float32)
+        idx = torch.zeros(xf.shape[:2], dtype=torch.uint8, device=xg.device)
+        best, losses = None, []
+        for i, r in enumerate(ratios):
+            d = quantize(scale_of(group_mse_threshold(stat, r))).float().reshape(xf.shape) - xf
+            e = torch.einsum('rja,jab,rjb->rj', d, hb, d)
+            losses.append(e)
+            if best is None:
+                best = e
+                continue
+            better = e < best
+            idx = torch.where(better, torch.full_like(idx, i), idx)
+            best = torch.where(better, e, best)
+    return idx, torch.stack(losses, dim=2)
+
+
 # ---- group-wise HQO zero-point (core/quant/int.py: GroupwiseHQOIntQuant), the composed route ------------------
 # The search takes the module's own integer conversion as a callable, to_int(zero_point [groups, 1]) -> q [groups, g], so
 # it runs the same ops as the plain asymmetric quantizer.  It serves CPU and device tensors alike and defines what the

@@ -39,7 +39,7 @@ MX_FLOOR, MX_CEIL = 0, 1
 LR_HARD_SIGMOID, LR_SIGMOID = 0, 1  # bvq_learned_round_impl
 NORM_L1, NORM_L2 = 0, 1  # bvq_norm_kind
 _CODES_TORCH = {CODES_I32: torch.int32, CODES_I8: torch.int8, CODES_U8: torch.uint8}
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -188,6 +188,8 @@ _SIG = {
     'bvq_group_hqo_bwd': (_i32, [_qd, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _vp, _vp]),
     'bvq_group_awq_supported': (_i32, [_qd, _vp, _vp, _vp, _i64, _i32]),
     'bvq_group_awq_fwd': (_i32, [_qd, _vp, _vp, _i64, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp]),
+    'bvq_group_clip_supported': (_i32, [_qd, _vp, _vp, _i64, _i32]),
+    'bvq_group_clip_fwd': (_i32, [_qd, _vp, _vp, _i64, _vp, _i32, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
     'bvq_row_shifted_max_row_bytes': (_i64, []),
     'bvq_row_shifted_supported': (_i32, [_qd, _vp]),
     'bvq_row_shifted_fwd': (_i32, [_qd, _vp, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
@@ -710,6 +712,38 @@ def group_awq_fwd(desc, x, table, min_val, thr_div):
     _launch(dev, 'bvq_group_awq_fwd', 'bvq_group_awq_fwd', ctypes.byref(desc), ptr(x), ptr(table), int(k), int(n),
             *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(zp))
     return y, scale, zp
+
+
+CLIP_MAX_CANDIDATES = 16
+
+
+def group_clip_supported(desc, x, hb, n_ratios):
+    """the AWQ clip-search kernel covers this descriptor (that of group_quant_*), the weight x [R, K], the Hessian
+    blocks hb float32 [K / g, g, g] and the candidate count"""
+    g = int(desc.inner)
+    if x.dim() != 2 or not (x.is_contiguous() and hb.is_contiguous()) or hb.dtype != torch.float32 or \
+            hb.device != x.device or tuple(hb.shape) != (x.shape[1] // g, g, g):
+        return False
+    return bool(lib.bvq_group_clip_supported(ctypes.byref(desc), ptr(x), ptr(hb), int(x.shape[1]), int(n_ratios)))
+
+
+def group_clip_fwd(desc, x, hb, table, min_val, thr_div):
+    """abs-max per group and the search over the thresholds abs-max * table[i] (mse_ratio_table) under the output error
+    d^T hb[j] d, in ONE launch -> (y like x, scale [R, K / g], stat [R, K / g], idx uint8 [R, K / g], losses float32
+    [R, K / g, n])"""
+    dev = require_device(x, hb)
+    assert x.is_contiguous() and hb.is_contiguous() and x.dim() == 2 and hb.dtype == torch.float32
+    rows, k = x.shape
+    groups, n = k // int(desc.inner), len(table)
+    y = torch.empty_like(x)
+    scale = torch.empty(rows, groups, dtype=x.dtype, device=dev)
+    stat = torch.empty(rows, groups, dtype=x.dtype, device=dev)
+    idx = torch.empty(rows, groups, dtype=torch.uint8, device=dev)
+    losses = torch.empty(rows, groups, n, dtype=torch.float32, device=dev)
+    _launch(dev, 'bvq_group_clip_fwd', 'bvq_group_clip_fwd', ctypes.byref(desc), ptr(x), ptr(hb), int(k),
+            ctypes.addressof(table), n, *_scale_args(min_val, thr_div), ptr(y), ptr(scale), ptr(stat), ptr(idx),
+            ptr(losses))
+    return y, scale, stat, idx, losses
 
 
 def row_shifted_max_row_bytes():

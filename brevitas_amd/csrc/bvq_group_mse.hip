@@ -26,12 +26,6 @@ struct GroupMseArgs : GroupArgs {
   float ratio[kMseMaxRatios];
 };
 
-// a candidate's threshold: the statistic (a value of T) times the float32 ratio, formed in float32, rounded once to T
-template <typename T>
-__device__ __forceinline__ float mse_threshold(float stat, float ratio) {
-  return rnd<T>(stat * ratio);
-}
-
 // this lane's part of a candidate's error: sum over its chunk of (float32(y) - float32(x))^2, y the value of T that the
 // forward would store for the scale s
 template <typename T, typename Div>

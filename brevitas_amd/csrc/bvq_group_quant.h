@@ -27,6 +27,13 @@ __device__ __forceinline__ float group_scale(float stat, bool use_min, float min
   return rnd<T>(thr / thr_div);
 }
 
+// a clip-search candidate's threshold (bvq_group_mse.hip, bvq_group_clip.hip): the statistic (a value of T) times the
+// float32 ratio, formed in float32, rounded once to T
+template <typename T>
+__device__ __forceinline__ float mse_threshold(float stat, float ratio) {
+  return rnd<T>(stat * ratio);
+}
+
 // the forward chain of IntQuant on a pair (the rounding points of bvq_quant_math.h; the last rounding is the caller's
 // pack2<T>).  16-bit types: the zero-point is +0, "+ zp" only turns -0 into +0 and "- zp" is the identity.
 // kZp: the group has a zero-point of its own (bvq_group_shifted.hip), added and subtracted with their roundings.

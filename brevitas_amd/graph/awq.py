@@ -21,21 +21,30 @@ Both hand their candidates to the same loss function.
 
 update() writes the dequantized codes Q into `layer.weight.data`, freezes the layer as GPTQ does and registers the
 buffer `awq_input_scale` [K]: the integer codes of the layer are round(weight * awq_input_scale / scale + zero_point).
-Folding 1 / s into a preceding layer, AWQ's clip search, convolutions and a backward are out of scope."""
+
+AWQ's second stage, the activation-aware clip search (`auto_clip` of the paper's code), is awq_clip_weight, and
+awq_mode(model, clip=True) runs it behind the column-factor search: per group of the scaled weight the threshold
+abs-max * ratio_i whose output error d^T H_jj d under the calibration activations is smallest ("AWQ clip
+search"), all candidates of all groups in one bvq_group_clip_fwd launch (csrc/bvq_group_clip.hip) or composed from the
+quantizer's sub-modules and one einsum per candidate.  Symmetric group-wise quantizers only.
+
+Folding 1 / s into a preceding layer, a clip search for asymmetric groups, convolutions and a backward are out of
+scope."""
 from typing import Iterator, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
 
 import brevitas_amd.config as config
+from brevitas_amd import _aten
 from brevitas_amd import _native as nat
 from brevitas_amd.core.quant import _fused
 from brevitas_amd.core.quant.int import (GroupwiseHQOIntQuant, GroupwiseMSEIntQuant, GroupwiseRescalingIntQuant,
-                                         RescalingIntQuant)
+                                         RescalingIntQuant, check_mse_ratios)
 from brevitas_amd.graph import gptq
 
 __all__ = ['awq_mode', 'awq_scale_weight', 'awq_candidates', 'awq_losses', 'awq_table', 'AWQResult',
-           'freeze_awq_weight']
+           'freeze_awq_weight', 'awq_clip_weight', 'awq_clip_ratios', 'hessian_blocks', 'AWQClipResult']
 
 
 class AWQResult(NamedTuple):
@@ -46,6 +55,15 @@ class AWQResult(NamedTuple):
     input_scale: Tensor  # [K] in the weight's dtype: the kept column factor
     index: int           # the kept candidate
     losses: Tensor       # float32 [n_grid]
+
+
+class AWQClipResult(NamedTuple):
+    q: Tensor            # the dequantized codes with the column factor divided out, shaped and typed like the weight
+    scale: Tensor        # [R, K / g, 1]: the scale of weight * input_scale at the kept threshold
+    zero_point: Tensor
+    bit_width: Tensor
+    index: Tensor        # uint8 [R, K / g]: the kept candidate of every group
+    losses: Tensor       # float32 [R, K / g, n]: every candidate's output error, of the scaled weight
 
 
 def _plan(quantizer, k: int) -> 'gptq._Plan':
@@ -185,6 +203,107 @@ def awq_scale_weight(weight: Tensor, hessian: Tensor, act_mean: Tensor, quantize
         return AWQResult(q.reshape(weight.shape), scale, zp, bit_width, table[index].clone(), index, torch.cat(losses))
 
 
+# ---- the clip search -------------------------------------------------------------------------------------------------
+
+def awq_clip_ratios(n_grid: int = 20, max_shrink: float = 0.5) -> Tensor:
+    """the candidate ratios of the clip search, float32 on the host: 1 - i / n_grid for i < int(max_shrink * n_grid), as
+    the AWQ reference implementation walks them; formed in float32 so that every device searches the same thresholds.
+    At least one, at most 16 (the kernel's candidate count)."""
+    if int(n_grid) < 1:
+        raise ValueError('awq: n_grid must be positive, got %r' % (n_grid,))
+    n = int(float(max_shrink) * int(n_grid))
+    if n > nat.CLIP_MAX_CANDIDATES:
+        raise ValueError('awq: %d clip ratios (max_shrink=%r of n_grid=%r); at most %d'
+                         % (n, max_shrink, n_grid, nat.CLIP_MAX_CANDIDATES))
+    ratios = 1.0 - torch.arange(n, dtype=torch.float32) / torch.tensor(float(n_grid), dtype=torch.float32)
+    check_mse_ratios(ratios.tolist())
+    return ratios
+
+
+def hessian_blocks(hessian: Tensor, g: int, input_scale: Optional[Tensor] = None) -> Tensor:
+    """float32 [K / g, g, g], contiguous: block j is hessian[j g:(j + 1) g, j g:(j + 1) g], what the output error of a
+    change inside group j depends on.  input_scale [K]: the blocks for a weight whose columns were multiplied by it --
+    entry (a, b) divided by s_a * s_b in float32, so that d^T block d is the error of d / s."""
+    k = hessian.shape[0]
+    if hessian.dim() != 2 or hessian.shape[1] != k or int(g) < 1 or k % int(g):
+        raise ValueError('awq: a Hessian of shape %s has no diagonal blocks of %r columns' % (tuple(hessian.shape), g))
+    nj = k // int(g)
+    j = torch.arange(nj, device=hessian.device)
+    hb = hessian.detach().float().reshape(nj, g, nj, g)[j, :, j, :]
+    if input_scale is not None:
+        s = input_scale.detach().to(device=hb.device, dtype=torch.float32).reshape(nj, g)
+        hb = hb / (s[:, :, None] * s[:, None, :])
+    return hb.contiguous()
+
+
+def _clip_fused_args(plan: 'gptq._Plan', x: Tensor, hb: Tensor, n: int):
+    """(descriptor, min_val, thr_div) of bvq_group_clip_fwd, or None: the configuration, the quantizer's graph or the
+    tensors are not what the kernel covers"""
+    if not (x.is_cuda and config.FUSED_PATHS and x.dtype in _fused._FLOATS):
+        return None
+    tmpl = plan.quant._group_template(plan.bit_width)
+    if tmpl is None or tmpl.shifted:
+        return None
+    desc, thr_div = _fused.unit_call(x, plan.group, False, tmpl.int_thr, tmpl.qmin, tmpl.qmax, tmpl.clamp_ste)
+    if not nat.group_clip_supported(desc, x, hb, n):
+        return None
+    return desc, tmpl.min_val, thr_div
+
+
+def awq_clip_weight(weight: Tensor, hessian: Tensor, quantizer, *, ratios=None, input_scale: Optional[Tensor] = None,
+                    name: str = '') -> AWQClipResult:
+    """AWQ's clip search for `weight` ([R, ...], flattened to [R, K]) under `hessian` ([K, K], as awq_mode accumulates
+    it) with the codes of `quantizer`, the weight's own symmetric group-wise quantizer.  Per row and group of
+    x = weight * input_scale (one torch.mul in the weight's dtype; the weight itself without a factor) the threshold
+    abs-max * ratios[i] is kept whose loss d^T hb d is the first strict minimum, d = y_i - x in float32 and hb =
+    hessian_blocks(hessian, g, input_scale): the loss is that of the SCALED weight under the blocks divided by the
+    factors, which is the output error of q = y / input_scale.  ratios: awq_clip_ratios() unless given (float32, the
+    first 1, at most 16).  Nothing is changed in place.  name: the layer's, for the errors."""
+    with torch.no_grad():
+        rows = weight.shape[0]
+        w2 = weight.detach().reshape(rows, -1).contiguous()
+        k = w2.shape[1]
+        plan = _plan(quantizer, k)
+        if plan.shifted:
+            raise TypeError('awq: the clip search of layer %r does not cover the asymmetric quantizer %s (its zero-point '
+                            'moves with the threshold; symmetric group-wise quantizers only)'
+                            % (name, type(quantizer).__name__))
+        if tuple(hessian.shape) != (k, k) or (input_scale is not None and input_scale.numel() != k):
+            raise ValueError('awq: a Hessian of shape %s%s for %d input columns'
+                             % (tuple(hessian.shape), '' if input_scale is None else
+                                ' and an input_scale of %d entries' % input_scale.numel(), k))
+        ratios = awq_clip_ratios() if ratios is None else torch.as_tensor(ratios, dtype=torch.float32).cpu()
+        table = check_mse_ratios(ratios.tolist())
+        if len(table) > nat.CLIP_MAX_CANDIDATES:
+            raise ValueError('awq: %d clip ratios; at most %d' % (len(table), nat.CLIP_MAX_CANDIDATES))
+        g, q = plan.group, plan.quant
+        if input_scale is not None:
+            input_scale = input_scale.detach().to(device=w2.device, dtype=w2.dtype).reshape(k)
+        x = w2 if input_scale is None else w2 * input_scale
+        hb = hessian_blocks(hessian.to(w2.device), g, input_scale)
+        fa = _clip_fused_args(plan, x, hb, len(table))
+        if fa is not None:
+            y, scale, _, index, losses = nat.group_clip_fwd(fa[0], x, hb, nat.mse_ratio_table(table), fa[1], fa[2])
+        else:
+            xg = x.reshape(-1, g)
+            sc = q.scaling_impl
+            stat = sc.parameter_list_stats.stats.stats_impl(xg).reshape(-1, 1)  # of the groups at hand (gptq._group_params)
+            int_threshold = q.int_scaling_impl(plan.bit_width)
+
+            def scale_of(threshold):
+                return sc.stats_scaling_impl(threshold) / int_threshold
+
+            def quantize(s):
+                return q.int_quant(s, q.zero_point_impl(xg, s, plan.bit_width), plan.bit_width, xg)
+            index, losses = _aten.group_clip_index(xg, hb, table, stat, scale_of, quantize)
+            y, scale = _aten.group_mse_quantize_at(table, index.reshape(-1), stat, scale_of, quantize)
+        y = y.reshape(rows, k)
+        scale = scale.reshape(rows, k // g, 1)
+        return AWQClipResult((y if input_scale is None else y / input_scale).reshape(weight.shape), scale,
+                             q.zero_point_impl(w2, scale, plan.bit_width), plan.bit_width, index.reshape(rows, k // g),
+                             losses)
+
+
 def freeze_awq_weight(layer, scale: Tensor, zero_point: Tensor, input_scale: Tensor) -> None:
     """freeze_weight_quant, and the buffer `awq_input_scale` [K] that says which column factor the codes were taken
     under: codes = round(weight * awq_input_scale / scale + zero_point).  (By hand: to load a checkpoint of a searched
@@ -205,13 +324,20 @@ class awq_mode(gptq.gptq_mode):
     width, half-even rounding) that is not frozen, in module order; anything else with a weight quantizer is refused on
     entry.  Next to the Hessian the current layer accumulates the mean of |x| per input column, from the same rows.
     update() searches the column factor (awq_scale_weight), writes Q into `layer.weight.data`, freezes the layer
-    (freeze_awq_weight) and moves on: the next layer calibrates on the output of the frozen ones."""
+    (freeze_awq_weight) and moves on: the next layer calibrates on the output of the frozen ones.
 
-    def __init__(self, model: torch.nn.Module, n_grid: int = 20):
+    clip=True: behind the column-factor search update() runs the clip search on the kept factor (awq_clip_weight with
+    awq_clip_ratios(n_grid, max_shrink)) and freezes the layer from its q and scale; the AWQClipResult of the last
+    layer is `last_clip`.  Symmetric quantizers only then: an asymmetric one is refused on entry."""
+
+    def __init__(self, model: torch.nn.Module, n_grid: int = 20, clip: bool = False, max_shrink: float = 0.5):
         super().__init__(model)
         if int(n_grid) < 1:
             raise ValueError('awq_mode: n_grid must be positive, got %r' % (n_grid,))
         self.n_grid = int(n_grid)
+        self.clip = bool(clip)
+        self.clip_ratios = awq_clip_ratios(n_grid, max_shrink) if self.clip else None
+        self.last_clip = None
         self._abs = None
 
     def _admit(self, name: str, m) -> None:
@@ -219,7 +345,9 @@ class awq_mode(gptq.gptq_mode):
         if not isinstance(m, QuantLinear):
             raise NotImplementedError('awq_mode: layer %r (%s with the weight quantizer %s) is not covered: '
                                       'QuantLinear only' % (name, type(m).__name__, type(m.weight_quant).__name__))
-        _plan(m.weight_quant, m.weight.shape[1])
+        if _plan(m.weight_quant, m.weight.shape[1]).shifted and self.clip:
+            raise TypeError('awq_mode: layer %r: the clip search does not cover the asymmetric quantizer %s'
+                            % (name, type(m.weight_quant).__name__))
 
     def _reset(self) -> None:
         super()._reset()
@@ -237,8 +365,13 @@ class awq_mode(gptq.gptq_mode):
 
     def _quantize(self, name: str, layer) -> AWQResult:
         dev = layer.weight.device
-        return awq_scale_weight(layer.weight, self._h.to(dev), self.act_mean.to(dev), layer.weight_quant,
-                                n_grid=self.n_grid, name=name)
+        res = awq_scale_weight(layer.weight, self._h.to(dev), self.act_mean.to(dev), layer.weight_quant,
+                               n_grid=self.n_grid, name=name)
+        if not self.clip:
+            return res
+        self.last_clip = awq_clip_weight(layer.weight, self._h.to(dev), layer.weight_quant, ratios=self.clip_ratios,
+                                         input_scale=res.input_scale, name=name)
+        return res._replace(q=self.last_clip.q, scale=self.last_clip.scale, zero_point=self.last_clip.zero_point)
 
     def _freeze(self, layer, res: AWQResult) -> None:
         freeze_awq_weight(layer, res.scale, res.zero_point, res.input_scale)

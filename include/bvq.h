@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define BVQ_ABI_VERSION 13
+#define BVQ_ABI_VERSION 14
 
 typedef void* bvq_stream_t; /* hipStream_t */
 
@@ -836,6 +836,34 @@ int bvq_group_awq_supported(const bvq_quant_desc* desc, const void* x, const voi
                             int n);
 int bvq_group_awq_fwd(const bvq_quant_desc* desc, const void* x, const void* table, int64_t k, int n, double min_val,
                       int use_min, double thr_div, void* y, void* scale, void* zp, bvq_stream_t stream);
+
+/* ---- AWQ: the activation-aware clip search over a group-wise weight -----------------------------------------------------
+ * The second stage of AWQ (`auto_clip` of the paper's code; no reference counterpart): the clip search of the MSE section
+ * with the data-free error sum d^2 replaced by the output error of the group under the calibration activations.  x is the
+ * weight [R, K] of dtype T, contiguous; the descriptor is that of the group-wise section (symmetric, zp_per_channel = 0)
+ * with channels = R * K / g groups, g = 16, 32, 64 or 128; k = K, a multiple of g.  hb: float32 [K / g, g, g] on the DEVICE,
+ * hb[j] the diagonal block of the layer's input Hessian over the columns of group j.  ratios: a HOST array of n_ratios
+ * floats, copied into the kernel's arguments; ratios[0] == 1, every ratio finite and in (0, 1], 1 <= n_ratios <= 16.
+ * min_val / use_min / thr_div as in the group-wise section.  Per row r and group j:
+ *     a   = max |x|                                      (stat, a value of T)
+ *     t_i = T(a * ratios[i]),  s_i = T(clamp_min(t_i, min_val) / thr_div)     (exactly bvq_group_mse_fwd's)
+ *     y_i = quantize-dequantize of the group at s_i      (the values of T that bvq_group_quant_fwd would store)
+ *     d_i = float32(y_i) - float32(x)
+ *     loss_i = sum_a sum_b d_i[a] * hb[j][a][b] * d_i[b]  (float32; products and sums in the kernel's own fixed order)
+ *     k   = the first i with loss_i < loss_m for every m < i   (strict; a NaN loss is below nothing: a group with a NaN or
+ *           Inf keeps k = 0)
+ *   y = y_k [R, K], scale = s_k and stat = a [R, K / g] in T, idx = k as uint8 [R, K / g], losses float32 [R, K / g, n].
+ *   For a given idx, y, scale and stat have the bits of bvq_group_mse_fwd with the same ratios.
+ * One launch: x is read once, a workgroup keeps hb[j] in LDS for 512 rows and forms the n losses of a (row, group) as one
+ * float32 matrix-instruction product; nothing of size [n, R, K] exists; no workspace, no atomics.  There is no backward:
+ * the search is applied after training and the layer is frozen afterwards.  Covered: what the group-wise entries cover
+ * with g <= 128; x, hb and y on 16-byte boundaries; the ratios as above.  Anything else -- asymmetric descriptors among it
+ * -- returns BVQ_ERR_UNSUPPORTED with a bvq_last_error() text, found before anything touches the device;
+ * bvq_group_clip_supported answers 1 / 0. */
+int bvq_group_clip_supported(const bvq_quant_desc* desc, const void* x, const void* hb, int64_t k, int n_ratios);
+int bvq_group_clip_fwd(const bvq_quant_desc* desc, const void* x, const void* hb, int64_t k, const float* ratios,
+                       int n_ratios, double min_val, int use_min, double thr_div, void* y, void* scale, void* stat,
+                       void* idx, void* losses, bvq_stream_t stream);
 
 /* ---- asymmetric per-row activations: one scale and one integer zero-point per row, from the row itself ----------------
  * The per-token quantizer of the dynamic activation quantizers (ShiftedUint8DynamicActPerRowFloat).  x is [rows, H],
