@@ -732,9 +732,13 @@ def group_clip_fwd(desc, x, hb, table, min_val, thr_div):
     d^T hb[j] d, in ONE launch -> (y like x, scale [R, K / g], stat [R, K / g], idx uint8 [R, K / g], losses float32
     [R, K / g, n])"""
     dev = require_device(x, hb)
-    assert x.is_contiguous() and hb.is_contiguous() and x.dim() == 2 and hb.dtype == torch.float32
+    assert x.is_contiguous() and hb.is_contiguous() and x.dim() == 2
     rows, k = x.shape
     groups, n = k // int(desc.inner), len(table)
+    if hb.dtype != torch.float32 or tuple(hb.shape) != (groups, int(desc.inner), int(desc.inner)):
+        # the kernel reads hb[j] for every group column j: a smaller hb would be read past its end
+        raise BvqError('bvq_group_clip_fwd: hb is %s %s, not float32 %s (one block per group column)'
+                       % (hb.dtype, tuple(hb.shape), (groups, int(desc.inner), int(desc.inner))))
     y = torch.empty_like(x)
     scale = torch.empty(rows, groups, dtype=x.dtype, device=dev)
     stat = torch.empty(rows, groups, dtype=x.dtype, device=dev)

@@ -5,6 +5,9 @@ compare with the rows of the Sylvester matrix and localise a wrong pairing or si
 import pytest
 import torch
 
+from test_group_mse_host import same_bits
+from test_gpu_group_walk import use_nt0  # noqa: F401  (fixture: the forced-NT build of the library)
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
@@ -54,9 +57,7 @@ def kernel_calls(monkeypatch):
     return calls
 
 
-@pytest.mark.parametrize('geometry', list(GEOMETRY))
-@pytest.mark.parametrize('dt', list(DTYPES))
-def test_size_sweep(dt, geometry):
+def size_sweep(dt, geometry):
     """every power-of-two block from 2 to the largest dividing the row, rows whose last load is ragged"""
     from brevitas_amd import _native as nat
     dtype = DTYPES[dt]
@@ -72,6 +73,59 @@ def test_size_sweep(dt, geometry):
             want = cpu_route(x, b)
             assert torch.equal(got.view(torch.uint8), want.view(torch.uint8)), \
                 (dt, cols, b, int((got != want).sum()), (got.float() - want.float()).abs().max().item())
+
+
+@pytest.mark.parametrize('geometry', list(GEOMETRY))
+@pytest.mark.parametrize('dt', list(DTYPES))
+def test_size_sweep(dt, geometry):
+    size_sweep(dt, geometry)
+
+
+@pytest.mark.parametrize('geometry', list(GEOMETRY))
+def test_size_sweep_forced_nt(geometry, use_nt0):  # noqa: F811
+    """the non-temporal loads and stores of every geometry: by size only the 4 GiB case takes them, at depth 8"""
+    use_nt0()
+    for dt in ('f32', 'bf16'):
+        size_sweep(dt, geometry)
+
+
+def special_rows(dtype, cols, block):
+    """[6, cols]: NaN, +inf, -inf and both infinities in four different blocks of an ordinary row; -0.0 everywhere;
+    zeros of both signs; subnormals of the dtype; the largest finite values (the sums overflow); subnormals among
+    ordinary values"""
+    assert cols >= 4 * block
+    gen = torch.Generator().manual_seed(29)
+    fi = torch.finfo(dtype)
+    x = torch.randn(6, cols, generator=gen)
+    x[0, 3], x[0, block + 5], x[0, 2 * block + 7] = float('nan'), float('inf'), float('-inf')
+    x[0, 3 * block + 1], x[0, 4 * block - 2] = float('inf'), float('-inf')
+    x[1] = -0.0
+    x[2] = torch.where(x[2] < 0, -0.0, 0.0)
+    x = x.to(dtype)
+    sub = (torch.randint(-100, 101, (cols,), generator=gen).double() * fi.smallest_normal * 2.0 ** -7).to(dtype)
+    assert bool(((sub != 0) & (sub.abs() < fi.smallest_normal)).any())
+    x[3] = sub
+    x[4] = torch.where(x[4] < 0, -fi.max, fi.max).to(dtype)
+    x[5, ::3] = sub[::3]
+    return x
+
+
+def test_special_values():
+    """inf - inf, NaN, signed zeros, subnormal inputs and overflowing sums follow the definition's float32 operations:
+    NaN where the composed route on the CPU has NaN, its bits everywhere else; every geometry and dtype"""
+    from brevitas_amd import _native as nat
+    for geometry in GEOMETRY:
+        for dt, dtype in DTYPES.items():
+            cols = GEOMETRY[geometry][-1] * vec(dtype)
+            x = special_rows(dtype, cols, 128)
+            for b in (128, cols):
+                got = nat.hadamard(x.to(DEV), 6, cols, b, b ** -0.5).cpu()
+                want = cpu_route(x, b)
+                if b == 128:   # the NaN fills its block, inf - inf half of its block, one infinity alone makes no NaN
+                    nan = torch.isnan(want[0])
+                    assert bool(nan[:128].all()) and bool(nan[384:512].any()) and not bool(nan[128:384].any())
+                assert same_bits(got, want), \
+                    (dt, cols, b, (~((got == want) | (got.isnan() & want.isnan()))).nonzero()[:8].tolist())
 
 
 @pytest.mark.parametrize('geometry', list(GEOMETRY))

@@ -5,6 +5,10 @@ import math
 import pytest
 import torch
 
+from test_gpu_group_walk import use_nt0  # noqa: F401  (fixture: the forced-NT build of the library)
+from test_gpu_hadamard import special_rows
+from test_group_mse_host import same_bits as same_bits_or_nan
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 BASES = (12, 20, 28, 36)
@@ -30,10 +34,7 @@ def same_bits(a, b):
     return torch.equal(a.cpu().view(torch.uint8), b.cpu().view(torch.uint8))
 
 
-@pytest.mark.parametrize('transpose', [False, True])
-@pytest.mark.parametrize('dt', list(DTYPES))
-@pytest.mark.parametrize('k', BASES)
-def test_kernel_has_the_bits_of_the_composed_route(k, dt, transpose):
+def bits_of_the_composed_route(k, dt, transpose):
     from brevitas_amd import _native as nat
     from brevitas_amd.function.hadamard import hadamard_transform
     gen = torch.Generator().manual_seed(123456)
@@ -46,6 +47,39 @@ def test_kernel_has_the_bits_of_the_composed_route(k, dt, transpose):
         want = hadamard_transform(x, b, base=k, transpose=transpose)
         assert same_bits(got, want), (p, cols, int((got.cpu() != want).sum()))
         assert nat.hadamard_kron(xd, ROWS, cols, k, b, transpose, b ** -0.5, out=xd) is xd and same_bits(xd, want)  # in place
+
+
+@pytest.mark.parametrize('transpose', [False, True])
+@pytest.mark.parametrize('dt', list(DTYPES))
+@pytest.mark.parametrize('k', BASES)
+def test_kernel_has_the_bits_of_the_composed_route(k, dt, transpose):
+    bits_of_the_composed_route(k, dt, transpose)
+
+
+def test_forced_nt_build(use_nt0):  # noqa: F811
+    """the NT = true instantiations of both depths of the row walk (by size no test reaches them), every K; the
+    transpose, which is another kernel at K = 12 and 20"""
+    use_nt0()
+    for k in BASES:
+        for dt in ('f32', 'bf16'):
+            bits_of_the_composed_route(k, dt, True)
+
+
+def test_special_values():
+    """NaN where the composed route on the CPU has NaN, its bits everywhere else: inf - inf, signed zeros, subnormal
+    inputs and overflowing sums through the Sylvester stages, the image in LDS and the K stage (Paley I and II)"""
+    from brevitas_amd import _native as nat
+    from brevitas_amd.function.hadamard import hadamard_transform
+    for k in (12, 28):
+        for dt, dtype in DTYPES.items():
+            b = k * 64
+            x = special_rows(dtype, 4 * b, b)
+            assert nat.hadamard_kron_supported(x.to(DEV), 6, 4 * b, k, b)
+            got = nat.hadamard_kron(x.to(DEV), 6, 4 * b, k, b, False, b ** -0.5).cpu()
+            want = hadamard_transform(x, b, base=k)
+            assert bool(torch.isnan(want[0]).any())
+            assert same_bits_or_nan(got, want), \
+                (k, dt, (~((got == want) | (got.isnan() & want.isnan()))).nonzero()[:8].tolist())
 
 
 @pytest.mark.parametrize('k', BASES)
